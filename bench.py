@@ -6,7 +6,17 @@ A "step" = one mkt_gate_batch call: B independent NAND gates (gate.jl:1-8 -> boo
 bootstrapping.jl:4-27) on ciphertexts already resident in HBM.  Default workload = BASELINE.json
 configs[1]: KMS multi-key k=2, N=1024, batch=1024 (synthetic shape, l_gsw=2 -- SURVEY.md 0.5).
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload NAME --batch B]
+  python bench.py [--gpus N --steps K --warmup W] [--workload NAME --batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line: the headline rate, ms_per_step, the decryption check of
+the last step's outputs and the rotation kernel's roofline (both read off the timed steps, no run of their own).  The legs that
+measure something else (`secondary`, `exact_mode`, `roofline_transform`, `cpu_baseline` with `oracle_bitexact`, the adder8
+`circuit`) run only under --full; --no-secondary / --no-roofline / --no-cpu-baseline drop single legs of a --full run.
+
+--dump-outputs DIR: after the timed steps, the output ciphertexts of the last step (what the caller of mkt_gate_batch receives)
+go to DIR/<op>.npy, one row per gate, each 32-bit word as a float64 (exact).  Inputs and keys are seeded, so two builds run with
+the same arguments can be compared word for word.  More than 64 MB of words are cut to a fixed sample of rows (seed 0), whose
+indices go to DIR/<op>_rows.npy.  Each rank of a multi-rank run writes its own shard, <op>_rank<r>.npy, within 64 MB in all.
 
 --scaling weak (default): --batch gates PER GPU; --scaling strong: --batch gates IN TOTAL, contiguous shards per rank
 (mktfhe_amd.distributed.shard_slices) -- BASELINE.json configs[2] / [3] are fixed-total batches:
@@ -28,7 +38,7 @@ process per GPU under torch.distributed (what the driver's census expects).
 one engine call per level (mkt_gate_batch_gather: mixed gate kinds, operands gathered from a ciphertext pool in HBM), beside
 the flat NAND rate of the same parameter set measured in the same run.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  Extra objects (roofline in every run, the others under --full):
   roofline           -- the kernel that costs the time, blindrotate_k1_kernel (93 % of a step): bound = f64 VALU issue
                         WITHOUT FMA (the reference's arithmetic rounds after every multiply and every add), achieved =
                         algorithmic flop per launch / average launch time from HIP events on the engine's stream;
@@ -251,6 +261,21 @@ def effective_cpus():
         except (OSError, ValueError):
             pass
     return n
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(d, name, res, budget=DUMP_BYTES):
+    """--dump-outputs: `res` (gates x words, uint32) -> d/<name>.npy as float64; beyond `budget` bytes a fixed sample of rows (seed 0,
+    ascending) and their indices in d/<name>_rows.npy"""
+    os.makedirs(d, exist_ok=True)
+    row_bytes = res.shape[1] * 8
+    if res.shape[0] * row_bytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(res.shape[0], budget // (row_bytes + 8), replace=False))
+        np.save(os.path.join(d, f"{name}_rows.npy"), idx.astype(np.float64))
+        res = res[idx]
+    np.save(os.path.join(d, f"{name}.npy"), res.astype(np.float64))
 
 
 def spawn_ranks(n, argv):
@@ -652,7 +677,7 @@ def main_inproc(args):
     p = getattr(mk, pname)
     total = args.batch if args.scaling == "strong" else n * args.batch
     arith = mk.ARITH_EXACT if args.arith == "exact" else mk.ARITH_F64REF
-    need_host_keys = not args.no_cpu_baseline
+    need_host_keys = args.full and not args.no_cpu_baseline
     if p.multikey:
         crs = mk.CRS(p, 1)
         keys = [mk.party_keygen(crs, p, party=i, secrets_only=not need_host_keys, deterministic_seed=1) for i in range(p.k)]
@@ -682,6 +707,8 @@ def main_inproc(args):
     for sh in shards:
         sh.enable_timing(False)
     res = out.cpu().numpy().view(np.uint32)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "nand", res)
     want = ~(bits[:total] & bits[total:])
     errs = int(np.count_nonzero(mk.lwe_decrypt(res, keys if p.multikey else keys[0], p) != want))
     lo, hi = sch.shard_range(total, 0)
@@ -704,7 +731,7 @@ def main_inproc(args):
     if args.arith == "exact":
         line["config"]["arith"] = EXACT_ARITH[kern == "fx_blindrotate_kernel"]
         line["dtype"] = "f64-fma-exact" if kern == "fx_blindrotate_kernel" else "u32x2-residue"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         allc = np.concatenate([x.cpu().numpy(), y.cpu().numpy()]).view(np.uint32)
         line["cpu_baseline"], line["oracle_bitexact"] = cpu_baseline(p, crs, keys, allc, total, res, args, args.arith == "f64ref")
         if args.arith == "f64ref":
@@ -730,7 +757,11 @@ def main():
     ap.add_argument("--no-roofline", action="store_true", help="skip the transform legs (roofline_transform)")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="gates in the CPU-baseline sample (0 = auto)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline: secondary, exact_mode, roofline_transform, cpu_baseline, the adder8 circuit")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output ciphertexts to DIR/<op>.npy (float64 words, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.launcher == "inproc":
         return main_inproc(args)                   # one process; nothing is spawned or exec'ed
@@ -769,15 +800,16 @@ def main():
         B = hi - lo
         if B == 0:
             raise SystemExit(f"rank {rank}: empty shard (batch {args.batch} over {world} ranks)")
-    need_host_keys = rank == 0 and not args.no_cpu_baseline
+    need_host_keys = rank == 0 and args.full and not args.no_cpu_baseline
     arith = mk.ARITH_EXACT if args.arith == "exact" else mk.ARITH_F64REF
     crs, keys, sch = make_scheme(mk, p, local, need_host_keys, arith)
     bits, x, y = make_inputs(mk, torch, p, keys, sch, B, rank, dev, args.inputs)
     torch.cuda.synchronize()
-    allc = np.concatenate([x.cpu().numpy(), y.cpu().numpy()]).view(np.uint32)
     t = time_gates(mk, torch, dist, D, sch, p, keys, x, y, bits, B, args.steps, args.warmup, world, red_dev, args.op)
     res = t["res"]
     kern = sch.last_kernel_name()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, args.op if world == 1 else f"{args.op}_rank{rank}", res, DUMP_BYTES // world)
 
     line = None
     if rank == 0:
@@ -806,11 +838,11 @@ def main():
             line["dtype"] = "f64-fma-exact" if fx else "u32x2-residue"
 
     # ---- circuit throughput (--workload adder8): rank 0, N = 1 ----
-    if rank == 0 and world == 1 and args.workload == "adder8":
+    if args.full and rank == 0 and world == 1 and args.workload == "adder8":
         line["circuit"] = run_circuit(mk, torch, p, keys, sch, args, dev, line["value"])
 
     # ---- secondary leg: the reference's own 2-party set, same measurement, short ----
-    if not args.no_secondary and args.workload == "kms2_n1024":
+    if args.full and not args.no_secondary and args.workload == "kms2_n1024":
         p2 = mk.KMS2party
         crs2, keys2, sch2 = make_scheme(mk, p2, local, False)
         bits2, x2, y2 = make_inputs(mk, torch, p2, keys2, sch2, B, rank, dev, args.inputs)
@@ -829,7 +861,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- the same workload in the integer-NTT arithmetic the north star names (MKT_ARITH_EXACT), short; rank 0 only ----
-    if rank == 0 and not args.no_secondary and args.arith == "f64ref" and args.workload == "kms2_n1024":
+    if args.full and rank == 0 and not args.no_secondary and args.arith == "f64ref" and args.workload == "kms2_n1024":
         crsx, keysx, schx = make_scheme(mk, p, local, False, mk.ARITH_EXACT)
         bitsx, xx, yx = make_inputs(mk, torch, p, keysx, schx, B, rank, dev, args.inputs)
         stx = max(2, args.steps // 2)
@@ -853,11 +885,12 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- transform roofline legs (BASELINE.json metric 2): rank 0, at every world size ----
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         line["roofline_transform"] = transform_roofline(mk, torch, local, dev)
 
     # ---- CPU baseline leg (oracle, "port"): rank 0, at every world size (the other ranks wait at the final barrier) ----
-    if rank == 0 and not args.no_cpu_baseline and args.op == "nand":
+    if args.full and rank == 0 and not args.no_cpu_baseline and args.op == "nand":
+        allc = np.concatenate([x.cpu().numpy(), y.cpu().numpy()]).view(np.uint32)
         line["cpu_baseline"], line["oracle_bitexact"] = cpu_baseline(p, crs, keys, allc, B, res, args, args.arith == "f64ref")   # EXACT words differ from the Float64 reference by construction (checked against big-integer arithmetic in tests)
         if args.arith == "f64ref":
             verify_wrong_gates(line, mk, p, crs, keys, allc, B, res, ~(bits[:B] & bits[B:]))

@@ -433,11 +433,11 @@ def test_baseline_multi_gpu_configs_at_full_batch_on_eight_logical_shards(requir
 
 
 # ---- first contact with a multi-GPU node, rehearsed on one GPU ----
-def _bench_line(args, env_extra, timeout):
+def _bench_line(args, env_extra, timeout, drop_legs=True):
     import json, subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--no-cpu-baseline", "--no-roofline", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + (["--no-cpu-baseline", "--no-roofline", "--no-secondary"] if drop_legs else []),
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -453,6 +453,37 @@ def test_bench_eight_ranks_rendezvous_on_a_shared_gpu(require_gpu):
     assert j["n_gpus"] == 8 and j["ranks_seen"] == 8 and len(j["per_rank_ms_per_step"]) == 8 and all(v > 0 for v in j["per_rank_ms_per_step"])
     assert j["config"]["batch_total"] == 8 * 16 and j["decrypt_checked"] == 8 * 16 and j["decrypt_errors"] == 0
     assert abs(j["value"] - 8 * 16 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True], ids=["plain", "full"])
+def test_bench_extra_legs_run_only_under_full(require_gpu, full):
+    """the headline workload with none of the --no-* options, where every extra leg would run: a plain run carries none of them, a
+    --full run all of them; likewise the adder8 circuit leg (which the --no-* options do not touch)"""
+    legs = {"secondary", "exact_mode", "roofline_transform", "cpu_baseline", "oracle_bitexact"}
+    opt = ["--full", "--cpu-sample", "16"] if full else []
+    j = _bench_line(["--batch", "64", "--steps", "2", "--warmup", "1"] + opt, {}, 900, drop_legs=False)
+    assert j["config"]["params"] == "KMS2party_N1024_l2" and j["steps"] == 2
+    assert (legs & set(j)) == (legs if full else set())
+    c = _bench_line(["--workload", "adder8", "--batch", "16", "--instances", "4", "--steps", "1", "--warmup", "0"] + opt, {}, 900)
+    assert ("circuit" in c) == full
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_steps_outputs(require_gpu, tmp_path):
+    """a plain run times exactly --steps steps; --dump-outputs writes the last step's output ciphertexts as float64 words, which
+    decrypt to the NAND of bench.py's seeded inputs"""
+    j = _bench_line(["--workload", "cggi", "--batch", "64", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], {}, 900)
+    assert j["steps"] == 3 and abs(j["value"] - 64 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    p = mk.CGGIparam
+    w = np.load(tmp_path / "nand.npy")
+    assert w.dtype == np.float64 and w.shape == (64, p.lwe_len) and w.min() >= 0 and w.max() < 2**32
+    words = w.astype(np.uint32)
+    assert np.array_equal(words.astype(np.float64), w)
+    rng = np.random.default_rng(2)                   # bench.make_inputs, rank 0, one party: the x bits, then the y bits
+    bx, by = rng.integers(0, 2, 64).astype(bool), rng.integers(0, 2, 64).astype(bool)
+    keys = mk.PartyKeys(p, secrets_only=True, deterministic_seed=1)
+    assert np.array_equal(mk.lwe_decrypt(words, keys, p), ~(bx & by))
 
 
 @pytest.mark.gpu

@@ -15,7 +15,7 @@ for f in newest(glob.glob(f"{src}/trace_{wl}/*/*kernel_stats.csv")):
 dirs = sorted(d for d in glob.glob(f"{src}/pmc_{wl}_*") if os.path.basename(d)[len(f"pmc_{wl}_"):] in ("fetch", "write", "clk", "sq1", "sq2"))   # exactly this name's passes (kms2_n1024 must not swallow kms2_n1024_exact)
 if dirs:
     with open(f"{dst}/{tag}_bench_{wl}_pmc.txt", "w") as out:
-        out.write(f"# rocprofv3 --kernel-trace --pmc <counters> (separate passes), python3 bench.py --steps 2 --warmup 0 --workload {wl} --no-cpu-baseline --no-secondary\n")
+        out.write(f"# rocprofv3 --kernel-trace --pmc <counters> (separate passes), python3 bench.py --full --steps 2 --warmup 0 --workload {wl} --no-cpu-baseline --no-secondary\n")
         meta = dict(l.strip().split(" ", 1) for l in open(f"{src}/pmc_{wl}_meta.txt") if " " in l.strip()) if os.path.exists(f"{src}/pmc_{wl}_meta.txt") else {}
         git = os.popen("git rev-parse --short HEAD 2>/dev/null").read().strip() + ("+dirty" if os.popen("git status --porcelain -- mktfhe_amd include 2>/dev/null").read().strip() else "")
         out.write(f"# build_id: {meta.get('build_id', 'unknown')}  so_sha256: {meta.get('so_sha256', 'unknown')}  device: {meta.get('device', 'unknown')}  git (at collection): {git}\n")

@@ -5,7 +5,7 @@
 #   summaries are committed under profiles/ (a line reads its traffic from there)
 # then: python3 tools/collect_profiles.py <tag> <name>  for every name (tools/collect_all.sh <tag>)
 TAG=${1:-r04}; PART=${2:-1}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
-line() { python3 bench.py "$@" 2>/dev/null | grep '"metric"'; }
+line() { python3 bench.py --full "$@" 2>/dev/null | grep '"metric"'; }
 if [ $PART = 1 ]; then
   line --steps 20 --warmup 5 > $O/bench_kms2_n1024.json
   NOROOF= bash tools/pmc_pass.sh $TAG kms2_n1024 kms2_n1024 full > /dev/null    # NOROOF=: the transform legs stay in the profiled command
