@@ -57,7 +57,21 @@ enum { MKT_CGGI = 0, MKT_LMSS = 1, MKT_CCS = 2, MKT_KMS = 3, MKT_KMS_BLOCK = 4 }
 enum { MKT_NAND = 0, MKT_AND = 1, MKT_OR = 2, MKT_XOR = 3, MKT_XNOR = 4, MKT_NOR = 5 };
 /* per-gate codes of mkt_gate_batch_ops / _gather: a gate of the enum above, optionally with one or both inputs negated first
  * (NOT!, gate.jl:55-58, folded into the gate's linear part: the same words as NOT! followed by the gate) */
-enum { MKT_OP_NOT_X = 8, MKT_OP_NOT_Y = 16 };
+enum { MKT_OP_NOT_X = 8, MKT_OP_NOT_Y = 16, MKT_OP_NOT_Z = 32 };
+/* three-input gates in ONE bootstrap (mkt_gate3_batch_*): codes 0-5 in bits 0-2, MKT_OP_NOT_X / _Y / _Z in bits 3-5, bits 6-7 clear.
+ * Built as gate.jl builds a gate -- a linear part, then bootstrapping! (bootstrapping.jl:4-27) as a sign function -- with a third
+ * operand: with a bit at +-2^29 (+-1/8) and x, y, z the operands after their flagged NOTs (NOT!, gate.jl:55-58), the linear part on
+ * the 32-bit torus (constant added to the b word) and the truth for 0 / 1 / 2 / 3 true inputs are
+ *   MKT_MAJ3  x + y + z                F F T T        MKT_MIN3   -(x + y + z)             T T F F
+ *   MKT_XOR3  -2(x + y + z)            F T F T        MKT_XNOR3  2(x + y + z)             T F T F
+ *   MKT_NAE3  x + y + z + 2^30         F T T F        MKT_AE3    3 2^30 - (x + y + z)     T F F T
+ * (NAE3 = not all equal, AE3 = all equal).  The test vector is antiperiodic, f(phase + 1/2) = -f(phase), so these six are exactly the
+ * symmetric three-input functions one bootstrap of the unweighted sum computes: AND3 and OR3 take two.  A full adder is
+ * sum = XOR3, carry = MAJ3; per-input NOTs give the asymmetric variants (a subtractor's borrow is MAJ3(NOT a, b, c)).
+ * NOISE: MAJ3 / MIN3 / NAE3 / AE3 put 3 sigma^2 on a margin of 1/8, XOR3 / XNOR3 12 sigma^2 on a margin of 1/4: in both cases
+ * margin / sigma is sqrt(2/3) of a two-input gate's, so the per-gate failure rate of a set is much higher than for its two-input
+ * gates (Gaussian predictions per shipped set, and measured rates). */
+enum { MKT_MAJ3 = 0, MKT_MIN3 = 1, MKT_XOR3 = 2, MKT_XNOR3 = 3, MKT_NAE3 = 4, MKT_AE3 = 5 };
 /* arithmetic modes of the negacyclic transform */
 enum {
     MKT_ARITH_F64REF = 0, /* the reference's Float64 twisted FFT, operation for operation (fft.jl) */
@@ -197,6 +211,15 @@ int mkt_gate_batch_ops(mkt_ctx *ctx, const uint8_t *ops, const uint32_t *x, cons
  * holds for mkt_gate_batch_ops and mkt_mux_batch_gather. */
 int mkt_gate_batch_gather(mkt_ctx *ctx, const uint8_t *ops, const uint32_t *pool, size_t pool_rows, const uint32_t *ix,
                           const uint32_t *iy, uint32_t *out, size_t B, int mem);
+/* three-input gates, one bootstrap each (codes above): out[j] = bootstrapping!(linear3(ops[j], x[j], y[j], z[j])); x, y, z, out: [B][k*n+1];
+ * ops lives where x, y, z, out live (`mem`).  With MKT_MEM_HOST a bad code is MKT_ERR_ARG. */
+int mkt_gate3_batch_ops(mkt_ctx *ctx, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem);
+/* one circuit level of three-input gates: gate j reads rows ix[j], iy[j], iz[j] of pool [pool_rows][k*n+1] and writes out[j]; out may
+ * be a later region of the pool that no gate of this call reads.  Validation as mkt_gate_batch_gather: with MKT_MEM_HOST a bad code or
+ * index is MKT_ERR_ARG; with MKT_MEM_DEVICE an index beyond the pool is clamped to its last row and a code is read modulo its defined
+ * bits (gate values 6 and 7 act as MKT_AE3).  An empty pool is refused. */
+int mkt_gate3_batch_gather(mkt_ctx *ctx, const uint8_t *ops, const uint32_t *pool, size_t pool_rows, const uint32_t *ix, const uint32_t *iy,
+                           const uint32_t *iz, uint32_t *out, size_t B, int mem);
 /* MUX(s, a, b) = s ? a : b -- named by the north star; the reference has no MUX gate (gate.jl:1-57).  Two blind rotations and one
  * key switch, built from the reference's own operators as CGGI16 builds it:
  *   acc = blindrotate!(AND-linear(s, a)) + blindrotate!(AND-linear(NOT! s, b)), + 1/8 at X^0 of acc.b;  out = keyswitch!(acc)
@@ -273,6 +296,7 @@ int mkt_multi_replicate(mkt_multi *m);
 int mkt_multi_set_option(mkt_multi *m, const char *name, int value);
 int mkt_multi_gate_batch(mkt_multi *m, int op, const uint32_t *x, const uint32_t *y, uint32_t *out, size_t B, int mem);
 int mkt_multi_gate_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x, const uint32_t *y, uint32_t *out, size_t B, int mem);
+int mkt_multi_gate3_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem);
 int mkt_multi_mux_batch(mkt_multi *m, const uint32_t *s, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t B, int mem);
 int mkt_multi_bootstrap_batch(mkt_multi *m, uint32_t *lwe, size_t B, int mem);
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem);

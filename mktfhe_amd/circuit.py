@@ -5,15 +5,24 @@ two-input bootstrapped gates (gate.jl:1-53) and free NOTs (gate.jl:55-58); ALL g
 type -- are evaluated in ONE engine call over all `B` independent input sets at once (mkt_gate_batch_gather: a per-gate op
 code, operands picked by row index from a ciphertext pool that stays in HBM, NOTs folded into the gate's linear part), so a
 level costs one round of launches however many gate kinds it mixes.
+
+Three-input nodes (Circuit.MAJ3 / XOR3 / ...: one bootstrap each, mktfhe.h MKT_MAJ3 .. MKT_AE3) are a node kind of their own: the
+three-input gates of a level are one contiguous pool region and one mkt_gate3_batch_gather call, so a level costs at most one
+call per node kind.  ripple_adder_fa builds the adder from them: 2 bootstraps per bit instead of 5, one level per bit instead of 2.
 """
 from collections import defaultdict
 
 import numpy as np
 
-from .params import NAND_OP, AND_OP, OR_OP, XOR_OP, XNOR_OP, NOR_OP
+from .params import NAND_OP, AND_OP, OR_OP, XOR_OP, XNOR_OP, NOR_OP, MAJ3_OP, MIN3_OP, XOR3_OP, XNOR3_OP, NAE3_OP, AE3_OP
 
 _NOT = -1
 _MUX = 6        # native three-input node (mkt_mux_batch_gather): nodes entry (_MUX, s, (a, b))
+_G3 = 7         # three-input gate in one bootstrap (mkt_gate3_batch_gather): nodes entry (_G3, x, (y, z, code)), code MAJ3_OP .. AE3_OP
+_KIND = {_MUX: 2, _G3: 1}      # pool order of the node kinds inside a level: two-input gates, three-input gates, native MUX nodes
+
+# plaintext truth of the three-input codes, by number of true inputs (mktfhe.h)
+_G3_TRUTH = {MAJ3_OP: (0, 0, 1, 1), MIN3_OP: (1, 1, 0, 0), XOR3_OP: (0, 1, 0, 1), XNOR3_OP: (1, 0, 1, 0), NAE3_OP: (0, 1, 1, 0), AE3_OP: (1, 0, 0, 1)}
 
 
 class Circuit:
@@ -55,19 +64,33 @@ class Circuit:
         self.nodes.append((_MUX, s, (a, b)))
         return len(self.nodes) - 1
 
+    def gate3(self, op, a, b, c):
+        """a three-input gate in ONE bootstrap (op = MAJ3_OP .. AE3_OP); NOTs on its inputs are folded into its code by Plan"""
+        assert 0 <= op <= 5 and all(0 <= v < len(self.nodes) for v in (a, b, c))
+        self.nodes.append((_G3, a, (b, c, op)))
+        return len(self.nodes) - 1
+
+    def MAJ3(self, a, b, c): return self.gate3(MAJ3_OP, a, b, c)
+    def MIN3(self, a, b, c): return self.gate3(MIN3_OP, a, b, c)
+    def XOR3(self, a, b, c): return self.gate3(XOR3_OP, a, b, c)
+    def XNOR3(self, a, b, c): return self.gate3(XNOR3_OP, a, b, c)
+    def NAE3(self, a, b, c): return self.gate3(NAE3_OP, a, b, c)
+    def AE3(self, a, b, c): return self.gate3(AE3_OP, a, b, c)
+
     def output(self, w):
         self.outputs.append(w)
         return w
 
     def levels(self):
-        """-> (depth per node, {level: {op: [node ids]}}) ; NOT and inputs cost no level"""
+        """-> (depth per node, {level: {op: [node ids]}}) ; NOT and inputs cost no level; every three-input gate of a level is under
+        the one key _G3 whatever its code"""
         depth = []
         for op, a, b in self.nodes:
             if op == "in":
                 depth.append(0)
             elif op == _NOT:
                 depth.append(depth[a])
-            elif op == _MUX:
+            elif op in (_MUX, _G3):
                 depth.append(1 + max(depth[a], depth[b[0]], depth[b[1]]))
             else:
                 depth.append(1 + max(depth[a], depth[b]))
@@ -85,6 +108,9 @@ class Circuit:
         for op, a, b in self.nodes:
             if op == _MUX:
                 v.append(np.where(v[a], v[b[0]], v[b[1]]))
+            elif op == _G3:
+                cnt = np.asarray(v[a], dtype=np.int8) + np.asarray(v[b[0]], dtype=np.int8) + np.asarray(v[b[1]], dtype=np.int8)
+                v.append(np.array(_G3_TRUTH[b[2]], dtype=bool)[cnt])
             else:
                 v.append(bits[a] if op == "in" else (~v[a] if op == _NOT else f[op](v[a], v[b])))
         return [v[w] for w in self.outputs]
@@ -97,11 +123,14 @@ def _cat(xs):
     return np.concatenate(xs, 0)
 
 
-def evaluate(circ: Circuit, inputs, gate_fn, not_fn, mux_fn=None):
+def evaluate(circ: Circuit, inputs, gate_fn, not_fn, mux_fn=None, gate3_fn=None):
     """inputs: list of n_inputs arrays [B, lwe_len] (numpy or GPU tensors).  gate_fn(op, x, y) -> out is the
-    batched gate (Scheme.gate), not_fn(x) -> negated COPY, mux_fn(s, a, b) -> out the native MUX (needed only for MUXN nodes).
+    batched gate (Scheme.gate), not_fn(x) -> negated COPY, mux_fn(s, a, b) -> out the native MUX (needed only for MUXN nodes),
+    gate3_fn(ops, x, y, z) -> out the three-input gates with one uint8 code per row (Scheme.gate3_ops; needed only for three-input
+    nodes: the codes carry no NOT flags, negated operands come from not_fn).
     Returns the output ciphertext arrays [B, lwe_len].
-    Number of gate_fn calls = number of distinct (level, op) pairs, independent of the circuit width."""
+    Number of gate_fn calls = number of distinct (level, op) pairs, independent of the circuit width; one gate3_fn call per level
+    that holds three-input gates."""
     assert len(inputs) == circ.n_inputs
     depth, sched = circ.levels()
     val = [None] * len(circ.nodes)
@@ -118,6 +147,12 @@ def evaluate(circ: Circuit, inputs, gate_fn, not_fn, mux_fn=None):
             x = _cat([resolve(circ.nodes[i][1]) for i in ids])
             if op == _MUX:
                 out = mux_fn(x, _cat([resolve(circ.nodes[i][2][0]) for i in ids]), _cat([resolve(circ.nodes[i][2][1]) for i in ids]))
+            elif op == _G3:
+                ops = np.repeat(np.array([circ.nodes[i][2][2] for i in ids], dtype=np.uint8), B)
+                if type(x).__module__.startswith("torch"):
+                    import torch
+                    ops = torch.from_numpy(ops).to(x.device)
+                out = gate3_fn(ops, x, _cat([resolve(circ.nodes[i][2][0]) for i in ids]), _cat([resolve(circ.nodes[i][2][1]) for i in ids]))
             else:
                 y = _cat([resolve(circ.nodes[i][2]) for i in ids])
                 out = gate_fn(op, x, y)
@@ -127,9 +162,11 @@ def evaluate(circ: Circuit, inputs, gate_fn, not_fn, mux_fn=None):
 
 
 class Plan:
-    """The launch schedule of a circuit over B instances: one mkt_gate_batch_gather per level.  Pool rows: node slot s,
+    """The launch schedule of a circuit over B instances: one mkt_gate_batch_gather per level (plus one mkt_gate3_batch_gather /
+    mkt_mux_batch_gather for a level that holds three-input gates / native MUX nodes).  Pool rows: node slot s,
     instance b -> row s * B + b; slots 0 .. n_inputs-1 are the inputs, then the gates level by level (so a level's outputs
-    are one contiguous region of the pool); NOT nodes own no slot -- they resolve to (slot of their source, negated)."""
+    are one contiguous region of the pool, each node kind a contiguous part of it); NOT nodes own no slot -- they resolve to
+    (slot of their source, negated), folded into the reading gate's code."""
 
     def __init__(self, circ: Circuit, B):
         depth, sched = circ.levels()
@@ -141,7 +178,7 @@ class Plan:
         nslots = circ.n_inputs
         order = []
         for lvl in sorted(sched):
-            ids = sorted((i for lst in sched[lvl].values() for i in lst), key=lambda i: (circ.nodes[i][0] == _MUX, i))   # two-input gates first, native MUX nodes after: each kind one contiguous region of the pool
+            ids = sorted((i for lst in sched[lvl].values() for i in lst), key=lambda i: (_KIND.get(circ.nodes[i][0], 0), i))   # two-input gates, three-input gates, native MUX nodes: each kind one contiguous region of the pool
             for i in ids:
                 slot[i] = nslots
                 nslots += 1
@@ -157,9 +194,11 @@ class Plan:
         inst = np.arange(B, dtype=np.uint32)
         self.levels = []        # two-input gates of a level: (first slot, count, ops, ix, iy)
         self.mux_levels = []    # its native MUX nodes, if any: (first slot, count, is, ia, ib, not_ab) or None
+        self.gate3_levels = []  # its three-input gates, if any: (first slot, count, ops, ix, iy, iz) or None
         for ids in order:
-            g2 = [i for i in ids if circ.nodes[i][0] != _MUX]
+            g2 = [i for i in ids if circ.nodes[i][0] not in (_MUX, _G3)]
             g3 = [i for i in ids if circ.nodes[i][0] == _MUX]
+            t3 = [i for i in ids if circ.nodes[i][0] == _G3]
             ops = np.empty((len(g2), B), dtype=np.uint8)
             ix = np.empty((len(g2), B), dtype=np.uint32)
             iy = np.empty((len(g2), B), dtype=np.uint32)
@@ -170,6 +209,17 @@ class Plan:
                 ix[j] = sa * B + inst
                 iy[j] = sb * B + inst
             self.levels.append((slot[g2[0]] if g2 else 0, len(g2), ops.ravel(), ix.ravel(), iy.ravel()))
+            if t3:
+                o3 = np.empty((len(t3), B), dtype=np.uint8)
+                jx, jy, jz = (np.empty((len(t3), B), dtype=np.uint32) for _ in range(3))
+                for j, i in enumerate(t3):
+                    _, a, (b, c, code) = circ.nodes[i]
+                    (sa, na), (sb, nb), (sc, nc) = src(a), src(b), src(c)
+                    o3[j] = code | (8 if na else 0) | (16 if nb else 0) | (32 if nc else 0)
+                    jx[j], jy[j], jz[j] = sa * B + inst, sb * B + inst, sc * B + inst
+                self.gate3_levels.append((slot[t3[0]], len(t3), o3.ravel(), jx.ravel(), jy.ravel(), jz.ravel()))
+            else:
+                self.gate3_levels.append(None)
             if g3:
                 js, ja, jb = (np.empty((len(g3), B), dtype=np.uint32) for _ in range(3))
                 fl = np.empty((len(g3), B), dtype=np.uint8)
@@ -184,12 +234,13 @@ class Plan:
             else:
                 self.mux_levels.append(None)
         self.rows = nslots * B
-        self.gates = (sum(n for _, n, _, _, _ in self.levels) + sum(m[1] for m in self.mux_levels if m)) * B
+        self.gates = (sum(n for _, n, _, _, _ in self.levels) + sum(m[1] for m in self.mux_levels if m) + sum(t[1] for t in self.gate3_levels if t)) * B
         self.outputs = [src(w) for w in circ.outputs]
 
 
 def evaluate_on(circ: Circuit, inputs, scheme, plan: Plan = None):
-    """evaluate with an engine Scheme (GPU tensors or numpy arrays): one engine call per LEVEL (all gate kinds merged)."""
+    """evaluate with an engine Scheme (GPU tensors or numpy arrays): one engine call per LEVEL and node kind (all two-input gate
+    kinds merged; all three-input codes merged)."""
     B = inputs[0].shape[0]
     plan = plan or Plan(circ, B)
     assert plan.B == B and len(inputs) == plan.n_inputs
@@ -205,9 +256,12 @@ def evaluate_on(circ: Circuit, inputs, scheme, plan: Plan = None):
         up = lambda a: a                                                                              # noqa: E731
     for s, x in enumerate(inputs):
         pool[s * B:(s + 1) * B] = x
-    for (slot0, ngates, ops, ix, iy), mx in zip(plan.levels, plan.mux_levels):
+    for (slot0, ngates, ops, ix, iy), mx, t3 in zip(plan.levels, plan.mux_levels, plan.gate3_levels):
         if ngates:
             scheme.gate_gather(up(ops), pool, up(ix), up(iy), pool[slot0 * B:(slot0 + ngates) * B])
+        if t3:
+            t0, nt, o3, jx, jy, jz = t3
+            scheme.gate3_gather(up(o3), pool, up(jx), up(jy), up(jz), pool[t0 * B:(t0 + nt) * B])
         if mx:
             m0, nm, js, ja, jb, fl = mx
             scheme.mux_gather(pool, up(js), up(ja), up(jb), pool[m0 * B:(m0 + nm) * B], not_ab=up(fl))
@@ -271,5 +325,21 @@ def ripple_adder(nbits):
         else:
             c.output(c.XOR(p, carry))
             carry = c.OR(g, c.AND(p, carry))
+    c.output(carry)
+    return c
+
+
+def ripple_adder_fa(nbits):
+    """the same adder as ripple_adder (same inputs and outputs) from full adders of three-input gates: a half adder (XOR, AND) at
+    bit 0, then sum = XOR3(a, b, carry) and carry = MAJ3(a, b, carry), one bootstrap each: 2 nbits bootstraps over nbits levels"""
+    c = Circuit()
+    a = [c.input() for _ in range(nbits)]
+    b = [c.input() for _ in range(nbits)]
+    carry = None
+    for i in range(nbits):
+        if carry is None:
+            c.output(c.XOR(a[i], b[i])); carry = c.AND(a[i], b[i])
+        else:
+            c.output(c.XOR3(a[i], b[i], carry)); carry = c.MAJ3(a[i], b[i], carry)
     c.output(carry)
     return c

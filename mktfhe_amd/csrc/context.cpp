@@ -1040,6 +1040,59 @@ int mkt_gate_batch_gather(mkt_ctx *c, const uint8_t *ops, const uint32_t *pool, 
     return gate_impl(c, 0, ops, pool, pool, pool_rows, ix, iy, out, B, mem);
 }
 
+// three-input gates in one bootstrap: gate_impl's chunk loop with the three-operand linear part, then bootstrap_chunk (every scheme,
+// both arithmetic modes).  Operands in batch order (x, y, z: [B][len]) or picked by row index from a pool (x = y = z = pool)
+static int gate3_impl(mkt_ctx *c, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, size_t rows_xyz, const uint32_t *ix,
+                      const uint32_t *iy, const uint32_t *iz, uint32_t *out, size_t B, int mem) {
+    MKT_EXACT_GATE(c);
+    int r;
+    if ((r = check_ready(c, true, true))) return r;
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    const size_t len = (size_t)c->sh.lwe_len;
+    const bool pool = ix != nullptr;
+    Staged sx{c}, sy{c}, sz{c}, so{c}, sops{c}, six{c}, siy{c}, siz{c};
+    if ((r = sx.in(x, rows_xyz * len * 4, mem, true))) return r;
+    if (pool) sy.dev = sz.dev = sx.dev;
+    else if ((r = sy.in(y, rows_xyz * len * 4, mem, true)) || (r = sz.in(z, rows_xyz * len * 4, mem, true))) return r;
+    if ((r = so.in(out, B * len * 4, mem, false))) return r;
+    if ((r = sops.in(ops, B, mem, true))) return r;
+    if (pool && ((r = six.in(ix, B * 4, mem, true)) || (r = siy.in(iy, B * 4, mem, true)) || (r = siz.in(iz, B * 4, mem, true)))) return r;
+    for (size_t off = 0; off < B; off += CHUNK_GATES) {
+        const size_t nb = std::min(CHUNK_GATES, B - off);
+        if ((r = ensure_workspace(c, nb))) return r;
+        const size_t xoff = pool ? 0 : off * len;
+        HIPCHK(c, mktd::launch_gate3_linear((const uint8_t *)sops.dev + off, (const uint32_t *)sx.dev + xoff, (const uint32_t *)sy.dev + xoff, (const uint32_t *)sz.dev + xoff,
+                                            pool ? (const uint32_t *)six.dev + off : nullptr, pool ? (const uint32_t *)siy.dev + off : nullptr,
+                                            pool ? (const uint32_t *)siz.dev + off : nullptr, pool ? rows_xyz : 0, c->ws_lin, (int)len, nb, c->stream));
+        if ((r = bootstrap_chunk(c, c->ws_lin, (uint32_t *)so.dev + off * len, nb))) return r;
+    }
+    return so.out(out);
+}
+
+static bool ops3_valid_host(const uint8_t *ops, size_t B) {
+    for (size_t j = 0; j < B; j++) if ((ops[j] & 7) > MKT_AE3 || (ops[j] & ~63u)) return false;
+    return true;
+}
+
+int mkt_gate3_batch_ops(mkt_ctx *c, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem) {
+    if (!c || !ops || !x || !y || !z || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (mem == MKT_MEM_HOST && !ops3_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_ops: unknown gate code");
+    return gate3_impl(c, ops, x, y, z, B, nullptr, nullptr, nullptr, out, B, mem);
+}
+
+int mkt_gate3_batch_gather(mkt_ctx *c, const uint8_t *ops, const uint32_t *pool, size_t pool_rows, const uint32_t *ix, const uint32_t *iy, const uint32_t *iz,
+                           uint32_t *out, size_t B, int mem) {
+    if (!c || !ops || !pool || !ix || !iy || !iz || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: gates over an empty pool");
+    if (mem == MKT_MEM_HOST) {
+        if (!ops3_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: unknown gate code");
+        for (size_t j = 0; j < B; j++)
+            if (ix[j] >= pool_rows || iy[j] >= pool_rows || iz[j] >= pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: operand index outside the pool");
+    }
+    return gate3_impl(c, ops, pool, pool, pool, pool_rows, ix, iy, iz, out, B, mem);
+}
+
 // MUX(s, a, b) = s ? a : b with TWO blind rotations and ONE key switch (the reference has no MUX gate, gate.jl:1-57; this is the
 // CGGI16 construction written with the reference's own operators):
 //   acc = blindrotate!(AND-linear(s, a)) + blindrotate!(AND-linear(NOT! s, b)), + 1/8 at X^0 of acc.b;  out = keyswitch!(acc)

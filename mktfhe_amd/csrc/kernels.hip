@@ -212,6 +212,42 @@ __global__ void gate_linear_kernel(int op_all, const uint8_t *__restrict__ ops, 
     }
 }
 
+// The three-input linear part (mktfhe.h MKT_MAJ3 .. MKT_AE3; gate.jl's pattern with a third operand): s = x + y + z after the
+// flagged inputs are negated (bits 3 / 4 / 5), then one of six sign-function inputs, the constant added to the b word.  A code is
+// read modulo its defined bits like gate_linear_kernel's: bits 6-7 are ignored, gate values 6 and 7 fall to the last case (AE3).
+// One workgroup per gate (grid-stride over gates): the code and the three row indices are the same for the whole workgroup, so they are
+// loaded once per gate, not once per word, and the words of the four rows are streamed coalesced (lane c reads word c of each row).
+__global__ void __launch_bounds__(256) gate3_linear_kernel(const uint8_t *__restrict__ ops, const uint32_t *__restrict__ x, const uint32_t *__restrict__ y,
+                                                           const uint32_t *__restrict__ z, const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iy,
+                                                           const uint32_t *__restrict__ iz, size_t pool_rows, uint32_t *__restrict__ out, int len, size_t B) {
+    for (size_t g = blockIdx.x; g < B; g += gridDim.x) {
+        const int code = ops[g];
+        size_t ra = ix ? (size_t)ix[g] : g, rb = iy ? (size_t)iy[g] : g, rc = iz ? (size_t)iz[g] : g;
+        if (pool_rows) {                       // rows clamped into the pool (see gate_linear_kernel)
+            const size_t last = pool_rows - 1;
+            ra = ra < pool_rows ? ra : last; rb = rb < pool_rows ? rb : last; rc = rc < pool_rows ? rc : last;
+        }
+        const uint32_t *pa = x + ra * len, *pb = y + rb * len, *pc = z + rc * len;
+        uint32_t *po = out + g * len;
+        const uint32_t na = (code & 8) ? ~0u : 0u, nb = (code & 16) ? ~0u : 0u, nc = (code & 32) ? ~0u : 0u;   // v -> (v ^ n) - n negates where n = ~0
+        const int gate = code & 7;
+        for (int c = threadIdx.x; c < len; c += blockDim.x) {
+            const uint32_t s = ((pa[c] ^ na) - na) + ((pb[c] ^ nb) - nb) + ((pc[c] ^ nc) - nc);
+            const bool isb = c == len - 1;
+            uint32_t r;
+            switch (gate) {
+            case 0:  r = s; break;                                              // MAJ3
+            case 1:  r = 0u - s; break;                                         // MIN3
+            case 2:  r = 0u - 2u * s; break;                                    // XOR3
+            case 3:  r = 2u * s; break;                                         // XNOR3
+            case 4:  r = (isb ? (1u << 30) : 0u) + s; break;                    // NAE3
+            default: r = (isb ? (3u << 30) : 0u) - s; break;                    // AE3
+            }
+            po[c] = r;
+        }
+    }
+}
+
 // native MUX: acc[j] += acc[B + j] (two blind-rotation outputs, polynomial by polynomial) and +1/8 at X^0 of the b polynomial
 template <typename WORD>
 __global__ void mux_combine_kernel(WORD *__restrict__ acc, size_t B, size_t words) {
@@ -1518,6 +1554,16 @@ hipError_t launch_gate_linear(int op, const uint8_t *ops, const uint32_t *x, con
     const size_t total = B * (size_t)len;
     if (!total) return hipSuccess;
     hipLaunchKernelGGL(gate_linear_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, op, ops, x, y, ix, iy, pool_rows, out, len, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_gate3_linear(const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, const uint32_t *ix, const uint32_t *iy, const uint32_t *iz,
+                               size_t pool_rows, uint32_t *out, int len, size_t B, hipStream_t s) {
+    if (!B || len <= 0) return hipSuccess;
+    // one workgroup per gate; a wave per 64 words up to four waves (the headline LWE length is ~1000 words: four passes of 256)
+    const int threads = len >= 256 ? 256 : ((len + 63) / 64) * 64;
+    const unsigned grid = (unsigned)(B < 65536 ? B : 65536);
+    hipLaunchKernelGGL(gate3_linear_kernel, dim3(grid), dim3(threads), 0, s, ops, x, y, z, ix, iy, iz, pool_rows, out, len, B);
     return hipGetLastError();
 }
 

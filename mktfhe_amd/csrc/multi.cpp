@@ -276,6 +276,13 @@ int mkt_multi_gate_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x
                         [&](mkt_ctx *c, void **a, size_t nb) { return mkt_gate_batch_ops(c, (const uint8_t *)a[0], (const uint32_t *)a[1], (const uint32_t *)a[2], (uint32_t *)a[3], nb, mem); });
 }
 
+int mkt_multi_gate3_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem) {
+    if (!m || !ops || !x || !y || !z || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
+    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4;
+    return sharded_call(m, B, mem, {{ops, 1, true, false}, {x, rb, true, false}, {y, rb, true, false}, {z, rb, true, false}, {out, rb, false, true}},
+                        [&](mkt_ctx *c, void **a, size_t nb) { return mkt_gate3_batch_ops(c, (const uint8_t *)a[0], (const uint32_t *)a[1], (const uint32_t *)a[2], (const uint32_t *)a[3], (uint32_t *)a[4], nb, mem); });
+}
+
 int mkt_multi_mux_batch(mkt_multi *m, const uint32_t *sel, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t B, int mem) {
     if (!m || !sel || !a || !b || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
     const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4;

@@ -6,6 +6,7 @@ from ._lib import MktParams
 
 CGGI, LMSS, CCS, KMS, KMS_BLOCK = range(5)
 NAND_OP, AND_OP, OR_OP, XOR_OP, XNOR_OP, NOR_OP = range(6)
+MAJ3_OP, MIN3_OP, XOR3_OP, XNOR3_OP, NAE3_OP, AE3_OP = range(6)     # three-input gates, one bootstrap each (mktfhe.h MKT_MAJ3 .. MKT_AE3)
 
 
 @dataclass(frozen=True)

@@ -397,6 +397,48 @@ class Scheme:
         self._ck(_lib.lib().mkt_gate_batch_gather(self.h, pops, pp, self._batch(kp), pix, piy, po, B, mem))
         return ko
 
+    def gate3(self, op, x, y, z, out=None):
+        """a three-input gate in ONE bootstrap for the whole batch (MAJ3_OP .. AE3_OP, optionally | OP_NOT_X / _Y / _Z): gate3_ops with
+        one code"""
+        return self.gate3_ops(_full_ops(op, x, self._batch(x)), x, y, z, out)
+
+    def gate3_ops(self, ops, x, y, z, out=None):
+        """a three-input gate per ciphertext triple, one bootstrap each (mkt_gate3_batch_ops): ops[j] in 0..5 (MAJ3..AE3), optionally
+        | OP_NOT_X / OP_NOT_Y / OP_NOT_Z; a uint8 array living where x, y and z live"""
+        px, mem, kx = _arg(x, np.uint32, scheme=self)
+        py, m1, ky = _arg(y, np.uint32, scheme=self)
+        pz, m2, kz = _arg(z, np.uint32, scheme=self)
+        pops, m3, kops = _arg(ops, np.uint8, scheme=self)
+        if not (mem == m1 == m2 == m3):
+            raise ValueError("ops, x, y and z must all be host arrays or all be GPU tensors")
+        if out is None:
+            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
+        po, m4, ko = _arg(out, np.uint32, writable=True, scheme=self)
+        if m4 != mem:
+            raise ValueError("out must live where the inputs live")
+        B = self._batch(kx)
+        if not (tuple(kx.shape) == tuple(ky.shape) == tuple(kz.shape) == tuple(ko.shape)) or kx.shape[-1] != self.params.lwe_len or int(np.prod(kops.shape)) != B:
+            raise ValueError("ciphertext / ops shape mismatch")
+        self._ck(_lib.lib().mkt_gate3_batch_ops(self.h, pops, px, py, pz, po, B, mem))
+        return ko
+
+    def gate3_gather(self, ops, pool, ix, iy, iz, out):
+        """one circuit level of three-input gates (mkt_gate3_batch_gather): gate j = ops[j](pool[ix[j]], pool[iy[j]], pool[iz[j]]) -> out[j];
+        out may be a later region of the pool"""
+        pp, mem, kp = _arg(pool, np.uint32, scheme=self)
+        pops, m1, kops = _arg(ops, np.uint8, scheme=self)
+        pix, m2, kix = _arg(ix, np.uint32, scheme=self)
+        piy, m3, kiy = _arg(iy, np.uint32, scheme=self)
+        piz, m4, kiz = _arg(iz, np.uint32, scheme=self)
+        po, m5, ko = _arg(out, np.uint32, writable=True, scheme=self)
+        if not (mem == m1 == m2 == m3 == m4 == m5):
+            raise ValueError("all arguments must live in the same memory")
+        B = int(np.prod(kops.shape))
+        if kp.shape[-1] != self.params.lwe_len or any(int(np.prod(k.shape)) != B for k in (kix, kiy, kiz)) or self._batch(ko) != B:
+            raise ValueError("shape mismatch")
+        self._ck(_lib.lib().mkt_gate3_batch_gather(self.h, pops, pp, self._batch(kp), pix, piy, piz, po, B, mem))
+        return ko
+
     def mux(self, s, a, b, out=None):
         """MUX(s, a, b) = s ? a : b with two blind rotations and one key switch (mkt_mux_batch; the reference has no MUX gate)"""
         ps, mem, ks = _arg(s, np.uint32, scheme=self)
@@ -517,6 +559,15 @@ class Scheme:
 
 
 OP_NOT_X, OP_NOT_Y = 8, 16      # mktfhe.h MKT_OP_NOT_X / _Y: per-gate code bits of gate_ops / gate_gather
+OP_NOT_Z = 32                   # mktfhe.h MKT_OP_NOT_Z: the third input of gate3_ops / gate3_gather
+
+
+def _full_ops(op, like, B):
+    """B copies of one gate code, living where `like` lives"""
+    if _is_torch(like):
+        import torch
+        return torch.full((B,), int(op), dtype=torch.uint8, device=like.device)
+    return np.full(B, op, dtype=np.uint8)
 
 
 class MultiScheme:
@@ -630,6 +681,23 @@ class MultiScheme:
         if not (mem == mem2 == mem3 == mem4) or tuple(kx.shape) != tuple(ky.shape) or kx.shape[-1] != self.params.lwe_len:
             raise ValueError("ciphertext shape / memory mismatch")
         self._ck(_lib.lib().mkt_multi_gate_batch_ops(self.h, pops, px, py, po, self._batch(kx), mem))
+        return ko
+
+    def gate3(self, op, x, y, z, out=None):
+        return self.gate3_ops(_full_ops(op, x, self._batch(x)), x, y, z, out)
+
+    def gate3_ops(self, ops, x, y, z, out=None):
+        px, mem, kx = _arg(x, np.uint32)
+        py, m1, ky = _arg(y, np.uint32)
+        pz, m2, kz = _arg(z, np.uint32)
+        pops, m3, kops = _arg(ops, np.uint8)
+        if out is None:
+            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
+        po, m4, ko = _arg(out, np.uint32, writable=True)
+        if not (mem == m1 == m2 == m3 == m4) or not (tuple(kx.shape) == tuple(ky.shape) == tuple(kz.shape)) or kx.shape[-1] != self.params.lwe_len \
+                or int(np.prod(kops.shape)) != self._batch(kx):
+            raise ValueError("ciphertext / ops shape / memory mismatch")
+        self._ck(_lib.lib().mkt_multi_gate3_batch_ops(self.h, pops, px, py, pz, po, self._batch(kx), mem))
         return ko
 
     def mux(self, s, a, b, out=None):
@@ -762,6 +830,33 @@ def MUX_composite(s, c1, c2, scheme: Scheme):
         both = scheme.gate(1, np.concatenate([np.atleast_2d(s), np.atleast_2d(ns)]), np.concatenate([np.atleast_2d(c1), np.atleast_2d(c2)]))
     h = both.shape[0] // 2
     return scheme.gate(2, both[:h], both[h:])      # 1 = AND, 2 = OR (params.py)
+
+
+def MAJ3(c1, c2, c3, scheme: Scheme, out=None):
+    """majority of three in ONE bootstrap (linear part c1 + c2 + c3; not a reference operator: mktfhe.h MKT_MAJ3)"""
+    return scheme.gate3(0, c1, c2, c3, out)
+
+
+def XOR3(c1, c2, c3, scheme: Scheme, out=None):
+    """c1 ^ c2 ^ c3 in ONE bootstrap (linear part -2(c1 + c2 + c3); mktfhe.h MKT_XOR3)"""
+    return scheme.gate3(2, c1, c2, c3, out)
+
+
+def full_adder(a, b, c, scheme: Scheme):
+    """-> (sum, carry) = (XOR3(a, b, c), MAJ3(a, b, c)): ONE gate3_ops call over 2B gates, two bootstraps per adder (the composite of
+    the reference's gates takes five: XOR, XOR, AND, AND, OR)"""
+    on_gpu = _is_torch(a)
+    if on_gpu:
+        import torch
+        cat = lambda u: torch.cat([u.reshape(-1, u.shape[-1])] * 2)      # noqa: E731
+    else:
+        cat = lambda u: np.concatenate([np.reshape(np.asarray(u, dtype=np.uint32), (-1, u.shape[-1]))] * 2)   # noqa: E731
+    x, y, z = cat(a), cat(b), cat(c)
+    B = x.shape[0] // 2
+    ops = np.repeat(np.array([2, 0], dtype=np.uint8), B)                # XOR3_OP for the sums, MAJ3_OP for the carries
+    out = scheme.gate3_ops(torch.from_numpy(ops).to(a.device) if on_gpu else ops, x, y, z)
+    shape = tuple(a.shape)
+    return out[:B].reshape(shape), out[B:].reshape(shape)
 
 
 def NOR(c1, c2, scheme: Scheme, out=None):
