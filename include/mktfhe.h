@@ -149,15 +149,20 @@ int mkt_synchronize(mkt_ctx *ctx);
  * "exact_kany" (MKT_ARITH_EXACT CGGI / LMSS: 1 = the run-time-RLWE-length kernel also at k <= 3),
  * "exact_impl" (MKT_ARITH_EXACT blind rotation of CGGI with RLWE length 1 and of KMS phase 1, and mkt_exact_polymul_batch:
  * 0 = the integer NTT over two 30-bit primes, 1 = Float64 FMA transforms over 16-bit key limbs wherever the proven rounding bound
- * certifies the loaded keys, -1 (default) = 1 for the gate paths; both give the same words).  Results never
- * depend on them.  The environment (MKT_ROT_*, MKT_CCS_*) seeds them once, at mkt_ctx_create; no batch call reads it. */
+ * certifies the loaded keys (for mkt_exact_polymul_batch: the call's operands), -1 (default) = 1 for the gate paths, 0 for
+ * mkt_exact_polymul_batch; both give the same words), "fx_polymul_force" (DIAGNOSTIC: 1 = mkt_exact_polymul_batch under exact_impl = 1
+ * runs the Float64 kernel even where its bound does not certify the operands -- the words are then unproven; tests measure the kernel
+ * at adversarial operands with it).  Results never depend on them, "fx_polymul_force" excepted.  The environment (MKT_ROT_*, MKT_CCS_*) seeds them once, at mkt_ctx_create; no batch call reads it. */
 int mkt_set_option(mkt_ctx *ctx, const char *name, int value);
-/* base name of the blind-rotation kernel the last batch call of this context launched ("" before the first) */
+/* base name of the blind-rotation kernel the last batch call of this context launched ("" before the first); after
+ * mkt_exact_polymul_batch the product kernel that served it: "fx_polymul_kernel" (Float64 pipe) or "exact_polymul_kernel" (integer NTT) */
 const char *mkt_last_kernel_name(const mkt_ctx *ctx);
 /* diagnostics of the Float64-pipe implementation of MKT_ARITH_EXACT: "fx_available" (1: the loaded keys are certified and exact_impl
  * admits it), "fx_bound" (proven bound on |computed - exact| of a rounded product sum for the loaded keys; must stay below 1/2),
- * "fx_kmax" (largest transform-domain magnitude of the loaded key limbs), "fx_last_resid" (largest rounding distance met by the last
- * mkt_exact_polymul_batch under exact_impl = 1) */
+ * "fx_kmax" (largest transform-domain magnitude of the loaded key limbs); of the last mkt_exact_polymul_batch of this context:
+ * "polymul_amax" (max|a_i| over its batch), "fx_polymul_bound" (the proven bound of its Float64 product, evaluated under exact_impl = 1
+ * before the kernel runs: below 0.45 the Float64 pipe served it; -1 = not evaluated), "fx_last_resid" (largest distance |q - round(q)|
+ * met by the Float64 kernel: a DIAGNOSTIC beside the proven bound, not a certificate; 0 when the integer NTT served) */
 int mkt_get_metric(mkt_ctx *ctx, const char *name, double *out);
 
 /* twiddle tables (fft.jl:31-41): which = 0 Psi, 1 Psiinv, 2 roots, 3 rootsinv; M complex each.
@@ -254,9 +259,13 @@ int mkt_transform_fwd_batch(mkt_ctx *ctx, const void *p, double *t, size_t B, in
 int mkt_transform_inv_batch(mkt_ctx *ctx, const double *t, void *p, size_t B, int mem);
 /* gsw.jl:86-96 decompto!: p [B][N] -> digits [B][l][N] ring words (wrapped signed digits) */
 int mkt_decompose_batch(mkt_ctx *ctx, const void *p, void *digits, int l, int logB, size_t B, int mem);
-/* MKT_ARITH_EXACT only: out = a (*) b in Z_{2^W}[X]/(X^N+1), EXACTLY, for a gadget-digit polynomial a (signed words,
- * N * max|a_i| < 2^28) and any ring polynomial b -- the product the reference's Float64 transform approximates
- * (polynomial.jl:99-113); a, b, out: [B][N] ring words */
+/* MKT_ARITH_EXACT only: out = a (*) b in Z_{2^W}[X]/(X^N+1), EXACTLY, for a gadget-digit polynomial a (signed W-bit words,
+ * N * max|a_i| <= 2^28 - 2^15 over the whole batch) and any ring polynomial b -- the product the reference's Float64 transform approximates
+ * (polynomial.jl:99-113); a, b, out: [B][N] ring words.  The bound keeps every true coefficient of a times a centered 32-bit piece of b,
+ * at most N max|a| 2^31, below P / 2 = 2^59 - 6.6e13 (the integer NTT's lift; it would wrap from N max|a| = 268 404 738 on).  max|a_i| is
+ * measured on the device; a batch outside the bound is refused with MKT_ERR_ARG and no words are written.  Under exact_impl = 1 the
+ * Float64 pipe serves the call where its proven error bound for these operands (from max|a_i| and the measured transform maximum of
+ * b's 16-bit limbs) is below 0.45, the integer NTT otherwise -- the same words (mkt_last_kernel_name says which served). */
 int mkt_exact_polymul_batch(mkt_ctx *ctx, const void *a, const void *b, void *out, size_t B, int mem);
 /* scheme.jl:121-146: copy monomial table entry e (1..2N) to host, M complex */
 int mkt_get_monomial(mkt_ctx *ctx, int e, double *out_host);

@@ -41,6 +41,7 @@ struct Tune {
                             // L2 misses -27 %), time -0.3 ... -2.5 % (profiles/r04j_bench_kms2_n1024_map{0,1}_pmc.txt)
     int exact_wide = 1;     // EXACT (integer NTT) KMS phase 1 at l_gsw = 2 and KMS_block phase 1: 1 = the paired-transform kernel / one set of digit transforms per block (default), 0 = the one-at-a-time kernel (reference loop order; tests force both)
     int exact_kany = 0;     // EXACT CGGI / LMSS: 1 = the run-time-RLWE-length kernel (sums in memory) also where the register kernels serve (k <= 3); tests
+    int fx_polymul_force = 0;   // diagnostic: 1 = mkt_exact_polymul_batch under exact_impl = 1 runs the Float64 kernel even where fx_polymul_bound does not certify the operands
     int exact_impl = -1;    // EXACT blind rotation of CGGI (RLWE length 1) and KMS phase 1: 0 = integer NTT over two 30-bit primes (ntt_exact.hip), 1 / -1 = the Float64 pipe (ahead at every measured shape: profiles/r06_fx_shapes.txt)
                             // (fx_exact.hip: FMA transforms over 16-bit key limbs) wherever its error bound certifies the loaded keys (fx_usable), the integer NTT elsewhere
     void from_env() {
@@ -87,7 +88,7 @@ struct KeySet {
     // MKT_ARITH_EXACT on the Float64 pipe (fx_exact.hip), where the shape has the kernel: the engine's own tables and the bootstrapping key as limb transforms
     cplx *d_fx_tab = nullptr;    // fx_om | fx_tw | fx_nat, M each
     cplx *d_fx_brk = nullptr;  size_t fx_brk_party_cplx = 0;   // [party][n][2l][2][W/16][M], scaled by 1 / M
-    unsigned long long *d_fx_stat = nullptr;   // [0] largest |key transform value|^2 over the loaded keys, [1] largest rounding distance of the last fx polymul (bit patterns)
+    unsigned long long *d_fx_stat = nullptr;   // largest |key transform value|^2 over the loaded keys (bit pattern)
     double fx_kmax = 0.0;        // sqrt of [0], read back after every key load
     ~KeySet() {
         int prev = -1;
@@ -124,7 +125,11 @@ struct mkt_ctx {
     std::vector<TimedSpan> spans;
     Tune tune;
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
-    double fx_last_resid = 0.0;         // fx polymul: largest |q - round(q)| of the last call
+    // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
+    unsigned long long *d_pm_stat = nullptr;   // [0] max|a_i| over the batch, [1] largest |limb transform of b|^2, [2] largest |q - round(q)| of the Float64 kernel (bit patterns)
+    double pm_amax = 0.0;               // max|a_i| of the last call
+    double pm_bound = -1.0;             // fx_polymul_bound of the last call (-1: not evaluated -- exact_impl != 1 or no Float64 tables)
+    double fx_last_resid = 0.0;         // largest |q - round(q)| of the last call that ran the Float64 kernel (diagnostic, not a certificate)
 
     const cplx *fx_om() const { return ks->d_fx_tab; }
     const cplx *fx_tw() const { return ks->d_fx_tab + M; }
@@ -552,6 +557,15 @@ bool fx_usable(const mkt_ctx *c) {
     if (2.0 * p.l_gsw * p.N * std::ldexp(1.0, p.logB_gsw - 1) * 32768.0 >= std::ldexp(1.0, 50)) return false;   // the rounding trick holds integers below 2^51
     return fx_bound(c, c->ks->fx_kmax) < 0.45;
 }
+// The same bound for ONE product a (*) limb of mkt_exact_polymul_batch (one term instead of 2l): |a|_2 <= sqrt(N) amax, |limb|_2 <= sqrt(N) 2^15,
+// kmax = the largest |transform value| of b's limbs, measured on the device before the product runs (fx_key_fwd_kernel without output);
+// the multiply chain is one complex product (gamma_m = 5 u).  At the contract edge (N amax = 2^28 - 2^15) with a worst-case b (kmax = N 2^15)
+// it is 0.37 at N = 128 and above 1/2 from N = 256 on -- such calls are served by the integer NTT.
+double fx_polymul_bound(const mkt_ctx *c, double amax, double kmax) {
+    const double u = std::ldexp(1.0, -53), N = (double)c->p.N;
+    const double gt = (3.0 + 5.5 * (c->logM - 2) + 1.5 * 2) * u, gm = 5.0 * u;
+    return (gt + (gt + u) + gm) * N * amax * 32768.0 + gt * std::sqrt(N) * amax * kmax * (1.0 + 1e-6);
+}
 int fx_after_key_load(mkt_ctx *c) {   // the key's largest transform magnitude, for fx_bound
     unsigned long long bits = 0;
     HIPCHK(c, hipMemcpy(&bits, c->ks->d_fx_stat, 8, hipMemcpyDeviceToHost));
@@ -646,8 +660,8 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
             c->ks->fx_brk_party_cplx = per;
             CK(hipMalloc((void **)&c->ks->d_fx_tab, (size_t)3 * M * sizeof(cplx)));
             CK(hipMalloc((void **)&c->ks->d_fx_brk, (size_t)np * per * sizeof(cplx)));
-            CK(hipMalloc((void **)&c->ks->d_fx_stat, 16));
-            CK(hipMemset(c->ks->d_fx_stat, 0, 16));
+            CK(hipMalloc((void **)&c->ks->d_fx_stat, 8));
+            CK(hipMemset(c->ks->d_fx_stat, 0, 8));
             const size_t tb = (size_t)M * sizeof(cplx);
             CK(hipMemcpy(c->ks->d_fx_tab, c->ks->tw.fx_om.data(), tb, hipMemcpyHostToDevice));
             CK(hipMemcpy(c->ks->d_fx_tab + M, c->ks->tw.fx_tw.data(), tb, hipMemcpyHostToDevice));
@@ -669,7 +683,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_fxacc};
+    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_fxacc, c->d_pm_stat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
@@ -738,7 +752,7 @@ int mkt_internal_clone_keys(mkt_ctx *src, mkt_ctx *dst, int no_peer) {
     }
     if (a.d_fx_brk && b.d_fx_brk) {
         if ((r = copy_across(dst, b.d_fx_brk, dd, a.d_fx_brk, sd, (size_t)np * a.fx_brk_party_cplx * cb, no_peer != 0))) return r;
-        if ((r = copy_across(dst, b.d_fx_stat, dd, a.d_fx_stat, sd, 16, no_peer != 0))) return r;
+        if ((r = copy_across(dst, b.d_fx_stat, dd, a.d_fx_stat, sd, 8, no_peer != 0))) return r;
         b.fx_kmax = a.fx_kmax;
     }
     b.brk_loaded = a.brk_loaded; b.ksk_loaded = a.ksk_loaded; b.rlk_loaded = a.rlk_loaded; b.pub_loaded = a.pub_loaded; b.crs_loaded = a.crs_loaded;
@@ -777,6 +791,7 @@ int mkt_set_option(mkt_ctx *c, const char *name, int value) {
     else if (k == "exact_wide") t.exact_wide = value;
     else if (k == "exact_impl") t.exact_impl = value;
     else if (k == "rot_map") t.rot_map = value;
+    else if (k == "fx_polymul_force") t.fx_polymul_force = value;
     else if (k == "exact_kany") { if (t.exact_kany != value) c->ws_gates = 0; t.exact_kany = value; }   // the workspace gains / loses the kernel's scratch at the next call
     else return fail(c, MKT_ERR_ARG, "mkt_set_option: unknown option '" + k + "'");
     return MKT_OK;
@@ -785,7 +800,8 @@ int mkt_set_option(mkt_ctx *c, const char *name, int value) {
 const char *mkt_last_kernel_name(const mkt_ctx *c) { return c ? c->last_rot_kernel : ""; }
 
 // diagnostics of the Float64-pipe EXACT implementation (fx_exact.hip): "fx_available" (1 if the loaded keys are certified and exact_impl admits it),
-// "fx_bound" (proven bound on |computed - exact| of a rounded sum for the loaded keys), "fx_kmax" (largest |key transform value|), "fx_last_resid"
+// "fx_bound" (proven bound on |computed - exact| of a rounded sum for the loaded keys), "fx_kmax" (largest |key transform value|); of the last
+// mkt_exact_polymul_batch on this context: "fx_last_resid" (diagnostic), "polymul_amax" (max|a_i|), "fx_polymul_bound" (fx_polymul_bound, -1 if not evaluated)
 int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     if (!c || !name || !out) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
@@ -793,6 +809,8 @@ int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     else if (k == "fx_bound") *out = c->ks->d_fx_brk ? fx_bound(c, c->ks->fx_kmax) : -1.0;
     else if (k == "fx_kmax") *out = c->ks->fx_kmax;
     else if (k == "fx_last_resid") *out = c->fx_last_resid;
+    else if (k == "polymul_amax") *out = c->pm_amax;
+    else if (k == "fx_polymul_bound") *out = c->pm_bound;
     else return fail(c, MKT_ERR_ARG, "mkt_get_metric: unknown metric '" + k + "'");
     return MKT_OK;
 }
@@ -1298,25 +1316,49 @@ int mkt_decompose_batch(mkt_ctx *c, const void *p, void *digits, int l, int logB
     return sd.out(digits);
 }
 
-// MKT_ARITH_EXACT: out = a (*) b in Z_{2^W}[X]/(X^N + 1), exact, for a gadget-digit polynomial a (signed, N * max|a_i| < 2^28: true coefficients below P / 2) and any b
+// MKT_ARITH_EXACT: out = a (*) b in Z_{2^W}[X]/(X^N + 1), exact, for a signed polynomial a with N * max|a_i| <= 2^28 - 2^15 and any b.
+// Contract: a true coefficient of a times a centered 32-bit piece of b is at most N max|a| 2^31 <= (2^28 - 2^15) 2^31 < P / 2 = 2^59 - 6.6e13, so
+// the integer NTT's centred lift returns it (it would wrap from N max|a| = 268 404 738 on, 30 718 below 2^28); the Float64 pipe's limb sums stay
+// below N max|a| 2^15 <= 2^43, inside its rounding trick.  max|a_i| is measured on the device over the whole batch; a call outside the contract is
+// refused (MKT_ERR_ARG), no words written.  Under exact_impl = 1 the Float64 kernel runs only where fx_polymul_bound certifies the operands
+// (< 0.45, a priori, from max|a_i| and the measured transform maximum of b's limbs); the integer NTT serves the other calls, with the same words.
+// mkt_last_kernel_name names the kernel that served the call.
+constexpr uint64_t POLYMUL_NA_MAX = (1ull << 28) - (1ull << 15);
 int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out, size_t B, int mem) {
     if (!c || !a || !b || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     if (!c->exact) return fail(c, MKT_ERR_UNSUPPORTED, "mkt_exact_polymul_batch needs an MKT_ARITH_EXACT context");
     DevGuard dg(c->device);
+    c->last_rot_kernel = ""; c->pm_amax = 0.0; c->pm_bound = -1.0; c->fx_last_resid = 0.0;
     Staged sa{c}, sb{c}, so{c};
     int r;
     if ((r = sa.in(a, B * poly_bytes(c), mem, true)) || (r = sb.in(b, B * poly_bytes(c), mem, true)) || (r = so.in(out, B * poly_bytes(c), mem, false))) return r;
-    if (c->ks->d_fx_tab && c->tune.exact_impl == 1) {   // the Float64-pipe product (fx_exact.hip), certified per call by its measured rounding distance
-        HIPCHK(c, hipMemsetAsync(c->ks->d_fx_stat + 1, 0, 8, c->stream));
-        { Timer tm(c, 3); HIPCHK(c, mktd::launch_fx_polymul(c->logM, c->p.W, c->fx_om(), c->fx_tw(), c->fx_nat(), sa.dev, sb.dev, so.dev, B, c->ks->d_fx_stat + 1, c->stream)); }
-        unsigned long long bits = 0;
-        HIPCHK(c, hipMemcpyAsync(&bits, c->ks->d_fx_stat + 1, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        std::memcpy(&c->fx_last_resid, &bits, 8);
-        if (!(c->fx_last_resid < 0.25)) return fail(c, MKT_ERR_UNSUPPORTED, "mkt_exact_polymul_batch (Float64 pipe): a rounding distance of 1/4 or more -- operands beyond what 16-bit limbs certify; use exact_impl = 0");
-        return so.out(out);
+    if (!c->d_pm_stat) HIPCHK(c, hipMalloc((void **)&c->d_pm_stat, 3 * sizeof(unsigned long long)));
+    const bool fx = c->ks->d_fx_tab && c->tune.exact_impl == 1;
+    unsigned long long st[2] = {0, 0};
+    HIPCHK(c, hipMemsetAsync(c->d_pm_stat, 0, 3 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, mktd::launch_exact_amax(c->p.W, sa.dev, B * (size_t)c->p.N, c->d_pm_stat, c->stream));
+    if (fx) HIPCHK(c, mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), sb.dev, nullptr, B, c->d_pm_stat + 1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st, c->d_pm_stat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pm_amax = (double)st[0];
+    if (st[0] > POLYMUL_NA_MAX / (uint64_t)c->p.N)
+        return fail(c, MKT_ERR_ARG, "mkt_exact_polymul_batch: max|a_i| = " + std::to_string(st[0]) + " at N = " + std::to_string(c->p.N) +
+                                    " is outside the contract N * max|a_i| <= 2^28 - 2^15 (max|a_i| <= " + std::to_string(POLYMUL_NA_MAX / (uint64_t)c->p.N) + ")");
+    if (fx) {
+        double k2; std::memcpy(&k2, &st[1], 8);
+        c->pm_bound = fx_polymul_bound(c, (double)st[0], std::sqrt(k2));
+        if (c->pm_bound < 0.45 || c->tune.fx_polymul_force) {   // the Float64-pipe product (fx_exact.hip)
+            { Timer tm(c, 3); HIPCHK(c, mktd::launch_fx_polymul(c->logM, c->p.W, c->fx_om(), c->fx_tw(), c->fx_nat(), sa.dev, sb.dev, so.dev, B, c->d_pm_stat + 2, c->stream)); }
+            unsigned long long bits = 0;
+            HIPCHK(c, hipMemcpyAsync(&bits, c->d_pm_stat + 2, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            std::memcpy(&c->fx_last_resid, &bits, 8);
+            c->last_rot_kernel = "fx_polymul_kernel";
+            return so.out(out);
+        }
     }
     { Timer tm(c, 3); HIPCHK(c, mktd::launch_exact_polymul(c->logN, c->p.W, c->d_ntt, sa.dev, sb.dev, so.dev, B, c->stream)); }
+    c->last_rot_kernel = "exact_polymul_kernel";
     return so.out(out);
 }
 

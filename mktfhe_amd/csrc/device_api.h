@@ -190,6 +190,8 @@ struct ExactCcsHostArgs {
 };
 hipError_t launch_exact_ccs(int logN, const uint64_t *tab, const ExactCcsHostArgs &a, size_t B, hipStream_t s);
 hipError_t launch_exact_polymul(int logN, int W, const uint64_t *tab, const void *a, const void *b, void *out, size_t B, hipStream_t s);
+// largest |a_i| over n signed W-bit ring words (atomicMax into *amax, which the caller zeroes): the operand measure of mkt_exact_polymul_batch
+hipError_t launch_exact_amax(int W, const void *a, size_t n, unsigned long long *amax, hipStream_t s);
 
 // MKT_ARITH_EXACT on the Float64 pipe (fx_exact.hip): exact products from FMA complex transforms over 16-bit key limbs.
 // Tables (host_internal.h Twiddles::fx_*): om = cyclic forward twiddles by block, twist = rho^j, nat = inverse twiddles by position.
@@ -208,7 +210,7 @@ struct FxRotArgs {
     int split;                // workgroups per launch: 0 = one chip-fill, -1 = everything in one launch (fx_exact.hip launch_fx_blindrotate)
 };
 bool fx_supported(int logM, int W, int l);
-hipError_t launch_fx_key_fwd(int logM, int W, const cplx *om, const cplx *twist, const void *p, cplx *out, size_t npolys, unsigned long long *kmax, hipStream_t s);   // out [npolys][W/16][M]; kmax: largest |transform value|^2 (bit pattern, atomicMax) or NULL
+hipError_t launch_fx_key_fwd(int logM, int W, const cplx *om, const cplx *twist, const void *p, cplx *out, size_t npolys, unsigned long long *kmax, hipStream_t s);   // out [npolys][W/16][M] or NULL (measure only); kmax: largest |transform value|^2 (bit pattern, atomicMax) or NULL
 hipError_t launch_fx_polymul(int logM, int W, const cplx *om, const cplx *twist, const cplx *nat, const void *a, const void *b, void *out, size_t B, unsigned long long *resid, hipStream_t s);
 hipError_t launch_fx_blindrotate(int logM, int W, const FxRotArgs &a, size_t nrot, hipStream_t s);
 

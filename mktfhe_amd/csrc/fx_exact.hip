@@ -174,7 +174,8 @@ __device__ __forceinline__ uint64_t round_bits(double q) { return (uint64_t)__do
 // -------------------------------------------------------------------------------------------------------------------
 // Key pre-transform: NP coefficient-form ring polynomials -> NL limb transforms each, scaled by 1 / M, device point order
 // (fft_device.h dev_pos order 1).  kmax: the largest |transform value|^2 of the launch (a positive double as its bit pattern,
-// atomicMax): what the host's error bound takes for the key (context.cpp fx_bound).
+// atomicMax): what the host's error bound takes for the key (context.cpp fx_bound).  out = NULL: measure only (the ring operand of
+// mkt_exact_polymul_batch, whose bound fx_polymul_bound is evaluated before the product runs).
 // -------------------------------------------------------------------------------------------------------------------
 template <int LOGM, typename WORD>
 __global__ __launch_bounds__((Plan<LOGM, FLR>::NT)) void fx_key_fwd_kernel(const cplx *__restrict__ om, const cplx *__restrict__ twist, const WORD *__restrict__ p,
@@ -199,11 +200,11 @@ __global__ __launch_bounds__((Plan<LOGM, FLR>::NT)) void fx_key_fwd_kernel(const
             }
             __syncthreads();
             fx_forward<LOGM, 1>(z, om, lds, t, lx);
-            cplx *o = out + (b * NL + h) * (size_t)M;
+            cplx *o = out ? out + (b * NL + h) * (size_t)M : nullptr;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 cplx v; v.re = z[0][e].re * (1.0 / M); v.im = z[0][e].im * (1.0 / M);
-                o[dev_pos(1, t * 4 + e, NT)] = v;
+                if (out) o[dev_pos(1, t * 4 + e, NT)] = v;
                 mx = fmax(mx, fma_(z[0][e].re, z[0][e].re, z[0][e].im * z[0][e].im));   // unscaled: |K_r|^2
             }
         }
@@ -217,8 +218,8 @@ __global__ __launch_bounds__((Plan<LOGM, FLR>::NT)) void fx_key_fwd_kernel(const
 
 // -------------------------------------------------------------------------------------------------------------------
 // Exact negacyclic product out = a (*) b mod 2^W of a digit polynomial a (|a_i| <= amax) and a ring polynomial b, transform level
-// (tests; the FX implementation of mkt_exact_polymul_batch).  resid: the largest distance |q - round(q)| met (bit pattern,
-// atomicMax) -- the measured counterpart of the proven bound.
+// (tests; the FX implementation of mkt_exact_polymul_batch, run where fx_polymul_bound certifies the operands).  resid: the largest
+// distance |q - round(q)| met (bit pattern, atomicMax) -- a diagnostic beside the proven bound, not a certificate.
 // -------------------------------------------------------------------------------------------------------------------
 template <int LOGM, typename WORD>
 __global__ __launch_bounds__((Plan<LOGM, FLR>::NT)) void fx_polymul_kernel(const cplx *__restrict__ om, const cplx *__restrict__ twist, const cplx *__restrict__ nat,

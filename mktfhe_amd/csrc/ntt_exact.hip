@@ -472,6 +472,22 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_polymul_kernel(cons
     }
 }
 
+// largest |a_i| over n ring words read as SIGNED W-bit integers (|-2^(W-1)| = 2^(W-1) as an unsigned 64-bit value), atomicMax into *amax:
+// the operand bound mkt_exact_polymul_batch checks against its contract before either implementation runs
+template <typename WORD>
+__global__ __launch_bounds__(256) void exact_amax_kernel(const WORD *__restrict__ a, size_t n, unsigned long long *__restrict__ amax) {
+    typedef typename WordTraits<WORD>::S SW;
+    unsigned long long m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const SW v = (SW)a[i];
+        const unsigned long long mag = v < 0 ? 0ull - (unsigned long long)(int64_t)v : (unsigned long long)v;
+        m = m > mag ? m : mag;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(m, d); m = m > o ? m : o; }
+    if ((threadIdx.x & 63) == 0) atomicMax(amax, m);
+}
+
 
 #endif  // unit 0
 
@@ -1568,6 +1584,14 @@ hipError_t launch_exact_polymul(int logN, int W, const uint64_t *tab, const void
         else { hipError_t e = ntt_set_lds(exact_polymul_kernel<LN, uint32_t>, lds); if (e != hipSuccess) return e;
             hipLaunchKernelGGL((exact_polymul_kernel<LN, uint32_t>), dim3(grid), dim3(1 << (LN - NLR)), lds, s, tb, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, B); }
     });
+    return hipGetLastError();
+}
+hipError_t launch_exact_amax(int W, const void *a, size_t n, unsigned long long *amax, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const size_t blocks = (n + 255) / 256;
+    const int grid = (int)(blocks < 1024 ? blocks : 1024);
+    if (W == 64) hipLaunchKernelGGL((exact_amax_kernel<uint64_t>), dim3(grid), dim3(256), 0, s, (const uint64_t *)a, n, amax);
+    else hipLaunchKernelGGL((exact_amax_kernel<uint32_t>), dim3(grid), dim3(256), 0, s, (const uint32_t *)a, n, amax);
     return hipGetLastError();
 }
 

@@ -311,13 +311,14 @@ class Scheme:
         self._ck(_lib.lib().mkt_set_option(self.h, name.encode(), int(value)))
 
     def get_metric(self, name):
-        """diagnostics of the Float64-pipe EXACT implementation (mkt_get_metric): "fx_available", "fx_bound", "fx_kmax", "fx_last_resid" """
+        """diagnostics of the Float64-pipe EXACT implementation (mkt_get_metric): "fx_available", "fx_bound", "fx_kmax"; of the last exact_polymul:
+        "polymul_amax", "fx_polymul_bound" (-1: not evaluated), "fx_last_resid" (a diagnostic, not a certificate)"""
         v = C.c_double(0.0)
         self._ck(_lib.lib().mkt_get_metric(self.h, name.encode(), C.byref(v)))
         return v.value
 
     def last_kernel_name(self):
-        """base name of the blind-rotation kernel the last batch call launched"""
+        """base name of the blind-rotation kernel the last batch call launched (after exact_polymul: the product kernel that served it)"""
         return (_lib.lib().mkt_last_kernel_name(self.h) or b"").decode()
 
     # -- tables (tests)
@@ -541,14 +542,26 @@ class Scheme:
         self._ck(_lib.lib().mkt_transform_inv_batch(self.h, pt, po, self._batch(kt), mem))
         return ko
 
-    def exact_polymul(self, a, b):
-        """MKT_ARITH_EXACT contexts: a (*) b mod (X^N + 1, 2^W), exactly, for digit polynomials a (signed, N * max|a| < 2^28) and ring
-        polynomials b; host arrays (..., N)"""
-        aa = np.ascontiguousarray(a, dtype=self.params.ring_dtype)
-        bb = np.ascontiguousarray(b, dtype=self.params.ring_dtype)
-        out = np.empty_like(aa)
-        self._ck(_lib.lib().mkt_exact_polymul_batch(self.h, _np_ptr(aa), _np_ptr(bb), _np_ptr(out), self._batch(aa), MEM_HOST))
-        return out
+    def exact_polymul(self, a, b, out=None):
+        """MKT_ARITH_EXACT contexts: a (*) b mod (X^N + 1, 2^W), exactly, for digit polynomials a (signed W-bit words,
+        N * max|a_i| <= 2^28 - 2^15 over the batch: outside it the call raises MktError and writes nothing) and ring polynomials b;
+        (..., N) numpy arrays, or GPU tensors of the ring's word size.  Under exact_impl = 1 the Float64 pipe serves the call where its
+        proven bound certifies the operands, the integer NTT otherwise (same words; last_kernel_name() says which)"""
+        pa, mem, ka = _arg(a, self.params.ring_dtype, scheme=self)
+        pb, memb, kb = _arg(b, self.params.ring_dtype, scheme=self)
+        if memb != mem or tuple(kb.shape) != tuple(ka.shape):
+            raise ValueError("a and b must have the same shape and live in the same memory")
+        if out is None:
+            if mem == MEM_DEVICE:
+                import torch
+                out = torch.empty_like(ka)
+            else:
+                out = np.empty_like(ka)
+        po, memo, ko = _arg(out, self.params.ring_dtype, writable=True, scheme=self)
+        if memo != mem or tuple(ko.shape) != tuple(ka.shape):
+            raise ValueError("out must match a in shape and memory")
+        self._ck(_lib.lib().mkt_exact_polymul_batch(self.h, pa, pb, po, self._batch(ka), mem))
+        return ko
 
     def decompose(self, p, l, logB):
         a = np.ascontiguousarray(p, dtype=self.params.ring_dtype)

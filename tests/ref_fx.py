@@ -102,3 +102,16 @@ def key_max(keys, W):
     N = len(keys[0])
     om, tw = tables(N)
     return max(float(np.abs(fx_transform(lb.astype(np.float64), om, tw)).max()) for k in keys for lb in limbs_of(k, W))
+
+
+def polymul_bound(N, amax, kmax):
+    """context.cpp fx_polymul_bound, restated: the same bound for ONE product a (*) limb of mkt_exact_polymul_batch (one term instead of 2l),
+    |a|_2 <= sqrt(N) amax, |limb|_2 <= sqrt(N) 2^15, kmax = the largest transform magnitude of b's limbs, one complex product (gamma_m = 5 u)"""
+    u, logM = 2.0 ** -53, int(math.log2(N)) - 1
+    gt = (3.0 + 5.5 * (logM - 2) + 1.5 * 2) * u
+    gm = 5.0 * u
+    return (gt + (gt + u) + gm) * N * amax * 32768.0 + gt * math.sqrt(N) * amax * kmax
+
+
+# the operand contract of mkt_exact_polymul_batch (include/mktfhe.h): N * max|a_i| <= POLYMUL_NA_MAX
+POLYMUL_NA_MAX = 2 ** 28 - 2 ** 15

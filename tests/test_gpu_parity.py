@@ -1031,16 +1031,135 @@ def test_exact_mode_integer_ntt(require_gpu, N, W):
     ex.close()
 
 
+POLYMUL_NA_MAX = 2 ** 28 - 2 ** 15       # the operand contract of mkt_exact_polymul_batch: N * max|a_i| <= POLYMUL_NA_MAX
+
+
 def test_exact_products_at_the_modulus_edge(require_gpu):
-    """The largest product the two-prime modulus admits: N = 4096, every digit -2^15, every centered 32-bit piece -2^31, so that
-    coefficient N - 1 of a piece product is 4096 * 2^46 = 2^58 (P / 2 = 2^58.9998) -- and the mirrored signs.  Exact, i.e. equal to
-    the oracle's schoolbook product mod 2^64 (the lazy ranges of the transforms and the Garner lift at their far end)."""
+    """The largest product the contract admits on the two-prime modulus: N = 4096, every digit -(2^28 - 2^15) / N = -65528, every centered
+    32-bit piece -2^31, so that coefficient N - 1 of a piece product is (2^28 - 2^15) 2^31 = 2^58.99989 (P / 2 = 2^58.99983 ... the lift wraps from
+    N max|a| = 268 404 738 on) -- and the mirrored signs; also the half-way products at |a| = 2^15 (2^58).  Exact, i.e. equal to the oracle's
+    schoolbook product mod 2^64 (the lazy ranges of the transforms and the Garner lift at their far end)."""
     p = mk.CGGIparam.scaled(n=8, N=4096, W=64)
     ex = mk.Scheme(p, arith=mk.ARITH_EXACT)
-    for sa, sb in ((-(1 << 15), 0x8000000080000000), ((1 << 15) - 1, 0x8000000080000000), (-(1 << 15), 0x7FFFFFFF7FFFFFFF)):
+    ex.set_option("exact_impl", 0)
+    edge = POLYMUL_NA_MAX // 4096
+    assert edge == 65528
+    for sa, sb in ((-edge, 0x8000000080000000), (edge, 0x8000000080000000), (-edge, 0x7FFFFFFF7FFFFFFF), (edge, 0x7FFFFFFF7FFFFFFF),
+                   (-(1 << 15), 0x8000000080000000), ((1 << 15) - 1, 0x8000000080000000), (-(1 << 15), 0x7FFFFFFF7FFFFFFF)):
         aw = np.full((1, 4096), sa, dtype=np.int64).astype(np.uint64)
         bw = np.full((1, 4096), sb, dtype=np.uint64)
         assert np.array_equal(ex.exact_polymul(aw, bw)[0].astype(np.uint64), O.negacyclic(aw[0], bw[0], 64)), (sa, hex(sb))
+        assert ex.last_kernel_name() == "exact_polymul_kernel" and ex.get_metric("polymul_amax") == abs(sa)
+    ex.close()
+
+
+def _edge_rows(N, amax, rng):
+    """digit polynomials with every a_i at +-amax: all -amax, all +amax, alternating and random signs"""
+    alt = np.where(np.arange(N) & 1, -amax, amax)
+    return np.stack([np.full(N, -amax), np.full(N, amax), alt, rng.choice([-amax, amax], N)]).astype(np.int64)
+
+
+def _ring(x, W):
+    return x.astype(np.uint64) if W == 64 else (x & 0xFFFFFFFF).astype(np.uint32)
+
+
+def _check_products(got, aw, bw, W, what):
+    for r in range(aw.shape[0]):
+        ref = O.negacyclic(aw[r].astype(np.uint64), bw[r].astype(np.uint64), W)
+        assert np.array_equal(got[r].astype(np.uint64), ref), (what, r, np.flatnonzero(got[r].astype(np.uint64) != ref)[:4])
+
+
+@pytest.mark.parametrize("N", [32, 64, 128, 256, 512, 1024, 2048, 4096])
+@pytest.mark.parametrize("W", [32, 64])
+def test_exact_products_at_the_contract_edge(require_gpu, N, W):
+    """mkt_exact_polymul_batch at the edge of its contract, N max|a_i| = 2^28 - 2^15, on both implementations (exact_impl 0: integer NTT;
+    1: the Float64 pipe where its a-priori bound certifies the operands -- N >= 128 has its tables -- the integer NTT otherwise): every a_i
+    at +-max with one sign, both signs alternating and random signs, against b = all 0x80..., all 0x7F... and edge_words.  Word-exact at
+    every coefficient against the big-integer schoolbook product; the kernel that served is the one the reported bound admits."""
+    rng = np.random.default_rng(7 * N + W)
+    p = mk.CGGIparam.scaled(n=8, N=N, W=W)
+    ex = mk.Scheme(p, arith=mk.ARITH_EXACT)
+    amax = POLYMUL_NA_MAX // N
+    aw = _ring(_edge_rows(N, amax, rng), W)
+    bs = {"0x80": np.full((4, N), 0x80000000 if W == 32 else 0x8000000080000000, dtype=np.uint64),
+          "0x7F": np.full((4, N), 0x7FFFFFFF if W == 32 else 0x7FFFFFFF7FFFFFFF, dtype=np.uint64),
+          "edge": np.stack([edge_words(W, N, rng) for _ in range(4)])}
+    for impl in (0, 1):
+        ex.set_option("exact_impl", impl)
+        for name, b in bs.items():
+            bw = b.astype(p.ring_dtype)
+            got = ex.exact_polymul(aw, bw)
+            _check_products(got, aw, bw, W, (impl, name))
+            kern, bound = ex.last_kernel_name(), ex.get_metric("fx_polymul_bound")
+            assert ex.get_metric("polymul_amax") == amax
+            if impl == 0 or N < 128:
+                assert kern == "exact_polymul_kernel" and bound == -1.0, (impl, name, kern, bound)
+                continue
+            assert bound > 0 and kern == ("fx_polymul_kernel" if bound < 0.45 else "exact_polymul_kernel"), (name, kern, bound)
+            if N == 128 or name == "edge":                      # bound 0.37 for any b at N = 128; a random b is certified at every N
+                assert kern == "fx_polymul_kernel", (name, bound)
+            if N >= 1024 and name == "0x80":                    # one sign throughout: not certified, the integer NTT serves
+                assert kern == "exact_polymul_kernel", bound
+            if kern == "fx_polymul_kernel":
+                assert ex.get_metric("fx_last_resid") < bound
+    ex.close()
+
+
+@pytest.mark.parametrize("N,W", [(32, 32), (128, 64), (1024, 32), (4096, 32), (4096, 64)])
+def test_exact_products_past_the_contract_edge(require_gpu, N, W):
+    """One step past the edge (max|a_i| = (2^28 - 2^15) / N + 1) is refused by both implementations -- host and device arrays, also when only
+    the LAST polynomial of the batch has one such coefficient -- with an error that names the bound, and nothing is written.  Before the
+    contract was enforced the integer NTT returned words here (wrong ones from N max|a| = 268 404 738 on: at N = 4096, W = 32, a_i = 65535,
+    b_i = 0x80000000, coefficient N - 1 came back as 1 476 272 129 instead of 0)."""
+    import torch
+    rng = np.random.default_rng(N + 3 * W)
+    p = mk.CGGIparam.scaled(n=8, N=N, W=W)
+    ex = mk.Scheme(p, arith=mk.ARITH_EXACT)
+    amax = POLYMUL_NA_MAX // N
+    tdt = torch.int64 if W == 64 else torch.int32
+    sdt = np.int64 if W == 64 else np.int32
+    full = _ring(np.full((2, N), -(amax + 1), dtype=np.int64), W)
+    last = _ring(np.stack([_edge_rows(N, amax, rng)[2], _edge_rows(N, amax, rng)[3]]), W)
+    last[1, N - 1] = _ring(np.array([amax + 1]), W)[0]          # one coefficient of the last polynomial one past the edge
+    bw = np.full((2, N), 0x80000000 if W == 32 else 0x8000000080000000, dtype=np.uint64).astype(p.ring_dtype)
+    for impl in (0, 1):
+        ex.set_option("exact_impl", impl)
+        for name, aw in (("full", full), ("last", last)):
+            out = np.full_like(aw, 0x5A)
+            with pytest.raises(mk.MktError, match=r"2\^28 - 2\^15"):
+                ex.exact_polymul(aw, bw, out=out)
+            assert (out == 0x5A).all() and ex.get_metric("polymul_amax") == amax + 1, (impl, name)
+            ta, tb = torch.from_numpy(aw.view(sdt)).cuda(), torch.from_numpy(bw.view(sdt)).cuda()
+            to = torch.full((2, N), 0x5A, dtype=tdt, device="cuda")
+            with pytest.raises(mk.MktError, match=r"2\^28 - 2\^15"):
+                ex.exact_polymul(ta, tb, out=to)
+            torch.cuda.synchronize()
+            assert bool((to == 0x5A).all()) and ex.get_metric("polymul_amax") == amax + 1, (impl, name, "device")
+        # the same batch with the offending coefficient back at the edge: served, exact, on the host and on the device
+        ok = last.copy()
+        ok[1, N - 1] = _ring(np.array([amax]), W)[0]
+        _check_products(ex.exact_polymul(ok, bw), ok, bw, W, (impl, "edge"))
+        got = ex.exact_polymul(torch.from_numpy(ok.view(sdt)).cuda(), torch.from_numpy(bw.view(sdt)).cuda())
+        _check_products(got.cpu().numpy().view(p.ring_dtype), ok, bw, W, (impl, "edge, device"))
+    ex.close()
+
+
+@pytest.mark.parametrize("W", [32, 64])
+def test_exact_products_refuse_full_word_digits(require_gpu, W):
+    """|a_i| = 2^31 (a word far outside the contract: a Float64-pipe sum near 2^58, where every double is an integer and the measured rounding
+    distance is identically 0) is refused on both implementations -- a per-call check of that distance would return it with status OK.
+    So is the most negative word (-2^(W-1), whose magnitude is read as 2^(W-1))."""
+    rng = np.random.default_rng(W)
+    p = mk.CGGIparam.scaled(n=8, N=1024, W=W)
+    ex = mk.Scheme(p, arith=mk.ARITH_EXACT)
+    bw = np.stack([edge_words(W, 1024, rng) for _ in range(2)]).astype(p.ring_dtype)
+    rows = {"2^31": rng.choice([-(1 << 31), (1 << 31) - 1], (2, 1024)).astype(np.int64), "typemin": np.full((2, 1024), -(1 << (W - 1)), dtype=np.int64)}
+    for impl in (1, 0):
+        ex.set_option("exact_impl", impl)
+        for name, a in rows.items():
+            with pytest.raises(mk.MktError, match=r"2\^28 - 2\^15"):
+                ex.exact_polymul(_ring(a, W), bw)
+            assert ex.get_metric("polymul_amax") == 2.0 ** (31 if name == "2^31" else W - 1), (impl, name)
     ex.close()
 
 

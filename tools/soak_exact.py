@@ -56,8 +56,8 @@ for N in (32, 64, 128, 256):
                         bad += 1; print('polymul mismatch', N, W, it, logB, b)
         ex.close()
         print('N', N, 'W', W, 'done, mismatches so far', bad, flush=True)
-# the worst case the modulus admits: N = 4096, every digit -2^15, every centered piece -2^31 -> coefficient N - 1 of each piece product
-# is 4096 * 2^46 = 2^58 (P / 2 = 2^58.9998); also the mirrored signs
+# large products at N = 4096: every digit -2^15, every centered piece -2^31 -> coefficient N - 1 of each piece product is 4096 * 2^46 = 2^58
+# (P / 2 = 2^58.9998; the contract edge, |a| = 65528, is twice as far: tests/test_gpu_parity.py test_exact_products_at_the_modulus_edge); also the mirrored signs
 p = mk.CGGIparam.scaled(n=8, N=4096, W=64)
 ex = mk.Scheme(p, arith=mk.ARITH_EXACT)
 for sa, sb in ((-(1 << 15), 0x8000000080000000), ((1 << 15) - 1, 0x8000000080000000), (-(1 << 15), 0x7FFFFFFF7FFFFFFF)):
