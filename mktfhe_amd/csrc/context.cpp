@@ -781,6 +781,9 @@ int mkt_set_option(mkt_ctx *c, const char *name, int value) {
     if (!c || !name) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
     Tune &t = c->tune;
+    // selectors with a fixed set of values refuse the others here (a call would otherwise fail late, inside a gate, or run nothing)
+    if ((k == "rot_variant" && value != 0 && value != 21 && value != 22) || (k == "rot_map" && value != 0 && value != 1))
+        return fail(c, MKT_ERR_ARG, "mkt_set_option: " + k + " = " + std::to_string(value) + " is not one of " + (k == "rot_map" ? "0, 1" : "0, 21, 22"));
     if (k == "rot_variant") t.rot_variant = value;
     else if (k == "rot_stagger") t.rot_stagger = value;
     else if (k == "rot_split") t.rot_split = value;

@@ -1873,7 +1873,7 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
     // KMS2partyblock 1024 gates 2.73 -> 2.35 ms; the unbalanced variant is fastest at 1024 at every batch size (tools/ks_blocks_sweep*.sh)
     if (a.balanced) target_blocks = a.mk ? 4096 : 8192;
     const LaunchTuning &lt = launch_tuning();
-    if (lt.ks_g > 0) q.G = lt.ks_g;
+    if (lt.ks_g == 8 || lt.ks_g == 16) q.G = lt.ks_g;   // launch_keyswitch has the 8-, 16- and 32-wide tiles only: any other MKT_KS_G keeps 32
     if (lt.ks_blocks > 0) target_blocks = lt.ks_blocks;
     q.pair = lt.ks_pair != 0 && a.logD == 2 && a.f % 2 == 0 && q.G == 32 && have_scratch;
     // (measured and left out: eight waves of 16 ciphertexts around one table -- half the slabs; KMS k=2 0.94 vs 0.79 ms, CGGIparam 0.51 vs 0.52)

@@ -306,8 +306,11 @@ class Scheme:
         return st.value or 0
 
     def set_option(self, name, value):
-        """kernel-selection switch (mkt_set_option): "rot_wide", "rot_blkg", "ccs_pipe", ... -- results never depend on them;
-        the parity tests force every kernel variant through this"""
+        """kernel-selection switch (mkt_set_option; INTEGRATION.md "Runtime switches"): "rot_wide", "rot_blkg", "rot_variant",
+        "rot_map", "rot_split", "rot_stagger", "ccs_stagger", "ccs_pipe", "exact_impl", "exact_wide", "exact_kany", "fx_polymul_force".
+        Results never depend on them (tests/test_gpu_switches.py forces each one).  An unknown name, rot_variant
+        outside {0, 21, 22} or rot_map outside {0, 1} raises MktError and leaves the context as it was.  The launcher-level
+        MKT_KS_* / MKT_FFT_* / MKT_NTT_GRID switches are environment variables read once per process, not options."""
         self._ck(_lib.lib().mkt_set_option(self.h, name.encode(), int(value)))
 
     def get_metric(self, name):
