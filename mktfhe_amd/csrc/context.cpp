@@ -1003,9 +1003,9 @@ int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
 
 // ---- batched hot path ----
 
-// the gate entry points share one body: `op` for the whole batch or per-gate `ops`; operands in batch order (x, y: [B][len]) or
-// picked by row index from a pool (x = y = pool, [pool_rows][len])
-static int gate_impl(mkt_ctx *c, int op, const uint8_t *ops, const uint32_t *x, const uint32_t *y, size_t rows_xy, const uint32_t *ix, const uint32_t *iy,
+// the gate entry points share one body: `op` for the whole batch or per-gate `ops`; `arity` (2 or 3) operands in batch order (v[i]:
+// [B][len]) or picked by row index iv[i] from a pool (v[0] = pool, [rows][len]); arity 3 = the three-input linear part in one bootstrap
+static int gate_impl(mkt_ctx *c, int arity, int op, const uint8_t *ops, const uint32_t *const *v, size_t rows, const uint32_t *const *iv,
                      uint32_t *out, size_t B, int mem) {
     MKT_EXACT_GATE(c);
     int r;
@@ -1013,39 +1013,54 @@ static int gate_impl(mkt_ctx *c, int op, const uint8_t *ops, const uint32_t *x, 
     DevGuard dg(c->device);
     Timer whole(c, 0);
     const size_t len = (size_t)c->sh.lwe_len;
-    const bool pool = ix != nullptr;
-    Staged sx{c}, sy{c}, so{c}, sops{c}, six{c}, siy{c};
-    if ((r = sx.in(x, rows_xy * len * 4, mem, true))) return r;
-    if (pool) sy.dev = sx.dev; else if ((r = sy.in(y, rows_xy * len * 4, mem, true))) return r;
+    const bool pool = iv != nullptr;
+    Staged sv[3]{{c}, {c}, {c}}, so{c}, sops{c}, si[3]{{c}, {c}, {c}};
+    for (int i = 0; i < (pool ? 1 : arity); i++) if ((r = sv[i].in(v[i], rows * len * 4, mem, true))) return r;
     if ((r = so.in(out, B * len * 4, mem, false))) return r;
     if (ops && (r = sops.in(ops, B, mem, true))) return r;
-    if (pool && ((r = six.in(ix, B * 4, mem, true)) || (r = siy.in(iy, B * 4, mem, true)))) return r;
+    for (int i = 0; pool && i < arity; i++) if ((r = si[i].in(iv[i], B * 4, mem, true))) return r;
     for (size_t off = 0; off < B; off += CHUNK_GATES) {
         const size_t nb = std::min(CHUNK_GATES, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
-        const size_t xoff = pool ? 0 : off * len;
-        HIPCHK(c, mktd::launch_gate_linear(op, ops ? (const uint8_t *)sops.dev + off : nullptr, (const uint32_t *)sx.dev + xoff, (const uint32_t *)sy.dev + xoff,
-                                           pool ? (const uint32_t *)six.dev + off : nullptr, pool ? (const uint32_t *)siy.dev + off : nullptr, pool ? rows_xy : 0, c->ws_lin, (int)len, nb, c->stream));
+        const uint8_t *o = ops ? (const uint8_t *)sops.dev + off : nullptr;
+        const uint32_t *d[3] = {}, *di[3] = {};
+        for (int i = 0; i < arity; i++) {
+            d[i] = pool ? (const uint32_t *)sv[0].dev : (const uint32_t *)sv[i].dev + off * len;
+            di[i] = pool ? (const uint32_t *)si[i].dev + off : nullptr;
+        }
+        const size_t prows = pool ? rows : 0;
+        HIPCHK(c, arity == 2 ? mktd::launch_gate_linear(op, o, d[0], d[1], di[0], di[1], prows, c->ws_lin, (int)len, nb, c->stream)
+                             : mktd::launch_gate3_linear(o, d[0], d[1], d[2], di[0], di[1], di[2], prows, c->ws_lin, (int)len, nb, c->stream));
         if ((r = bootstrap_chunk(c, c->ws_lin, (uint32_t *)so.dev + off * len, nb))) return r;
     }
     return so.out(out);
 }
 
+// host arrays only (a device array is not read back): every code's gate (bits 0-2) at most `max_code`, no bit outside `flags` above them
+static bool codes_valid_host(const uint8_t *ops, size_t B, unsigned max_code, unsigned flags) {
+    for (size_t j = 0; j < B; j++) if ((ops[j] & 7u) > max_code || (ops[j] & ~(7u | flags))) return false;
+    return true;
+}
+
+// host arrays only: every entry of the n index arrays idx[i][0 .. B) names a row of the pool
+static bool in_pool_host(const uint32_t *const *idx, int n, size_t B, size_t pool_rows) {
+    for (int i = 0; i < n; i++) for (size_t j = 0; j < B; j++) if (idx[i][j] >= pool_rows) return false;
+    return true;
+}
+
 int mkt_gate_batch(mkt_ctx *c, int op, const uint32_t *x, const uint32_t *y, uint32_t *out, size_t B, int mem) {
     if (!c || !x || !y || !out || !mem_ok(mem) || op < MKT_NAND || op > MKT_NOR) return fail(c, MKT_ERR_ARG, "bad argument");
-    return gate_impl(c, op, nullptr, x, y, B, nullptr, nullptr, out, B, mem);
+    const uint32_t *v[] = {x, y};
+    return gate_impl(c, 2, op, nullptr, v, B, nullptr, out, B, mem);
 }
 
 // a different gate per ciphertext pair -- the shape of the reference's own tests (test/KMS.jl:29-34 draws a random gate per step;
 // gate.jl:1-53) -- in ONE launch sequence: ops[j] = MKT_NAND .. MKT_NOR, optionally | MKT_OP_NOT_X / MKT_OP_NOT_Y
-static bool ops_valid_host(const uint8_t *ops, size_t B) {
-    for (size_t j = 0; j < B; j++) if ((ops[j] & 7) > MKT_NOR || (ops[j] & ~31u)) return false;
-    return true;
-}
 int mkt_gate_batch_ops(mkt_ctx *c, const uint8_t *ops, const uint32_t *x, const uint32_t *y, uint32_t *out, size_t B, int mem) {
     if (!c || !ops || !x || !y || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (mem == MKT_MEM_HOST && !ops_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_ops: unknown gate code");
-    return gate_impl(c, 0, ops, x, y, B, nullptr, nullptr, out, B, mem);
+    if (mem == MKT_MEM_HOST && !codes_valid_host(ops, B, MKT_NOR, MKT_OP_NOT_X | MKT_OP_NOT_Y)) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_ops: unknown gate code");
+    const uint32_t *v[] = {x, y};
+    return gate_impl(c, 2, 0, ops, v, B, nullptr, out, B, mem);
 }
 
 // one circuit level: gate j reads pool[ix[j]] and pool[iy[j]] (rows of [pool_rows][k*n+1]) and writes out[j]; `out` may be a
@@ -1054,64 +1069,33 @@ int mkt_gate_batch_gather(mkt_ctx *c, const uint8_t *ops, const uint32_t *pool, 
                           uint32_t *out, size_t B, int mem) {
     if (!c || !ops || !pool || !ix || !iy || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_gather: gates over an empty pool");     // (the kernel clamps indices into [0, pool_rows): there must be a row to clamp to, in either memory kind)
+    const uint32_t *v[] = {pool}, *iv[] = {ix, iy};
     if (mem == MKT_MEM_HOST) {
-        if (!ops_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_gather: unknown gate code");
-        for (size_t j = 0; j < B; j++) if (ix[j] >= pool_rows || iy[j] >= pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_gather: operand index outside the pool");
+        if (!codes_valid_host(ops, B, MKT_NOR, MKT_OP_NOT_X | MKT_OP_NOT_Y)) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_gather: unknown gate code");
+        if (!in_pool_host(iv, 2, B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_gate_batch_gather: operand index outside the pool");
     }
-    return gate_impl(c, 0, ops, pool, pool, pool_rows, ix, iy, out, B, mem);
+    return gate_impl(c, 2, 0, ops, v, pool_rows, iv, out, B, mem);
 }
 
-// three-input gates in one bootstrap: gate_impl's chunk loop with the three-operand linear part, then bootstrap_chunk (every scheme,
-// both arithmetic modes).  Operands in batch order (x, y, z: [B][len]) or picked by row index from a pool (x = y = z = pool)
-static int gate3_impl(mkt_ctx *c, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, size_t rows_xyz, const uint32_t *ix,
-                      const uint32_t *iy, const uint32_t *iz, uint32_t *out, size_t B, int mem) {
-    MKT_EXACT_GATE(c);
-    int r;
-    if ((r = check_ready(c, true, true))) return r;
-    DevGuard dg(c->device);
-    Timer whole(c, 0);
-    const size_t len = (size_t)c->sh.lwe_len;
-    const bool pool = ix != nullptr;
-    Staged sx{c}, sy{c}, sz{c}, so{c}, sops{c}, six{c}, siy{c}, siz{c};
-    if ((r = sx.in(x, rows_xyz * len * 4, mem, true))) return r;
-    if (pool) sy.dev = sz.dev = sx.dev;
-    else if ((r = sy.in(y, rows_xyz * len * 4, mem, true)) || (r = sz.in(z, rows_xyz * len * 4, mem, true))) return r;
-    if ((r = so.in(out, B * len * 4, mem, false))) return r;
-    if ((r = sops.in(ops, B, mem, true))) return r;
-    if (pool && ((r = six.in(ix, B * 4, mem, true)) || (r = siy.in(iy, B * 4, mem, true)) || (r = siz.in(iz, B * 4, mem, true)))) return r;
-    for (size_t off = 0; off < B; off += CHUNK_GATES) {
-        const size_t nb = std::min(CHUNK_GATES, B - off);
-        if ((r = ensure_workspace(c, nb))) return r;
-        const size_t xoff = pool ? 0 : off * len;
-        HIPCHK(c, mktd::launch_gate3_linear((const uint8_t *)sops.dev + off, (const uint32_t *)sx.dev + xoff, (const uint32_t *)sy.dev + xoff, (const uint32_t *)sz.dev + xoff,
-                                            pool ? (const uint32_t *)six.dev + off : nullptr, pool ? (const uint32_t *)siy.dev + off : nullptr,
-                                            pool ? (const uint32_t *)siz.dev + off : nullptr, pool ? rows_xyz : 0, c->ws_lin, (int)len, nb, c->stream));
-        if ((r = bootstrap_chunk(c, c->ws_lin, (uint32_t *)so.dev + off * len, nb))) return r;
-    }
-    return so.out(out);
-}
-
-static bool ops3_valid_host(const uint8_t *ops, size_t B) {
-    for (size_t j = 0; j < B; j++) if ((ops[j] & 7) > MKT_AE3 || (ops[j] & ~63u)) return false;
-    return true;
-}
-
+// three-input gates in one bootstrap (every scheme, both arithmetic modes): operands in batch order (x, y, z: [B][len]) or picked by
+// row index from a pool
 int mkt_gate3_batch_ops(mkt_ctx *c, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem) {
     if (!c || !ops || !x || !y || !z || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (mem == MKT_MEM_HOST && !ops3_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_ops: unknown gate code");
-    return gate3_impl(c, ops, x, y, z, B, nullptr, nullptr, nullptr, out, B, mem);
+    if (mem == MKT_MEM_HOST && !codes_valid_host(ops, B, MKT_AE3, MKT_OP_NOT_X | MKT_OP_NOT_Y | MKT_OP_NOT_Z)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_ops: unknown gate code");
+    const uint32_t *v[] = {x, y, z};
+    return gate_impl(c, 3, 0, ops, v, B, nullptr, out, B, mem);
 }
 
 int mkt_gate3_batch_gather(mkt_ctx *c, const uint8_t *ops, const uint32_t *pool, size_t pool_rows, const uint32_t *ix, const uint32_t *iy, const uint32_t *iz,
                            uint32_t *out, size_t B, int mem) {
     if (!c || !ops || !pool || !ix || !iy || !iz || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: gates over an empty pool");
+    const uint32_t *v[] = {pool}, *iv[] = {ix, iy, iz};
     if (mem == MKT_MEM_HOST) {
-        if (!ops3_valid_host(ops, B)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: unknown gate code");
-        for (size_t j = 0; j < B; j++)
-            if (ix[j] >= pool_rows || iy[j] >= pool_rows || iz[j] >= pool_rows) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: operand index outside the pool");
+        if (!codes_valid_host(ops, B, MKT_AE3, MKT_OP_NOT_X | MKT_OP_NOT_Y | MKT_OP_NOT_Z)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: unknown gate code");
+        if (!in_pool_host(iv, 3, B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_gate3_batch_gather: operand index outside the pool");
     }
-    return gate3_impl(c, ops, pool, pool, pool, pool_rows, ix, iy, iz, out, B, mem);
+    return gate_impl(c, 3, 0, ops, v, pool_rows, iv, out, B, mem);
 }
 
 // MUX(s, a, b) = s ? a : b with TWO blind rotations and ONE key switch (the reference has no MUX gate, gate.jl:1-57; this is the
@@ -1119,28 +1103,44 @@ int mkt_gate3_batch_gather(mkt_ctx *c, const uint8_t *ops, const uint32_t *pool,
 //   acc = blindrotate!(AND-linear(s, a)) + blindrotate!(AND-linear(NOT! s, b)), + 1/8 at X^0 of acc.b;  out = keyswitch!(acc)
 // Each rotation leaves +-1/8 and at most one of the two ANDs holds, so the sum + 1/8 is +-1/8 again.  A composite of the
 // reference's gates, OR(AND(s, a), AND(NOT s, b)), costs three full bootstraps.
-int mkt_mux_batch(mkt_ctx *c, const uint32_t *sel, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t B, int mem) {
-    if (!c || !sel || !a || !b || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+// Both entry points share one body: operands v = (s, a, b) in batch order ([B][len]), or picked by row index iv[i] from a pool
+// (v[0] = pool, [rows][len]) with the optional per-gate negations not_ab
+static int mux_impl(mkt_ctx *c, const uint32_t *const *v, size_t rows, const uint32_t *const *iv, const uint8_t *not_ab, uint32_t *out, size_t B, int mem) {
     MKT_EXACT_GATE(c);
     int r;
     if ((r = check_ready(c, true, true))) return r;
     DevGuard dg(c->device);
     Timer whole(c, 0);
     const size_t len = (size_t)c->sh.lwe_len, words = (size_t)(1 + c->sh.kacc) * c->p.N;
-    Staged ss{c}, sa{c}, sb{c}, so{c};
-    if ((r = ss.in(sel, B * len * 4, mem, true)) || (r = sa.in(a, B * len * 4, mem, true)) || (r = sb.in(b, B * len * 4, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
+    const bool pool = iv != nullptr;
+    Staged sv[3]{{c}, {c}, {c}}, si[3]{{c}, {c}, {c}}, so{c}, sf{c};
+    for (int i = 0; i < (pool ? 1 : 3); i++) if ((r = sv[i].in(v[i], rows * len * 4, mem, true))) return r;
+    for (int i = 0; pool && i < 3; i++) if ((r = si[i].in(iv[i], B * 4, mem, true))) return r;
+    if ((r = so.in(out, B * len * 4, mem, false))) return r;
+    if (not_ab && (r = sf.in(not_ab, B, mem, true))) return r;
     constexpr size_t HALF = CHUNK_GATES / 2;                  // two rotations per gate share the workspace chunk
     for (size_t off = 0; off < B; off += HALF) {
         const size_t nb = std::min(HALF, B - off);
         if ((r = ensure_workspace(c, 2 * nb))) return r;
-        const uint32_t *ps = (const uint32_t *)ss.dev + off * len;
-        HIPCHK(c, mktd::launch_gate_linear(MKT_AND, nullptr, ps, (const uint32_t *)sa.dev + off * len, nullptr, nullptr, 0, c->ws_lin, (int)len, nb, c->stream));
-        HIPCHK(c, mktd::launch_gate_linear(MKT_AND | MKT_OP_NOT_X, nullptr, ps, (const uint32_t *)sb.dev + off * len, nullptr, nullptr, 0, c->ws_lin + nb * len, (int)len, nb, c->stream));
+        if (pool) {
+            HIPCHK(c, mktd::launch_mux_linear((const uint32_t *)sv[0].dev, rows, (const uint32_t *)si[0].dev + off, (const uint32_t *)si[1].dev + off, (const uint32_t *)si[2].dev + off,
+                                              not_ab ? (const uint8_t *)sf.dev + off : nullptr, c->ws_lin, (int)len, nb, c->stream));
+        } else {
+            const uint32_t *ps = (const uint32_t *)sv[0].dev + off * len;
+            HIPCHK(c, mktd::launch_gate_linear(MKT_AND, nullptr, ps, (const uint32_t *)sv[1].dev + off * len, nullptr, nullptr, 0, c->ws_lin, (int)len, nb, c->stream));
+            HIPCHK(c, mktd::launch_gate_linear(MKT_AND | MKT_OP_NOT_X, nullptr, ps, (const uint32_t *)sv[2].dev + off * len, nullptr, nullptr, 0, c->ws_lin + nb * len, (int)len, nb, c->stream));
+        }
         if ((r = rotate_chunk(c, c->ws_lin, 2 * nb))) return r;
         HIPCHK(c, mktd::launch_mux_combine(c->p.W, c->ws_acc, nb, words, c->stream));
         if ((r = do_keyswitch(c, c->ws_acc, (uint32_t *)so.dev + off * len, nb))) return r;
     }
     return so.out(out);
+}
+
+int mkt_mux_batch(mkt_ctx *c, const uint32_t *sel, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t B, int mem) {
+    if (!c || !sel || !a || !b || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    const uint32_t *v[] = {sel, a, b};
+    return mux_impl(c, v, B, nullptr, nullptr, out, B, mem);
 }
 
 // the same MUX with its operands picked by row index from a ciphertext pool (a circuit level of MUX gates): gate j = MUX(pool[is[j]],
@@ -1151,29 +1151,10 @@ int mkt_mux_batch_gather(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, con
                          uint32_t *out, size_t B, int mem) {
     if (!c || !pool || !is || !ia || !ib || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_mux_batch_gather: gates over an empty pool");
-    if (mem == MKT_MEM_HOST)
-        for (size_t j = 0; j < B; j++) if (is[j] >= pool_rows || ia[j] >= pool_rows || ib[j] >= pool_rows || (not_ab && (not_ab[j] & ~3u))) return fail(c, MKT_ERR_ARG, "mkt_mux_batch_gather: operand index outside the pool, or unknown flag");
-    MKT_EXACT_GATE(c);
-    int r;
-    if ((r = check_ready(c, true, true))) return r;
-    DevGuard dg(c->device);
-    Timer whole(c, 0);
-    const size_t len = (size_t)c->sh.lwe_len, words = (size_t)(1 + c->sh.kacc) * c->p.N;
-    Staged sp{c}, ss{c}, sa{c}, sb{c}, so{c}, sf{c};
-    if ((r = sp.in(pool, pool_rows * len * 4, mem, true)) || (r = ss.in(is, B * 4, mem, true)) || (r = sa.in(ia, B * 4, mem, true)) || (r = sb.in(ib, B * 4, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
-    if (not_ab && (r = sf.in(not_ab, B, mem, true))) return r;
-    constexpr size_t HALF = CHUNK_GATES / 2;
-    for (size_t off = 0; off < B; off += HALF) {
-        const size_t nb = std::min(HALF, B - off);
-        if ((r = ensure_workspace(c, 2 * nb))) return r;
-        const uint32_t *pp = (const uint32_t *)sp.dev, *js = (const uint32_t *)ss.dev + off;
-        const uint8_t *fl = not_ab ? (const uint8_t *)sf.dev + off : nullptr;
-        HIPCHK(c, mktd::launch_mux_linear(pp, pool_rows, js, (const uint32_t *)sa.dev + off, (const uint32_t *)sb.dev + off, fl, c->ws_lin, (int)len, nb, c->stream));
-        if ((r = rotate_chunk(c, c->ws_lin, 2 * nb))) return r;
-        HIPCHK(c, mktd::launch_mux_combine(c->p.W, c->ws_acc, nb, words, c->stream));
-        if ((r = do_keyswitch(c, c->ws_acc, (uint32_t *)so.dev + off * len, nb))) return r;
-    }
-    return so.out(out);
+    const uint32_t *v[] = {pool}, *iv[] = {is, ia, ib};
+    if (mem == MKT_MEM_HOST && (!in_pool_host(iv, 3, B, pool_rows) || (not_ab && !codes_valid_host(not_ab, B, 3, 0))))   // not_ab[j] in 0 .. 3
+        return fail(c, MKT_ERR_ARG, "mkt_mux_batch_gather: operand index outside the pool, or unknown flag");
+    return mux_impl(c, v, pool_rows, iv, not_ab, out, B, mem);
 }
 
 int mkt_not_batch(mkt_ctx *c, uint32_t *x, size_t B, int mem) {

@@ -11,6 +11,7 @@ is a BATCH: a numpy uint32 array (..., k*n+1) in host memory or a torch CUDA int
 holds no arithmetic of its own and raises if the HIP library or a gfx950 GPU is missing.
 """
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -31,15 +32,11 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-def _arg(x, dtype, writable=False, scheme=None):
-    """-> (pointer, mem kind, keepalive).  GPU tensors must live on the scheme's device; unless the caller pinned a stream
-    with Scheme.set_stream, the engine enqueues on torch's CURRENT stream of that device, so its kernels are ordered
-    with the producer and the consumer of the tensor like any torch op."""
+def _arg(x, dtype, writable=False):
+    """-> (pointer, mem kind, keepalive)"""
     if _is_torch(x):
         if not x.is_cuda:
             raise ValueError("torch tensors must live on the GPU; pass numpy arrays for host memory")
-        if scheme is not None:
-            scheme._follow_torch(x)
         if not x.is_contiguous():
             raise ValueError("tensor must be contiguous")
         if x.element_size() != np.dtype(dtype).itemsize:
@@ -49,6 +46,45 @@ def _arg(x, dtype, writable=False, scheme=None):
     if writable and a is not x:
         raise ValueError("output / in-place argument must be a contiguous numpy array of dtype %s" % np.dtype(dtype))
     return _np_ptr(a), MEM_HOST, a
+
+
+def _rows(shape):
+    """gates in an array of shape (..., row): a 1-D array is one"""
+    return int(np.prod(shape[:-1])) if len(shape) > 1 else 1
+
+
+def _count(x):
+    return int(np.prod(np.shape(x)))
+
+
+def _empty(like, shape, dtype, tdtype=None):
+    """a new array of `shape` living where `like` lives: numpy `dtype` on the host; on the GPU a tensor of the torch type named
+    `tdtype`, by default like's own"""
+    if _is_torch(like):
+        import torch
+        return like.new_empty(shape, dtype=getattr(torch, tdtype) if tdtype else like.dtype)
+    return np.empty(shape, dtype=dtype)
+
+
+def _one_shape(x, *others, out, dtype=np.uint32):
+    """-> (B, out) of a batch-ordered call: the other operands and out have x's shape; out None = a new array where x lives"""
+    shape = tuple(np.shape(x))
+    if out is None:
+        out = _empty(x, shape, dtype)
+    if any(tuple(np.shape(v)) != shape for v in (*others, out)):
+        raise ValueError(f"operands and out must all have the shape {shape}")
+    return _rows(shape), out
+
+
+class _Buf(NamedTuple):
+    """a buffer argument of a batch call: it must hold n rows of `row` elements (shape (..., row)), or, with row None, n elements in any
+    shape -- exactly what the C function reads or writes through it.  out: the library writes it, so a host array must already be
+    contiguous and of `dtype`"""
+    x: object
+    dtype: type
+    n: int
+    row: int = None
+    out: bool = False
 
 
 # ------------------------------------------------------------------------------------------------
@@ -186,7 +222,98 @@ def lwe_decrypt(ctxt, keys, params: Params):
 # ------------------------------------------------------------------------------------------------
 # evaluator: the scheme object lives on one MI355X
 # ------------------------------------------------------------------------------------------------
-class Scheme:
+class _Batched:
+    """The batch methods Scheme and MultiScheme share, and the one checked path every batch call of either class takes.  The C ABI
+    takes plain pointers and a batch count B, so _call is where each buffer's size is compared with what the library reads or writes."""
+    _PREFIX = "mkt_"
+
+    def _follow_torch(self, tensors):
+        """hook run once per call with GPU tensor arguments, before the library call: MultiScheme takes tensors on any device, and its
+        calls are synchronous"""
+
+    def _ct(self, x, n, out=False):
+        return _Buf(x, np.uint32, n, self.params.lwe_len, out)
+
+    def _call(self, name, B, *args):
+        """_PREFIX + name called as (handle, *args, B, mem), every _Buf in args passed as its pointer -> the _Bufs as _arg resolved
+        them, in order.  Before any library call: ValueError unless all of them live in one memory kind and each holds exactly what
+        the C function reads or writes for B gates"""
+        fn, cargs, kept, mems = self._PREFIX + name, [], [], set()
+        for a in args:
+            if isinstance(a, _Buf):
+                ptr, mem, k = _arg(a.x, a.dtype, writable=a.out)
+                shape = tuple(k.shape)
+                if a.row is None:
+                    ok, want = int(np.prod(shape)) == a.n, f"{a.n} elements"
+                else:
+                    ok, want = shape[-1:] == (a.row,) and _rows(shape) == a.n, f"{a.n} rows of {a.row}"
+                if not ok:
+                    raise ValueError(f"{fn}: an argument of shape {shape}, expected {want}")
+                a = ptr
+                kept.append(k)
+                mems.add(mem)
+            cargs.append(a)
+        if len(mems) > 1:
+            raise ValueError(f"{fn}: all arguments must be host arrays or all be GPU tensors")
+        mem = mems.pop()
+        if mem == MEM_DEVICE:
+            self._follow_torch(kept)
+        self._ck(getattr(_lib.lib(), fn)(self.h, *cargs, B, mem))
+        return kept
+
+    def gate(self, op, x, y, out=None):
+        B, out = _one_shape(x, y, out=out)
+        return self._call("gate_batch", B, op, self._ct(x, B), self._ct(y, B), self._ct(out, B, out=True))[-1]
+
+    def gate_ops(self, ops, x, y, out=None):
+        """a different gate per ciphertext pair (mkt_gate_batch_ops; the reference's tests draw a random gate per step,
+        test/KMS.jl:29-34): ops[j] in 0..5 (NAND..NOR), optionally | OP_NOT_X / OP_NOT_Y (that input negated first, NOT!);
+        a uint8 array living where x and y live"""
+        B, out = _one_shape(x, y, out=out)
+        return self._call("gate_batch_ops", B, _Buf(ops, np.uint8, B), self._ct(x, B), self._ct(y, B), self._ct(out, B, out=True))[-1]
+
+    def gate3(self, op, x, y, z, out=None):
+        """a three-input gate in ONE bootstrap for the whole batch (MAJ3_OP .. AE3_OP, optionally | OP_NOT_X / _Y / _Z): gate3_ops with
+        one code"""
+        return self.gate3_ops(_full_ops(op, x, _rows(np.shape(x))), x, y, z, out)
+
+    def gate3_ops(self, ops, x, y, z, out=None):
+        """a three-input gate per ciphertext triple, one bootstrap each (mkt_gate3_batch_ops): ops[j] in 0..5 (MAJ3..AE3), optionally
+        | OP_NOT_X / OP_NOT_Y / OP_NOT_Z; a uint8 array living where x, y and z live"""
+        B, out = _one_shape(x, y, z, out=out)
+        return self._call("gate3_batch_ops", B, _Buf(ops, np.uint8, B), self._ct(x, B), self._ct(y, B), self._ct(z, B), self._ct(out, B, out=True))[-1]
+
+    def mux(self, s, a, b, out=None):
+        """MUX(s, a, b) = s ? a : b with two blind rotations and one key switch (mkt_mux_batch; the reference has no MUX gate)"""
+        B, out = _one_shape(s, a, b, out=out)
+        return self._call("mux_batch", B, self._ct(s, B), self._ct(a, B), self._ct(b, B), self._ct(out, B, out=True))[-1]
+
+    def bootstrapping_(self, ctxt):
+        B = _rows(np.shape(ctxt))
+        return self._call("bootstrap_batch", B, self._ct(ctxt, B, out=True))[0]
+
+    def not_(self, ctxt):
+        B = _rows(np.shape(ctxt))
+        return self._call("not_batch", B, self._ct(ctxt, B, out=True))[0]
+
+    def blindrotate_(self, atilde, acc):
+        """acc: (k+1) * N ring words per ciphertext of atilde, in any shape"""
+        p = self.params
+        B = _rows(np.shape(atilde))
+        return self._call("blindrotate_batch", B, _Buf(atilde, np.uint32, B, p.lwe_len - 1), _Buf(acc, p.ring_dtype, B * (p.k + 1) * p.N, out=True))[1]
+
+    def keyswitch(self, acc):
+        """acc: (..., k+1, N) ring words"""
+        p = self.params
+        shape = tuple(np.shape(acc))
+        if shape[-2:] != (p.k + 1, p.N):
+            raise ValueError(f"accumulator of shape {shape}, expected (..., {p.k + 1}, {p.N})")
+        B = int(np.prod(shape[:-2]))
+        out = np.empty(shape[:-2] + (p.lwe_len,), dtype=np.uint32)
+        return self._call("keyswitch_batch", B, _Buf(acc, p.ring_dtype, B * (p.k + 1) * p.N), self._ct(out, B, out=True))[1]
+
+
+class Scheme(_Batched):
     """The reference's CGGI / LMSS / CCS / KMS / KMS_block scheme object (scheme.jl:107-116, :168-179,
     :209-219, :256-265, :301-312) as a per-device engine context: twiddle tables (fft.jl:18-45),
     monomial table (scheme.jl:121-146) and the pre-transformed evaluation keys, all resident in HBM."""
@@ -200,12 +327,16 @@ class Scheme:
         self.arith = arith
         self._user_stream = False     # True once set_stream pinned a stream; else torch's current stream is followed
 
-    def _follow_torch(self, t):
-        if t.device.index != self.device:
-            raise ValueError(f"tensor lives on cuda:{t.device.index}, this scheme on device {self.device}")
+    def _follow_torch(self, tensors):
+        """GPU tensors must live on this scheme's device; unless the caller pinned a stream with set_stream, the engine enqueues on
+        torch's CURRENT stream of that device, so its kernels are ordered with the producer and the consumer of the tensors like any
+        torch op"""
+        for t in tensors:
+            if t.device.index != self.device:
+                raise ValueError(f"tensor lives on cuda:{t.device.index}, this scheme on device {self.device}")
         if not self._user_stream:
             import torch
-            self._ck(_lib.lib().mkt_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+            self._ck(_lib.lib().mkt_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(tensors[0].device).cuda_stream)))
 
     def fork(self):
         """a second Scheme over the SAME resident keys (mkt_ctx_fork: no copy) with its own stream and workspace -- one
@@ -346,232 +477,76 @@ class Scheme:
         n = self._ck(_lib.lib().mkt_last_kernel_ms(self.h, which, C.byref(ms)))
         return ms.value, n
 
-    # -- hot path
-    def _batch(self, x):
-        return int(np.prod(x.shape[:-1])) if len(x.shape) > 1 else 1
-
-    def gate(self, op, x, y, out=None):
-        px, mem, kx = _arg(x, np.uint32, scheme=self)
-        py, mem2, ky = _arg(y, np.uint32, scheme=self)
-        if mem != mem2:
-            raise ValueError("x and y must both be host arrays or both be GPU tensors")
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, mem3, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if mem3 != mem:
-            raise ValueError("out must live where the inputs live")
-        if tuple(kx.shape) != tuple(ky.shape) or kx.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape mismatch")       # reference: @assert length checks
-        self._ck(_lib.lib().mkt_gate_batch(self.h, op, px, py, po, self._batch(kx), mem))
-        return ko
-
-    def gate_ops(self, ops, x, y, out=None):
-        """a different gate per ciphertext pair (mkt_gate_batch_ops; the reference's tests draw a random gate per step,
-        test/KMS.jl:29-34): ops[j] in 0..5 (NAND..NOR), optionally | OP_NOT_X / OP_NOT_Y (that input negated first, NOT!);
-        a uint8 array living where x and y live"""
-        px, mem, kx = _arg(x, np.uint32, scheme=self)
-        py, mem2, ky = _arg(y, np.uint32, scheme=self)
-        po_, mem4, kops = _arg(ops, np.uint8, scheme=self)
-        if not (mem == mem2 == mem4):
-            raise ValueError("ops, x and y must all be host arrays or all be GPU tensors")
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, mem3, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if mem3 != mem:
-            raise ValueError("out must live where the inputs live")
-        B = self._batch(kx)
-        if tuple(kx.shape) != tuple(ky.shape) or kx.shape[-1] != self.params.lwe_len or int(np.prod(kops.shape)) != B:
-            raise ValueError("ciphertext / ops shape mismatch")
-        self._ck(_lib.lib().mkt_gate_batch_ops(self.h, po_, px, py, po, B, mem))
-        return ko
-
+    # -- hot path: the shared batch methods (_Batched) and these
     def gate_gather(self, ops, pool, ix, iy, out):
         """one circuit level (mkt_gate_batch_gather): gate j = ops[j](pool[ix[j]], pool[iy[j]]) -> out[j]; pool (rows, k*n+1),
         ix / iy uint32 (int32 tensors) row indices; out may be a later region of the pool"""
-        pp, mem, kp = _arg(pool, np.uint32, scheme=self)
-        pops, m1, kops = _arg(ops, np.uint8, scheme=self)
-        pix, m2, kix = _arg(ix, np.uint32, scheme=self)
-        piy, m3, kiy = _arg(iy, np.uint32, scheme=self)
-        po, m4, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if not (mem == m1 == m2 == m3 == m4):
-            raise ValueError("all arguments must live in the same memory")
-        B = int(np.prod(kops.shape))
-        if kp.shape[-1] != self.params.lwe_len or int(np.prod(kix.shape)) != B or int(np.prod(kiy.shape)) != B or self._batch(ko) != B:
-            raise ValueError("shape mismatch")
-        self._ck(_lib.lib().mkt_gate_batch_gather(self.h, pops, pp, self._batch(kp), pix, piy, po, B, mem))
-        return ko
-
-    def gate3(self, op, x, y, z, out=None):
-        """a three-input gate in ONE bootstrap for the whole batch (MAJ3_OP .. AE3_OP, optionally | OP_NOT_X / _Y / _Z): gate3_ops with
-        one code"""
-        return self.gate3_ops(_full_ops(op, x, self._batch(x)), x, y, z, out)
-
-    def gate3_ops(self, ops, x, y, z, out=None):
-        """a three-input gate per ciphertext triple, one bootstrap each (mkt_gate3_batch_ops): ops[j] in 0..5 (MAJ3..AE3), optionally
-        | OP_NOT_X / OP_NOT_Y / OP_NOT_Z; a uint8 array living where x, y and z live"""
-        px, mem, kx = _arg(x, np.uint32, scheme=self)
-        py, m1, ky = _arg(y, np.uint32, scheme=self)
-        pz, m2, kz = _arg(z, np.uint32, scheme=self)
-        pops, m3, kops = _arg(ops, np.uint8, scheme=self)
-        if not (mem == m1 == m2 == m3):
-            raise ValueError("ops, x, y and z must all be host arrays or all be GPU tensors")
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, m4, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if m4 != mem:
-            raise ValueError("out must live where the inputs live")
-        B = self._batch(kx)
-        if not (tuple(kx.shape) == tuple(ky.shape) == tuple(kz.shape) == tuple(ko.shape)) or kx.shape[-1] != self.params.lwe_len or int(np.prod(kops.shape)) != B:
-            raise ValueError("ciphertext / ops shape mismatch")
-        self._ck(_lib.lib().mkt_gate3_batch_ops(self.h, pops, px, py, pz, po, B, mem))
-        return ko
+        B, P = _count(ops), _rows(np.shape(pool))
+        return self._call("gate_batch_gather", B, _Buf(ops, np.uint8, B), self._ct(pool, P), P, _Buf(ix, np.uint32, B), _Buf(iy, np.uint32, B),
+                          self._ct(out, B, out=True))[-1]
 
     def gate3_gather(self, ops, pool, ix, iy, iz, out):
         """one circuit level of three-input gates (mkt_gate3_batch_gather): gate j = ops[j](pool[ix[j]], pool[iy[j]], pool[iz[j]]) -> out[j];
         out may be a later region of the pool"""
-        pp, mem, kp = _arg(pool, np.uint32, scheme=self)
-        pops, m1, kops = _arg(ops, np.uint8, scheme=self)
-        pix, m2, kix = _arg(ix, np.uint32, scheme=self)
-        piy, m3, kiy = _arg(iy, np.uint32, scheme=self)
-        piz, m4, kiz = _arg(iz, np.uint32, scheme=self)
-        po, m5, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if not (mem == m1 == m2 == m3 == m4 == m5):
-            raise ValueError("all arguments must live in the same memory")
-        B = int(np.prod(kops.shape))
-        if kp.shape[-1] != self.params.lwe_len or any(int(np.prod(k.shape)) != B for k in (kix, kiy, kiz)) or self._batch(ko) != B:
-            raise ValueError("shape mismatch")
-        self._ck(_lib.lib().mkt_gate3_batch_gather(self.h, pops, pp, self._batch(kp), pix, piy, piz, po, B, mem))
-        return ko
-
-    def mux(self, s, a, b, out=None):
-        """MUX(s, a, b) = s ? a : b with two blind rotations and one key switch (mkt_mux_batch; the reference has no MUX gate)"""
-        ps, mem, ks = _arg(s, np.uint32, scheme=self)
-        pa, m1, ka = _arg(a, np.uint32, scheme=self)
-        pb, m2, kb = _arg(b, np.uint32, scheme=self)
-        if out is None:
-            out = ks.new_empty(ks.shape) if mem == MEM_DEVICE else np.empty_like(ks)
-        po, m3, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        if not (mem == m1 == m2 == m3) or not (tuple(ks.shape) == tuple(ka.shape) == tuple(kb.shape)) or ks.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape / memory mismatch")
-        self._ck(_lib.lib().mkt_mux_batch(self.h, ps, pa, pb, po, self._batch(ks), mem))
-        return ko
+        B, P = _count(ops), _rows(np.shape(pool))
+        return self._call("gate3_batch_gather", B, _Buf(ops, np.uint8, B), self._ct(pool, P), P, _Buf(ix, np.uint32, B), _Buf(iy, np.uint32, B),
+                          _Buf(iz, np.uint32, B), self._ct(out, B, out=True))[-1]
 
     def mux_gather(self, pool, i_s, i_a, i_b, out, not_ab=None):
         """a circuit level of native MUX gates (mkt_mux_batch_gather): out[j] = MUX(pool[i_s[j]], a', b'), a' = pool[i_a[j]] or its
         negation if bit 0 of not_ab[j] is set (b' likewise, bit 1)"""
-        pp, mem, kp = _arg(pool, np.uint32, scheme=self)
-        ps, m1, ks = _arg(i_s, np.uint32, scheme=self)
-        pa, m2, ka = _arg(i_a, np.uint32, scheme=self)
-        pb, m3, kb = _arg(i_b, np.uint32, scheme=self)
-        po, m4, ko = _arg(out, np.uint32, writable=True, scheme=self)
-        pf, m5, kf = (None, mem, None) if not_ab is None else _arg(not_ab, np.uint8, scheme=self)
-        if not (mem == m1 == m2 == m3 == m4 == m5):
-            raise ValueError("all arguments must live in the same memory")
-        B = int(np.prod(ks.shape))
-        if kp.shape[-1] != self.params.lwe_len or int(np.prod(ka.shape)) != B or int(np.prod(kb.shape)) != B or self._batch(ko) != B:
-            raise ValueError("shape mismatch")
-        self._ck(_lib.lib().mkt_mux_batch_gather(self.h, pp, self._batch(kp), ps, pa, pb, pf, po, B, mem))
-        return ko
-
-    def bootstrapping_(self, ctxt):
-        p, mem, k = _arg(ctxt, np.uint32, writable=True, scheme=self)
-        if k.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape mismatch")
-        self._ck(_lib.lib().mkt_bootstrap_batch(self.h, p, self._batch(k), mem))
-        return k
-
-    def not_(self, ctxt):
-        p, mem, k = _arg(ctxt, np.uint32, writable=True, scheme=self)
-        self._ck(_lib.lib().mkt_not_batch(self.h, p, self._batch(k), mem))
-        return k
+        B, P = _count(i_s), _rows(np.shape(pool))
+        return self._call("mux_batch_gather", B, self._ct(pool, P), P, _Buf(i_s, np.uint32, B), _Buf(i_a, np.uint32, B), _Buf(i_b, np.uint32, B),
+                          None if not_ab is None else _Buf(not_ab, np.uint8, B), self._ct(out, B, out=True))[-1]
 
     def modswitch(self, ctxt):
-        c = np.ascontiguousarray(ctxt, dtype=np.uint32)
-        B = self._batch(c)
-        at = np.empty(c.shape[:-1] + (self.params.lwe_len - 1,), dtype=np.uint32)
-        bt = np.empty(c.shape[:-1] if c.ndim > 1 else (1,), dtype=np.uint32)
-        self._ck(_lib.lib().mkt_modswitch_batch(self.h, _np_ptr(c), _np_ptr(at), _np_ptr(bt), B, MEM_HOST))
+        shape = tuple(np.shape(ctxt))
+        B = _rows(shape)
+        at = np.empty(shape[:-1] + (self.params.lwe_len - 1,), dtype=np.uint32)
+        bt = np.empty(shape[:-1] if len(shape) > 1 else (1,), dtype=np.uint32)
+        self._call("modswitch_batch", B, self._ct(ctxt, B), _Buf(at, np.uint32, B, self.params.lwe_len - 1, out=True), _Buf(bt, np.uint32, B, out=True))
         return at, bt
 
-    def blindrotate_(self, atilde, acc):
-        pa, mem, ka = _arg(atilde, np.uint32, scheme=self)
-        pc, mem2, kc = _arg(acc, self.params.ring_dtype, writable=True, scheme=self)
-        if mem != mem2:
-            raise ValueError("atilde and acc must live in the same memory")
-        self._ck(_lib.lib().mkt_blindrotate_batch(self.h, pa, pc, self._batch(ka), mem))
-        return kc
-
-    def keyswitch(self, acc):
-        a = np.ascontiguousarray(acc, dtype=self.params.ring_dtype)
-        B = int(np.prod(a.shape[:-2])) if a.ndim > 2 else 1
-        out = np.empty(a.shape[:-2] + (self.params.lwe_len,), dtype=np.uint32)
-        self._ck(_lib.lib().mkt_keyswitch_batch(self.h, _np_ptr(a), _np_ptr(out), B, MEM_HOST))
-        return out
-
     def kms_phase1(self, atilde):
-        a = np.ascontiguousarray(atilde, dtype=np.uint32)
-        B = self._batch(a)
         p = self.params
+        shape = tuple(np.shape(atilde))
+        B = _rows(shape)
         rtot = 1 + (p.k - 1) * p.l_lev
         if self.arith == ARITH_EXACT:    # split residue tables: [rows][polynomial b / a][low / high 32-bit half][N] residue pairs, Montgomery form
-            out = np.empty(a.shape[:-1] + (rtot, 2, 2, p.N), dtype=np.uint64)
+            row, dt = (rtot, 2, 2, p.N), np.uint64
         else:
-            out = np.empty(a.shape[:-1] + (rtot, 2, p.N // 2), dtype=np.complex128)
-        self._ck(_lib.lib().mkt_kms_phase1_batch(self.h, _np_ptr(a), _np_ptr(out), B, MEM_HOST))
-        return out
+            row, dt = (rtot, 2, p.N // 2), np.complex128
+        out = np.empty(shape[:-1] + row, dtype=dt)
+        return self._call("kms_phase1_batch", B, _Buf(atilde, np.uint32, B, p.lwe_len - 1), _Buf(out, dt, B * int(np.prod(row)), out=True))[1]
 
     def transform_fwd(self, p, out=None):
-        pp, mem, kp = _arg(p, self.params.ring_dtype, scheme=self)
+        N, shape = self.params.N, tuple(np.shape(p))
+        B = _rows(shape)
         if out is None:
-            if mem == MEM_DEVICE:
-                import torch
-                out = torch.empty(tuple(kp.shape[:-1]) + (self.params.N // 2,), dtype=torch.complex128, device=kp.device)
-            else:
-                out = np.empty(kp.shape[:-1] + (self.params.N // 2,), dtype=np.complex128)
-        po, _, ko = _arg(out, np.complex128, writable=True, scheme=self)
-        self._ck(_lib.lib().mkt_transform_fwd_batch(self.h, pp, po, self._batch(kp), mem))
-        return ko
+            out = _empty(p, shape[:-1] + (N // 2,), np.complex128, "complex128")
+        return self._call("transform_fwd_batch", B, _Buf(p, self.params.ring_dtype, B, N), _Buf(out, np.complex128, B, N // 2, out=True))[1]
 
     def transform_inv(self, t, out=None):
-        pt, mem, kt = _arg(t, np.complex128, scheme=self)
+        N, shape = self.params.N, tuple(np.shape(t))
+        B = _rows(shape)
         if out is None:
-            if mem == MEM_DEVICE:
-                import torch
-                tdt = torch.int64 if self.params.W == 64 else torch.int32
-                out = torch.empty(tuple(kt.shape[:-1]) + (self.params.N,), dtype=tdt, device=kt.device)
-            else:
-                out = np.empty(kt.shape[:-1] + (self.params.N,), dtype=self.params.ring_dtype)
-        po, _, ko = _arg(out, self.params.ring_dtype, writable=True, scheme=self)
-        self._ck(_lib.lib().mkt_transform_inv_batch(self.h, pt, po, self._batch(kt), mem))
-        return ko
+            out = _empty(t, shape[:-1] + (N,), self.params.ring_dtype, "int64" if self.params.W == 64 else "int32")
+        return self._call("transform_inv_batch", B, _Buf(t, np.complex128, B, N // 2), _Buf(out, self.params.ring_dtype, B, N, out=True))[1]
 
     def exact_polymul(self, a, b, out=None):
         """MKT_ARITH_EXACT contexts: a (*) b mod (X^N + 1, 2^W), exactly, for digit polynomials a (signed W-bit words,
         N * max|a_i| <= 2^28 - 2^15 over the batch: outside it the call raises MktError and writes nothing) and ring polynomials b;
         (..., N) numpy arrays, or GPU tensors of the ring's word size.  Under exact_impl = 1 the Float64 pipe serves the call where its
         proven bound certifies the operands, the integer NTT otherwise (same words; last_kernel_name() says which)"""
-        pa, mem, ka = _arg(a, self.params.ring_dtype, scheme=self)
-        pb, memb, kb = _arg(b, self.params.ring_dtype, scheme=self)
-        if memb != mem or tuple(kb.shape) != tuple(ka.shape):
-            raise ValueError("a and b must have the same shape and live in the same memory")
-        if out is None:
-            if mem == MEM_DEVICE:
-                import torch
-                out = torch.empty_like(ka)
-            else:
-                out = np.empty_like(ka)
-        po, memo, ko = _arg(out, self.params.ring_dtype, writable=True, scheme=self)
-        if memo != mem or tuple(ko.shape) != tuple(ka.shape):
-            raise ValueError("out must match a in shape and memory")
-        self._ck(_lib.lib().mkt_exact_polymul_batch(self.h, pa, pb, po, self._batch(ka), mem))
-        return ko
+        rd, N = self.params.ring_dtype, self.params.N
+        B, out = _one_shape(a, b, out=out, dtype=rd)
+        return self._call("exact_polymul_batch", B, _Buf(a, rd, B, N), _Buf(b, rd, B, N), _Buf(out, rd, B, N, out=True))[-1]
 
     def decompose(self, p, l, logB):
-        a = np.ascontiguousarray(p, dtype=self.params.ring_dtype)
-        B = self._batch(a)
-        out = np.empty(a.shape[:-1] + (l, self.params.N), dtype=self.params.ring_dtype)
-        self._ck(_lib.lib().mkt_decompose_batch(self.h, _np_ptr(a), _np_ptr(out), l, logB, B, MEM_HOST))
-        return out
+        rd, N, shape = self.params.ring_dtype, self.params.N, tuple(np.shape(p))
+        B = _rows(shape)
+        out = np.empty(shape[:-1] + (l, N), dtype=rd)
+        return self._call("decompose_batch", B, _Buf(p, rd, B, N), _Buf(out, rd, B * l, N, out=True), l, logB)[1]
 
 
 OP_NOT_X, OP_NOT_Y = 8, 16      # mktfhe.h MKT_OP_NOT_X / _Y: per-gate code bits of gate_ops / gate_gather
@@ -586,12 +561,13 @@ def _full_ops(op, like, B):
     return np.full(B, op, dtype=np.uint8)
 
 
-class MultiScheme:
+class MultiScheme(_Batched):
     """ONE scheme object over several MI355X (mkt_multi_*): the reference's caller is one process whose threads
     share one read-only scheme (README.md:38-44, bootstrapping.jl:38-45); here the batch is cut into contiguous shards, one per
     entry of `devices` (a device named twice = two logical shards over that device's one key set), keys uploaded once and
     replicated device-to-device, every shard writing its slice of the caller's one output array.  No collective.  Same batch
     methods as Scheme; arrays are host numpy arrays or GPU tensors on ANY of the devices."""
+    _PREFIX = "mkt_multi_"
 
     def __init__(self, params: Params, devices, arith=ARITH_F64REF, private_keys=False, stage_always=False, no_peer=False):
         """private_keys: shards that share a device each get their own replicated key copy (MKT_MULTI_PRIVATE_KEYS: the
@@ -668,90 +644,6 @@ class MultiScheme:
 
     def set_option(self, name, value):
         self._ck(_lib.lib().mkt_multi_set_option(self.h, name.encode(), int(value)))
-
-    # -- hot path (no stream following: calls are synchronous, inputs are settled by the library)
-    @staticmethod
-    def _batch(x):
-        return int(np.prod(x.shape[:-1])) if len(x.shape) > 1 else 1
-
-    def gate(self, op, x, y, out=None):
-        px, mem, kx = _arg(x, np.uint32)
-        py, mem2, ky = _arg(y, np.uint32)
-        if mem != mem2:
-            raise ValueError("x and y must both be host arrays or both be GPU tensors")
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, mem3, ko = _arg(out, np.uint32, writable=True)
-        if mem3 != mem or tuple(kx.shape) != tuple(ky.shape) or kx.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape / memory mismatch")
-        self._ck(_lib.lib().mkt_multi_gate_batch(self.h, op, px, py, po, self._batch(kx), mem))
-        return ko
-
-    def gate_ops(self, ops, x, y, out=None):
-        px, mem, kx = _arg(x, np.uint32)
-        py, mem2, ky = _arg(y, np.uint32)
-        pops, mem4, kops = _arg(ops, np.uint8)
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, mem3, ko = _arg(out, np.uint32, writable=True)
-        if not (mem == mem2 == mem3 == mem4) or tuple(kx.shape) != tuple(ky.shape) or kx.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape / memory mismatch")
-        self._ck(_lib.lib().mkt_multi_gate_batch_ops(self.h, pops, px, py, po, self._batch(kx), mem))
-        return ko
-
-    def gate3(self, op, x, y, z, out=None):
-        return self.gate3_ops(_full_ops(op, x, self._batch(x)), x, y, z, out)
-
-    def gate3_ops(self, ops, x, y, z, out=None):
-        px, mem, kx = _arg(x, np.uint32)
-        py, m1, ky = _arg(y, np.uint32)
-        pz, m2, kz = _arg(z, np.uint32)
-        pops, m3, kops = _arg(ops, np.uint8)
-        if out is None:
-            out = kx.new_empty(kx.shape) if mem == MEM_DEVICE else np.empty_like(kx)
-        po, m4, ko = _arg(out, np.uint32, writable=True)
-        if not (mem == m1 == m2 == m3 == m4) or not (tuple(kx.shape) == tuple(ky.shape) == tuple(kz.shape)) or kx.shape[-1] != self.params.lwe_len \
-                or int(np.prod(kops.shape)) != self._batch(kx):
-            raise ValueError("ciphertext / ops shape / memory mismatch")
-        self._ck(_lib.lib().mkt_multi_gate3_batch_ops(self.h, pops, px, py, pz, po, self._batch(kx), mem))
-        return ko
-
-    def mux(self, s, a, b, out=None):
-        ps, mem, ks = _arg(s, np.uint32)
-        pa, m1, ka = _arg(a, np.uint32)
-        pb, m2, kb = _arg(b, np.uint32)
-        if out is None:
-            out = ks.new_empty(ks.shape) if mem == MEM_DEVICE else np.empty_like(ks)
-        po, m3, ko = _arg(out, np.uint32, writable=True)
-        if not (mem == m1 == m2 == m3) or not (tuple(ks.shape) == tuple(ka.shape) == tuple(kb.shape)) or ks.shape[-1] != self.params.lwe_len:
-            raise ValueError("ciphertext shape / memory mismatch")
-        self._ck(_lib.lib().mkt_multi_mux_batch(self.h, ps, pa, pb, po, self._batch(ks), mem))
-        return ko
-
-    def bootstrapping_(self, ctxt):
-        p, mem, k = _arg(ctxt, np.uint32, writable=True)
-        self._ck(_lib.lib().mkt_multi_bootstrap_batch(self.h, p, self._batch(k), mem))
-        return k
-
-    def not_(self, ctxt):
-        p, mem, k = _arg(ctxt, np.uint32, writable=True)
-        self._ck(_lib.lib().mkt_multi_not_batch(self.h, p, self._batch(k), mem))
-        return k
-
-    def blindrotate_(self, atilde, acc):
-        pa, mem, ka = _arg(atilde, np.uint32)
-        pc, mem2, kc = _arg(acc, self.params.ring_dtype, writable=True)
-        if mem != mem2:
-            raise ValueError("atilde and acc must live in the same memory")
-        self._ck(_lib.lib().mkt_multi_blindrotate_batch(self.h, pa, pc, self._batch(ka), mem))
-        return kc
-
-    def keyswitch(self, acc):
-        a = np.ascontiguousarray(acc, dtype=self.params.ring_dtype)
-        B = int(np.prod(a.shape[:-2])) if a.ndim > 2 else 1
-        out = np.empty(a.shape[:-2] + (self.params.lwe_len,), dtype=np.uint32)
-        self._ck(_lib.lib().mkt_multi_keyswitch_batch(self.h, _np_ptr(a), _np_ptr(out), B, MEM_HOST))
-        return out
 
 
 def setup_multi(params: Params, devices, keys=None, a=None, arith=ARITH_F64REF, private_keys=False, stage_always=False, no_peer=False):
