@@ -1682,6 +1682,7 @@ hipError_t launch_exact_kms_phase1(int logN, const uint64_t *tab, const ExactKms
         } else {
             if (a.wide != 0 && a.l_gsw == 2) {                                     // the paired-transform kernel (default); exact_wide = 0: the one-at-a-time kernel below (tests force both)
                 const size_t lds2 = lds_bytes<LN>(1, 2);
+                last_rot_kernel = "exact_kms_phase1_p2pf_kernel";
                 e = ntt_set_lds(exact_kms_phase1_p2pf_kernel<LN>, lds2); if (e != hipSuccess) return e;
                 hipLaunchKernelGGL((exact_kms_phase1_p2pf_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds2, s, tb, a.brk, a.brk_party_stride,
                                    a.lwe, a.lwe_stride, a.pre_switched, a.n, a.logB_gsw, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);

@@ -139,3 +139,222 @@ def kat_decrypt(p, d, ct):
     if p.multikey:
         return ph < (1 << 31)
     return ((ph >> np.uint64(29)) + ((ph >> np.uint64(28)) & np.uint64(1))) == 1
+
+
+# ---- boundary inputs of the rotation / key-switch kernels' own rounding steps (tests/test_edges_cpu.py, tests/test_gpu_edges.py) ----
+BT_TARGETS = ("0", "1", "N-1", "N", "N+1", "2N-1", "2N")
+
+
+def modswitch_words(N):
+    """name -> 32-bit word at a boundary of divbits(w, 32 - logN - 1) (bootstrapping.jl:8-9, arithmetic.jl:23-27)"""
+    s = 32 - (N.bit_length() - 1) - 1
+    h = 1 << (s - 1)
+    return {"zero": 0, "max->0": h - 1, "tie->1": h, "->N-1": 2**31 - h - 1, "tie->N": 2**31 - h, "->N": 2**31, "max->N": 2**31 + h - 1,
+            "tie->N+1": 2**31 + h, "->2N-1": 2**32 - h - 1, "min->2N": 2**32 - h, "ones->2N": 2**32 - 1}
+
+
+def btilde_words(N):
+    """BT_TARGETS name -> (smallest, largest) 32-bit word that the mod switch rounds to it"""
+    s = 32 - (N.bit_length() - 1) - 1
+    T, h = 1 << s, 1 << (s - 1)
+    val = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
+    return {k: (max(v * T - h, 0), min(v * T + h - 1, 2**32 - 1)) for k, v in val.items()}
+
+
+def lwe_edge_rows(p, rng, even=False):
+    """LWE rows (not encryptions) on the boundaries of the mod switch -> (rows uint32 [R][lwe_len], kinds [R]).
+    kinds: "zero" mask of zero words; "skip" every mask word non-zero but rounding to 0; "dense" random words with the boundary words
+    at the first / last position and on both sides of every block and party border; "blocks" whole blocks (block length, or single
+    words) of non-zero words that round to 0 next to blocks of boundary words that do not; "party" (multi-key) one party's block all
+    rounding to 0, the others dense.  Every kind meets every btilde of BT_TARGETS, through the smallest or the largest word that
+    rounds to it.  even: bit 0 of every word cleared -- the words a XOR / XNOR linear part 2 (x + y) can take (gate.jl:28-44)."""
+    N, n, nm = p.N, p.n, p.lwe_len - 1
+    s = 32 - (N.bit_length() - 1) - 1
+    h = 1 << (s - 1)
+    mw = modswitch_words(N)
+    live = [v for k, v in mw.items() if k not in ("zero", "max->0")]           # boundary words that do not round to 0
+    L = p.blk_len if p.blk_len > 1 else 1
+    borders = {0, nm - 1} | {b for i in range(1, p.nparty) for b in (i * n - 1, i * n)}
+    if L > 1:
+        borders |= {b for i in range(1, nm // L) for b in (i * L - 1, i * L)}
+    borders = sorted(borders)
+    skipw = lambda m: rng.integers(2, h, m, dtype=np.uint64).astype(np.uint32)      # noqa: E731  (non-zero also after bit 0 is cleared)
+    rows, kinds = [], []
+    kindlist = ["zero", "skip", "dense", "blocks"] + (["party"] if p.multikey else [])
+    r = 0
+    for kind in kindlist:
+        for ti, t in enumerate(BT_TARGETS):
+            row = np.zeros(p.lwe_len, dtype=np.uint32)
+            if kind == "skip":
+                row[:nm] = skipw(nm)
+                row[0], row[nm - 1] = mw["max->0"], 1 if not even else 2
+            elif kind in ("dense", "party"):
+                row[:nm] = rng.integers(0, 2**32, nm, dtype=np.uint64).astype(np.uint32)
+                for i, b in enumerate(borders):
+                    row[b] = live[(i + r) % len(live)]
+                if kind == "party":
+                    pi = ti % p.nparty
+                    row[pi * n:(pi + 1) * n] = skipw(n)
+            elif kind == "blocks":
+                for b0 in range(0, nm, L):
+                    blk = (b0 // L + ti) % 2
+                    row[b0:b0 + L] = skipw(min(L, nm - b0)) if blk else [live[(b0 + j + r) % len(live)] for j in range(min(L, nm - b0))]
+            lo, hi = btilde_words(N)[t]
+            row[nm] = hi if (ti + len(rows)) % 2 else lo
+            rows.append(row)
+            kinds.append(kind)
+            r += 1
+    rows = np.stack(rows)
+    if even:
+        rows &= np.uint32(0xFFFFFFFE)
+    return rows, kinds
+
+
+def gadget_words(l, logB, W):
+    """name -> W-bit word on a boundary of the balanced decomposition with l digits of logB bits (gsw.jl:42-52): the digits are the
+    logB-bit fields of divbits(x, W - l logB) + sum_j B/2 B^j, each minus B/2; the top field drops its carry"""
+    Lb, bit, m = l * logB, W - l * logB, (1 << W) - 1
+    off = sum((1 << (logB - 1)) << (logB * j) for j in range(l))
+    out = {"all-min": ((1 << Lb) - off) << bit,                 # prepared value 2^Lb: the smallest that carries out of the field; all digits -B/2
+           "all-max": ((1 << Lb) - 1 - off) << bit,             # prepared value 2^Lb - 1: all digits B/2 - 1
+           "top-min": (1 << (Lb - 1)) << bit}                   # 2^(W-1): top digit -B/2 (the word that is its own negative)
+    if bit >= 1:
+        hb = 1 << (bit - 1)
+        out.update({"tie": (0x5 << bit | hb) & m, "tie-1": (0x5 << bit | hb) - 1 & m,
+                    "round-carry": (1 << W) - hb,               # the smallest word that rounds to 2^Lb: every digit 0
+                    "round-carry-1": (1 << W) - hb - 1,         # one below: rounds to 2^Lb - 1, the lowest digit -1, the others 0
+                    "tie->all-min": ((((1 << Lb) - off - 1) << bit) | hb) & m})    # a tie that rounds up INTO the carry of the prepared value
+    if bit >= 2:
+        out["tie+1"] = ((0x5 << bit | (1 << (bit - 1))) + 1) & m
+    if W == 64:                                                 # the same high parts over a low half of all ones / only the top bit
+        for k, v in list(out.items()):
+            out[k + "|lowFF"] = (v & ~0xFFFFFFFF) | 0xFFFFFFFF
+            out[k + "|low80"] = (v & ~0xFFFFFFFF) | 0x80000000
+    return out
+
+
+def rot_gadgets(p):
+    """the (l, logB) gadgets a blind rotation applies to its accumulator: GSW (CGGI, LMSS, KMS phase 1), LEV and UniEnc (KMS phase 2),
+    UniEnc (CCS)"""
+    if p.scheme == mk.CCS:
+        return [(p.l_uni, p.logB_uni)]
+    if p.scheme in (mk.KMS, mk.KMS_BLOCK):
+        return [(p.l_gsw, p.logB_gsw), (p.l_lev, p.logB_lev), (p.l_uni, p.logB_uni)]
+    return [(p.l_gsw, p.logB_gsw)]
+
+
+def edge_positions(N):
+    """0, M - 1, M, N - 1 first (index i and i + M feed the real and imaginary slot of one transform point), then pairs (i, i + M)"""
+    M = N // 2
+    pos = [0, M - 1, M, N - 1]
+    for i in range(1, M - 1):
+        pos += [i, i + M]
+    return pos
+
+
+def acc_edge(p, gadgets, rng, B):
+    """accumulators [B][1 + k][N] (uint64 holding W-bit words) with EVERY polynomial populated: edge_words, and on top the
+    gadget_words of every gadget in `gadgets` at the first edge_positions, the list rotated from polynomial to polynomial (what that
+    reaches -- every class in both halves, a boundary word at each of 0, M - 1, M, N - 1 -- is asserted in tests/test_edges_cpu.py)"""
+    N, W = p.N, p.W
+    S = [v for (l, logB) in gadgets for v in gadget_words(l, logB, W).values()]
+    pos = edge_positions(N)
+    m = min(len(S), len(pos), N // 2)
+    acc = np.empty((B, 1 + p.k, N), dtype=np.uint64)
+    for b in range(B):
+        for q in range(1 + p.k):
+            acc[b, q] = edge_words(W, N, rng)
+            rot = (b * (1 + p.k) + q) * 3
+            for i in range(m):
+                acc[b, q, pos[i]] = S[(i + rot) % len(S)]
+    return acc
+
+
+def ks_words(f, logD):
+    """name -> 32-bit extracted word on a boundary of the key switch's digits (unbalanced: the fields of divbits(w, 32 - f logD),
+    gsw.jl:34-40; balanced: gadget_words)"""
+    Lb, bit = f * logD, 32 - f * logD
+    out = {"zero": 0, "0x80000000": 1 << 31, "all-D-1": ((1 << Lb) - 1) << bit, "one": 1, "ones": 2**32 - 1}
+    if bit >= 1:
+        hb = 1 << (bit - 1)
+        out.update({"u-carry": 2**32 - hb,                      # rounds to 2^Lb: the carry leaves the field, every digit 0, like the zero word
+                    "u-carry-1": 2**32 - hb - 1,                # every digit D - 1
+                    "u-tie": (0x9 << bit) | hb, "u-tie-1": ((0x9 << bit) | hb) - 1})
+    out.update({"b-" + k: v for k, v in gadget_words(f, logD, 32).items()})
+    return out
+
+
+def ks_border(p, c):
+    """first switched coefficient of component c: below it the block schemes copy the extracted word (bootstrapping.jl:179-204, :676-690)"""
+    if p.scheme == mk.LMSS:
+        cur = c * p.N
+        return 0 if cur >= p.n else min(p.N, p.n - cur)
+    return p.n if p.scheme == mk.KMS_BLOCK else 0
+
+
+def ks_positions(p, c):
+    js = border = ks_border(p, c)
+    return sorted({j for j in (0, 1, p.N - 1, p.N // 2, border - 1, border, js + 1) if 0 <= j < p.N})
+
+
+def extract_words(p, poly):
+    """the N extracted LWE words of an accumulator mask polynomial: c_0 = a[0], c_j = -a[N - j], after the truncation of a 64-bit
+    word to its high half (bootstrapping.jl:91, :99, :575, :583)"""
+    a = (np.asarray(poly, dtype=np.uint64) >> np.uint64(p.W - 32)).astype(np.uint32)
+    out = (0 - a[::-1]).astype(np.uint32)
+    return np.concatenate([a[:1], out[:-1]])
+
+
+def ks_edge_acc(p, rng, B):
+    """accumulators [B][1 + k][N] whose EXTRACTED words sit on the key-switch gadget's boundaries: in every ciphertext and component
+    the ks_words at ks_positions (j = 0 is not negated, j = N - 1 reads a[1]; both sides of the copied / switched border), rotated
+    from ciphertext to ciphertext, and the whole list from the first switched coefficient on.  64-bit ring: the low half of those
+    words is all ones or the top bit alone -- it is cut off, never rounded into the word"""
+    N, W, sh = p.N, p.W, p.W - 32
+    S = list(ks_words(p.f, p.logD).values())
+    acc = rng.integers(0, 2**63, (B, 1 + p.k, N), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (B, 1 + p.k, N), dtype=np.uint64)
+    acc &= np.uint64((1 << W) - 1)
+
+    def put(b, c, j, w, t):
+        v = (w if j == 0 else (-w) & 0xFFFFFFFF) << sh
+        if sh:
+            v |= (0xFFFFFFFF, 0x80000000, 0x7FFFFFFF)[t % 3]
+        acc[b, 1 + c, 0 if j == 0 else N - j] = v
+
+    for b in range(B):
+        acc[b, 0, 0] = (S[b % len(S)] << sh) | ((0xFFFFFFFF, 0x80000000)[b % 2] if sh else 0)
+        for c in range(p.k):
+            j0 = ks_border(p, c)
+            if j0 < N:
+                for i, w in enumerate(S):
+                    j = j0 + 2 + i
+                    if j < N - 1:
+                        put(b, c, j, S[(i + b) % len(S)], i + b)
+            for i, j in enumerate(ks_positions(p, c)):
+                put(b, c, j, S[(i + b + c) % len(S)], i + b)
+    return acc
+
+
+_GATE_CONST = {0: 1 << 29, 1: 7 << 29, 2: 1 << 29, 3: 1 << 30, 4: 3 << 30, 5: 7 << 29}
+
+
+def gate_input(op, rows):
+    """x with gate_linear(op, x, 0-row) == rows[j] (gate.jl:1-53 solved for x); XOR / XNOR: rows of even words only (their linear part
+    is 2 (x + y) plus a constant), the halved word"""
+    r = rows.astype(np.int64)
+    c = np.zeros_like(r)
+    c[..., -1] = _GATE_CONST[op]
+    x = {0: c - r, 1: r - c, 2: r - c, 3: (r - c) // 2, 4: (c - r) // 2, 5: c - r}[op]
+    return (x & 0xFFFFFFFF).astype(np.uint32)
+
+
+def ks_edge_check(p, so, sg, rng, batches):
+    """sg.keyswitch(ks_edge_acc) == the oracle's keyswitch! for EVERY ciphertext of every batch size -> number of ciphertexts compared"""
+    checks = 0
+    for B in batches:
+        acc = ks_edge_acc(p, rng, B)
+        out = sg.keyswitch(acc.astype(p.ring_dtype))
+        for j in range(B):
+            assert np.array_equal(out[j], so.keyswitch(acc[j])), ("keyswitch (edge words)", p.name, p.n, p.f, p.logD, B, j)
+            checks += 1
+    return checks

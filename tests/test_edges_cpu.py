@@ -1,0 +1,287 @@
+"""The inputs of tests/test_gpu_edges.py, checked with the oracle alone (no GPU): every boundary class is present in what the
+builders of helpers.py produce for every parameter set of tests/edge_cases.py (a count per class > 0: the condition that keeps
+the GPU tests from silently testing nothing), the oracle's own composition identity holds on the crafted rows, and each class
+separates the oracle from the plausible wrong variant written next to it."""
+import numpy as np
+import pytest
+
+import edge_cases as EC
+from helpers import (BT_TARGETS, O, acc_edge, btilde_words, extract_words, gadget_words, gate_input, keygen, ks_border, ks_edge_acc,
+                     ks_words, lwe_edge_rows, mk, modswitch_words, oracle_scheme, rot_gadgets)
+
+
+def _switch(w, N):
+    return O.divbits(int(w), 32 - (N.bit_length() - 1) - 1, 32)
+
+
+def _sw_row(row, N):
+    return np.array([_switch(w, N) for w in row], dtype=np.int64)
+
+
+# ---------------------------------------------------------------- 1. class counts
+@pytest.mark.parametrize("even", [False, True], ids=["any", "even"])
+@pytest.mark.parametrize("p", EC.all_rotation_sets(), ids=EC.sid)
+def test_lwe_edge_rows_hold_every_class(p, even):
+    N, n, nm = p.N, p.n, p.lwe_len - 1
+    rows, kinds = lwe_edge_rows(p, np.random.default_rng(1), even=even)
+    if even:
+        assert not (rows & 1).any()
+    want = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
+    sw = np.stack([_sw_row(r, N) for r in rows])
+    for kind in ("zero", "skip", "dense", "blocks") + (("party",) if p.multikey else ()):
+        sel = [i for i, k in enumerate(kinds) if k == kind]
+        assert {int(sw[i, nm]) for i in sel} >= set(want.values()), (kind, "btilde")                    # every btilde in every kind
+        for i in sel:
+            raw, s = rows[i, :nm], sw[i, :nm]
+            if kind == "zero":
+                assert not raw.any()
+            if kind == "skip":
+                assert raw.all() and not s.any()                                                       # raw words non-zero, every step skipped
+            if kind == "dense":
+                assert s[0] and s[nm - 1]
+                for q in range(1, p.nparty):
+                    assert s[q * n - 1] and s[q * n], "party border"
+            if kind == "party":
+                dead = [q for q in range(p.nparty) if not s[q * n:(q + 1) * n].any()]
+                assert dead and all(rows[i, q * n:(q + 1) * n].all() for q in dead) and s.any()
+        if kind == "blocks":
+            L = p.blk_len if p.blk_len > 1 else 1
+            hit = 0
+            for i in sel:
+                b = sw[i, :nm // L * L].reshape(-1, L)
+                dead, full = ~b.any(axis=1), b.all(axis=1)
+                assert (dead | full).all() and rows[i, :nm].all()
+                hit += int((dead[:-1] & full[1:]).sum() + (full[:-1] & dead[1:]).sum())
+            assert hit > 0, "a block that rounds to 0 next to a full block"
+    mask_sw = sw[:, :nm]
+    counts = {k: int((mask_sw == v).sum()) for k, v in want.items()}
+    counts["raw != 0 -> 0"] = int(((mask_sw == 0) & (rows[:, :nm] != 0)).sum())
+    h = 1 << (32 - (N.bit_length() - 1) - 2)
+    counts["tie"] = int(((rows[:, :nm] & np.uint32(2 * h - 1)) == h).sum())
+    assert all(c > 0 for c in counts.values()), counts
+
+
+def _digit_classes(words, l, logB, W):
+    """class -> boolean array over words, by the oracle's digits (O.decomp_poly) and the words' own low bits"""
+    w = np.asarray(words, dtype=np.uint64).ravel()
+    d = O.decomp_poly(w, l, logB, W).astype(np.int64) if W == 64 else O.decomp_poly(w, l, logB, W).astype(np.uint32).astype(np.int32).astype(np.int64)
+    half, bit = 1 << (logB - 1), W - l * logB
+    cls = {"all-min": (d == -half).all(axis=0), "all-max": (d == half - 1).all(axis=0), "top-min": w == np.uint64(1 << (W - 1))}
+    if bit >= 1:
+        hb = 1 << (bit - 1)
+        low = w & np.uint64((1 << bit) - 1)
+        cls["tie"] = low == np.uint64(hb)
+        cls["tie-1"] = low == np.uint64(hb - 1)
+        cls["round-carry"] = (w >= np.uint64((1 << W) - hb)) & (d == 0).all(axis=0)
+        cls["tie->all-min"] = cls["tie"] & cls["all-min"]
+        if bit >= 2:
+            cls["tie+1"] = low == np.uint64(hb + 1)
+    return cls
+
+
+@pytest.mark.parametrize("p", EC.all_rotation_sets(), ids=EC.sid)
+def test_acc_edge_holds_every_class_for_every_gadget(p):
+    N, M, W = p.N, p.N // 2, p.W
+    acc = acc_edge(p, rot_gadgets(p), np.random.default_rng(2), 3)
+    assert acc.shape == (3, 1 + p.k, N) and (acc.reshape(-1, N) != 0).any(axis=1).all(), "every polynomial populated"
+    for (l, logB) in rot_gadgets(p):
+        cls = _digit_classes(acc, l, logB, W)
+        counts = {k: int(v.sum()) for k, v in cls.items()}
+        assert all(c > 0 for c in counts.values()), ((l, logB), counts)
+        special = np.zeros(acc.size, dtype=bool)
+        for v in cls.values():
+            special |= v
+        special = special.reshape(-1, N)
+        assert all(special[:, i].any() for i in (0, M - 1, M, N - 1)), "a boundary word at each of 0, M - 1, M, N - 1"
+        for k, v in cls.items():
+            v = v.reshape(-1, N)
+            assert v[:, :M].any() and v[:, M:].any(), (k, "both halves")
+        if W == 64 and W - l * logB > 32:            # the gadget reads the high half only: the same digits over a low half of all ones / the top bit alone
+            low = (acc & np.uint64(0xFFFFFFFF)).ravel()
+            for k in ("all-min", "all-max"):
+                assert (cls[k] & (low == 0xFFFFFFFF)).any() and (cls[k] & (low == 0x80000000)).any(), (k, "low half")
+    if W == 64:
+        low = acc & np.uint64(0xFFFFFFFF)
+        assert (low == 0xFFFFFFFF).any() and (low == 0x80000000).any()
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("p", EC.KS_SETS + EC.KS_CHILD_SETS, ids=EC.sid)
+def test_ks_edge_acc_holds_every_class(p, B):
+    N, f, logD = p.N, p.f, p.logD
+    Lb, bit, D = f * logD, 32 - f * logD, 1 << logD
+    balanced = p.scheme in (mk.LMSS, mk.KMS_BLOCK)
+    acc = ks_edge_acc(p, np.random.default_rng(3), B)
+    special_words = set(ks_words(f, logD).values())
+    counts = {}
+    for b in range(B):
+        for c in range(p.k):
+            w = extract_words(p, acc[b, 1 + c])
+            j0 = ks_border(p, c)
+            src = acc[b, 1 + c]
+            for name, j in (("0", 0), ("1", 1), ("N-1", N - 1), ("border-1", j0 - 1), ("border", j0)):
+                if name.startswith("border") and not 0 < j0 < N:
+                    continue                                                  # this component has no copied / switched border
+                here = int(w[j]) in special_words
+                if p.W == 64:                                                 # ... over one of the crafted low halves (cut off, never rounded in)
+                    here = here and int(src[0 if j == 0 else N - j]) & 0xFFFFFFFF in (0xFFFFFFFF, 0x80000000, 0x7FFFFFFF)
+                counts["a boundary word at j = " + name] = counts.get("a boundary word at j = " + name, 0) + here
+            sw = w[j0:]                                                       # the switched words
+            if not len(sw):
+                continue
+            jj = np.arange(j0, N)
+            add = lambda k, m: counts.__setitem__(k, counts.get(k, 0) + int(np.sum(m)))      # noqa: E731
+            add("zero", sw == 0)
+            add("0x80000000 at a negated position", (sw == 0x80000000) & (jj > 0))
+            if balanced:
+                for k, m in _digit_classes(sw, f, logD, 32).items():
+                    add("b-" + k, m)
+            else:
+                dg = np.stack([O.unbalanced_decomp_word(int(x), f, logD, 32) for x in np.unique(sw)])
+                rounded = np.array([O.divbits(int(x), bit, 32) for x in np.unique(sw)])
+                add("carry leaves the field (digits 0, word not 0)", (rounded == 1 << Lb) & ~dg.any(axis=1))
+                add("all digits D-1", (dg == D - 1).all(axis=1))
+                if bit >= 1:
+                    low = np.unique(sw) & np.uint32((1 << bit) - 1)
+                    add("tie", low == 1 << (bit - 1))
+                    add("tie-1", low == (1 << (bit - 1)) - 1)
+    assert all(v > 0 for v in counts.values()), counts
+    assert {"a boundary word at j = 0", "a boundary word at j = 1", "a boundary word at j = N-1"} <= set(counts)
+    if any(0 < ks_border(p, c) < N for c in range(p.k)):
+        assert {"a boundary word at j = border-1", "a boundary word at j = border"} <= set(counts)
+    if balanced:
+        assert any(ks_border(p, c) > 0 for c in range(p.k))
+    if p.W == 64:
+        low = acc[:, 1:] & np.uint64(0xFFFFFFFF)
+        assert (low == 0xFFFFFFFF).any() and (low == 0x80000000).any()
+
+
+# ---------------------------------------------------------------- 2. the oracle's composition identity on the crafted rows
+@pytest.mark.parametrize("p", EC.GATE_SETS, ids=EC.sid)
+def test_oracle_bootstrap_is_the_composition_of_its_stages_on_edge_rows(p):
+    crs, keys = keygen(p, 11)
+    so = oracle_scheme(p, crs, keys)
+    rows, kinds = lwe_edge_rows(p, np.random.default_rng(4))
+    for row, kind in zip(rows, kinds):
+        at, bt = so.modswitch(row)
+        assert np.array_equal(so.bootstrap(row), so.keyswitch(so.blindrotate(at, so.testvector(bt)))), kind
+        if kind in ("zero", "skip"):                                          # nothing rotates: the key switch of the test vector itself
+            assert np.array_equal(so.bootstrap(row), so.keyswitch(so.testvector(bt)))
+    # an accumulator word of all ones key-switches like a zero word under the unbalanced gadget: the carry leaves the field
+    if p.scheme not in (mk.LMSS, mk.KMS_BLOCK):
+        a0 = np.zeros((1 + p.k, p.N), dtype=np.uint64)
+        a1 = a0.copy()
+        a1[1, 0] = (1 << p.W) - 1
+        assert np.array_equal(so.keyswitch(a0), so.keyswitch(a1))
+
+
+def test_gate_inputs_reproduce_the_crafted_rows():
+    """x with gate_linear(op, x, 0) == row for the six gates (helpers.gate_input); XOR / XNOR reach even words only"""
+    p = EC.GATE_SETS[0]
+    for op in range(6):
+        rows, _ = lwe_edge_rows(p, np.random.default_rng(5), even=op in (3, 4))
+        x = gate_input(op, rows)
+        for j in range(len(rows)):
+            assert np.array_equal(O.gate_linear(op, x[j], np.zeros_like(x[j])), rows[j]), op
+
+
+# ---------------------------------------------------------------- 3. each class separates the oracle from a plausible wrong variant
+@pytest.mark.parametrize("N", [64, 256, 1024, 4096])
+def test_modswitch_classes_discriminate(N):
+    s = 32 - (N.bit_length() - 1) - 1
+    h = 1 << (s - 1)
+    mw = modswitch_words(N)
+    ora = {k: _switch(w, N) for k, w in mw.items()}
+    assert [ora[k] for k in ("zero", "max->0", "tie->1", "->N-1", "tie->N", "->N", "max->N", "tie->N+1", "->2N-1", "min->2N", "ones->2N")] == \
+        [0, 0, 1, N - 1, N, N, N, N + 1, 2 * N - 1, 2 * N, 2 * N]
+    for k in ("tie->1", "tie->N", "tie->N+1", "min->2N", "ones->2N"):
+        assert mw[k] >> s != ora[k], ("a plain shift (truncation)", k)
+    for k in ("tie->1", "tie->N", "tie->N+1", "min->2N"):
+        assert (mw[k] + h - 1) >> s != ora[k], ("ties rounded down", k)
+    assert ora["min->2N"] & (2 * N - 1) != ora["min->2N"], "the full turn reduced mod 2N (entry 2N of the monomial table is its own)"
+    assert (mw["max->0"] != 0) != (ora["max->0"] != 0), "the skip decided on the raw word"
+    for t, (lo, hi) in btilde_words(N).items():
+        v = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}[t]
+        assert _switch(lo, N) == v == _switch(hi, N)
+        assert lo == 0 or _switch(lo - 1, N) == v - 1
+        assert hi == 2**32 - 1 or _switch(hi + 1, N) == v + 1
+
+
+@pytest.mark.parametrize("W", [32, 64])
+def test_testvector_classes_discriminate(W):
+    N = 64
+    so = O.Scheme(O.OraParams(O.CGGI, 4, N, 1, W, 2, 8, 0, 0, 0, 0, 8, 2, 0, 0))
+    e, m = 1 << (W - 3), (1 << W) - 1
+    i = np.arange(N)
+
+    def tv(bt, above=lambda tb: tb > N, below=lambda i, tb: i < tb, flip=True):
+        lo, hi = e, (-e) & m
+        if above(bt):
+            bt -= N
+            if flip:
+                lo, hi = hi, lo
+        return np.where(below(i, bt), lo, hi).astype(np.uint64)
+
+    vals = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
+    for t in BT_TARGETS:
+        bt = vals[t]
+        want = so.testvector(bt)[0]
+        assert np.array_equal(tv(bt), want), t
+        # `tb >= N` in place of `tb > N` is the SAME function: at tb == N either branch writes +1/8 to all N coefficients
+        assert np.array_equal(tv(bt, above=lambda tb: tb >= N), want), t
+    differs = lambda **kw: {t for t in BT_TARGETS if not np.array_equal(tv(vals[t], **kw), so.testvector(vals[t])[0])}      # noqa: E731
+    assert differs(below=lambda i, tb: i <= tb) >= {"0", "1", "N-1", "N+1", "2N-1"}, "i <= tb for i < tb"
+    assert differs(flip=False) >= {"N+1", "2N-1", "2N"}, "the sign not flipped above N"
+    assert differs(above=lambda tb: tb > N + 1) >= {"N+1"}, "the half turn taken one late"
+    assert differs(above=lambda tb: tb >= N - 1) >= {"N-1"}, "the half turn taken one early"
+
+
+def _digits_variant(x, l, logB, W, mode):
+    """gsw.jl:42-52 in Python integers, in the kernels' form (digit j = field j of divbits(x, W - l logB) + sum_j B/2 B^j, minus B/2),
+    with one step changed: "trunc" a plain shift for divbits; "tiedown"; "carry" the top field keeps what lies above its logB bits"""
+    bit, B, m = W - l * logB, 1 << logB, (1 << W) - 1
+    a = x >> bit if mode == "trunc" else (x + (1 << (bit - 1)) - (mode == "tiedown")) >> bit if bit else x
+    tp = a + sum((B >> 1) << (logB * j) for j in range(l))
+    return [(((tp >> (logB * (l - 1 - j))) & (B - 1 if (j or mode != "carry") else ~0)) - (B >> 1)) & m for j in range(l)]
+
+
+@pytest.mark.parametrize("l,logB,W", sorted({(l, logB, p.W) for p in EC.all_rotation_sets() for (l, logB) in rot_gadgets(p)}
+                                             | {(p.f, p.logD, 32) for p in EC.KS_SETS}))
+def test_gadget_classes_discriminate(l, logB, W):
+    gw = gadget_words(l, logB, W)
+    ora = {k: [int(v) for v in O.decomp_word(x, l, logB, W)] for k, x in gw.items()}
+    for k, x in gw.items():
+        assert _digits_variant(x, l, logB, W, "ok") == ora[k], k                                       # the restatement is the oracle's function
+    half, m = 1 << (logB - 1), (1 << W) - 1
+    assert ora["all-min"] == [(-half) & m] * l and ora["all-max"] == [half - 1] * l and ora["top-min"][0] == (-half) & m
+    assert _digits_variant(gw["all-min"], l, logB, W, "carry") != ora["all-min"], "the carry of the prepared value kept in the top digit"
+    if W - l * logB >= 1:
+        assert ora["round-carry"] == [0] * l and ora["tie->all-min"] == ora["all-min"]
+        assert _digits_variant(gw["round-carry"], l, logB, W, "carry") != ora["round-carry"], "the rounding carry kept"
+        for k in ("tie", "round-carry", "tie->all-min"):
+            assert _digits_variant(gw[k], l, logB, W, "trunc") != ora[k], ("truncation", k)
+            assert _digits_variant(gw[k], l, logB, W, "tiedown") != ora[k], ("tie down", k)
+        assert _digits_variant(gw["tie-1"], l, logB, W, "trunc") == ora["tie-1"]                        # one below the tie: both agree, the tie alone tells
+
+
+@pytest.mark.parametrize("f,logD", sorted({(p.f, p.logD) for p in EC.KS_SETS + EC.KS_CHILD_SETS}))
+def test_keyswitch_classes_discriminate(f, logD):
+    Lb, bit, D = f * logD, 32 - f * logD, 1 << logD
+    kw = ks_words(f, logD)
+    dig = lambda w: [int(v) for v in O.unbalanced_decomp_word(w, f, logD, 32)]      # noqa: E731
+    assert dig(kw["all-D-1"]) == [D - 1] * f and dig(kw["zero"]) == [0] * f
+    if bit >= 1:
+        v = O.divbits(kw["u-carry"], bit, 32)
+        assert v == 1 << Lb and dig(kw["u-carry"]) == [0] * f                       # like the zero word
+        assert [(v >> (logD * (f - 1 - t))) & (D - 1 if t else ~0) for t in range(f)] != dig(kw["u-carry"]), "the carry kept in the top digit's index (no & Dm)"
+        assert dig(kw["u-carry-1"]) == [D - 1] * f
+        assert [(kw["u-tie"] >> bit >> (logD * (f - 1 - t))) & (D - 1) for t in range(f)] != dig(kw["u-tie"]), "truncation"
+        assert [(kw["u-tie-1"] >> bit >> (logD * (f - 1 - t))) & (D - 1) for t in range(f)] == dig(kw["u-tie-1"])
+    # 64-bit ring: the extracted word is the HIGH half, cut off (bootstrapping.jl:575): rounding the low half in gives another word
+    p = mk.KMS2party.scaled(n=4, N=64)
+    a = np.zeros(64, dtype=np.uint64)
+    a[0], a[63] = (5 << 32) | 0xFFFFFFFF, (7 << 32) | 0x80000000
+    w = extract_words(p, a)
+    assert int(w[0]) == 5 and int(w[1]) == (-7) & 0xFFFFFFFF
+    assert ((int(a[0]) + (1 << 31)) >> 32) != int(w[0]) and (-((int(a[63]) + (1 << 31)) >> 32)) & 0xFFFFFFFF != int(w[1])
+    assert int(extract_words(p, np.full(64, 1 << 63, dtype=np.uint64))[1]) == 0x80000000                # -x wraps to itself

@@ -16,7 +16,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import (GATE_FUNCS, O, ROOT, bits_equal, edge_words, encrypt_bits, gpu_scheme, keygen, mixed_party_check, mk,
+from helpers import (GATE_FUNCS, O, ROOT, bits_equal, edge_words, encrypt_bits, gpu_scheme, keygen, ks_edge_check, mixed_party_check, mk,
                      oracle_scheme)
 
 pytestmark = pytest.mark.gpu
@@ -464,6 +464,13 @@ def _child_ks():
         js = _sample(B, rng)
         assert np.array_equal(out[js], so.gate_batch(0, c[:B][js], c[B:][js], threads=8)), (p.name, "NAND")
         checks += len(js)
+        sg.close()
+    # the key-switch gadget's own boundaries (tests/test_gpu_edges.py), every ciphertext compared
+    from edge_cases import KS_BATCHES, KS_CHILD_FULL, KS_CHILD_SETS
+    for p, batches in [KS_CHILD_FULL] + [(q, KS_BATCHES) for q in KS_CHILD_SETS]:       # the full key length first: the launcher settings tile it
+        crs, keys = keygen(p, 98)
+        sg = gpu_scheme(p, crs, keys)
+        checks += ks_edge_check(p, oracle_scheme(p, crs, keys), sg, rng, batches)
         sg.close()
     return checks
 
