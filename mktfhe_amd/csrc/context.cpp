@@ -29,29 +29,36 @@ int env_int(const char *name, int dflt) { const char *v = getenv(name); return v
 // environment seeds them ONCE, at mkt_ctx_create; afterwards only mkt_set_option changes them -- the call path never
 // reads the environment.
 struct Tune {
-    int rot_variant = 0;
-    int rot_stagger = 16;   // tools/stagger.sh: 16.99 -> 15.63 ms at KMS k=2 N=1024 on one device, neutral elsewhere
-    int rot_split = 0;
-    int rot_wide = 0;       // latency variant: 0 automatic, 1 never, 2 always where supported
-    int rot_blkg = 0;       // block schemes: rotations per workgroup, 0 automatic
-    int ccs_stagger = 0;
-    int ccs_pipe = -1;      // two-group CCS kernel: -1 automatic (below one chip-fill), 0 never, 1 always
-    int rot_map = 1;        // workgroup id -> (ciphertext, slot) mapping of the k = 1 rotation kernels (kernel_common.h rot_decode): 1 = the RLEV rows of one
-                            // (ciphertext, party) on one XCD at one time -- 25 % less fabric traffic at KMS k = 2 (FETCH_SIZE 15.3 -> 11.4 GB per launch,
-                            // L2 misses -27 %), time -0.3 ... -2.5 % (profiles/r04j_bench_kms2_n1024_map{0,1}_pmc.txt)
-    int exact_wide = 1;     // EXACT (integer NTT) KMS phase 1 at l_gsw = 2 and KMS_block phase 1: 1 = the paired-transform kernel / one set of digit transforms per block (default), 0 = the one-at-a-time kernel (reference loop order; tests force both)
-    int exact_kany = 0;     // EXACT CGGI / LMSS: 1 = the run-time-RLWE-length kernel (sums in memory) also where the register kernels serve (k <= 3); tests
-    int fx_polymul_force = 0;   // diagnostic: 1 = mkt_exact_polymul_batch under exact_impl = 1 runs the Float64 kernel even where fx_polymul_bound does not certify the operands
-    int exact_impl = -1;    // EXACT blind rotation of CGGI (RLWE length 1) and KMS phase 1: 0 = integer NTT over two 30-bit primes (ntt_exact.hip), 1 / -1 = the Float64 pipe (ahead at every measured shape: profiles/r06_fx_shapes.txt)
-                            // (fx_exact.hip: FMA transforms over 16-bit key limbs) wherever its error bound certifies the loaded keys (fx_usable), the integer NTT elsewhere
-    void from_env() {
-        exact_impl = env_int("MKT_EXACT_IMPL", exact_impl);
-        rot_variant = env_int("MKT_ROT_VARIANT", rot_variant); rot_stagger = env_int("MKT_ROT_STAGGER", rot_stagger);
-        rot_split = env_int("MKT_ROT_SPLIT", rot_split); rot_wide = env_int("MKT_ROT_WIDE", rot_wide);
-        rot_blkg = env_int("MKT_ROT_BLKG", rot_blkg); ccs_stagger = env_int("MKT_CCS_STAGGER", ccs_stagger);
-        ccs_pipe = env_int("MKT_CCS_PIPE", ccs_pipe); exact_wide = env_int("MKT_EXACT_WIDE", exact_wide); rot_map = env_int("MKT_ROT_MAP", rot_map); exact_kany = env_int("MKT_EXACT_KANY", exact_kany);
-    }
+    int rot_variant, rot_stagger, rot_split, rot_wide, rot_blkg, ccs_stagger, ccs_pipe, rot_map, exact_wide, exact_kany, fx_polymul_force, exact_impl;
 };
+// One row per switch: mkt_set_option name, the environment variable that seeds it (nullptr: none), the member, its default, the values it
+// admits (none listed: any), and whether a change drops the workspace.
+struct Switch { const char *name, *env; int Tune::*member; int dflt; std::vector<int> allowed; bool resets_workspace; };
+const Switch SWITCHES[] = {
+    {"rot_variant", "MKT_ROT_VARIANT", &Tune::rot_variant, 0, {0, 21, 22}, false},   // a selector with a fixed set of values refuses the others (a call would otherwise fail late, inside a gate, or run nothing)
+    {"rot_stagger", "MKT_ROT_STAGGER", &Tune::rot_stagger, 16, {}, false},   // tools/stagger.sh: 16.99 -> 15.63 ms at KMS k=2 N=1024 on one device, neutral elsewhere
+    {"rot_split", "MKT_ROT_SPLIT", &Tune::rot_split, 0, {}, false},
+    {"rot_wide", "MKT_ROT_WIDE", &Tune::rot_wide, 0, {}, false},       // latency variant: 0 automatic, 1 never, 2 always where supported
+    {"rot_blkg", "MKT_ROT_BLKG", &Tune::rot_blkg, 0, {}, false},       // block schemes: rotations per workgroup, 0 automatic
+    {"ccs_stagger", "MKT_CCS_STAGGER", &Tune::ccs_stagger, 0, {}, false},
+    {"ccs_pipe", "MKT_CCS_PIPE", &Tune::ccs_pipe, -1, {}, false},      // two-group CCS kernel: -1 automatic (below one chip-fill), 0 never, 1 always
+    // workgroup id -> (ciphertext, slot) mapping of the k = 1 rotation kernels (kernel_common.h rot_decode): 1 = the RLEV rows of one
+    // (ciphertext, party) on one XCD at one time -- 25 % less fabric traffic at KMS k = 2 (FETCH_SIZE 15.3 -> 11.4 GB per launch,
+    // L2 misses -27 %), time -0.3 ... -2.5 % (profiles/r04j_bench_kms2_n1024_map{0,1}_pmc.txt)
+    {"rot_map", "MKT_ROT_MAP", &Tune::rot_map, 1, {0, 1}, false},
+    {"exact_wide", "MKT_EXACT_WIDE", &Tune::exact_wide, 1, {}, false},   // EXACT (integer NTT) KMS phase 1 at l_gsw = 2 and KMS_block phase 1: 1 = the paired-transform kernel / one set of digit transforms per block (default), 0 = the one-at-a-time kernel (reference loop order; tests force both)
+    {"exact_kany", "MKT_EXACT_KANY", &Tune::exact_kany, 0, {}, true},    // EXACT CGGI / LMSS: 1 = the run-time-RLWE-length kernel (sums in memory) also where the register kernels serve (k <= 3); tests.  The workspace gains / loses the kernel's scratch at the next call
+    {"fx_polymul_force", nullptr, &Tune::fx_polymul_force, 0, {}, false},   // diagnostic: 1 = mkt_exact_polymul_batch under exact_impl = 1 runs the Float64 kernel even where fx_polymul_bound does not certify the operands
+    // EXACT blind rotation of CGGI (RLWE length 1) and KMS phase 1: 0 = integer NTT over two 30-bit primes (ntt_exact.hip), 1 / -1 = the Float64 pipe (ahead at every measured shape: profiles/r06_fx_shapes.txt)
+    // (fx_exact.hip: FMA transforms over 16-bit key limbs) wherever its error bound certifies the loaded keys (fx_usable), the integer NTT elsewhere
+    {"exact_impl", "MKT_EXACT_IMPL", &Tune::exact_impl, -1, {}, false},
+};
+struct DevGuard {   // make the context's device current for the duration of a call
+    int prev = -1; bool ok = true;
+    explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; }
+    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+Tune tune_from_env() { Tune t; for (const Switch &w : SWITCHES) t.*w.member = w.env ? env_int(w.env, w.dflt) : w.dflt; return t; }
 }  // namespace
 
 thread_local const char *mktd::last_rot_kernel = "";
@@ -68,6 +75,14 @@ const mktd::LaunchTuning &mktd::launch_tuning() {
     return t;
 }
 
+// The resident tables of a key set, in the order they are allocated and replicated.  describe_key_set states each one ONCE;
+// allocation, replication, release and the per-party base pointers all read that description.
+enum KeyTable { T_TW, T_MONOMIAL, T_BRK, T_KSK, T_PUB, T_CRS, T_RLK_D, T_RLK_F, T_SLOT_PARTY, T_SLOT_ROW, T_FX_TAB, T_FX_BRK, T_FX_STAT, T_NTT, T_COUNT };
+struct ResidentTable {
+    void **slot = nullptr; size_t elems = 0, esize = 0;   // the KeySet member that holds the device pointer; elements per party (or in the whole table): the party stride; bytes per element
+    bool per_party = false, present = false, cloned = false;   // [nparty][elems], else one per key set; this scheme, arithmetic and shape have the table; mkt_internal_clone_keys copies it (false: every context builds its own at mkt_ctx_create)
+    size_t bytes(int nparty) const { return (per_party ? (size_t)nparty : 1) * elems * esize; }
+};
 // The evaluation keys and tables of one scheme on one device: immutable once a second context shares them
 // (mkt_ctx_fork), freed when the last context that holds them is destroyed.  This is the reference's scheme object
 // proper -- read-only during evaluation, shared by concurrent callers (bootstrapping.jl:38-45 allocates all scratch per
@@ -77,8 +92,8 @@ struct KeySet {
     mkt::Twiddles tw;
     cplx *d_tw = nullptr;        // psi | psiinv | roots | rootsinv, M each
     cplx *d_monomial = nullptr;  // [2N][M]
-    cplx *d_brk = nullptr;  size_t brk_party_cplx = 0;  std::vector<char> brk_loaded;
-    uint32_t *d_ksk = nullptr; size_t ksk_party_words = 0; int n1p = 0; std::vector<char> ksk_loaded;
+    cplx *d_brk = nullptr;  std::vector<char> brk_loaded;
+    uint32_t *d_ksk = nullptr; int n1p = 0; std::vector<char> ksk_loaded;
     cplx *d_rlk_d = nullptr, *d_rlk_f = nullptr, *d_pub = nullptr, *d_crs = nullptr;
     std::vector<char> rlk_loaded, pub_loaded; bool crs_loaded = false;
     // rotation slots (KMS phase 1: party-major rows)
@@ -87,16 +102,15 @@ struct KeySet {
     uint64_t *d_ntt = nullptr;   // MKT_ARITH_EXACT: psi_rev (negated) | N^-1, N^-1 w | N^-1 2^32, N^-1 2^32 w, with Shoup companions
     // MKT_ARITH_EXACT on the Float64 pipe (fx_exact.hip), where the shape has the kernel: the engine's own tables and the bootstrapping key as limb transforms
     cplx *d_fx_tab = nullptr;    // fx_om | fx_tw | fx_nat, M each
-    cplx *d_fx_brk = nullptr;  size_t fx_brk_party_cplx = 0;   // [party][n][2l][2][W/16][M], scaled by 1 / M
+    cplx *d_fx_brk = nullptr;    // [party][n][2l][2][W/16][M], scaled by 1 / M
     unsigned long long *d_fx_stat = nullptr;   // largest |key transform value|^2 over the loaded keys (bit pattern)
     double fx_kmax = 0.0;        // sqrt of [0], read back after every key load
+    ResidentTable tab[T_COUNT];  // describe_key_set
+    size_t stride(KeyTable t) const { return tab[t].elems; }   // elements from one party's rows to the next
+    template <class T> T *party(KeyTable t, int party) const { return static_cast<T *>(*tab[t].slot) + (size_t)party * tab[t].elems; }   // base of one party's rows
     ~KeySet() {
-        int prev = -1;
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-        void *ptrs[] = {d_tw, d_monomial, d_brk, d_ksk, d_rlk_d, d_rlk_f, d_pub, d_crs, d_slot_party, d_slot_row, d_ntt, d_fx_tab, d_fx_brk, d_fx_stat};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-        if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+        DevGuard g(device);
+        for (const ResidentTable &t : tab) if (t.slot && *t.slot) (void)hipFree(*t.slot);
     }
 };
 
@@ -111,7 +125,6 @@ struct mkt_ctx {
     std::string err;
     std::shared_ptr<KeySet> ks;  // shared with the contexts forked from this one
     bool exact = false;          // MKT_ARITH_EXACT (integer NTT, two 30-bit primes)
-    uint64_t *d_ntt = nullptr;   // = ks->d_ntt (owned by the key set: shared by forks)
     int split = 1;               // EXACT on the 64-bit ring: every resident 64-bit table is kept as (low, high) residue polynomials -> 2 per logical polynomial
     // workspace
     size_t ws_gates = 0;
@@ -123,7 +136,7 @@ struct mkt_ctx {
     // timing
     bool timing = false;
     std::vector<TimedSpan> spans;
-    Tune tune;
+    Tune tune{};
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
     // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
     unsigned long long *d_pm_stat = nullptr;   // [0] max|a_i| over the batch, [1] largest |limb transform of b|^2, [2] largest |q - round(q)| of the Float64 kernel (bit patterns)
@@ -146,11 +159,7 @@ int hipfail(mkt_ctx *c, hipError_t e, const char *what) {
 }
 #define HIPCHK(c, call) do { hipError_t _e = (call); if (_e != hipSuccess) return hipfail((c), _e, #call); } while (0)
 
-struct DevGuard {   // make the context's device current for the duration of a call
-    int prev = -1; bool ok = true;
-    explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+int keys_writable(mkt_ctx *c) { return c->keys_shared() ? fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable") : MKT_OK; }
 
 struct Timer {
     mkt_ctx *c; int cls; hipEvent_t a = nullptr, b = nullptr;
@@ -171,11 +180,20 @@ void clear_spans(mkt_ctx *c) {
 
 size_t poly_bytes(const mkt_ctx *c) { return (size_t)c->p.N * c->sh.word; }
 
-// transform `npolys` coefficient-form polynomials (host) into TransPolys at `dst` (device)
 int fx_after_key_load(mkt_ctx *c);
 bool fx_usable(const mkt_ctx *c);
 mktd::FxRotArgs fx_rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre);
-int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt, bool small = false, cplx *fx_dst = nullptr) {   // small: coefficients far below 2^32 in magnitude (monomials): never split; fx_dst: also as limb transforms (fx_exact.hip)
+// `npolys` coefficient-form polynomials on the device (src) into the resident form of this context's tables at dst.  small: coefficients far below 2^32 in magnitude
+// (monomials): never split; fx_dst: also as limb transforms (fx_exact.hip), their largest magnitude gathered in d_fx_stat (fx_after_key_load reads it once the stream is drained)
+hipError_t to_resident(mkt_ctx *c, const void *src, size_t npolys, cplx *dst, bool small, cplx *fx_dst) {
+    hipError_t e = !c->exact ? mktd::launch_transform_fwd(c->logM, c->p.W, c->twp(), src, dst, npolys, c->dev_order, c->stream)
+                   : (c->split == 2 && !small) ? mktd::launch_ntt_fwd_split(c->logN, c->ks->d_ntt, src, reinterpret_cast<uint64_t *>(dst), npolys, c->stream)   // 2 residue polynomials per input
+                   : mktd::launch_ntt_fwd(c->logN, c->p.W, c->ks->d_ntt, src, reinterpret_cast<uint64_t *>(dst), npolys, 1, c->stream);   // N residues = the bytes of M complex
+    if (e == hipSuccess && fx_dst) e = mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), src, fx_dst, npolys, c->ks->d_fx_stat, c->stream);
+    return e;
+}
+// transform `npolys` coefficient-form polynomials (host) into TransPolys at `dst` (device)
+int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt, bool small = false, cplx *fx_dst = nullptr) {
     if (c->exact && fmt != MKT_FMT_INT_COEFF) return fail(c, MKT_ERR_UNSUPPORTED, "an MKT_ARITH_EXACT context takes keys in integer form (MKT_FMT_INT_COEFF)");
     if (fmt == MKT_FMT_F64_FFT) {   // the reference's Trans* values: copy, then natural -> device point order
         cplx *tmpc = nullptr;
@@ -192,10 +210,7 @@ int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt
     void *tmp = nullptr;
     HIPCHK(c, hipMalloc(&tmp, npolys * poly_bytes(c)));
     hipError_t e = hipMemcpyAsync(tmp, host, npolys * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = !c->exact ? mktd::launch_transform_fwd(c->logM, c->p.W, c->twp(), tmp, dst, npolys, c->dev_order, c->stream)
-                           : (c->split == 2 && !small) ? mktd::launch_ntt_fwd_split(c->logN, c->d_ntt, tmp, reinterpret_cast<uint64_t *>(dst), npolys, c->stream)   // 2 residue polynomials per input
-                           : mktd::launch_ntt_fwd(c->logN, c->p.W, c->d_ntt, tmp, reinterpret_cast<uint64_t *>(dst), npolys, 1, c->stream);   // N residues = the bytes of M complex
-    if (e == hipSuccess && fx_dst) e = mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), tmp, fx_dst, npolys, c->ks->d_fx_stat, c->stream);
+    if (e == hipSuccess) e = to_resident(c, tmp, npolys, dst, small, fx_dst);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(tmp);
     if (e != hipSuccess) return hipfail(c, e, "key pre-transform");
@@ -238,27 +253,45 @@ int upload_twiddles(mkt_ctx *c) {
     return MKT_OK;
 }
 
+// Which blind-rotation kernel family serves the context now: do_blindrotate launches by it, ensure_workspace sizes the scratch it hands over by it.
+enum class Route { F64_K1, F64_KR, F64_KANY, F64_KMS, F64_CCS, EXACT_CCS, EXACT_KMS, EXACT_KANY, EXACT_KR, EXACT_FX, EXACT_K1 };   // what each is: do_blindrotate
+Route rot_route(const mkt_ctx *c) {
+    const mkt_params &p = c->p;
+    if (p.scheme == MKT_CCS) return c->exact ? Route::EXACT_CCS : Route::F64_CCS;
+    if (c->exact) {
+        if (mkt::is_kms(p.scheme)) return Route::EXACT_KMS;
+        if (p.k > 3 || c->tune.exact_kany == 1) return Route::EXACT_KANY;
+        if (p.k > 1 || (mkt::is_block(p.scheme) && p.blk_len != 3)) return Route::EXACT_KR;
+        return p.scheme == MKT_CGGI && fx_usable(c) ? Route::EXACT_FX : Route::EXACT_K1;
+    }
+    if (mkt::is_kms(p.scheme)) return Route::F64_KMS;
+    return p.k > 3 ? Route::F64_KANY : p.k > 1 ? Route::F64_KR : Route::F64_K1;
+}
+
 int ensure_workspace(mkt_ctx *c, size_t gates) {
     if (gates <= c->ws_gates) return MKT_OK;
-    if (c->ws_lin) (void)hipFree(c->ws_lin);
-    if (c->ws_acc) (void)hipFree(c->ws_acc);
-    if (c->ws_lev) (void)hipFree(c->ws_lev);
-    if (c->ws_scratch) (void)hipFree(c->ws_scratch);
-    if (c->ws_fxacc) (void)hipFree(c->ws_fxacc);
-    c->ws_lin = nullptr; c->ws_acc = nullptr; c->ws_lev = nullptr; c->ws_scratch = nullptr; c->ws_fxacc = nullptr; c->ws_gates = 0;
-    const mkt_params &p = c->p;
-    HIPCHK(c, hipMalloc((void **)&c->ws_lin, gates * (size_t)c->sh.lwe_len * 4));
-    HIPCHK(c, hipMalloc(&c->ws_acc, gates * (size_t)(1 + c->sh.kacc) * poly_bytes(c)));
-    if (mkt::is_kms(p.scheme)) {
-        HIPCHK(c, hipMalloc((void **)&c->ws_lev, gates * (size_t)c->ks->rtot * 2 * c->M * sizeof(cplx) * c->split));
-        HIPCHK(c, hipMalloc((void **)&c->ws_scratch, gates * (size_t)2 * (p.k + 1) * c->M * sizeof(cplx) * c->split));
-        if (c->ks->d_fx_brk) HIPCHK(c, hipMalloc(&c->ws_fxacc, gates * (size_t)c->ks->rtot * 2 * poly_bytes(c)));
-    } else if (p.scheme == MKT_CCS) {
-        HIPCHK(c, hipMalloc((void **)&c->ws_lev, gates * 3 * poly_bytes(c)));    // v scratch (ring words): parked v + two hand-off slots
-        HIPCHK(c, hipMalloc((void **)&c->ws_scratch, gates * (size_t)(p.k + 1) * c->M * sizeof(cplx)));
-    } else if (p.k > 3 || (c->exact && c->tune.exact_kany == 1)) {                      // CGGI / LMSS beyond RLWE length 3: tacc and tacc2 of blindrotate_kany_kernel / exact_blindrotate_kany_kernel (same byte count)
-        HIPCHK(c, hipMalloc((void **)&c->ws_scratch, gates * (size_t)2 * (p.k + 1) * c->M * sizeof(cplx)));
+    void **ws[] = {(void **)&c->ws_lin, &c->ws_acc, (void **)&c->ws_lev, (void **)&c->ws_scratch, &c->ws_fxacc};
+    for (void **w : ws) { if (*w) (void)hipFree(*w); *w = nullptr; }
+    c->ws_gates = 0;
+    const size_t tpoly = (size_t)c->M * sizeof(cplx);   // one transformed polynomial
+    size_t lev = 0, scratch = 0, fxacc = 0;              // bytes per gate of what the route's kernels are handed
+    switch (rot_route(c)) {
+    case Route::F64_KMS: case Route::EXACT_KMS:
+        lev = (size_t)c->ks->rtot * 2 * tpoly * c->split;
+        scratch = (size_t)2 * (c->p.k + 1) * tpoly * c->split;
+        if (c->ks->d_fx_brk) fxacc = (size_t)c->ks->rtot * 2 * poly_bytes(c);   // whenever the key set holds limb transforms: fx_phase1 is a per-call choice
+        break;
+    case Route::F64_CCS: case Route::EXACT_CCS:
+        lev = 3 * poly_bytes(c);    // v scratch (ring words): parked v + two hand-off slots
+        scratch = (size_t)(c->p.k + 1) * tpoly;
+        break;
+    case Route::F64_KANY: case Route::EXACT_KANY:   // CGGI / LMSS beyond RLWE length 3: tacc and tacc2 of blindrotate_kany_kernel / exact_blindrotate_kany_kernel (same byte count)
+        scratch = (size_t)2 * (c->p.k + 1) * tpoly;
+        break;
+    default: break;                                 // the register kernels keep their sums to themselves
     }
+    const size_t need[] = {(size_t)c->sh.lwe_len * 4, (size_t)(1 + c->sh.kacc) * poly_bytes(c), lev, scratch, fxacc};
+    for (int i = 0; i < 5; i++) if (need[i]) HIPCHK(c, hipMalloc(ws[i], gates * need[i]));
     c->ws_gates = gates;
     return MKT_OK;
 }
@@ -279,7 +312,7 @@ int check_ready(mkt_ctx *c, bool need_brk, bool need_ksk) {
 mktd::RotArgs rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre) {
     const mkt_params &p = c->p;
     mktd::RotArgs a{};
-    a.tw = c->twp(); a.brk = c->ks->d_brk; a.brk_party_stride = c->ks->brk_party_cplx; a.monomial = c->ks->d_monomial;
+    a.tw = c->twp(); a.brk = c->ks->d_brk; a.brk_party_stride = c->ks->stride(T_BRK); a.monomial = c->ks->d_monomial;
     a.lwe = lwe; a.lwe_stride = stride; a.pre_switched = pre; a.n = p.n; a.logN = c->logN;
     a.l = p.l_gsw; a.logB = p.logB_gsw;
     a.blk_len = mkt::is_block(p.scheme) ? p.blk_len : 1;
@@ -291,23 +324,66 @@ mktd::RotArgs rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre) {
     return a;
 }
 
+// EXACT KMS (64-bit ring, split tables; ntt_exact.hip): everything the context and its key set fix; the caller adds levkey, the phase flags and, for phase 2, lin_for_tv / acc / scratch
+mktd::ExactKmsArgs exact_kms_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre) {
+    const mkt_params &p = c->p;
+    mktd::ExactKmsArgs q{};
+    q.brk = reinterpret_cast<const uint64_t *>(c->ks->d_brk); q.brk_party_stride = c->ks->stride(T_BRK) * 2 /* in 8-byte residue pairs */; q.mono = reinterpret_cast<const uint64_t *>(c->ks->d_monomial);
+    q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.k = p.k; q.l_gsw = p.l_gsw; q.logB_gsw = p.logB_gsw;
+    q.l_lev = p.l_lev; q.logB_lev = p.logB_lev; q.l_uni = p.l_uni; q.logB_uni = p.logB_uni; q.rtot = c->ks->rtot; q.lwe_len = c->sh.lwe_len; q.blk_len = p.scheme == MKT_KMS_BLOCK ? p.blk_len : 1;
+    q.slot_party = c->ks->d_slot_party; q.slot_row = c->ks->d_slot_row;
+    q.rlk_d = reinterpret_cast<const uint64_t *>(c->ks->d_rlk_d); q.rlk_f = reinterpret_cast<const uint64_t *>(c->ks->d_rlk_f);
+    q.pub_b = reinterpret_cast<const uint64_t *>(c->ks->d_pub); q.crs = reinterpret_cast<const uint64_t *>(c->ks->d_crs);
+    q.wide = c->tune.exact_wide;
+    return q;
+}
+// EXACT KMS phase 1 of `gates` gates on the Float64 pipe (a per-call choice: fx_usable; ensure_workspace holds ws_fxacc whenever the key set has the limb transforms): rows as ring words in ws_fxacc, then as split residue tables at levkey for the integer phase 2
+int fx_phase1(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, size_t gates, uint64_t *levkey) {
+    mktd::FxRotArgs f = fx_rot_args(c, lwe, stride, pre);
+    f.init_mode = 1; f.acc_io = c->ws_fxacc; f.ngates = gates;
+    const size_t nrot = gates * (size_t)c->ks->rtot;
+    HIPCHK(c, mktd::launch_fx_blindrotate(c->logM, c->p.W, f, nrot, c->stream));
+    HIPCHK(c, mktd::launch_ntt_fwd_split(c->logN, c->ks->d_ntt, c->ws_fxacc, levkey, nrot * 2, c->stream));
+    return MKT_OK;
+}
+
 // blind rotation of `B` accumulators resident at `acc` ([B][1+k][N]); atilde source described by (lwe, stride, pre)
 int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const uint32_t *lin_for_tv, void *acc, cplx *lev, cplx *scratch, size_t B) {
     const mkt_params &p = c->p;
-    if (p.scheme == MKT_CCS && c->exact) {   // hybrid products over Z_P (ntt_exact.hip)
-        mktd::ExactCcsHostArgs q{};
-        q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.k = p.k; q.l = p.l_uni; q.logB = p.logB_uni;
-        q.brk = reinterpret_cast<const uint64_t *>(c->ks->d_brk); q.brk_party_stride = c->ks->brk_party_cplx * 2;
-        q.pub_b = reinterpret_cast<const uint64_t *>(c->ks->d_pub); q.crs = reinterpret_cast<const uint64_t *>(c->ks->d_crs);
-        q.mono = reinterpret_cast<const uint64_t *>(c->ks->d_monomial); q.acc = (uint32_t *)acc; q.scratch = reinterpret_cast<uint64_t *>(scratch);
-        Timer tm(c, 1);
-        HIPCHK(c, mktd::launch_exact_ccs(c->logN, c->d_ntt, q, B, c->stream));
+    const Route route = rot_route(c);
+    if (route == Route::F64_KMS) {   // phase 1 (the rows of every party, as transforms), then phase 2
+        {
+            mktd::RotArgs a = rot_args(c, lwe, stride, pre);
+            a.init_mode = 1; a.out_mode = 1; a.tout = lev; a.tout_natural = 0; a.ngates = B;
+            Timer tm(c, 1);
+            HIPCHK(c, mktd::launch_blindrotate_k1(c->logM, p.W, a, B * (size_t)c->ks->rtot, c->stream));
+        }
+        mktd::Phase2Args q{};
+        q.tw = c->twp(); q.lin = lin_for_tv; q.lwe_stride = c->sh.lwe_len; q.logN = c->logN;
+        q.k = p.k; q.l_lev = p.l_lev; q.logB_lev = p.logB_lev; q.l_uni = p.l_uni; q.logB_uni = p.logB_uni;
+        q.levkey = lev; q.rtot = c->ks->rtot; q.rlk_d = c->ks->d_rlk_d; q.rlk_f = c->ks->d_rlk_f; q.pub_b = c->ks->d_pub; q.crs = c->ks->d_crs;
+        q.acc = acc; q.scratch = scratch; q.dev_order = c->dev_order;
+        Timer tm(c, 4);
+        HIPCHK(c, mktd::launch_kms_phase2(c->logM, p.W, q, B, c->stream));
         return MKT_OK;
     }
-    if (p.scheme == MKT_CCS) {
+    const uint64_t *xbrk = reinterpret_cast<const uint64_t *>(c->ks->d_brk), *xmono = reinterpret_cast<const uint64_t *>(c->ks->d_monomial);   // the tables as the integer kernels read them
+    const int blk_len = mkt::is_block(p.scheme) ? p.blk_len : 1;
+    Timer tm(c, 1);   // every other route is one span of class 1 around its launches
+    switch (route) {
+    case Route::EXACT_CCS: {   // hybrid products over Z_P (ntt_exact.hip)
+        mktd::ExactCcsHostArgs q{};
+        q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.k = p.k; q.l = p.l_uni; q.logB = p.logB_uni;
+        q.brk = xbrk; q.brk_party_stride = c->ks->stride(T_BRK) * 2;
+        q.pub_b = reinterpret_cast<const uint64_t *>(c->ks->d_pub); q.crs = reinterpret_cast<const uint64_t *>(c->ks->d_crs);
+        q.mono = xmono; q.acc = (uint32_t *)acc; q.scratch = reinterpret_cast<uint64_t *>(scratch);
+        HIPCHK(c, mktd::launch_exact_ccs(c->logN, c->ks->d_ntt, q, B, c->stream));
+        return MKT_OK;
+    }
+    case Route::F64_CCS: {
         mktd::CcsArgs q{};
         q.tw = c->twp(); q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.logN = c->logN; q.k = p.k;
-        q.l = p.l_uni; q.logB = p.logB_uni; q.brk = c->ks->d_brk; q.brk_party_stride = c->ks->brk_party_cplx; q.pub_b = c->ks->d_pub; q.crs = c->ks->d_crs;
+        q.l = p.l_uni; q.logB = p.logB_uni; q.brk = c->ks->d_brk; q.brk_party_stride = c->ks->stride(T_BRK); q.pub_b = c->ks->d_pub; q.crs = c->ks->d_crs;
         q.monomial = c->ks->d_monomial; q.acc = acc; q.scratch = scratch; q.vscratch = lev;
         q.stagger = c->tune.ccs_stagger; q.dev_order = c->dev_order;
         // batches that leave compute units idle run each ciphertext on two thread groups (ccs_pipe.hip); option ccs_pipe: 0 never,
@@ -315,7 +391,6 @@ int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const u
         const int pipe = c->tune.ccs_pipe;
         const size_t fill = (size_t)256 * (c->logM <= 9 ? 4 : 2);
         const bool use_pipe = pipe == 1 || (pipe < 0 && B * 2 <= fill);
-        Timer tm(c, 1);
         if (use_pipe) {
             const hipError_t e = mktd::launch_ccs_pipe(c->logM, p.W, q, B, c->stream);
             if (e == hipSuccess) return MKT_OK;
@@ -324,92 +399,47 @@ int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const u
         HIPCHK(c, mktd::launch_ccs_blindrotate(c->logM, p.W, q, B, c->stream));
         return MKT_OK;
     }
-    if (c->exact && mkt::is_kms(p.scheme)) {   // 64-bit ring, split tables: phase 1 and phase 2 with exact products (ntt_exact.hip)
-        mktd::ExactKmsArgs q{};
-        q.brk = reinterpret_cast<const uint64_t *>(c->ks->d_brk); q.brk_party_stride = c->ks->brk_party_cplx * 2 /* in 8-byte residue pairs */; q.mono = reinterpret_cast<const uint64_t *>(c->ks->d_monomial);
-        q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.k = p.k; q.l_gsw = p.l_gsw; q.logB_gsw = p.logB_gsw;
-        q.l_lev = p.l_lev; q.logB_lev = p.logB_lev; q.l_uni = p.l_uni; q.logB_uni = p.logB_uni; q.rtot = c->ks->rtot; q.lwe_len = c->sh.lwe_len; q.blk_len = p.scheme == MKT_KMS_BLOCK ? p.blk_len : 1;
-        q.slot_party = c->ks->d_slot_party; q.slot_row = c->ks->d_slot_row; q.levkey = reinterpret_cast<uint64_t *>(lev);
-        q.rlk_d = reinterpret_cast<const uint64_t *>(c->ks->d_rlk_d); q.rlk_f = reinterpret_cast<const uint64_t *>(c->ks->d_rlk_f);
-        q.pub_b = reinterpret_cast<const uint64_t *>(c->ks->d_pub); q.crs = reinterpret_cast<const uint64_t *>(c->ks->d_crs);
-        q.lin_for_tv = lin_for_tv; q.acc = reinterpret_cast<uint64_t *>(acc); q.scratch = reinterpret_cast<uint64_t *>(scratch); q.phase1_only = 0; q.wide = c->tune.exact_wide;
-        Timer tm(c, 1);
-        if (p.scheme == MKT_KMS && fx_usable(c) && c->ws_fxacc) {   // phase 1 on the Float64 pipe: rows as ring words, then as split residue tables for the integer phase 2
-            mktd::FxRotArgs f = fx_rot_args(c, lwe, stride, pre);
-            f.init_mode = 1; f.acc_io = c->ws_fxacc; f.ngates = B;
-            const size_t nrot = B * (size_t)c->ks->rtot;
-            HIPCHK(c, mktd::launch_fx_blindrotate(c->logM, p.W, f, nrot, c->stream));
-            HIPCHK(c, mktd::launch_ntt_fwd_split(c->logN, c->d_ntt, c->ws_fxacc, q.levkey, nrot * 2, c->stream));
+    case Route::EXACT_KMS: {   // 64-bit ring, split tables: phase 1 and phase 2 with exact products (ntt_exact.hip)
+        mktd::ExactKmsArgs q = exact_kms_args(c, lwe, stride, pre);
+        q.levkey = reinterpret_cast<uint64_t *>(lev); q.lin_for_tv = lin_for_tv; q.acc = reinterpret_cast<uint64_t *>(acc); q.scratch = reinterpret_cast<uint64_t *>(scratch);
+        if (p.scheme == MKT_KMS && fx_usable(c)) {
+            if (int r = fx_phase1(c, lwe, stride, pre, B, q.levkey)) return r;
             q.phase2_only = 1;
         }
-        HIPCHK(c, mktd::launch_exact_kms(c->logN, c->d_ntt, q, B, c->stream));
+        HIPCHK(c, mktd::launch_exact_kms(c->logN, c->ks->d_ntt, q, B, c->stream));
         if (q.phase2_only) mktd::last_rot_kernel = "fx_blindrotate_kernel";
         return MKT_OK;
     }
-    if (c->exact && (p.k > 3 || c->tune.exact_kany == 1)) {   // CGGI / LMSS, any RLWE length: sums in memory
-        Timer tm(c, 1);
-        HIPCHK(c, mktd::launch_exact_blindrotate_kany(c->logN, c->d_ntt, reinterpret_cast<const uint64_t *>(c->ks->d_brk), reinterpret_cast<const uint64_t *>(c->ks->d_monomial),
-                                                      lwe, stride, pre, p.n, p.k, p.l_gsw, p.logB_gsw, mkt::is_block(p.scheme) ? p.blk_len : 1, (uint32_t *)acc,
+    case Route::EXACT_KANY:   // CGGI / LMSS, any RLWE length: sums in memory
+        HIPCHK(c, mktd::launch_exact_blindrotate_kany(c->logN, c->ks->d_ntt, xbrk, xmono, lwe, stride, pre, p.n, p.k, p.l_gsw, p.logB_gsw, blk_len, (uint32_t *)acc,
                                                       reinterpret_cast<uint64_t *>(scratch), B, c->stream));
         return MKT_OK;
-    }
-    if (c->exact && (p.k > 1 || (mkt::is_block(p.scheme) && p.blk_len != 3))) {   // CGGI / LMSS with RLWE length 2, 3 or another block length: the general kernel
-        Timer tm(c, 1);
-        HIPCHK(c, mktd::launch_exact_blindrotate_kr(c->logN, c->d_ntt, reinterpret_cast<const uint64_t *>(c->ks->d_brk), reinterpret_cast<const uint64_t *>(c->ks->d_monomial),
-                                                    lwe, stride, pre, p.n, p.k, p.l_gsw, p.logB_gsw, mkt::is_block(p.scheme) ? p.blk_len : 1, (uint32_t *)acc, B, c->stream));
+    case Route::EXACT_KR:     // CGGI / LMSS with RLWE length 2, 3 or another block length: the general kernel
+        HIPCHK(c, mktd::launch_exact_blindrotate_kr(c->logN, c->ks->d_ntt, xbrk, xmono, lwe, stride, pre, p.n, p.k, p.l_gsw, p.logB_gsw, blk_len, (uint32_t *)acc, B, c->stream));
         return MKT_OK;
-    }
-    if (c->exact && p.scheme == MKT_CGGI && fx_usable(c)) {   // CGGI on the Float64 pipe (fx_exact.hip)
+    case Route::EXACT_K1:     // CGGI / LMSS, RLWE length 1, 32-bit ring (exact_gate_ok): every product exact mod 2^32
+        HIPCHK(c, mktd::launch_exact_blindrotate(c->logN, c->ks->d_ntt, xbrk, xmono, lwe, stride, pre, p.n, p.l_gsw, p.logB_gsw, blk_len, (uint32_t *)acc, B, c->stream));
+        return MKT_OK;
+    case Route::EXACT_FX: {   // CGGI on the Float64 pipe (fx_exact.hip)
         mktd::FxRotArgs f = fx_rot_args(c, lwe, stride, pre);
         f.init_mode = 0; f.acc_io = acc; f.ngates = B;
-        Timer tm(c, 1);
         HIPCHK(c, mktd::launch_fx_blindrotate(c->logM, p.W, f, B, c->stream));
         return MKT_OK;
     }
-    if (c->exact) {          // CGGI / LMSS, RLWE length 1, 32-bit ring (exact_gate_ok): every product exact mod 2^32
-        Timer tm(c, 1);
-        HIPCHK(c, mktd::launch_exact_blindrotate(c->logN, c->d_ntt, reinterpret_cast<const uint64_t *>(c->ks->d_brk), reinterpret_cast<const uint64_t *>(c->ks->d_monomial),
-                                                 lwe, stride, pre, p.n, p.l_gsw, p.logB_gsw, mkt::is_block(p.scheme) ? p.blk_len : 1, (uint32_t *)acc, B, c->stream));
-        return MKT_OK;
+    default: break;           // F64_K1, F64_KR, F64_KANY
     }
-    if (!mkt::is_kms(p.scheme)) {
-        mktd::RotArgs a = rot_args(c, lwe, stride, pre);
-        a.init_mode = 0; a.out_mode = 0; a.acc_io = acc;
-        Timer tm(c, 1);
-        if (p.k > 3) {   // any RLWE length: accumulators in memory (blindrotate_kany_kernel)
-            a.ngates = B;
-            HIPCHK(c, mktd::launch_blindrotate_kany(c->logM, p.W, p.k, a, scratch, B, c->stream));
-            return MKT_OK;
-        }
-        if (p.k > 1) {   // RLWE length 2, 3 (CGGI, LMSS): accumulators in registers
-            a.ngates = B;
-            HIPCHK(c, mktd::launch_blindrotate_kr(c->logM, p.W, p.k, a, B, c->stream));
-            return MKT_OK;
-        }
-        a.ngates = B;
-        HIPCHK(c, mktd::launch_blindrotate_k1(c->logM, p.W, a, B, c->stream));
-        return MKT_OK;
-    }
-    {
-        mktd::RotArgs a = rot_args(c, lwe, stride, pre);
-        a.init_mode = 1; a.out_mode = 1; a.tout = lev; a.tout_natural = 0; a.ngates = B;
-        Timer tm(c, 1);
-        HIPCHK(c, mktd::launch_blindrotate_k1(c->logM, p.W, a, B * (size_t)c->ks->rtot, c->stream));
-    }
-    mktd::Phase2Args q{};
-    q.tw = c->twp(); q.lin = lin_for_tv; q.lwe_stride = c->sh.lwe_len; q.logN = c->logN;
-    q.k = p.k; q.l_lev = p.l_lev; q.logB_lev = p.logB_lev; q.l_uni = p.l_uni; q.logB_uni = p.logB_uni;
-    q.levkey = lev; q.rtot = c->ks->rtot; q.rlk_d = c->ks->d_rlk_d; q.rlk_f = c->ks->d_rlk_f; q.pub_b = c->ks->d_pub; q.crs = c->ks->d_crs;
-    q.acc = acc; q.scratch = scratch; q.dev_order = c->dev_order;
-    Timer tm(c, 4);
-    HIPCHK(c, mktd::launch_kms_phase2(c->logM, p.W, q, B, c->stream));
+    mktd::RotArgs a = rot_args(c, lwe, stride, pre);
+    a.init_mode = 0; a.out_mode = 0; a.acc_io = acc; a.ngates = B;
+    if (route == Route::F64_KANY) HIPCHK(c, mktd::launch_blindrotate_kany(c->logM, p.W, p.k, a, scratch, B, c->stream));   // any RLWE length: accumulators in memory (blindrotate_kany_kernel)
+    else if (route == Route::F64_KR) HIPCHK(c, mktd::launch_blindrotate_kr(c->logM, p.W, p.k, a, B, c->stream));         // RLWE length 2, 3 (CGGI, LMSS): accumulators in registers
+    else HIPCHK(c, mktd::launch_blindrotate_k1(c->logM, p.W, a, B, c->stream));
     return MKT_OK;
 }
 
 int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B) {
     const mkt_params &p = c->p;
     mktd::KsArgs a{};
-    a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->ksk_party_words; a.n1p = c->ks->n1p;
+    a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->stride(T_KSK); a.n1p = c->ks->n1p;
     a.N = p.N; a.n = p.n; a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.kacc = c->sh.kacc;
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
     size_t dw = 0, pw = 0;
@@ -496,12 +526,9 @@ int upload_ntt_tables(mkt_ctx *c) {
         const uint32_t cs[4] = {ninv, ntt_mulmod(ninv, wlast, p), ninv_r, ntt_mulmod(ninv_r, wlast, p)};
         for (int q = 0; q < 4; q++) { tab[(size_t)(N + q) * 4 + 2 * k] = cs[q]; tab[(size_t)(N + q) * 4 + 2 * k + 1] = ntt_shoup(cs[q], p); }
     }
-    HIPCHK(c, hipMalloc((void **)&c->ks->d_ntt, tab.size() * 4));
-    c->d_ntt = c->ks->d_ntt;
-    HIPCHK(c, hipMemcpy(c->d_ntt, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ks->d_ntt, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     return MKT_OK;
 }
-// the gate path of an EXACT context: CGGI with RLWE length 1 on the 32-bit ring (every true product coefficient < p / 2)
 // (every true product coefficient below P / 2 = 2^58.9998: 2l polynomials of N digits of magnitude <= 2^(logB-1) against 32-bit words)
 bool exact_gate_ok(const mkt_ctx *c) {
     const double half_P = 0.5 * (double)NTT_P[0] * (double)NTT_P[1];
@@ -576,11 +603,40 @@ int fx_after_key_load(mkt_ctx *c) {   // the key's largest transform magnitude, 
 mktd::FxRotArgs fx_rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre) {
     const mkt_params &p = c->p;
     mktd::FxRotArgs q{};
-    q.om = c->fx_om(); q.twist = c->fx_tw(); q.nat = c->fx_nat(); q.brk = c->ks->d_fx_brk; q.brk_party_stride = c->ks->fx_brk_party_cplx;
+    q.om = c->fx_om(); q.twist = c->fx_tw(); q.nat = c->fx_nat(); q.brk = c->ks->d_fx_brk; q.brk_party_stride = c->ks->stride(T_FX_BRK);
     q.lwe = lwe; q.lwe_stride = stride; q.pre_switched = pre; q.n = p.n; q.logN = c->logN; q.l = p.l_gsw; q.logB = p.logB_gsw;
     q.rows_per_gate = c->ks->rtot; q.slot_party = c->ks->d_slot_party; q.slot_row = c->ks->d_slot_row; q.logB_lev = p.logB_lev;
     q.stagger = c->tune.rot_stagger; q.map_mode = c->tune.rot_map; q.split = c->tune.rot_split;
     return q;
+}
+
+// The one description of the resident key set of `c` (KeySet::tab, n1p); c->ks->rtot and the switches are set before.
+void describe_key_set(mkt_ctx *c) {
+    KeySet &ks = *c->ks;
+    const mkt_params &p = c->p;
+    const size_t M = (size_t)c->M, N = (size_t)p.N;
+    const size_t tp = M * c->split;   // complex values of one resident key polynomial (EXACT on the 64-bit ring: two residue polynomials per logical one)
+    const bool mk = mkt::is_mk(p.scheme), kms = mkt::is_kms(p.scheme);
+    ks.n1p = (p.n + 1 + 3) / 4 * 4;   // device rows padded to 16 B
+    // second copy of the bootstrapping key as limb transforms + the engine's own tables, where a party's copy fits one buffer descriptor (2 GiB)
+    const size_t fx_per = (size_t)p.n * 2 * p.l_gsw * 2 * (p.W / 16) * M;
+    const bool fx = fx_shape(c) && c->tune.exact_impl != 0 && fx_per * sizeof(cplx) <= 0x7fffffffull;
+    auto row = [&](KeyTable t, auto &member, size_t elems, bool per_party, bool present, bool cloned) { ks.tab[t] = ResidentTable{(void **)&member, elems, sizeof(*member), per_party, present, cloned}; };
+    //  table         pointer          elements                                                       per party  present  cloned
+    row(T_TW,         ks.d_tw,         4 * M,                                                         false,     true,    true);    // a caller may have replaced them on the source (mkt_set_twiddles)
+    row(T_MONOMIAL,   ks.d_monomial,   2 * N * M,                                                     false,     true,    true);    // depends on the twiddles; small coefficients, never split
+    row(T_BRK,        ks.d_brk,        (size_t)p.n * c->sh.brk_polys * tp,                            true,      true,    true);
+    row(T_KSK,        ks.d_ksk,        (size_t)c->sh.ksk_kr * N * c->sh.ksk_drows * p.f * ks.n1p,     true,      true,    true);
+    row(T_PUB,        ks.d_pub,        (size_t)p.l_uni * tp,                                          true,      mk,      true);
+    row(T_CRS,        ks.d_crs,        (size_t)p.l_uni * tp,                                          false,     mk,      true);
+    row(T_RLK_D,      ks.d_rlk_d,      (size_t)p.l_uni * tp,                                          true,      kms,     true);
+    row(T_RLK_F,      ks.d_rlk_f,      (size_t)p.l_uni * 2 * tp,                                      true,      kms,     true);
+    row(T_SLOT_PARTY, ks.d_slot_party, (size_t)ks.rtot,                                               false,     true,    false);
+    row(T_SLOT_ROW,   ks.d_slot_row,   (size_t)ks.rtot,                                               false,     true,    false);
+    row(T_FX_TAB,     ks.d_fx_tab,     3 * M,                                                         false,     fx,      false);
+    row(T_FX_BRK,     ks.d_fx_brk,     fx_per,                                                        true,      fx,      true);
+    row(T_FX_STAT,    ks.d_fx_stat,    1,                                                             false,     fx,      true);
+    row(T_NTT,        ks.d_ntt,        (N + 4) * 2,                                                   false,     c->exact, false);   // (N + 4) points of 4 words (upload_ntt_tables)
 }
 
 }  // namespace
@@ -617,56 +673,34 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     c->split = (c->exact && params->W == 64) ? 2 : 1;
     // the RLWE-length-k kernels of the plain schemes want the slot-pair order, everything else the slot-major one (fft_device.h)
     c->dev_order = ((params->scheme == MKT_CGGI || params->scheme == MKT_LMSS) && params->k > 1) ? MKT_DEVORDER_KR : MKT_DEVORDER;
-    c->tune.from_env();   // the one place the MKT_ROT_* / MKT_CCS_* environment is read; mkt_set_option afterwards
+    c->tune = tune_from_env();   // the one place the MKT_ROT_* / MKT_CCS_* environment is read; mkt_set_option afterwards
     DevGuard dg(device);
     auto bail = [&](int code) { std::string m = c->err; mkt_ctx_destroy(c); g_create_error = m; return code; };
     if (!dg.ok) { c->err = "hipSetDevice failed"; return bail(MKT_ERR_HIP); }
     const mkt_params &p = c->p;
-    const int np = c->sh.nparty, N = p.N, M = c->M;
+    const int np = c->sh.nparty, M = c->M;
     c->ks->brk_loaded.assign(np, 0); c->ks->ksk_loaded.assign(np, 0); c->ks->rlk_loaded.assign(np, 0); c->ks->pub_loaded.assign(np, 0);
-    mkt::make_twiddles(N, c->ks->tw);
-#define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { c->err = std::string(#call) + ": " + hipGetErrorString(_e); return bail(_e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP); } } while (0)
-    CK(hipMalloc((void **)&c->ks->d_tw, (size_t)4 * M * sizeof(cplx)));
-    CK(hipMalloc((void **)&c->ks->d_monomial, (size_t)2 * N * M * sizeof(cplx)));
-    c->ks->brk_party_cplx = (size_t)p.n * c->sh.brk_polys * M * c->split;
-    // the rotation kernels read a party's key rows through one buffer descriptor (kernel_common.h table_rsrc: 31-bit record
-    // count, 32-bit row offsets); a larger key would read zeros silently, so it is refused here (largest shipped set: 0.25 GB)
-    if (c->ks->brk_party_cplx * sizeof(cplx) > 0x7fffffffull) { c->err = "per-party bootstrapping key exceeds the 2 GiB window of the rotation kernels' buffer descriptors"; return bail(MKT_ERR_UNSUPPORTED); }
-    CK(hipMalloc((void **)&c->ks->d_brk, (size_t)np * c->ks->brk_party_cplx * sizeof(cplx)));
-    c->ks->n1p = (p.n + 1 + 3) / 4 * 4;   // device rows padded to 16 B
-    c->ks->ksk_party_words = (size_t)c->sh.ksk_kr * N * c->sh.ksk_drows * p.f * c->ks->n1p;
-    CK(hipMalloc((void **)&c->ks->d_ksk, (size_t)np * c->ks->ksk_party_words * sizeof(uint32_t)));
-    if (mkt::is_mk(p.scheme)) {
-        CK(hipMalloc((void **)&c->ks->d_pub, (size_t)np * p.l_uni * M * sizeof(cplx) * c->split));
-        CK(hipMalloc((void **)&c->ks->d_crs, (size_t)p.l_uni * M * sizeof(cplx) * c->split));
-    }
-    if (mkt::is_kms(p.scheme)) {
-        CK(hipMalloc((void **)&c->ks->d_rlk_d, (size_t)np * p.l_uni * M * sizeof(cplx) * c->split));
-        CK(hipMalloc((void **)&c->ks->d_rlk_f, (size_t)np * p.l_uni * 2 * M * sizeof(cplx) * c->split));
-    }
+    mkt::make_twiddles(p.N, c->ks->tw);
     // rotation slots: KMS phase 1 runs 1 row for party 0 and l_lev rows for the others (bootstrapping.jl:400)
     std::vector<int> sp, sr;
     if (mkt::is_kms(p.scheme)) {
         for (int i = 0; i < p.k; i++) { int rows = i == 0 ? 1 : p.l_lev; for (int r = 0; r < rows; r++) { sp.push_back(i); sr.push_back(r); } }
     } else { sp.push_back(0); sr.push_back(0); }
     c->ks->rtot = (int)sp.size();
-    CK(hipMalloc((void **)&c->ks->d_slot_party, sp.size() * sizeof(int)));
-    CK(hipMalloc((void **)&c->ks->d_slot_row, sr.size() * sizeof(int)));
+    describe_key_set(c);
+    // the rotation kernels read a party's key rows through one buffer descriptor (kernel_common.h table_rsrc: 31-bit record
+    // count, 32-bit row offsets); a larger key would read zeros silently, so it is refused here (largest shipped set: 0.25 GB)
+    if (c->ks->stride(T_BRK) * sizeof(cplx) > 0x7fffffffull) { c->err = "per-party bootstrapping key exceeds the 2 GiB window of the rotation kernels' buffer descriptors"; return bail(MKT_ERR_UNSUPPORTED); }
+#define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { c->err = std::string(#call) + ": " + hipGetErrorString(_e); return bail(_e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP); } } while (0)
+    for (const ResidentTable &t : c->ks->tab) if (t.present) CK(hipMalloc(t.slot, t.bytes(np)));
     CK(hipMemcpy(c->ks->d_slot_party, sp.data(), sp.size() * sizeof(int), hipMemcpyHostToDevice));
     CK(hipMemcpy(c->ks->d_slot_row, sr.data(), sr.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (fx_shape(c) && c->tune.exact_impl != 0) {   // second copy of the bootstrapping key as limb transforms + the engine's own tables
-        const size_t per = (size_t)p.n * 2 * p.l_gsw * 2 * (p.W / 16) * M;
-        if (per * sizeof(cplx) <= 0x7fffffffull) {
-            c->ks->fx_brk_party_cplx = per;
-            CK(hipMalloc((void **)&c->ks->d_fx_tab, (size_t)3 * M * sizeof(cplx)));
-            CK(hipMalloc((void **)&c->ks->d_fx_brk, (size_t)np * per * sizeof(cplx)));
-            CK(hipMalloc((void **)&c->ks->d_fx_stat, 8));
-            CK(hipMemset(c->ks->d_fx_stat, 0, 8));
-            const size_t tb = (size_t)M * sizeof(cplx);
-            CK(hipMemcpy(c->ks->d_fx_tab, c->ks->tw.fx_om.data(), tb, hipMemcpyHostToDevice));
-            CK(hipMemcpy(c->ks->d_fx_tab + M, c->ks->tw.fx_tw.data(), tb, hipMemcpyHostToDevice));
-            CK(hipMemcpy(c->ks->d_fx_tab + 2 * (size_t)M, c->ks->tw.fx_nat.data(), tb, hipMemcpyHostToDevice));
-        }
+    if (c->ks->d_fx_tab) {
+        CK(hipMemset(c->ks->d_fx_stat, 0, 8));
+        const size_t tb = (size_t)M * sizeof(cplx);
+        CK(hipMemcpy(c->ks->d_fx_tab, c->ks->tw.fx_om.data(), tb, hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->ks->d_fx_tab + M, c->ks->tw.fx_tw.data(), tb, hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->ks->d_fx_tab + 2 * (size_t)M, c->ks->tw.fx_nat.data(), tb, hipMemcpyHostToDevice));
     }
 #undef CK
     int r = upload_twiddles(c);
@@ -698,7 +732,7 @@ int mkt_ctx_fork(mkt_ctx *c, mkt_ctx **out) {
     if (!c || !out) return fail(c, MKT_ERR_ARG, "null argument");
     auto *f = new mkt_ctx();
     f->p = c->p; f->sh = c->sh; f->device = c->device; f->logM = c->logM; f->logN = c->logN; f->M = c->M; f->dev_order = c->dev_order;
-    f->ks = c->ks; f->exact = c->exact; f->split = c->split; f->d_ntt = c->d_ntt; f->tune = c->tune;
+    f->ks = c->ks; f->exact = c->exact; f->split = c->split; f->tune = c->tune;
     // the fork's own stream: non-blocking, so forks driven from several host threads neither serialise on the NULL stream
     // nor against each other; mkt_set_stream may re-point the context at a caller's stream later
     {
@@ -711,50 +745,37 @@ int mkt_ctx_fork(mkt_ctx *c, mkt_ctx **out) {
     return MKT_OK;
 }
 
-// ---- internal (multi.cpp): replicate the resident, pre-transformed key set of `src` onto `dst`'s device ----
-// dst is a fresh context of the same parameters and arithmetic on another device.  Device-to-device with hipMemcpyPeer (xGMI
-// when the devices are linked; the runtime stages through the host otherwise); if the peer copy is refused, an explicit host
-// bounce.  The key upload and its transforms run ONCE, on src's device ("optional one-time device-to-device key copy").
-static int copy_across(mkt_ctx *dst, void *d, int ddev, const void *s_, int sdev, size_t bytes, bool no_peer) {
-    if (!bytes) return MKT_OK;
+// ---- internal (multi.cpp) ----
+// The one device-to-device copy (the clone below, ShardArg::across in multi.cpp): hipMemcpyPeer (xGMI when the devices are linked; the runtime stages through the host otherwise); if the
+// peer copy is refused or switched off, an explicit host bounce.  Returns a hipError_t value.  It does not synchronise: a peer copy may return before the data has landed, each caller drains what it has to.
+int mkt_internal_copy_across(void *dst, int ddev, const void *src, int sdev, size_t bytes, int no_peer) {
+    if (!bytes) return hipSuccess;
     if (!no_peer) {
-        if (hipMemcpyPeer(d, ddev, s_, sdev, bytes) == hipSuccess) return MKT_OK;
+        if (hipMemcpyPeer(dst, ddev, src, sdev, bytes) == hipSuccess) return hipSuccess;
         (void)hipGetLastError();
     }
     std::vector<unsigned char> bounce(bytes);
-    { DevGuard g(sdev); HIPCHK(dst, hipMemcpy(bounce.data(), s_, bytes, hipMemcpyDeviceToHost)); }
-    { DevGuard g(ddev); HIPCHK(dst, hipMemcpy(d, bounce.data(), bytes, hipMemcpyHostToDevice)); }
-    return MKT_OK;
+    hipError_t e;
+    { DevGuard g(sdev); e = hipMemcpy(bounce.data(), src, bytes, hipMemcpyDeviceToHost); }
+    if (e == hipSuccess) { DevGuard g(ddev); e = hipMemcpy(dst, bounce.data(), bytes, hipMemcpyHostToDevice); }
+    return e;
 }
+// Replicate the resident, pre-transformed key set of `src` onto `dst`'s device.  dst is a fresh context of the same parameters and
+// arithmetic on another device.  The key upload and its transforms run ONCE, on src's device ("optional one-time
+// device-to-device key copy").
 int mkt_internal_clone_keys(mkt_ctx *src, mkt_ctx *dst, int no_peer) {
     if (!src || !dst) return MKT_ERR_ARG;
     if (std::memcmp(&src->p, &dst->p, sizeof(mkt_params)) != 0 || src->exact != dst->exact) return fail(dst, MKT_ERR_ARG, "key replication between contexts of different parameters");
-    if (dst->keys_shared()) return fail(dst, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(dst)) return w;
     { DevGuard g(src->device); HIPCHK(dst, hipStreamSynchronize(src->stream)); }
-    const mkt_params &p = src->p;
-    const int np = src->sh.nparty, M = src->M, N = p.N, sd = src->device, dd = dst->device;
+    const int sd = src->device, dd = dst->device;
     KeySet &a = *src->ks, &b = *dst->ks;
-    const size_t cb = sizeof(cplx);
-    int r;
-    // tables a caller may have replaced on src (mkt_set_twiddles), and the monomial table that depends on them
-    b.tw = a.tw;
-    if ((r = copy_across(dst, b.d_tw, dd, a.d_tw, sd, (size_t)4 * M * cb, no_peer != 0))) return r;
-    if ((r = copy_across(dst, b.d_monomial, dd, a.d_monomial, sd, (size_t)2 * N * M * cb, no_peer != 0))) return r;
-    if ((r = copy_across(dst, b.d_brk, dd, a.d_brk, sd, (size_t)np * a.brk_party_cplx * cb, no_peer != 0))) return r;
-    if ((r = copy_across(dst, b.d_ksk, dd, a.d_ksk, sd, (size_t)np * a.ksk_party_words * 4, no_peer != 0))) return r;
-    if (mkt::is_mk(p.scheme)) {
-        if ((r = copy_across(dst, b.d_pub, dd, a.d_pub, sd, (size_t)np * p.l_uni * M * cb * src->split, no_peer != 0))) return r;
-        if ((r = copy_across(dst, b.d_crs, dd, a.d_crs, sd, (size_t)p.l_uni * M * cb * src->split, no_peer != 0))) return r;
-    }
-    if (mkt::is_kms(p.scheme)) {
-        if ((r = copy_across(dst, b.d_rlk_d, dd, a.d_rlk_d, sd, (size_t)np * p.l_uni * M * cb * src->split, no_peer != 0))) return r;
-        if ((r = copy_across(dst, b.d_rlk_f, dd, a.d_rlk_f, sd, (size_t)np * p.l_uni * 2 * M * cb * src->split, no_peer != 0))) return r;
-    }
-    if (a.d_fx_brk && b.d_fx_brk) {
-        if ((r = copy_across(dst, b.d_fx_brk, dd, a.d_fx_brk, sd, (size_t)np * a.fx_brk_party_cplx * cb, no_peer != 0))) return r;
-        if ((r = copy_across(dst, b.d_fx_stat, dd, a.d_fx_stat, sd, 8, no_peer != 0))) return r;
-        b.fx_kmax = a.fx_kmax;
-    }
+    b.tw = a.tw;   // tables a caller may have replaced on src (mkt_set_twiddles)
+    // every table the two key sets both hold (the Float64-pipe copy of the key only where both contexts were created with it)
+    for (int t = 0; t < T_COUNT; t++)
+        if (a.tab[t].cloned && a.tab[t].present && b.tab[t].present)
+            HIPCHK(dst, (hipError_t)mkt_internal_copy_across(*b.tab[t].slot, dd, *a.tab[t].slot, sd, a.tab[t].bytes(src->sh.nparty), no_peer));
+    if (a.d_fx_brk && b.d_fx_brk) b.fx_kmax = a.fx_kmax;
     b.brk_loaded = a.brk_loaded; b.ksk_loaded = a.ksk_loaded; b.rlk_loaded = a.rlk_loaded; b.pub_loaded = a.pub_loaded; b.crs_loaded = a.crs_loaded;
     dst->tune = src->tune;
     // hipMemcpyPeer may return before the copy has landed, and the shards evaluate on non-blocking streams that the NULL stream does
@@ -780,24 +801,18 @@ int mkt_get_stream(mkt_ctx *c, void **hip_stream) { if (!c || !hip_stream) retur
 int mkt_set_option(mkt_ctx *c, const char *name, int value) {
     if (!c || !name) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
-    Tune &t = c->tune;
-    // selectors with a fixed set of values refuse the others here (a call would otherwise fail late, inside a gate, or run nothing)
-    if ((k == "rot_variant" && value != 0 && value != 21 && value != 22) || (k == "rot_map" && value != 0 && value != 1))
-        return fail(c, MKT_ERR_ARG, "mkt_set_option: " + k + " = " + std::to_string(value) + " is not one of " + (k == "rot_map" ? "0, 1" : "0, 21, 22"));
-    if (k == "rot_variant") t.rot_variant = value;
-    else if (k == "rot_stagger") t.rot_stagger = value;
-    else if (k == "rot_split") t.rot_split = value;
-    else if (k == "rot_wide") t.rot_wide = value;
-    else if (k == "rot_blkg") t.rot_blkg = value;
-    else if (k == "ccs_stagger") t.ccs_stagger = value;
-    else if (k == "ccs_pipe") t.ccs_pipe = value;
-    else if (k == "exact_wide") t.exact_wide = value;
-    else if (k == "exact_impl") t.exact_impl = value;
-    else if (k == "rot_map") t.rot_map = value;
-    else if (k == "fx_polymul_force") t.fx_polymul_force = value;
-    else if (k == "exact_kany") { if (t.exact_kany != value) c->ws_gates = 0; t.exact_kany = value; }   // the workspace gains / loses the kernel's scratch at the next call
-    else return fail(c, MKT_ERR_ARG, "mkt_set_option: unknown option '" + k + "'");
-    return MKT_OK;
+    for (const Switch &w : SWITCHES) {
+        if (k != w.name) continue;
+        if (!w.allowed.empty() && std::find(w.allowed.begin(), w.allowed.end(), value) == w.allowed.end()) {
+            std::string list;
+            for (int v : w.allowed) list += (list.empty() ? "" : ", ") + std::to_string(v);
+            return fail(c, MKT_ERR_ARG, "mkt_set_option: " + k + " = " + std::to_string(value) + " is not one of " + list);
+        }
+        if (w.resets_workspace && c->tune.*w.member != value) c->ws_gates = 0;
+        c->tune.*w.member = value;
+        return MKT_OK;
+    }
+    return fail(c, MKT_ERR_ARG, "mkt_set_option: unknown option '" + k + "'");
 }
 
 const char *mkt_last_kernel_name(const mkt_ctx *c) { return c ? c->last_rot_kernel : ""; }
@@ -837,7 +852,7 @@ int mkt_get_twiddles(mkt_ctx *c, int which, double *out_host) {
 int mkt_set_twiddles(mkt_ctx *c, const double *psi, const double *psiinv, const double *roots, const double *rootsinv) {
     if (!c || !psi || !psiinv || !roots || !rootsinv) return fail(c, MKT_ERR_ARG, "null table");
     MKT_F64_ONLY(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
     const size_t nd = (size_t)2 * c->M;
     // the kernels derive the inverse twiddles from the forward table: Psiinv must be conj(Psi) entry for entry,
@@ -871,10 +886,10 @@ int mkt_get_monomial(mkt_ctx *c, int e, double *out_host) {
 int mkt_load_brk(mkt_ctx *c, int party, const void *data, int fmt) {
     if (!c || !data || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_EXACT_GATE(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
-    int r = upload_polys(c, data, (size_t)c->p.n * c->sh.brk_polys, c->ks->d_brk + (size_t)party * c->ks->brk_party_cplx, fmt, false,
-                         c->ks->d_fx_brk ? c->ks->d_fx_brk + (size_t)party * c->ks->fx_brk_party_cplx : nullptr);
+    int r = upload_polys(c, data, (size_t)c->p.n * c->sh.brk_polys, c->ks->party<cplx>(T_BRK, party), fmt, false,
+                         c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
     if (!r) c->ks->brk_loaded[party] = 1;
     return r;
 }
@@ -882,11 +897,11 @@ int mkt_load_brk(mkt_ctx *c, int party, const void *data, int fmt) {
 int mkt_load_ksk(mkt_ctx *c, int party, const uint32_t *data) {
     if (!c || !data || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_EXACT_GATE(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
     const size_t rows = (size_t)c->sh.ksk_kr * c->p.N * c->sh.ksk_drows * c->p.f, n1 = (size_t)c->p.n + 1;
-    HIPCHK(c, hipMemset(c->ks->d_ksk + (size_t)party * c->ks->ksk_party_words, 0, c->ks->ksk_party_words * sizeof(uint32_t)));
-    HIPCHK(c, hipMemcpy2D(c->ks->d_ksk + (size_t)party * c->ks->ksk_party_words, (size_t)c->ks->n1p * 4, data, n1 * 4, n1 * 4, rows, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->ks->party<uint32_t>(T_KSK, party), 0, c->ks->stride(T_KSK) * sizeof(uint32_t)));
+    HIPCHK(c, hipMemcpy2D(c->ks->party<uint32_t>(T_KSK, party), (size_t)c->ks->n1p * 4, data, n1 * 4, n1 * 4, rows, hipMemcpyHostToDevice));
     c->ks->ksk_loaded[party] = 1;
     return MKT_OK;
 }
@@ -894,11 +909,11 @@ int mkt_load_ksk(mkt_ctx *c, int party, const uint32_t *data) {
 int mkt_load_rlk(mkt_ctx *c, int party, const void *d, const void *f, int fmt) {
     if (!c || !d || !f || party < 0 || party >= c->sh.nparty || !mkt::is_kms(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_F64_OR_EXACT_KMS(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
     const size_t l = (size_t)c->p.l_uni;
-    int r = upload_polys(c, d, l, c->ks->d_rlk_d + (size_t)party * l * c->M * c->split, fmt);
-    if (!r) r = upload_polys(c, f, 2 * l, c->ks->d_rlk_f + (size_t)party * 2 * l * c->M * c->split, fmt);
+    int r = upload_polys(c, d, l, c->ks->party<cplx>(T_RLK_D, party), fmt);
+    if (!r) r = upload_polys(c, f, 2 * l, c->ks->party<cplx>(T_RLK_F, party), fmt);
     if (!r) c->ks->rlk_loaded[party] = 1;
     return r;
 }
@@ -906,9 +921,9 @@ int mkt_load_rlk(mkt_ctx *c, int party, const void *d, const void *f, int fmt) {
 int mkt_load_pubkey(mkt_ctx *c, int party, const void *b, int fmt) {
     if (!c || !b || party < 0 || party >= c->sh.nparty || !mkt::is_mk(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_F64_OR_EXACT_KMS(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
-    int r = upload_polys(c, b, (size_t)c->p.l_uni, c->ks->d_pub + (size_t)party * c->p.l_uni * c->M * c->split, fmt);
+    int r = upload_polys(c, b, (size_t)c->p.l_uni, c->ks->party<cplx>(T_PUB, party), fmt);
     if (!r) c->ks->pub_loaded[party] = 1;
     return r;
 }
@@ -916,7 +931,7 @@ int mkt_load_pubkey(mkt_ctx *c, int party, const void *b, int fmt) {
 int mkt_load_crs(mkt_ctx *c, const void *a, int fmt) {
     if (!c || !a || !mkt::is_mk(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_F64_OR_EXACT_KMS(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     DevGuard dg(c->device);
     int r = upload_polys(c, a, (size_t)c->p.l_uni, c->ks->d_crs, fmt);
     if (!r) c->ks->crs_loaded = true;
@@ -928,7 +943,7 @@ int mkt_load_crs(mkt_ctx *c, const void *a, int fmt) {
 static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, const void *crs, void *brk_out, uint32_t *ksk_out) {
     if (!c || !K || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_EXACT_GATE(c);
-    if (c->keys_shared()) return fail(c, MKT_ERR_STATE, "the key set is shared with forked contexts and immutable");
+    if (int w = keys_writable(c)) return w;
     const mkt_params &p = c->p;
     if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: the party's keys were made for other parameters / another party index");
     const bool unienc = p.scheme == MKT_CCS;
@@ -960,12 +975,9 @@ static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, 
     else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; a.zoff = 0; }
     e = mktd::launch_keygen_brk(a, unienc ? 1 : 0, c->stream);
     if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, d_out, brk_polys_total * poly_bytes(c), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = (c->exact && c->split == 2) ? mktd::launch_ntt_fwd_split(c->logN, c->d_ntt, d_out, reinterpret_cast<uint64_t *>(c->ks->d_brk + (size_t)party * c->ks->brk_party_cplx), brk_polys_total, c->stream)
-                           : c->exact ? mktd::launch_ntt_fwd(c->logN, p.W, c->d_ntt, d_out, reinterpret_cast<uint64_t *>(c->ks->d_brk + (size_t)party * c->ks->brk_party_cplx), brk_polys_total, 1, c->stream)
-                               : mktd::launch_transform_fwd(c->logM, p.W, c->twp(), d_out, c->ks->d_brk + (size_t)party * c->ks->brk_party_cplx, brk_polys_total, c->dev_order, c->stream);
-    if (e == hipSuccess && c->ks->d_fx_brk) e = mktd::launch_fx_key_fwd(c->logM, p.W, c->fx_om(), c->fx_tw(), d_out, c->ks->d_fx_brk + (size_t)party * c->ks->fx_brk_party_cplx, brk_polys_total, c->ks->d_fx_stat, c->stream);
-    uint32_t *ksk = c->ks->d_ksk + (size_t)party * c->ks->ksk_party_words;
-    if (e == hipSuccess) e = hipMemsetAsync(ksk, 0, c->ks->ksk_party_words * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = to_resident(c, d_out, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
+    uint32_t *ksk = c->ks->party<uint32_t>(T_KSK, party);
+    if (e == hipSuccess) e = hipMemsetAsync(ksk, 0, c->ks->stride(T_KSK) * sizeof(uint32_t), c->stream);
     a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
     if (e == hipSuccess) e = mktd::launch_keygen_ksk(a, ksk, c->ks->n1p, c->sh.ksk_kr, c->sh.ksk_drows, mkt::is_block(p.scheme) ? 1 : 0, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -997,7 +1009,7 @@ int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
     DevGuard dg(c->device);
     const size_t rows = (size_t)c->sh.ksk_kr * c->p.N * c->sh.ksk_drows * c->p.f, n1 = (size_t)c->p.n + 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(out_host, n1 * 4, c->ks->d_ksk + (size_t)party * c->ks->ksk_party_words, (size_t)c->ks->n1p * 4, n1 * 4, rows, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy2D(out_host, n1 * 4, c->ks->party<uint32_t>(T_KSK, party), (size_t)c->ks->n1p * 4, n1 * 4, rows, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 
@@ -1228,25 +1240,19 @@ int mkt_kms_phase1_batch(mkt_ctx *c, const uint32_t *atilde, double *levkey, siz
     Staged sa{c}, sl{c};
     if ((r = sa.in(atilde, B * alen * 4, mem, true)) || (r = sl.in(levkey, B * lb, mem, false))) return r;
     if (c->exact) {   // the rows as split residue tables [B][rows][2 polys][2 halves][N] (uint64 residue pairs, Montgomery form)
-        const mkt_params &p = c->p;
-        mktd::ExactKmsArgs q{};
-        q.brk = reinterpret_cast<const uint64_t *>(c->ks->d_brk); q.brk_party_stride = c->ks->brk_party_cplx * 2 /* in 8-byte residue pairs */; q.mono = reinterpret_cast<const uint64_t *>(c->ks->d_monomial);
-        q.lwe = (const uint32_t *)sa.dev; q.lwe_stride = (int)alen; q.pre_switched = 1; q.n = p.n; q.k = p.k; q.l_gsw = p.l_gsw; q.logB_gsw = p.logB_gsw;
-        q.l_lev = p.l_lev; q.logB_lev = p.logB_lev; q.l_uni = p.l_uni; q.logB_uni = p.logB_uni; q.rtot = c->ks->rtot; q.lwe_len = c->sh.lwe_len; q.blk_len = p.scheme == MKT_KMS_BLOCK ? p.blk_len : 1;
-        q.slot_party = c->ks->d_slot_party; q.slot_row = c->ks->d_slot_row; q.levkey = (uint64_t *)sl.dev; q.phase1_only = 1; q.wide = c->tune.exact_wide;
-        if (p.scheme == MKT_KMS && fx_usable(c)) {
+        if (c->p.scheme == MKT_KMS && fx_usable(c)) {
             if ((r = ensure_workspace(c, B < CHUNK_GATES ? B : CHUNK_GATES))) return r;
             for (size_t off = 0; off < B; off += CHUNK_GATES) {
-                const size_t nb = B - off < CHUNK_GATES ? B - off : CHUNK_GATES, nrot = nb * (size_t)c->ks->rtot;
-                mktd::FxRotArgs f = fx_rot_args(c, (const uint32_t *)sa.dev + off * alen, (int)alen, 1);
-                f.init_mode = 1; f.acc_io = c->ws_fxacc; f.ngates = nb;
+                const size_t nb = B - off < CHUNK_GATES ? B - off : CHUNK_GATES;
                 Timer tm(c, 1);
-                HIPCHK(c, mktd::launch_fx_blindrotate(c->logM, p.W, f, nrot, c->stream));
-                HIPCHK(c, mktd::launch_ntt_fwd_split(c->logN, c->d_ntt, c->ws_fxacc, (uint64_t *)sl.dev + off * (lb / 8), nrot * 2, c->stream));
+                if ((r = fx_phase1(c, (const uint32_t *)sa.dev + off * alen, (int)alen, 1, nb, (uint64_t *)sl.dev + off * (lb / 8)))) return r;
             }
-            return sl.out(levkey);
+        } else {
+            mktd::ExactKmsArgs q = exact_kms_args(c, (const uint32_t *)sa.dev, (int)alen, 1);
+            q.levkey = (uint64_t *)sl.dev; q.phase1_only = 1;
+            Timer tm(c, 1);
+            HIPCHK(c, mktd::launch_exact_kms(c->logN, c->ks->d_ntt, q, B, c->stream));
         }
-        { Timer tm(c, 1); HIPCHK(c, mktd::launch_exact_kms(c->logN, c->d_ntt, q, B, c->stream)); }
         return sl.out(levkey);
     }
     mktd::RotArgs a = rot_args(c, (const uint32_t *)sa.dev, (int)alen, 1);
@@ -1274,7 +1280,7 @@ int mkt_transform_fwd_batch(mkt_ctx *c, const void *p, double *t, size_t B, int 
     Staged sp{c}, st{c};
     int r;
     if ((r = sp.in(p, B * poly_bytes(c), mem, true)) || (r = st.in(t, B * (size_t)c->M * sizeof(cplx), mem, false))) return r;
-    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_fwd(c->logN, c->p.W, c->d_ntt, sp.dev, (uint64_t *)st.dev, B, 0, c->stream)); }
+    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_fwd(c->logN, c->p.W, c->ks->d_ntt, sp.dev, (uint64_t *)st.dev, B, 0, c->stream)); }
     else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_fwd(c->logM, c->p.W, c->twp(), sp.dev, (cplx *)st.dev, B, 0, c->stream)); }
     return st.out(t);
 }
@@ -1285,7 +1291,7 @@ int mkt_transform_inv_batch(mkt_ctx *c, const double *t, void *p, size_t B, int 
     Staged st{c}, sp{c};
     int r;
     if ((r = st.in(t, B * (size_t)c->M * sizeof(cplx), mem, true)) || (r = sp.in(p, B * poly_bytes(c), mem, false))) return r;
-    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_inv(c->logN, c->p.W, c->d_ntt, (const uint64_t *)st.dev, sp.dev, B, c->stream)); }
+    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_inv(c->logN, c->p.W, c->ks->d_ntt, (const uint64_t *)st.dev, sp.dev, B, c->stream)); }
     else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_inv(c->logM, c->p.W, c->twp(), (const cplx *)st.dev, sp.dev, B, c->stream)); }
     return sp.out(p);
 }
@@ -1341,7 +1347,7 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
             return so.out(out);
         }
     }
-    { Timer tm(c, 3); HIPCHK(c, mktd::launch_exact_polymul(c->logN, c->p.W, c->d_ntt, sa.dev, sb.dev, so.dev, B, c->stream)); }
+    { Timer tm(c, 3); HIPCHK(c, mktd::launch_exact_polymul(c->logN, c->p.W, c->ks->d_ntt, sa.dev, sb.dev, so.dev, B, c->stream)); }
     c->last_rot_kernel = "exact_polymul_kernel";
     return so.out(out);
 }

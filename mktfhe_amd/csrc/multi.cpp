@@ -73,18 +73,10 @@ struct ShardArg {
     size_t bytes = 0;
     int dev = 0, remote_dev = 0;
     bool copy_back = false, no_peer = false;
-    // device -> device: a peer copy (xGMI where the devices are linked), through a host buffer where that is refused or switched off
+    // device -> device (context.cpp mkt_internal_copy_across), landed on return: a peer copy may return early, so the NULL stream is drained after one
     static int across(void *d, int ddev, const void *s, int sdev, size_t n, bool no_peer) {
-        if (!no_peer) {
-            if (hipMemcpyPeer(d, ddev, s, sdev, n) == hipSuccess) return hipStreamSynchronize(nullptr) == hipSuccess ? 0 : -1;
-            (void)hipGetLastError();
-        }
-        std::vector<unsigned char> bounce(n);
-        int cur = 0; (void)hipGetDevice(&cur);
-        bool ok = hipSetDevice(sdev) == hipSuccess && hipMemcpy(bounce.data(), s, n, hipMemcpyDeviceToHost) == hipSuccess;
-        ok = ok && hipSetDevice(ddev) == hipSuccess && hipMemcpy(d, bounce.data(), n, hipMemcpyHostToDevice) == hipSuccess;
-        (void)hipSetDevice(cur);
-        return ok ? 0 : -1;
+        if (mkt_internal_copy_across(d, ddev, s, sdev, n, no_peer) != hipSuccess) return -1;
+        return no_peer || hipStreamSynchronize(nullptr) == hipSuccess ? 0 : -1;
     }
     int prepare(const void *base, size_t row_bytes, size_t lo, size_t hi, int mem, int shard_dev, bool in, bool out, mkt_multi::Stage &pool, bool always, bool nopeer = false) {
         no_peer = nopeer;

@@ -20,9 +20,9 @@ def _table_switches():
 
 def _set_option_names():
     text = open(os.path.join(ROOT, "mktfhe_amd", "csrc", "context.cpp")).read()
-    body = text[text.index("int mkt_set_option("):]
-    body = body[:body.index("\n}\n")]
-    return set(re.findall(r'k == "([a-z0-9_]+)"', body))
+    body = text[text.index("const Switch SWITCHES[] = {"):]      # the one table mkt_set_option and the environment seeding loop over
+    body = body[:body.index("\n};\n")]
+    return set(re.findall(r'^\s*\{"([a-z0-9_]+)", (?:"MKT_[A-Z0-9_]+"|nullptr), &Tune::\1,', body, re.M))
 
 
 def _strings(v):
@@ -52,7 +52,8 @@ def _parametrised_strings():
 def test_table_and_set_option_parse():
     table, opts = _table_switches(), _set_option_names()
     assert {"MKT_KS_G", "MKT_FFT_NB", "MKT_NTT_GRID", "MKT_ROT_VARIANT"} <= table and len(table) >= 15, table
-    assert {"rot_variant", "rot_map", "exact_impl", "ccs_stagger"} <= opts and len(opts) >= 10, opts
+    assert opts == set("rot_variant rot_stagger rot_split rot_wide rot_blkg ccs_stagger ccs_pipe exact_wide exact_impl rot_map fx_polymul_force "
+                       "exact_kany".split()), opts
 
 
 def test_every_documented_switch_is_listed():
