@@ -173,6 +173,16 @@ template <int LOGN> struct NttLds { static constexpr int WORDS = MKT_NTT_LAYOUT 
 #ifndef MKT_ABLATE
 #define MKT_ABLATE 0
 #endif
+// exact_blindrotate_kernel: the monomial row of the (first non-zero) key bit is requested a whole step ahead of its use (at use it was one
+// exposed L2 round trip per step); 0: at use (A/B builds)
+#ifndef MKT_EXACT_MONO_AHEAD
+#define MKT_EXACT_MONO_AHEAD 1
+#endif
+// exact_blindrotate_kernel, a block's other key bits: the rows of key bit q + 1 are requested before the multiply-adds of key bit q (two row
+// buffers in turn) -- at use, each was an exposed round trip per digit and key bit; 0: at use (A/B builds)
+#ifndef MKT_EXACT_BLK_PIPE
+#define MKT_EXACT_BLK_PIPE 1
+#endif
 __device__ __forceinline__ int launder(int v) { asm volatile("" : "+v"(v)); return v; }
 // NB transforms side by side (the pair of digit polynomials of one accumulator; the low and the high half of one lifted sum) go through
 // the passes together: ONE set of twiddle reads, slot addresses and barriers for NB x the butterflies, and every wait on an exchange or a
@@ -344,6 +354,43 @@ __device__ __forceinline__ void stage_tables(const uint4 *tab, uint4 *dst, int t
     __syncthreads();
 }
 template <int LOGN> constexpr size_t lds_bytes(int ntab, int ppw = 1) { return (size_t)ppw * NttLds<LOGN>::WORDS * 8 + (TwLds<LOGN>::on ? (size_t)ntab * (1 << LOGN) * 16 : 0); }
+
+// ------------------------------------------------------------------------------------------------
+// Steps the gate kernels share, written once -- where the device code comes out the same through the helper as spelled out in the kernel.
+// These kernels sit at the register limit and their instruction streams are pinned, and a step moved into a function is simplified
+// on its own before it is inlined: operands commute and sums re-associate differently.  So the workgroup preamble is shared by the
+// 64-bit-ring kernels that pair their transforms and by the split-table transform only, and the any-check of a block, the KMS row
+// preamble, the 32-bit inverse-and-add, X^at - 1 through LDS and the split-table epilogue stay spelled out in the kernel bodies.
+// ------------------------------------------------------------------------------------------------
+// What every workgroup of N / 8 threads starts with: NBUF staging buffers (two where the halves of a lifted sum are transformed side by
+// side, lift_pair), behind them the staged twiddle table, and the constants at its tail
+template <int LOGN, int NBUF = 1>
+struct Workgroup {
+    uint64_t *lds; int t; const uint4 *tw; NttConsts k;
+    __device__ __forceinline__ explicit Workgroup(const uint4 *tab) {
+        lds = reinterpret_cast<uint64_t *>(ntt_smem);
+        t = threadIdx.x;
+        const uint4 *out[1]; const int which[1] = {0};
+        stage_tables<LOGN, 1>(tab, reinterpret_cast<uint4 *>(lds + NBUF * NttLds<LOGN>::WORDS), t, 1 << (LOGN - NLR), out, which);
+        tw = out[0];
+        k = tab_consts<LOGN>(tab);
+    }
+};
+// the mod switch of one mask word to an exponent of X (bootstrapping.jl:8); pre_switched: the caller has done it.  Whether the result goes
+// through readfirstlane is the call site's business
+__device__ __forceinline__ uint32_t mask_exponent(uint32_t v0, int pre_switched, int msbit) { return pre_switched ? v0 : divbits<uint32_t>(v0, msbit); }
+// digit -> residues -> forward transform; tp: PREPARED words (gd.prep) held in registers by the caller
+template <int LOGN, typename WORD>
+__device__ __forceinline__ void digit_forward(Pt (&z)[8], const WORD (&tp)[8], const Gadget<WORD> &gd, int j, const uint4 *tw, uint64_t *lds, int t) {
+#pragma unroll
+    for (int e = 0; e < 8; e++) z[e] = res_small(gd.digit(tp[e], j));
+    ntt_forward<LOGN>(z, tw, lds, t);
+}
+__device__ __forceinline__ void pt_zero(Pt &x) { x.a = 0; x.b = 0; }
+template <typename T, int A> __device__ __forceinline__ void pt_zero(T (&x)[A]) {      // Pt arrays of any rank
+#pragma unroll
+    for (int i = 0; i < A; i++) pt_zero(x[i]);
+}
 
 // Batched transforms: PPW polynomials per workgroup side by side (N / 8 threads each) share the staged twiddle table, which
 // lifts the number of resident waves per CU from 12 to 20 at N = 1024.
@@ -526,24 +573,13 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kernel(
         bool any = false;
 #pragma unroll
         for (int q = 0; q < LB; q++) {
-            const uint32_t v0 = at_src[blk * LB + q];
-            ats[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            ats[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[blk * LB + q], pre_switched, msbit));
             any |= ats[q] != 0;
         }
         if (!any) continue;                                              // :48 / :145 (an all-zero block adds 0)
         Pt tacc[LB][2][8];
-#pragma unroll
-        for (int q = 0; q < LB; q++)
-#pragma unroll
-            for (int pp = 0; pp < 2; pp++)
-#pragma unroll
-                for (int e = 0; e < 8; e++) { tacc[q][pp][e].a = 0; tacc[q][pp][e].b = 0; }
-        // the monomial row of the (first non-zero) key bit, requested a whole step ahead of its use (at use it was one exposed L2 round
-        // trip per step); MKT_EXACT_MONO_AHEAD=0: at use (A/B builds)
-#ifndef MKT_EXACT_MONO_AHEAD
-#define MKT_EXACT_MONO_AHEAD 1
-#endif
-        uint64_t mr0[8];
+        pt_zero(tacc);
+        uint64_t mr0[8];                                                 // the monomial row of the key bit, requested a whole step ahead (MKT_EXACT_MONO_AHEAD)
         if constexpr (LB == 1 && MKT_EXACT_MONO_AHEAD) {
             const uint64_t *mrow = mono + (size_t)(ats[0] - 1) * N + 8 * t;
 #pragma unroll
@@ -567,13 +603,8 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kernel(
 #pragma unroll
                 for (int e = 0; e < 8; e++) z[e] = res_small(gd.digit(tp[e], j));
                 ntt_forward<LOGN>(z, tw[0], lds, t);
-#ifndef MKT_EXACT_BLK_PIPE
-#define MKT_EXACT_BLK_PIPE 1
-#endif
                 if constexpr (LB > 1 && MKT_EXACT_BLK_PIPE) {
-                    // a block's other key bits: the rows of key bit q + 1 are requested before the multiply-adds of key bit q (two row
-                    // buffers in turn) -- at use, each was an exposed round trip per digit and key bit
-                    uint64_t kn[2][8];
+                    uint64_t kn[2][8];                                   // the rows of key bit q + 1, requested before the multiply-adds of key bit q
 #pragma unroll
                     for (int q = 0; q < LB; q++) {
                         uint64_t kc[2][8];
@@ -610,8 +641,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kernel(
 #pragma unroll
         for (int pp = 0; pp < 2; pp++) {
             Pt s2[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) { s2[e].a = 0; s2[e].b = 0; }
+            pt_zero(s2);
 #pragma unroll
             for (int q = 0; q < LB; q++) {
                 if (ats[q] == 0) continue;
@@ -662,16 +692,10 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kr_kern
     const int msbit = 32 - LOGN - 1;
     for (int blk = 0; blk < n / blk_len; blk++) {
         bool any = false;
-        for (int q = 0; q < blk_len; q++) {
-            const uint32_t v0 = at_src[blk * blk_len + q];
-            any |= (pre_switched ? v0 : divbits<uint32_t>(v0, msbit)) != 0;
-        }
+        for (int q = 0; q < blk_len; q++) any |= mask_exponent(at_src[blk * blk_len + q], pre_switched, msbit) != 0;
         if (!__builtin_amdgcn_readfirstlane((int)any)) continue;                   // :48 / :145 (an all-zero block adds 0)
         Pt sum[NP][8];
-#pragma unroll
-        for (int pp = 0; pp < NP; pp++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) { sum[pp][e].a = 0; sum[pp][e].b = 0; }
+        pt_zero(sum);
         if (blk_len > 1) {
             // a block of several key bits: ONE set of digit transforms; sum_q mono_q (*) (sum_g z_g (*) K_qg) = sum_g sum_q (mono_q (*) z_g) (*) K_qg
             // in exact integers mod P -- each transform is multiplied by the key bit's monomial row, then into the key bit's rows, straight
@@ -685,8 +709,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kr_kern
                     ntt_forward<LOGN>(z, tw[0], lds, t);
                     for (int q = 0; q < blk_len; q++) {
                         const int i = blk * blk_len + q;
-                        const uint32_t v0 = at_src[i];
-                        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+                        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
                         if (at == 0) continue;                                     // :145
                         const uint64_t *mrow = mono + (size_t)(at - 1) * N + 8 * t;
                         const uint64_t *row = brk + (((size_t)i * NP * l + (size_t)(c * l + j)) * NP) * N + 8 * t;   // [row c l + j][poly][N]
@@ -702,14 +725,10 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kr_kern
         } else
         for (int q = 0; q < blk_len; q++) {
             const int i = blk * blk_len + q;
-            const uint32_t v0 = at_src[i];
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
             if (at == 0) continue;
             Pt tacc[NP][8];
-#pragma unroll
-            for (int pp = 0; pp < NP; pp++)
-#pragma unroll
-                for (int e = 0; e < 8; e++) { tacc[pp][e].a = 0; tacc[pp][e].b = 0; }
+            pt_zero(tacc);
 #pragma unroll
             for (int c = 0; c < NP; c++)
                 for (int j = 0; j < l; j++) {
@@ -775,8 +794,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kany_ke
         bool first_bit = true;                                                     // the block sum starts at this key bit's product (:157 from zero)
         for (int q = 0; q < blk_len; q++) {
             const int i = blk * blk_len + q;
-            const uint32_t v0 = at_src[i];
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
             if (at == 0) continue;                                                 // :48 / :145
             for (int c = 0; c < np; c++)
                 for (int j = 0; j < l; j++) {
@@ -835,10 +853,8 @@ template <int LOGN>
 __global__ __launch_bounds__((1 << (LOGN - NLR))) void ntt_fwd_split_kernel(const uint4 *__restrict__ tab, const uint64_t *__restrict__ p,
                                                                            uint64_t *__restrict__ out, size_t B) {
     constexpr int N = 1 << LOGN, NT = N >> NLR;
-    uint64_t *lds = reinterpret_cast<uint64_t *>(ntt_smem);
-    const int t = threadIdx.x;
-    const uint4 *tw[1]; const int which[1] = {0};
-    stage_tables<LOGN, 1>(tab, reinterpret_cast<uint4 *>(lds + NttLds<LOGN>::WORDS), t, NT, tw, which);
+    const Workgroup<LOGN> wg(tab);
+    const int t = wg.t;
     for (size_t b = blockIdx.x; b < B; b += gridDim.x) {
         uint64_t w[8];
 #pragma unroll
@@ -848,7 +864,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void ntt_fwd_split_kernel(cons
             Pt z[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) z[e] = fwd_in(piece_of(w[e], h), e);
-            ntt_forward<LOGN>(z, tw[0], lds, t);
+            ntt_forward<LOGN>(z, wg.tw, wg.lds, t);
 #pragma unroll
             for (int e = 0; e < 8; e++) out[(2 * b + h) * N + 8 * t + e] = pack(Pt{montmul<P1, PI1>(z[e].a, RR1), montmul<P2, PI2>(z[e].b, RR2)});
             __syncthreads();
@@ -903,32 +919,18 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
     // recomputed per key bit (same values) instead of being held for the block: registers, not arithmetic, are short here.
     for (int blk = 0; blk < n / blk_len; blk++) {
         bool any = false;
-        for (int q = 0; q < blk_len; q++) {
-            const uint32_t v0 = at_src[blk * blk_len + q];
-            any |= (pre_switched ? v0 : divbits<uint32_t>(v0, msbit)) != 0;
-        }
+        for (int q = 0; q < blk_len; q++) any |= mask_exponent(at_src[blk * blk_len + q], pre_switched, msbit) != 0;
         if (!__builtin_amdgcn_readfirstlane((int)any)) continue;                   // :413 / :638
         Pt sum[2][2][8];                                                           // [output polynomial][half]; BLK only (one key bit: the product itself)
         if (BLK) {
-#pragma unroll
-            for (int pp = 0; pp < 2; pp++)
-#pragma unroll
-                for (int h = 0; h < 2; h++)
-#pragma unroll
-                    for (int e = 0; e < 8; e++) { sum[pp][h][e].a = 0; sum[pp][h][e].b = 0; }
+            pt_zero(sum);
         }
         for (int q = 0; q < (BLK ? blk_len : 1); q++) {
             const int i = blk * blk_len + q;
-            const uint32_t v0 = at_src[i];
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
             if (at == 0) continue;
             Pt tacc[2][2][8];
-#pragma unroll
-            for (int pp = 0; pp < 2; pp++)
-#pragma unroll
-                for (int h = 0; h < 2; h++)
-#pragma unroll
-                    for (int e = 0; e < 8; e++) { tacc[pp][h][e].a = 0; tacc[pp][h][e].b = 0; }
+            pt_zero(tacc);
             for (int c = 0; c < 2; c++)
                 for (int j = 0; j < l; j++) {
                     // the digit's four key rows are REQUESTED here and consumed after its transform: left to the compiler they were loaded
@@ -1053,18 +1055,10 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
     const int msbit = 32 - LOGN - 1;
     for (int blk = 0; blk < n / blk_len; blk++) {
         bool any = false;
-        for (int q = 0; q < blk_len; q++) {
-            const uint32_t v0 = at_src[blk * blk_len + q];
-            any |= (pre_switched ? v0 : divbits<uint32_t>(v0, msbit)) != 0;
-        }
+        for (int q = 0; q < blk_len; q++) any |= mask_exponent(at_src[blk * blk_len + q], pre_switched, msbit) != 0;
         if (!__builtin_amdgcn_readfirstlane((int)any)) continue;                   // :638 for every key bit of the block
         Pt sum[2][2][8];                                                           // [output polynomial][half]
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++)
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-#pragma unroll
-                for (int e = 0; e < 8; e++) { sum[pp][h][e].a = 0; sum[pp][h][e].b = 0; }
+        pt_zero(sum);
         for (int c = 0; c < 2; c++)
             for (int j = 0; j < l; j++) {
                 Pt z[8];
@@ -1073,8 +1067,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
                 ntt_forward<LOGN>(z, tw[0], lds, t);
                 for (int q = 0; q < blk_len; q++) {
                     const int i = blk * blk_len + q;
-                    const uint32_t v0 = at_src[i];
-                    const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+                    const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
                     if (at == 0) continue;                                         // :638 per key bit
                     const uint64_t *mrow = mono + (size_t)(at - 1) * N + 8 * t;
                     const uint64_t *rowp = brk + (((size_t)i * 2 * l + (size_t)(c * l + j)) * 4) * N + 8 * t;   // [poly][half][N]
@@ -1128,11 +1121,8 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
                                                                               const int *__restrict__ slot_party, const int *__restrict__ slot_row, int logB_lev,
                                                                               uint64_t *__restrict__ lev_out) {
     constexpr int N = 1 << LOGN, NT = N >> NLR;
-    uint64_t *lds = reinterpret_cast<uint64_t *>(ntt_smem);                        // two staging buffers, then the table
-    const int t = threadIdx.x;
-    const uint4 *tw[1]; const int which[1] = {0};
-    stage_tables<LOGN, 1>(tab, reinterpret_cast<uint4 *>(lds + 2 * NttLds<LOGN>::WORDS), t, NT, tw, which);
-    const NttConsts k = tab_consts<LOGN>(tab);
+    const Workgroup<LOGN, 2> wg(tab);                            // two staging buffers (lift_pair), then the table
+    const int t = wg.t;
     const size_t gate = blockIdx.x % ngates;
     const int slot = (int)(blockIdx.x / ngates);
     const size_t rot = gate * (size_t)rows_per_gate + slot;
@@ -1148,8 +1138,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
     if (t == 0) acc[0][0] = (uint64_t)1 << (64 - (row + 1) * logB_lev);           // :403-406 trivial RLEV row
     const int msbit = 32 - LOGN - 1;
     for (int i = 0; i < n; i++) {
-        const uint32_t v0 = at_src[i];
-        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
         if (at == 0) continue;                                                     // :413
         const uint4 *rowb = reinterpret_cast<const uint4 *>(brk + ((size_t)i * 4 * 4) * N + 8 * t);   // [digit g][poly][half][N], two points per 16 bytes
         // piece (g, ep) of (polynomial pp, half h): K[g * 4 + ep]
@@ -1170,7 +1159,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
             for (int j = 0; j < 2; j++)
 #pragma unroll
                 for (int e = 0; e < 8; e++) zp[j][e] = res_small(gd.digit(gd.prep(c ? acc[1][e] : acc[0][e]), j));   // :415-425 decompto!
-            ntt_forward_n<LOGN, 0, false, 2>(zp, tw[0], lds, t);
+            ntt_forward_n<LOGN, 0, false, 2>(zp, wg.tw, wg.lds, t);
 #pragma unroll
             for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -1194,18 +1183,18 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
         };
         auto lift_rotate = [&](Pt (&th)[2][8], auto ppc) {                        // inverse pair, lift, X^at - 1 (:435-437)
             constexpr int pp = decltype(ppc)::value;
-            ntt_inverse_n<LOGN, Plan<LOGN, NLR>::NPASS - 1, false, 2>(th, tw[0], lds, t, k.ninv);
+            ntt_inverse_n<LOGN, Plan<LOGN, NLR>::NPASS - 1, false, 2>(th, wg.tw, wg.lds, t, wg.k.ninv);
             uint64_t w[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) w[e] = crt_signed(th[0][e]) + (crt_signed(th[1][e]) << 32);
             __syncthreads();
 #pragma unroll
-            for (int e = 0; e < 8; e++) lds[e * NT + t] = w[e];
+            for (int e = 0; e < 8; e++) wg.lds[e * NT + t] = w[e];
             __syncthreads();
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 const uint32_t src = (uint32_t)(e * NT + t - (int)at) & (2u * N - 1u);
-                const uint64_t v = lds[src & (N - 1)];
+                const uint64_t v = wg.lds[src & (N - 1)];
                 acc[pp][e] += (src >= (uint32_t)N ? (uint64_t)0 - v : v) - w[e];
             }
         };
@@ -1233,7 +1222,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
         for (int h = 0; h < 2; h++)
 #pragma unroll
             for (int e = 0; e < 8; e++) z[h][e] = fwd_in(piece_of(acc[c][e], h), e);
-        ntt_forward_n<LOGN, 0, false, 2>(z, tw[0], lds, t);
+        ntt_forward_n<LOGN, 0, false, 2>(z, wg.tw, wg.lds, t);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             uint64_t *o = lev_out + ((rot * 2 + c) * 2 + h) * (size_t)N + 8 * t;
@@ -1263,11 +1252,8 @@ struct ExactPhase2Args {
 template <int LOGN>
 __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(const uint4 *__restrict__ tab, const ExactPhase2Args a) {
     constexpr int N = 1 << LOGN, NT = N >> NLR;
-    uint64_t *lds = reinterpret_cast<uint64_t *>(ntt_smem);
-    const int t = threadIdx.x;
-    const uint4 *tw[1]; const int which[1] = {0};
-    stage_tables<LOGN, 1>(tab, reinterpret_cast<uint4 *>(lds + 2 * NttLds<LOGN>::WORDS), t, NT, tw, which);   // two staging buffers (lift_pair), then the table
-    const NttConsts kc = tab_consts<LOGN>(tab);
+    const Workgroup<LOGN, 2> wg(tab);                            // two staging buffers (lift_pair), then the table
+    const int t = wg.t;
     const size_t g = blockIdx.x;
     const int k = a.k;
     uint64_t *acc = a.acc + g * (size_t)(k + 1) * N;
@@ -1286,17 +1272,6 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(c
             for (int q = 1; q <= k; q++) acc[(size_t)q * N + i] = 0;
         }
     }
-    auto zero2 = [](Pt (&x)[2][8]) {
-#pragma unroll
-        for (int h = 0; h < 2; h++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) { x[h][e].a = 0; x[h][e].b = 0; }
-    };
-    auto digit_ntt = [&](Pt (&z)[8], const uint64_t (&tp)[8], const Gadget<uint64_t> &gd, int j) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) z[e] = res_small(gd.digit(tp[e], j));
-        ntt_forward<LOGN>(z, tw[0], lds, t);
-    };
     auto mac2 = [&](Pt (&dst)[2][8], const Pt (&z)[8], const uint64_t *tbl, bool subtract) {   // dst += / -= z * (low, high) of one split polynomial
 #pragma unroll
         for (int h = 0; h < 2; h++)
@@ -1313,16 +1288,16 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(c
         const uint64_t *rd = a.rlk_d + (size_t)idx * a.l_uni * 2 * N;
         const uint64_t *rf = a.rlk_f + (size_t)idx * a.l_uni * 4 * N;
         Pt tv[2][8];
-        zero2(tv);
+        pt_zero(tv);
         for (int q = 0; q <= idx; q++) {
             uint64_t tp[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) tp[e] = glev.prep(acc[(size_t)q * N + e * NT + t]);   // :470-471
             Pt txq[2][8], tyq[2][8];
-            zero2(txq); zero2(tyq);
+            pt_zero(txq); pt_zero(tyq);
             for (int j = 0; j < iter; j++) {                                       // :485-499 LEV multiplication
                 Pt z[8];
-                digit_ntt(z, tp, glev, j);
+                digit_forward<LOGN>(z, tp, glev, j, wg.tw, wg.lds, t);
                 mac2(txq, z, lev + (size_t)(2 * j) * 2 * N, false);
                 mac2(tyq, z, lev + (size_t)(2 * j + 1) * 2 * N, false);
             }
@@ -1331,15 +1306,15 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(c
 #pragma unroll
                 for (int e = 0; e < 8; e++) tx[((size_t)q * 2 + h) * N + 8 * t + e] = pack(txq[h][e]);
             uint64_t yw[8];
-            lift_pair<LOGN>(tyq, yw, tw[0], kc, lds, t);                // :501-504
+            lift_pair<LOGN>(tyq, yw, wg.tw, wg.k, wg.lds, t);                // :501-504
 #pragma unroll
             for (int e = 0; e < 8; e++) tp[e] = guni.prep(yw[e]);                  // :508-509
             Pt tyu[2][8];
-            zero2(tyu);
+            pt_zero(tyu);
             const uint64_t *vk = q == 0 ? a.crs : a.pub_b + (size_t)(q - 1) * a.l_uni * 2 * N;
             for (int j = 0; j < a.l_uni; j++) {                                    // :521-535 u and v
                 Pt z[8];
-                digit_ntt(z, tp, guni, j);
+                digit_forward<LOGN>(z, tp, guni, j, wg.tw, wg.lds, t);
                 mac2(tyu, z, rd + (size_t)j * 2 * N, false);
                 mac2(tv, z, vk + (size_t)j * 2 * N, q == 0);                       // mulsubto! with crs, muladdto! with b_i
             }
@@ -1349,19 +1324,19 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(c
                 for (int e = 0; e < 8; e++) ty2[((size_t)q * 2 + h) * N + 8 * t + e] = pack(tyu[h][e]);
         }
         uint64_t vw[8];
-        lift_pair<LOGN>(tv, vw, tw[0], kc, lds, t);                      // :538
+        lift_pair<LOGN>(tv, vw, wg.tw, wg.k, wg.lds, t);                      // :538
         uint64_t tp[8];
 #pragma unroll
         for (int e = 0; e < 8; e++) tp[e] = guni.prep(vw[e]);                      // :541
         Pt tyb[2][8], tya[2][8];
-        zero2(tya);
+        pt_zero(tya);
 #pragma unroll
         for (int h = 0; h < 2; h++)
 #pragma unroll
             for (int e = 0; e < 8; e++) tyb[h][e] = unpack(ty2[(size_t)h * N + 8 * t + e]);
         for (int i = 0; i < a.l_uni; i++) {                                        // :547-550 w
             Pt z[8];
-            digit_ntt(z, tp, guni, i);
+            digit_forward<LOGN>(z, tp, guni, i, wg.tw, wg.lds, t);
             mac2(tyb, z, rf + (size_t)(2 * i) * 2 * N, false);
             mac2(tya, z, rf + (size_t)(2 * i + 1) * 2 * N, false);
         }
@@ -1371,13 +1346,13 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_kms_phase2_kernel(c
             for (int h = 0; h < 2; h++)
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
-                    Pt xv; xv.a = 0; xv.b = 0;
+                    Pt xv; pt_zero(xv);
                     if (q <= idx) xv = unpack(tx[((size_t)q * 2 + h) * N + 8 * t + e]);
                     const Pt yv = q == 0 ? tyb[h][e] : (q == idx + 1 ? tya[h][e] : unpack(ty2[((size_t)q * 2 + h) * N + 8 * t + e]));
                     s[h][e] = pt_add_lazy(xv, yv);
                 }
             uint64_t w[8];
-            lift_pair<LOGN>(s, w, tw[0], kc, lds, t);
+            lift_pair<LOGN>(s, w, wg.tw, wg.k, wg.lds, t);
 #pragma unroll
             for (int e = 0; e < 8; e++) acc[(size_t)q * N + e * NT + t] = w[e];
         }
@@ -1414,27 +1389,22 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
     uint64_t *sc = a.scratch + g * (size_t)(k + 1) * N;
     const Gadget<uint32_t> gd(l, a.logB);
     const int msbit = 32 - LOGN - 1;
-    auto zero = [](Pt (&x)[8]) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) { x[e].a = 0; x[e].b = 0; }
-    };
     for (int idx = 0; idx < k; idx++) {
         const int np = idx + 1;
         const uint32_t *at_src = a.lwe + g * (size_t)a.lwe_stride + (size_t)idx * n;
         for (int i = 0; i < n; i++) {
-            const uint32_t v0 = at_src[i];
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], a.pre_switched, msbit));
             if (at == 0) continue;                                                 // :261
             const uint64_t *uni = a.brk + (size_t)idx * a.brk_party_stride + (size_t)i * 3 * l * N;
             const uint64_t *ud = uni, *uf = uni + (size_t)l * N;
             Pt tb[8], ta[8];
-            zero(tb); zero(ta);
+            pt_zero(tb); pt_zero(ta);
             for (int q = 0; q <= np; q++) {
                 uint32_t tp[8];
 #pragma unroll
                 for (int e = 0; e < 8; e++) tp[e] = gd.prep(acc[(size_t)q * N + e * NT + t]);   // :264-275
                 Pt tu[8], tv[8];
-                zero(tu); zero(tv);
+                pt_zero(tu); pt_zero(tv);
                 const uint64_t *vk = q == 0 ? a.crs : a.pub_b + (size_t)(q - 1) * l * N;
                 for (int j = 0; j < l; j++) {                                      // :279-294 u and v
                     uint64_t kd[8], kv[8];                                         // key rows requested before the transform that hides them (at use: an exposed round trip per digit)
