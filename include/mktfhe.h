@@ -248,6 +248,32 @@ int mkt_keyswitch_batch(mkt_ctx *ctx, const void *acc, uint32_t *out, size_t B, 
  * levkey [B][Rtot][2][M] complex, Rtot = 1 + (k-1)*l_lev, party-major rows */
 int mkt_kms_phase1_batch(mkt_ctx *ctx, const uint32_t *atilde, double *levkey, size_t B, int mem);
 
+/* ---- programmable bootstrap: bootstrapping! (bootstrapping.jl:4-27) with a caller-supplied lookup table in place of its constant test
+ *      vector.  A lookup table (LUT) is a test-vector polynomial T: N ring words.  For a ciphertext whose body word mod-switches to
+ *      btilde in [0, 2N] (bootstrapping.jl:8-9, divbits), the accumulator handed to blindrotate! is acc = (X^btilde * T, 0, ..., 0) in
+ *      Z[X]/(X^N + 1): with r = btilde mod N and s = -1 for N <= btilde < 2N, else +1 (btilde = 2N is the identity),
+ *          acc.b[i] = s T[i - r] for i >= r,        acc.b[i] = -s T[N + i - r] for i < r.
+ *      blindrotate! and keyswitch! follow unchanged.  With T = (-2^(W-3), ..., -2^(W-3)) this is bootstrapping.jl:11-23 word for word, and
+ *      mkt_lut_bootstrap_batch returns the words of mkt_bootstrap_batch.
+ *      LAYING OUT A TABLE.  The bootstrap rotates T by the mod-switched phase phi in [0, 2N) of the input and extracts coefficient 0:
+ *          T[0] for phi = 0,        -T[N - phi] for 1 <= phi <= N,        T[2N - phi] for N < phi < 2N
+ *      (times the ring word's scale; the key switch keeps the top 32 bits).  The function computed is negacyclic by construction,
+ *      f(phi + 1/2) = -f(phi): a table is free on one half of the torus only (layout, recipes, noise).  Every ring word is
+ *      a valid table entry; tables are not validated.
+ *      luts: [nluts][N] ring words; sel: [B] rows of luts, or NULL = row 0 for the whole batch; both live where the ciphertexts live
+ *      (`mem`).  Validation as mkt_gate_batch_gather: with MKT_MEM_HOST a sel[j] >= nluts or an operand index >= pool_rows is MKT_ERR_ARG
+ *      and nothing is written; with MKT_MEM_DEVICE they are clamped to the last row -- never an out-of-bounds access.  nluts == 0 and
+ *      gates over an empty pool are refused in either memory kind.  Both arithmetic modes, every scheme the gate path serves. ---- */
+/* unit level: acc[j] = (X^btilde(lwe[j]) * luts[sel[j]], 0 ...); lwe [B][k*n+1], acc [B][1+k][N] ring words.  Needs no keys */
+int mkt_lut_testvector_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, void *acc, size_t B, int mem);
+/* out[j] = keyswitch!(blindrotate!(acc[j] as above)); lwe, out: [B][k*n+1]; out may alias lwe */
+int mkt_lut_bootstrap_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem);
+/* one circuit level of table lookups: gate j bootstraps  cst[j] e_b + sum_{t<4} wt[j][t] pool[idx[j][t]]  through luts[sel[j]] -> out[j]
+ * (pool [pool_rows][k*n+1]; idx [B][4] rows; wt [B][4] int8 weights, 0 = no term; cst [B] added to the b word); out may be a later region of
+ * the pool that no gate of this call reads */
+int mkt_lut_batch_gather(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows,
+                         const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem);
+
 /* ---- unit-level entry points (parity tests, transform roofline) ----
  * On an MKT_ARITH_EXACT context a TransPoly is N residue pairs (x mod p1) | (x mod p2) << 32 (uint64, the same 8 N bytes as
  * M complex doubles), in the bit-reversed order the Cooley-Tukey network with psi_rev[m + i] leaves them; forward reads
@@ -308,6 +334,8 @@ int mkt_multi_gate_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x
 int mkt_multi_gate3_batch_ops(mkt_multi *m, const uint8_t *ops, const uint32_t *x, const uint32_t *y, const uint32_t *z, uint32_t *out, size_t B, int mem);
 int mkt_multi_mux_batch(mkt_multi *m, const uint32_t *s, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t B, int mem);
 int mkt_multi_bootstrap_batch(mkt_multi *m, uint32_t *lwe, size_t B, int mem);
+/* mkt_lut_bootstrap_batch, sharded: lwe, out and sel are cut with the batch; every shard reads all of luts (in place, or staged per shard) */
+int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem);
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem);
 int mkt_multi_blindrotate_batch(mkt_multi *m, const uint32_t *atilde, void *acc, size_t B, int mem);
 int mkt_multi_keyswitch_batch(mkt_multi *m, const void *acc, uint32_t *out, size_t B, int mem);
@@ -354,9 +382,16 @@ const void *mkt_client_pubkey(const mkt_client_party *p, size_t *bytes);
 /* lwe_encrypt (SK: party = 0) / lwe_ith_encrypt (MK): out [k*n+1] */
 int mkt_client_lwe_encrypt(const mkt_params *params, const mkt_client_party *p, int party, int bit,
                            double sigma_lwe, const uint8_t *seed, uint32_t *out);
+/* the same encryption of ANY message mu on the 32-bit torus (mkt_client_lwe_encrypt is mu = +-2^29): multi-valued inputs of a programmable
+ * bootstrap.  Same streams: with the same seed and mu = +-2^29 the words of mkt_client_lwe_encrypt */
+int mkt_client_lwe_encrypt_word(const mkt_params *params, const mkt_client_party *p, int party, uint32_t mu,
+                                double sigma_lwe, const uint8_t *seed, uint32_t *out);
 /* lwe_decrypt: keys = nparties pointers; returns 0/1, <0 on error */
 int mkt_client_lwe_decrypt(const mkt_params *params, const mkt_client_party *const *keys, int nparties,
                            const uint32_t *lwe);
+/* the phase lwe_decrypt rounds: message + noise on the 32-bit torus.  In this library's sign convention (the mask is stored with the sign
+ * that makes decryption a sum) that is b + sum_i <a_i, s_i> */
+int mkt_client_lwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const uint32_t *lwe, uint32_t *phase);
 
 #ifdef __cplusplus
 }

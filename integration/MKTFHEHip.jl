@@ -145,6 +145,15 @@ function MKTFHE.bootstrapping!(ctxts::Vector{MKTFHE.LWE{UInt32}}, s::HipScheme)
     ctxts
 end
 
+# programmable bootstrap: bootstrapping! with a caller's test-vector polynomial `lut` (N ring words; mktfhe.h "programmable bootstrap":
+# coefficient layout, the negacyclic constraint).  fill(-(R(1) << (bits(R) - 3)), N) is bootstrapping! itself
+function lut_bootstrapping!(ctxt::MKTFHE.LWE{UInt32}, lut::Vector{R}, s::HipScheme) where {R<:Unsigned}
+    v = flat(ctxt)
+    check(ccall((:mkt_lut_bootstrap_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{R}, Csize_t, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Csize_t, Cint),
+                s.ctx, lut, 1, C_NULL, v, v, 1, HOST), s.ctx)
+    unflat!(ctxt, v)
+end
+
 # blindrotate!(ã, acc, scheme)  (bootstrapping.jl:32 / :114 / :234 / :369): ã = mod-switched mask (k*n words in [0, 2N]),
 # acc updated in place
 function MKTFHE.blindrotate!(atilde::Vector{UInt32}, acc::MKTFHE.RLWE{R}, s::HipScheme{R}) where R

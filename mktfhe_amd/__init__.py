@@ -2,7 +2,7 @@
 
 Keeps the operator surface of the Julia reference SNUCP/MKTFHE for the gate-bootstrapping hot
 path (bootstrapping!, blindrotate!, keyswitch!, NAND/AND/OR/XOR/XNOR/NOR/NOT!, and three-input gates in one
-bootstrap: MAJ3/XOR3/..., full_adder) behind a C ABI
+bootstrap: MAJ3/XOR3/..., full_adder; programmable bootstrap with caller-supplied lookup tables: lut_bootstrap) behind a C ABI
 (include/mktfhe.h) implemented with hand-written HIP kernels for gfx950.  No CPU fallback.
 """
 from .params import *  # noqa: F401,F403
@@ -12,6 +12,7 @@ from .scheme import (  # noqa: F401
     bootstrapping_, blindrotate_, keyswitch, NAND, AND, OR, XOR, XNOR, NOR, NOT_, MUX, MUX_composite, MAJ3, XOR3, full_adder,
     MEM_DEVICE, MEM_HOST, FMT_INT_COEFF, FMT_F64_FFT, ARITH_F64REF, ARITH_EXACT,
 )
+from .lut import lut_poly, sign_lut, lut_testvector, lut_bootstrap, lut_gather, lwe_encrypt_word, lwe_phase  # noqa: F401
 from ._lib import MktError, LIB_PATH, build_id  # noqa: F401
 from . import keyblob  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402

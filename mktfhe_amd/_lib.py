@@ -61,6 +61,9 @@ SYMBOLS = {
     "mkt_mux_batch_gather": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_not_batch": (_i, [_vp, _vp, _sz, _i]),
     "mkt_bootstrap_batch": (_i, [_vp, _vp, _sz, _i]),
+    "mkt_lut_testvector_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _i]),
+    "mkt_lut_bootstrap_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _i]),
+    "mkt_lut_batch_gather": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_modswitch_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_blindrotate_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mkt_keyswitch_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
@@ -90,6 +93,7 @@ SYMBOLS = {
     "mkt_multi_gate3_batch_ops": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_multi_mux_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_multi_bootstrap_batch": (_i, [_vp, _vp, _sz, _i]),
+    "mkt_multi_lut_bootstrap_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _i]),
     "mkt_multi_not_batch": (_i, [_vp, _vp, _sz, _i]),
     "mkt_multi_blindrotate_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mkt_multi_keyswitch_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
@@ -109,6 +113,8 @@ SYMBOLS = {
     "mkt_client_rlk_f": (_vp, [_vp, C.POINTER(_sz)]),
     "mkt_client_pubkey": (_vp, [_vp, C.POINTER(_sz)]),
     "mkt_client_lwe_encrypt": (_i, [_pp, _vp, _i, _i, _dbl, _vp, _vp]),
+    "mkt_client_lwe_encrypt_word": (_i, [_pp, _vp, _i, C.c_uint32, _dbl, _vp, _vp]),
+    "mkt_client_lwe_phase": (_i, [_pp, C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint32)]),
     "mkt_client_lwe_decrypt": (_i, [_pp, C.POINTER(_vp), _i, _vp]),
 }
 

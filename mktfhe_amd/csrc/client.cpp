@@ -347,9 +347,9 @@ const void *mkt_client_rlk_d(const mkt_client_party *p, size_t *bytes) { if (byt
 const void *mkt_client_rlk_f(const mkt_client_party *p, size_t *bytes) { if (bytes) *bytes = p->rlk_f.size(); return p->rlk_f.data(); }
 const void *mkt_client_pubkey(const mkt_client_party *p, size_t *bytes) { if (bytes) *bytes = p->pub.size(); return p->pub.data(); }
 
-// scheme.jl:352-386 lwe_encrypt / lwe_ith_encrypt: b = e - <a,s> + (2m-1)*2^29, mask in the party's block
-int mkt_client_lwe_encrypt(const mkt_params *params, const mkt_client_party *K, int party, int bit,
-                           double sigma_lwe, const uint8_t *seed, uint32_t *out) {
+// scheme.jl:352-386 lwe_encrypt / lwe_ith_encrypt with ANY torus message: b = e - <a,s> + mu, mask in the party's block
+int mkt_client_lwe_encrypt_word(const mkt_params *params, const mkt_client_party *K, int party, uint32_t mu,
+                                double sigma_lwe, const uint8_t *seed, uint32_t *out) {
     if (!params || !K || !out) return MKT_ERR_ARG;
     const mkt_params &p = *params;
     Shape sh = shape_of(p);
@@ -362,9 +362,29 @@ int mkt_client_lwe_encrypt(const mkt_params *params, const mkt_client_party *K, 
     uint32_t dot = 0;
     uint32_t e = (uint32_t)r.noise(sigma_lwe);
     for (int i = 0; i < p.n; i++) { a[i] = (uint32_t)r.next(); dot += a[i] * K->lwekey[i]; }
-    uint32_t mu = (uint32_t)(2 * (bit ? 1 : 0) - 1);
-    out[sh.lwe_len - 1] = e + (0u - dot + (mu << 29));
+    out[sh.lwe_len - 1] = e + (0u - dot + mu);
     explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// the reference's bit encryption: the message (2m - 1) 2^29
+int mkt_client_lwe_encrypt(const mkt_params *params, const mkt_client_party *K, int party, int bit,
+                           double sigma_lwe, const uint8_t *seed, uint32_t *out) {
+    return mkt_client_lwe_encrypt_word(params, K, party, (uint32_t)(2 * (bit ? 1 : 0) - 1) << 29, sigma_lwe, seed, out);
+}
+
+// the phase lwe_decrypt decides on (scheme.jl:388-407 before its rounding): b + sum_i <a_i, s_i>, message + noise on the 32-bit torus
+int mkt_client_lwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const uint32_t *lwe, uint32_t *phase) {
+    if (!params || !keys || !lwe || !phase) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    Shape sh = shape_of(p);
+    if (nparties != sh.nparty) return MKT_ERR_ARG;
+    uint32_t b = lwe[sh.lwe_len - 1];
+    for (int i = 0; i < nparties; i++) {
+        if (!keys[i]) return MKT_ERR_ARG;
+        for (int q = 0; q < p.n; q++) b += keys[i]->lwekey[q] * lwe[(size_t)i * p.n + q];
+    }
+    *phase = b;
     return MKT_OK;
 }
 

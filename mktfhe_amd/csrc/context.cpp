@@ -473,6 +473,23 @@ int bootstrap_chunk(mkt_ctx *c, const uint32_t *lin, uint32_t *out, size_t B) {
     return do_keyswitch(c, c->ws_acc, out, B);
 }
 
+// A caller's lookup tables on the device: luts [nluts][N] ring words, sel [B] rows or nullptr (row 0)
+struct LutArgs { const void *luts; size_t nluts; const uint32_t *sel; };
+
+// rotate_chunk with the test vector of a caller's table (mktfhe.h "programmable bootstrap"): ws_acc <- blindrotate!((X^btilde T, 0 ...)).
+// Every route takes the accumulator it is handed (the multi-key phase 2 with lin_for_tv == nullptr, as mkt_blindrotate_batch runs it)
+int lut_rotate_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, size_t B) {
+    HIPCHK(c, mktd::launch_lut_testvector(c->p.W, t.luts, t.nluts, t.sel, lin, c->sh.lwe_len, c->logN, c->sh.kacc, c->ws_acc, B, c->stream));
+    return do_blindrotate(c, lin, c->sh.lwe_len, 0, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B);
+}
+
+// the programmable bootstrap of a device-resident chunk: lin -> out (out may be lin: the masks and b are read before the key switch writes)
+int lut_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, uint32_t *out, size_t B) {
+    int r;
+    if ((r = lut_rotate_chunk(c, t, lin, B))) return r;
+    return do_keyswitch(c, c->ws_acc, out, B);
+}
+
 // staging helper for MKT_MEM_HOST callers
 struct Staged {
     mkt_ctx *c; void *dev = nullptr; void *host_out = nullptr; size_t bytes = 0; bool owned = false;
@@ -1198,6 +1215,83 @@ int mkt_bootstrap_batch(mkt_ctx *c, uint32_t *lwe, size_t B, int mem) {
         if ((r = bootstrap_chunk(c, chunk, chunk, nb))) return r;
     }
     return sx.out(lwe);
+}
+
+// ---- programmable bootstrap (mktfhe.h): a caller's lookup tables in place of the constant test vector ----
+// the tables and row selectors of one call on the device; with MKT_MEM_HOST a selector beyond the table is refused here (a device array is
+// clamped by the kernel: no out-of-bounds read)
+struct StagedLuts {
+    Staged luts, sel;
+    explicit StagedLuts(mkt_ctx *c) : luts{c}, sel{c} {}
+    int in(mkt_ctx *c, const char *who, const void *l, size_t nluts, const uint32_t *s, size_t B, int mem) {
+        if (!nluts) return fail(c, MKT_ERR_ARG, std::string(who) + ": no lookup table");
+        const uint32_t *iv[] = {s};
+        if (s && mem == MKT_MEM_HOST && !in_pool_host(iv, 1, B, nluts)) return fail(c, MKT_ERR_ARG, std::string(who) + ": table selector outside the tables");
+        int r;
+        if ((r = luts.in(l, nluts * poly_bytes(c), mem, true))) return r;
+        return s ? sel.in(s, B * 4, mem, true) : MKT_OK;
+    }
+    LutArgs chunk(size_t nluts, size_t off) const { return LutArgs{luts.dev, nluts, sel.dev ? (const uint32_t *)sel.dev + off : nullptr}; }
+};
+
+// unit level: acc[j] = (X^btilde(lwe[j]) * luts[sel[j]], 0 ...), what the programmable bootstrap hands to blindrotate!; no keys needed
+int mkt_lut_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, void *acc, size_t B, int mem) {
+    if (!c || !luts || !lwe || !acc || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    DevGuard dg(c->device);
+    const size_t len = (size_t)c->sh.lwe_len, accb = (size_t)(1 + c->sh.kacc) * poly_bytes(c);
+    StagedLuts t(c);
+    Staged sx{c}, sc{c};
+    int r;
+    if ((r = t.in(c, "mkt_lut_testvector_batch", luts, nluts, sel, B, mem)) || (r = sx.in(lwe, B * len * 4, mem, true)) || (r = sc.in(acc, B * accb, mem, false))) return r;
+    const LutArgs a = t.chunk(nluts, 0);
+    HIPCHK(c, mktd::launch_lut_testvector(c->p.W, a.luts, a.nluts, a.sel, (const uint32_t *)sx.dev, (int)len, c->logN, c->sh.kacc, sc.dev, B, c->stream));
+    return sc.out(acc);
+}
+
+// both programmable-bootstrap entry points share one body: the inputs in batch order (src: [B][len]), or built per gate from a pool
+// (src = pool [rows][len]; idx [B][4], wt [B][4], cst [B]) by lut_linear_kernel
+static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *src, size_t rows, const uint32_t *idx,
+                    const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem) {
+    MKT_EXACT_GATE(c);
+    int r;
+    if ((r = check_ready(c, true, true))) return r;
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    const size_t len = (size_t)c->sh.lwe_len;
+    const bool pool = idx != nullptr;
+    StagedLuts t(c);
+    Staged sv{c}, so{c}, si{c}, sw{c}, sk{c};
+    if ((r = t.in(c, who, luts, nluts, sel, B, mem)) || (r = sv.in(src, rows * len * 4, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
+    if (pool && ((r = si.in(idx, B * 16, mem, true)) || (r = sw.in(wt, B * 4, mem, true)) || (r = sk.in(cst, B * 4, mem, true)))) return r;
+    for (size_t off = 0; off < B; off += CHUNK_GATES) {
+        const size_t nb = std::min(CHUNK_GATES, B - off);
+        if ((r = ensure_workspace(c, nb))) return r;
+        const uint32_t *lin = (const uint32_t *)sv.dev + off * len;
+        if (pool) {
+            HIPCHK(c, mktd::launch_lut_linear((const uint32_t *)sv.dev, rows, (const uint32_t *)si.dev + off * 4, (const int8_t *)sw.dev + off * 4, (const uint32_t *)sk.dev + off,
+                                              c->ws_lin, (int)len, nb, c->stream));
+            lin = c->ws_lin;
+        }
+        if ((r = lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, (uint32_t *)so.dev + off * len, nb))) return r;
+    }
+    return so.out(out);
+}
+
+// out[j] = keyswitch!(blindrotate!((X^btilde(lwe[j]) * luts[sel[j]], 0 ...))): bootstrapping! with a caller's table; out may be lwe
+int mkt_lut_bootstrap_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !lwe || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    return lut_impl(c, "mkt_lut_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, out, B, mem);
+}
+
+// one circuit level of table lookups: gate j bootstraps cst[j] e_b + sum_t wt[j][t] pool[idx[j][t]] through luts[sel[j]]; out may be a later
+// region of the pool that no gate of this call reads.  Validation as mkt_gate_batch_gather
+int mkt_lut_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
+                         const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !pool || !idx || !wt || !cst || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: gates over an empty pool");
+    const uint32_t *iv[] = {idx};
+    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: operand index outside the pool");
+    return lut_impl(c, "mkt_lut_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, out, B, mem);
 }
 
 int mkt_modswitch_batch(mkt_ctx *c, const uint32_t *lwe, uint32_t *atilde, uint32_t *btilde, size_t B, int mem) {

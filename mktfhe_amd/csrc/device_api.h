@@ -137,6 +137,11 @@ hipError_t launch_mux_linear(const uint32_t *pool, size_t pool_rows, const uint3
 hipError_t launch_mux_combine(int W, void *acc, size_t B, size_t words, hipStream_t s);   // acc[j] += acc[B + j], + 2^(W-3) at X^0 of b: [2B][words] -> [B][words]
 hipError_t launch_modswitch(const uint32_t *lwe, uint32_t *atilde, uint32_t *btilde, int len, int logN, size_t B, hipStream_t s);
 hipError_t launch_testvector(int W, const uint32_t *lin, int lwe_stride, int logN, int kacc, void *acc, size_t B, hipStream_t s);
+// programmable bootstrap (lut.hip; mktfhe.h "programmable bootstrap"): acc[g] = (X^btilde(lin[g]) * luts[sel[g]], 0 ...), luts [nluts][N] ring
+// words, sel [B] or NULL (row 0), rows clamped to nluts - 1; acc [B][1+kacc][N]
+hipError_t launch_lut_testvector(int W, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lin, int lwe_stride, int logN, int kacc, void *acc, size_t B, hipStream_t s);
+// its gather front end: out[g] = cst[g] e_b + sum_{t<4} wt[g][t] pool[idx[g][t]] (int8 weights, 0 skips the term; rows clamped into the pool); out [B][len]
+hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s);
 hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);
 bool blockg_supported(int logM, int G);
 hipError_t launch_rot_blockg_u32(int logM, int G, int npolys, const RotArgs &a, size_t nslots, hipStream_t s);   // npolys = RLWE length + 1 (2; 3 at block length 1 or 3 and 4 at block length 1, 32-bit ring, G = 4)

@@ -145,9 +145,9 @@ void settle_inputs(const void *ptr, int mem) {
     if (prev >= 0) (void)hipSetDevice(prev);
 }
 
-struct ArgSpec { const void *base; size_t row_bytes; bool in, out; };
+struct ArgSpec { const void *base; size_t row_bytes; bool in, out; size_t whole_rows = 0; };   // whole_rows > 0: not cut with the batch -- every shard is handed all whole_rows rows (lookup tables)
 
-// the common shape of a sharded batch call: every argument is [B][row_bytes]; `call` receives the shard's pointers in order
+// the common shape of a sharded batch call: every argument is [B][row_bytes] (or whole: ArgSpec); `call` receives the shard's pointers in order
 int sharded_call(mkt_multi *m, size_t B, int mem, const std::vector<ArgSpec> &specs,
                  const std::function<int(mkt_ctx *, void **, size_t)> &call) {
     for (const ArgSpec &a : specs) if (a.in) settle_inputs(a.base, mem);
@@ -157,7 +157,8 @@ int sharded_call(mkt_multi *m, size_t B, int mem, const std::vector<ArgSpec> &sp
         int rc = MKT_OK;
         if (m->stage[s].size() < specs.size()) m->stage[s].resize(specs.size());     // this shard's thread only
         for (size_t i = 0; i < specs.size(); i++) {
-            if (args[i].prepare(specs[i].base, specs[i].row_bytes, lo, hi, mem, m->devices[s], specs[i].in, specs[i].out, m->stage[s][i], m->stage_always, m->no_peer) != 0) { rc = MKT_ERR_HIP; why = "staging a remote device buffer failed"; }
+            const size_t alo = specs[i].whole_rows ? 0 : lo, ahi = specs[i].whole_rows ? specs[i].whole_rows : hi;
+            if (args[i].prepare(specs[i].base, specs[i].row_bytes, alo, ahi, mem, m->devices[s], specs[i].in, specs[i].out, m->stage[s][i], m->stage_always, m->no_peer) != 0) { rc = MKT_ERR_HIP; why = "staging a remote device buffer failed"; }
             ptrs[i] = args[i].use;
         }
         if (rc == MKT_OK) {
@@ -286,6 +287,20 @@ int mkt_multi_bootstrap_batch(mkt_multi *m, uint32_t *lwe, size_t B, int mem) {
     if (!m || !lwe) return mfail(m, MKT_ERR_ARG, "bad argument");
     const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4;
     return sharded_call(m, B, mem, {{lwe, rb, true, true}}, [&](mkt_ctx *c, void **a, size_t nb) { return mkt_bootstrap_batch(c, (uint32_t *)a[0], nb, mem); });
+}
+
+// the programmable bootstrap, sharded: the batch (lwe, out, sel) is cut as everywhere, every shard reads the WHOLE of luts -- in place
+// where it can (host memory, or its own device), through its staging buffer otherwise
+int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem) {
+    if (!m || !luts || !lwe || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
+    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_batch: no lookup table");
+    if (sel && mem == MKT_MEM_HOST) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_batch: table selector outside the tables");   // before any shard writes
+    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);   // one table: N ring words
+    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb, false, true}};
+    if (sel) specs.push_back({sel, 4, true, false});
+    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
+        return mkt_lut_bootstrap_batch(c, a[0], nluts, sel ? (const uint32_t *)a[3] : nullptr, (const uint32_t *)a[1], (uint32_t *)a[2], nb, mem);
+    });
 }
 
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem) {

@@ -1,0 +1,113 @@
+"""Programmable bootstrap (include/mktfhe.h "programmable bootstrap"): bootstrapping! (tfhe/bootstrapping.jl:4-27) with a caller-supplied
+lookup table in place of its constant test vector -- any negacyclic function of the input's phase in one bootstrap.
+
+A lookup table is a test-vector polynomial T of N ring words; lut_poly lays one out from the output word wanted on each of P equal windows of
+the half torus (the other half is the negation: f(phi + 1/2) = -f(phi)), sign_lut is the reference's own table.  The functions take the
+scheme as an argument -- a Scheme, or for lut_bootstrap also a MultiScheme -- and go through its checked call path: every buffer's size is
+compared with what the library reads or writes before the library is called.  Arrays are numpy arrays (host) or GPU tensors, all of one kind
+per call.  This module holds no arithmetic beyond laying out tables.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .params import Params
+from .scheme import PartyKeys, _Buf, _count, _empty, _is_torch, _np_ptr, _rows, _seed_arg
+
+
+def lut_poly(values, params: Params):
+    """the table whose bootstrap returns values[v] for an input phase in window [v/(2P), (v+1)/(2P)) of the torus, P = len(values) a divisor
+    of N, and -values[v] half a turn further: T[0] = values[0], T[j] = -values[floor((N - j) P / N)] for j >= 1 (mktfhe.h: the bootstrap
+    extracts -T[N - phi] for a mod-switched phase 1 <= phi <= N).  values: ring words (any integers, taken mod 2^W) -> (N,) ring words"""
+    N, W = params.N, params.W
+    vals = [int(v) & ((1 << W) - 1) for v in np.asarray(values, dtype=object).ravel()]
+    P = len(vals)
+    if P < 1 or N % P:
+        raise ValueError(f"{P} table values: the count must divide N = {N}")
+    t = np.empty(N, dtype=object)
+    t[0] = vals[0]
+    for j in range(1, N):
+        t[j] = (-vals[(N - j) * P // N]) & ((1 << W) - 1)
+    return t.astype(params.ring_dtype)
+
+
+def sign_lut(params: Params):
+    """the reference's test vector (bootstrapping.jl:11-23): every coefficient -2^(W-3).  lut_bootstrap with it is bootstrapping!"""
+    return np.full(params.N, (1 << params.W) - (1 << (params.W - 3)), dtype=params.ring_dtype)
+
+
+def _tables(luts, params):
+    """-> the _Buf of luts ((nluts, N) or (N,) ring words) and nluts.  Host tables must already hold ring words: integers of the ring's word
+    size (another size would be converted silently, value by value, into something else than the caller laid out)"""
+    rd = np.dtype(params.ring_dtype)
+    if not _is_torch(luts):
+        luts = np.asarray(luts)
+        if luts.dtype.kind not in "iu" or luts.dtype.itemsize != rd.itemsize:
+            raise ValueError(f"lookup tables of dtype {luts.dtype}, expected {rd} (ring words)")
+        luts = np.ascontiguousarray(luts).view(rd)
+    shape = tuple(luts.shape)
+    if not shape or shape[-1] != params.N:
+        raise ValueError(f"lookup tables of shape {shape}, expected (nluts, {params.N})")
+    nluts = _rows(shape)
+    return _Buf(luts, rd, nluts, params.N), nluts
+
+
+def _sel(sel, B):
+    return None if sel is None else _Buf(sel, np.uint32, B)
+
+
+def lut_testvector(scheme, luts, ctxt, sel=None):
+    """mkt_lut_testvector_batch: the accumulators (X^btilde(ctxt[j]) * luts[sel[j]], 0 ...) a programmable bootstrap hands to blindrotate!
+    -> (..., k + 1, N) ring words living where ctxt lives.  sel: uint32 rows of luts (int32 tensor), None = row 0"""
+    p = scheme.params
+    shape = tuple(np.shape(ctxt))
+    B = _rows(shape)
+    tb, nluts = _tables(luts, p)
+    acc = _empty(ctxt, shape[:-1] + (p.k + 1, p.N), p.ring_dtype, "int64" if p.W == 64 else "int32")
+    return scheme._call("lut_testvector_batch", B, tb, nluts, _sel(sel, B), scheme._ct(ctxt, B), _Buf(acc, p.ring_dtype, B * (p.k + 1) * p.N, out=True))[-1]
+
+
+def lut_bootstrap(scheme, luts, ctxt, sel=None, out=None):
+    """mkt_lut_bootstrap_batch (a Scheme) / mkt_multi_lut_bootstrap_batch (a MultiScheme): out[j] = the bootstrap of ctxt[j] through table
+    luts[sel[j]] (None: row 0).  out None = a new array where ctxt lives; out may be ctxt"""
+    shape = tuple(np.shape(ctxt))
+    B = _rows(shape)
+    tb, nluts = _tables(luts, scheme.params)
+    if out is None:
+        out = _empty(ctxt, shape, np.uint32)
+    return scheme._call("lut_bootstrap_batch", B, tb, nluts, _sel(sel, B), scheme._ct(ctxt, B), scheme._ct(out, B, out=True))[-1]
+
+
+def lut_gather(scheme, luts, sel, pool, idx, wt, cst, out):
+    """one circuit level of table lookups (mkt_lut_batch_gather): gate j bootstraps cst[j] on the b word + sum_t wt[j][t] * pool[idx[j][t]]
+    through luts[sel[j]] -> out[j].  pool (rows, k*n+1); idx (B, 4) uint32 rows (int32 tensor), wt (B, 4) int8 weights (0: no term),
+    cst (B,) uint32; sel (B,) or None; out may be a later region of the pool"""
+    B, P = _count(cst), _rows(np.shape(pool))
+    tb, nluts = _tables(luts, scheme.params)
+    return scheme._call("lut_batch_gather", B, tb, nluts, _sel(sel, B), scheme._ct(pool, P), P, _Buf(idx, np.uint32, B, 4), _Buf(wt, np.int8, B, 4),
+                        _Buf(cst, np.uint32, B), scheme._ct(out, B, out=True))[-1]
+
+
+def lwe_encrypt_word(mu, i, key: PartyKeys, params: Params, deterministic_seed=None):
+    """lwe_ith_encrypt (scheme.jl:370-386) of ANY message mu on the 32-bit torus under party i (single-key schemes: 0): a multi-valued input
+    of a programmable bootstrap.  mu = +-2^29 with the same pinned seed gives the words of lwe_ith_encrypt"""
+    out = np.empty(params.lwe_len, dtype=np.uint32)
+    sp, _keep = _seed_arg(deterministic_seed)
+    check(_lib.lib().mkt_client_lwe_encrypt_word(C.byref(params.c()), key.h, i, int(mu) & 0xFFFFFFFF, params.alpha, sp, _np_ptr(out)))
+    return out
+
+
+def lwe_phase(ctxt, keys, params: Params):
+    """the phase lwe_decrypt rounds (scheme.jl:388-407): message + noise as a uint32 torus word (an array of them for a batch)"""
+    keys = [keys] if isinstance(keys, PartyKeys) else list(keys)
+    arr = (C.c_void_p * len(keys))(*[k.h for k in keys])
+    c = np.ascontiguousarray(ctxt, dtype=np.uint32)
+    flat = c.reshape(-1, params.lwe_len)
+    res = np.empty(flat.shape[0], dtype=np.uint32)
+    ph = C.c_uint32(0)
+    for j in range(flat.shape[0]):
+        check(_lib.lib().mkt_client_lwe_phase(C.byref(params.c()), arr, len(keys), _np_ptr(flat[j]), C.byref(ph)))
+        res[j] = ph.value
+    return res.reshape(c.shape[:-1]) if c.ndim > 1 else int(res[0])
