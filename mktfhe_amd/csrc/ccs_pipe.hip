@@ -119,7 +119,7 @@ __global__ __launch_bounds__((2 * Plan<LOGM, LOGR>::NT)) __attribute__((amdgpu_w
         const uint32_t *at_src = a.lwe + g * (size_t)a.lwe_stride + (size_t)idx * n;
         for (int i = 0; i < n; i++) {
             const uint32_t v0 = at_src[i];
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+            const uint32_t at = mask_exponent_uniform(v0, a.pre_switched, msbit);
             if (at == 0) continue;                                               // :261
             const cplx *uni = a.brk + (size_t)idx * a.brk_party_stride + (size_t)i * 3 * l * M;
             const cplx *ud = uni, *uf = uni + (size_t)l * M;

@@ -557,6 +557,12 @@ __device__ __forceinline__ WORD divbits(WORD a, int bit) {
     const WORD carry = (WORD)(a << (W - bit)) >> (W - 1);
     return (WORD)((a >> bit) + carry);
 }
+// the mod switch of one mask word to an exponent of X (bootstrapping.jl:8); pre_switched: the caller has done it.  The plain form leaves
+// the result per lane; _uniform tells the compiler that it is the same over the wave (readfirstlane).  Each call site keeps its flavour.
+__device__ __forceinline__ uint32_t mask_exponent(uint32_t v0, int pre_switched, int msbit) { return pre_switched ? v0 : divbits<uint32_t>(v0, msbit); }
+__device__ __forceinline__ uint32_t mask_exponent_uniform(uint32_t v0, int pre_switched, int msbit) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(v0, pre_switched, msbit));
+}
 
 // Balanced gadget decomposition (gsw.jl:42-52 / :86-96, unienc.jl:4-18), closed form:
 //   t' = divbits(x, W - l*logB) + sum_j (B/2) * B^j ;  digit_j = ((t' >> logB*(l-1-j)) & (B-1)) - B/2

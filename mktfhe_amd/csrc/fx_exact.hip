@@ -369,7 +369,7 @@ void fx_blindrotate_kernel(const FxRotArgs a) {
     const int msbit = 32 - a.logN - 1;
     uint32_t at_raw = at_src[0];
     for (int i = 0; i < a.n; i++) {
-        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.pre_switched ? at_raw : divbits<uint32_t>(at_raw, msbit)));
+        const uint32_t at = mask_exponent_uniform(at_raw, a.pre_switched, msbit);
         at_raw = at_src[i + 1 < a.n ? i + 1 : i];
         if (at == 0) continue;                                          // :48 / :413
 

@@ -1,5 +1,6 @@
-// Pieces shared by the kernel translation units (kernels.hip, rot_block.hip): points per thread, the dynamic LDS symbol,
-// exchange state, digit -> transform helpers, buffer-descriptor table loads, launch helpers.  Internal to the library.
+// Pieces shared by the kernel translation units (kernels.hip, rot_block.hip, ccs_pipe.hip): points per thread, the dynamic LDS symbol,
+// exchange state, steps the Float64 kernels share (czero, digit_points, inverse_to_words; mask_exponent is in fft_device.h beside divbits, where
+// the exact-mode units see it too), buffer-descriptor table loads, launch helpers.  Internal to the library.
 #pragma once
 #include "device_api.h"
 #include "fft_device.h"
@@ -28,6 +29,21 @@ __device__ __forceinline__ void fft_inverse1(cplx (&z)[1 << LOGR], const cplx *_
 }
 
 // ------------------------------------------------------------------------------------------------
+// Steps the Float64 kernels share, written once -- where the device code comes out the same through the helper as spelled out in the kernel
+// (every kernel symbol of a full default build against the build before: disassembly text and the notes' register, LDS, scratch and spill counts).
+// These kernels are as sensitive as the exact-mode ones (ntt_exact.hip), so most sites keep their lines.  Tried and kept inline, with where the
+// code changed: mask_exponent_uniform at blindrotate_k1_kernel (every LB > 1 instantiation); czero at blindrotate_k1_kernel (N = 512 .. 4096),
+// blindrotate_kany_kernel (N <= 512), kms_phase2_kernel (all N, and the untouched CCS kernel beside it), blindrotate_blk_kernel (all N); accumulator words to / from registers as a
+// helper (scattered N of k1, kr, wide, phase 2, blk); the forward twiddles into LDS as a helper (transform_fwd_kernel at N >= 2048, or at every N
+// with the sizes as template arguments); untwist + native as a helper inside inverse_to_words (kms_phase2_kernel, N >= 128); uv / wpart /
+// inv_words of the two CCS kernels as shared templates (every instantiation of both kernels, by -57 .. +60 instructions).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void czero(cplx &x) { x.re = 0.0; x.im = 0.0; }
+template <typename T, int A> __device__ __forceinline__ void czero(T (&x)[A]) {      // cplx arrays of any rank
+#pragma unroll
+    for (int i = 0; i < A; i++) czero(x[i]);
+}
+
 // digit -> transform helper: z[e] = (d(c_idx) - i*d(c_{idx+M})) * roots[idx]   (fft.jl:57-63)
 // ------------------------------------------------------------------------------------------------
 template <typename WORD, int R>

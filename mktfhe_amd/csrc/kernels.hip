@@ -583,17 +583,12 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) void blindrotate_kr_kernel(
 #pragma unroll
             for (int q = 0; q < BL; q++) {
                 const uint32_t v0 = at_src[blk * BL + q];
-                ats[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+                ats[q] = mask_exponent_uniform(v0, a.pre_switched, msbit);
                 any |= ats[q] != 0;
             }
             if (!any) continue;                                          // an all-zero block adds native(0) = 0 (:162-163)
             cplx tacc[BL][NP][R];
-#pragma unroll
-            for (int q = 0; q < BL; q++)
-#pragma unroll
-                for (int pp = 0; pp < NP; pp++)
-#pragma unroll
-                    for (int e = 0; e < R; e++) { tacc[q][pp][e].re = 0.0; tacc[q][pp][e].im = 0.0; }
+            czero(tacc);
 #pragma unroll
             for (int c = 0; c < NP; c++) {                               // :131-140 one decomposition per block
                 WORD tp[R][2];
@@ -622,8 +617,7 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) void blindrotate_kr_kernel(
 #pragma unroll
             for (int pp = 0; pp < NP; pp++) {
                 cplx s2[R];
-#pragma unroll
-                for (int e = 0; e < R; e++) { s2[e].re = 0.0; s2[e].im = 0.0; }
+                czero(s2);
 #pragma unroll
                 for (int q = 0; q < BL; q++) {                           // :157 tacc2 += monomial * tacc
                     if (ats[q] == 0) continue;
@@ -649,24 +643,16 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) void blindrotate_kr_kernel(
     const int blen = BLK ? a.blk_len : 1;
     for (int blk = 0; blk < a.n / blen; blk++) {
         cplx t2[BLK ? NP : 1][R];                                        // :142 tacc2 (LMSS only)
-        if (BLK) {
-#pragma unroll
-            for (int q = 0; q < NP; q++)
-#pragma unroll
-                for (int e = 0; e < R; e++) { t2[BLK ? q : 0][e].re = 0.0; t2[BLK ? q : 0][e].im = 0.0; }
-        }
+        if (BLK) czero(t2);
         bool any = false;
         for (int qb = 0; qb < blen; qb++) {
             const int idx = blk * blen + qb;
             const uint32_t v0 = at_src[idx];
-            const uint32_t at = a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit);
+            const uint32_t at = mask_exponent(v0, a.pre_switched, msbit);
             if (at == 0) continue;                                       // :48 / :145
             any = true;
             cplx tacc[NP][R];
-#pragma unroll
-            for (int q = 0; q < NP; q++)
-#pragma unroll
-                for (int e = 0; e < R; e++) { tacc[q][e].re = 0.0; tacc[q][e].im = 0.0; }
+            czero(tacc);
             const cplx *brk = a.brk + (size_t)idx * NP * l * NP * M;
 #pragma unroll
             for (int c = 0; c < NP; c++) {                               // b digits, then a_0, a_1 ... (:63-68 / :146-154)
@@ -780,7 +766,7 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) void blindrotate_kany_kerne
         for (int qb = 0; qb < blen; qb++) {
             const int idx = blk * blen + qb;
             const uint32_t v0 = at_src[idx];
-            const uint32_t at = a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit);
+            const uint32_t at = mask_exponent(v0, a.pre_switched, msbit);
             if (at == 0) continue;                                       // :48 / :145
             any = true;
             for (int q = 0; q < np; q++)
@@ -1101,7 +1087,7 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) __attribute__((amdgpu_waves
         const uint32_t *at_src = a.lwe + g * (size_t)a.lwe_stride + (size_t)idx * n;
         for (int i = 0; i < n; i++) {
             const uint32_t v0 = at_src[i];
-            const uint32_t at = a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit);
+            const uint32_t at = mask_exponent(v0, a.pre_switched, msbit);
             if (at == 0) continue;                                               // :261
             const cplx *uni = (MKT_CCS_ABLATE & 4) ? a.brk : a.brk + (size_t)idx * a.brk_party_stride + (size_t)i * 3 * l * M;   // ablation 4: every step reads the rows of step 0 (cache-resident)
             const cplx *ud = uni, *uf = uni + (size_t)l * M;
@@ -2014,7 +2000,7 @@ __global__ __launch_bounds__((2 * LT * Plan<LOGM, LR>::NT)) void blindrotate_wid
     const int msbit = 32 - a.logN - 1;
     for (int blk = 0; blk < a.n; blk++) {
         const uint32_t v0 = at_src[blk];
-        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.pre_switched ? v0 : divbits<uint32_t>(v0, msbit)));
+        const uint32_t at = mask_exponent_uniform(v0, a.pre_switched, msbit);
         if (at == 0) continue;                                           // :48 / :413 (uniform over the workgroup)
         cplx z[1][R];
 #pragma unroll
@@ -2039,8 +2025,7 @@ __global__ __launch_bounds__((2 * LT * Plan<LOGM, LR>::NT)) void blindrotate_wid
             for (int e = 0; e < R; e++) stage[e * NT + t] = ph ? pa[e] : pb[e];
             __syncthreads();
             if (c == ph && j == 0) {
-#pragma unroll
-                for (int e = 0; e < R; e++) { ts[e].re = 0.0; ts[e].im = 0.0; }
+                czero(ts);
 #pragma unroll
                 for (int g = 0; g < G; g++)
 #pragma unroll

@@ -376,9 +376,6 @@ struct Workgroup {
         k = tab_consts<LOGN>(tab);
     }
 };
-// the mod switch of one mask word to an exponent of X (bootstrapping.jl:8); pre_switched: the caller has done it.  Whether the result goes
-// through readfirstlane is the call site's business
-__device__ __forceinline__ uint32_t mask_exponent(uint32_t v0, int pre_switched, int msbit) { return pre_switched ? v0 : divbits<uint32_t>(v0, msbit); }
 // digit -> residues -> forward transform; tp: PREPARED words (gd.prep) held in registers by the caller
 template <int LOGN, typename WORD>
 __device__ __forceinline__ void digit_forward(Pt (&z)[8], const WORD (&tp)[8], const Gadget<WORD> &gd, int j, const uint4 *tw, uint64_t *lds, int t) {
@@ -573,7 +570,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kernel(
         bool any = false;
 #pragma unroll
         for (int q = 0; q < LB; q++) {
-            ats[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[blk * LB + q], pre_switched, msbit));
+            ats[q] = mask_exponent_uniform(at_src[blk * LB + q], pre_switched, msbit);
             any |= ats[q] != 0;
         }
         if (!any) continue;                                              // :48 / :145 (an all-zero block adds 0)
@@ -709,7 +706,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kr_kern
                     ntt_forward<LOGN>(z, tw[0], lds, t);
                     for (int q = 0; q < blk_len; q++) {
                         const int i = blk * blk_len + q;
-                        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+                        const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
                         if (at == 0) continue;                                     // :145
                         const uint64_t *mrow = mono + (size_t)(at - 1) * N + 8 * t;
                         const uint64_t *row = brk + (((size_t)i * NP * l + (size_t)(c * l + j)) * NP) * N + 8 * t;   // [row c l + j][poly][N]
@@ -725,7 +722,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kr_kern
         } else
         for (int q = 0; q < blk_len; q++) {
             const int i = blk * blk_len + q;
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+            const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
             if (at == 0) continue;
             Pt tacc[NP][8];
             pt_zero(tacc);
@@ -794,7 +791,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) void exact_blindrotate_kany_ke
         bool first_bit = true;                                                     // the block sum starts at this key bit's product (:157 from zero)
         for (int q = 0; q < blk_len; q++) {
             const int i = blk * blk_len + q;
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+            const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
             if (at == 0) continue;                                                 // :48 / :145
             for (int c = 0; c < np; c++)
                 for (int j = 0; j < l; j++) {
@@ -927,7 +924,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
         }
         for (int q = 0; q < (BLK ? blk_len : 1); q++) {
             const int i = blk * blk_len + q;
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+            const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
             if (at == 0) continue;
             Pt tacc[2][2][8];
             pt_zero(tacc);
@@ -1067,7 +1064,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
                 ntt_forward<LOGN>(z, tw[0], lds, t);
                 for (int q = 0; q < blk_len; q++) {
                     const int i = blk * blk_len + q;
-                    const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+                    const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
                     if (at == 0) continue;                                         // :638 per key bit
                     const uint64_t *mrow = mono + (size_t)(at - 1) * N + 8 * t;
                     const uint64_t *rowp = brk + (((size_t)i * 2 * l + (size_t)(c * l + j)) * 4) * N + 8 * t;   // [poly][half][N]
@@ -1138,7 +1135,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
     if (t == 0) acc[0][0] = (uint64_t)1 << (64 - (row + 1) * logB_lev);           // :403-406 trivial RLEV row
     const int msbit = 32 - LOGN - 1;
     for (int i = 0; i < n; i++) {
-        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], pre_switched, msbit));
+        const uint32_t at = mask_exponent_uniform(at_src[i], pre_switched, msbit);
         if (at == 0) continue;                                                     // :413
         const uint4 *rowb = reinterpret_cast<const uint4 *>(brk + ((size_t)i * 4 * 4) * N + 8 * t);   // [digit g][poly][half][N], two points per 16 bytes
         // piece (g, ep) of (polynomial pp, half h): K[g * 4 + ep]
@@ -1393,7 +1390,7 @@ __global__ __launch_bounds__((1 << (LOGN - NLR))) __attribute__((amdgpu_waves_pe
         const int np = idx + 1;
         const uint32_t *at_src = a.lwe + g * (size_t)a.lwe_stride + (size_t)idx * n;
         for (int i = 0; i < n; i++) {
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask_exponent(at_src[i], a.pre_switched, msbit));
+            const uint32_t at = mask_exponent_uniform(at_src[i], a.pre_switched, msbit);
             if (at == 0) continue;                                                 // :261
             const uint64_t *uni = a.brk + (size_t)idx * a.brk_party_stride + (size_t)i * 3 * l * N;
             const uint64_t *ud = uni, *uf = uni + (size_t)l * N;

@@ -158,7 +158,7 @@ void blindrotate_blk_kernel(const RotArgs a, int wg_per_slot) {
 #pragma unroll
             for (int q = 0; q < LB; q++) {
                 const uint32_t v = at_next[r][q];
-                ats[r][q] = a.pre_switched ? v : divbits<uint32_t>(v, msbit);   // bootstrapping.jl:8
+                ats[r][q] = mask_exponent(v, a.pre_switched, msbit);   // bootstrapping.jl:8
                 any |= ats[r][q] != 0;
             }
         {

@@ -2,6 +2,8 @@
 """Instruction-class counts of the loaded library's rotation / transform kernels, from the gfx950 code objects INSIDE the built .so
 (no recompile): profiles/isa_<build_id>.json, which bench.py reads under the same build-id rule as the PMC traffic.
     python tools/isa_report.py [path/to/libmktfhe_hip.so] [--out profiles/]
+    python tools/isa_report.py --diff old.so new.so     every kernel symbol of two builds compared: disassembly text and the notes' metadata
+                                                        (register counts, LDS, scratch, spills); exit status 1 if any symbol differs
 Per kernel: the instruction count of its largest loop (one CMux step / one block of key bits / one polynomial of a batched transform) by issue
 class -- the classes of tools/int_probe.hip / valu_probe.hip (profiles/r05_int_probe.txt): `slow` = every Float64 instruction, integer multiplies,
 v_min / v_max, three-operand and carry forms, 64-bit shifts and adds, compares + selects, DPP moves, lane permutes, conversions: 4.4 cycles per
@@ -94,8 +96,51 @@ def report(path):
     return out
 
 
+def symbols(path):
+    """{(code object index, symbol): (disassembly without addresses, metadata of the notes without the argument list)} of every kernel"""
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for i, co in enumerate(code_objects(path)):
+            f = os.path.join(td, f"co{i}.o")
+            open(f, "wb").write(co)
+            meta, cur = {}, None
+            notes = subprocess.run([os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf"), "--notes", f], capture_output=True, text=True, check=True).stdout
+            for ln in notes.splitlines():
+                if ln.startswith("  - "):
+                    cur = {}
+                    ln = "    " + ln[4:]
+                m = re.match(r"^    (\.\w+):\s*(\S.*)$", ln)           # the kernel's own scalar fields (.args entries sit deeper)
+                if m and cur is not None:
+                    cur[m.group(1)] = m.group(2)
+                    if m.group(1) == ".symbol":
+                        meta[m.group(2).strip("'").removesuffix(".kd")] = cur
+            dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "--mcpu=gfx950", f], capture_output=True, text=True, check=True).stdout
+            cur = None
+            for ln in dis.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(.+)>:$", ln)
+                if m:
+                    cur = (i, m.group(1)); out[cur] = ([], meta.get(m.group(1)))
+                elif cur is not None and ln.strip():
+                    out[cur][0].append(re.sub(r"\s*//.*$", "", ln.strip()))
+    return out
+
+
+def diff(old, new):
+    a, b = symbols(old), symbols(new)
+    kernels = [k for k in a if a[k][1] is not None]
+    bad = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
+    for i, name in bad:
+        x, y = a.get((i, name)), b.get((i, name))
+        what = "only in one build" if x is None or y is None else ("metadata" if x[0] == y[0] else f"code ({len(x[0])} -> {len(y[0])} instructions)")
+        print(f"DIFFERS code object {i}: {name}: {what}")
+    print(f"{len(kernels)} kernel symbols in {1 + max(i for i, _ in a)} code objects compared (disassembly and notes), {len(bad)} differ")
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
+    if argv[:1] == ["--diff"]:
+        sys.exit(diff(argv[1], argv[2]))
     outdir = os.path.join(ROOT, "profiles")
     if "--out" in argv:
         i = argv.index("--out"); outdir = argv[i + 1]; del argv[i:i + 2]
