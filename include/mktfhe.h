@@ -274,6 +274,34 @@ int mkt_lut_bootstrap_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const 
 int mkt_lut_batch_gather(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows,
                          const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem);
 
+/* ---- many-table bootstrap (Chillotti et al., "PBSmanyLUT"): nout = 2^nu functions of ONE encrypted input for one blind rotation and
+ *      nout key switches.  nout is 1, 2, 4 or 8 and at most N; any other count is MKT_ERR_ARG and nothing is written.
+ *      COARSE MOD-SWITCH.  Every 32-bit LWE word w, mask words and b alike, goes onto a grid nout times coarser:
+ *          sw(w) = divbits32(w, 32 - (log2 N + 1) + nu) << nu,
+ *      a multiple of nout in [0, 2N] (2N is the identity, as above); nu = 0 is mkt_modswitch_batch word for word.  The rotated phase is
+ *      then a multiple of nout too.
+ *      PACKED TABLE.  From tables T_0 .. T_{nout-1} laid out as above, U[nout i + v] = T_v[nout i] for 0 <= i < N / nout: only every
+ *      nout-th entry of a table is ever read.  For every phase phi in {0, nout, ..., 2N - nout}, coefficient v of X^phi * U is what a
+ *      single-table bootstrap of T_v extracts at phi.  `luts` holds PACKED tables here: [nluts][N] ring words, `sel` as above.
+ *      EXTRACTION AT COEFFICIENT v.  E_v(acc) = X^-v * acc on every one of the 1 + k polynomials: E_v(acc)[c][i] = acc[c][i + v] for
+ *      i + v < N, -acc[c][i + v - N] otherwise.  Output v of input j is keyswitch!(E_v(blindrotate!(sw(a), (X^sw(b) * U, 0, ...)))).
+ *      nout = 1 returns the words of mkt_lut_bootstrap_batch.  The output noise is that of any bootstrap; the INPUT's mod-switch error
+ *      grows nout-fold.  The nout rotated copies of a chunk live in a buffer of the accumulator workspace's size that a
+ *      context allocates at its first such call (MKT_ERR_NOMEM / MKT_ERR_HIP from that call if it cannot; forks hold their own).
+ *      Validation of luts, sel, pool indices: as in the programmable-bootstrap block.  Both arithmetic modes, every scheme. ---- */
+/* out [B][nout][k*n+1]: output v of input j at row j * nout + v.  out must not overlap lwe when nout > 1 (MKT_ERR_ARG) */
+int mkt_lut_many_bootstrap_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B,
+                                 int mem);
+/* the linear front end of mkt_lut_batch_gather, then the above; out [B][nout][k*n+1] may be a later region of the pool that no gate of
+ * this call reads */
+int mkt_lut_many_batch_gather(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows,
+                              const uint32_t *idx, const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem);
+/* unit level: atilde [B][k*n] = sw of the mask words, acc[j] = (X^sw(b) * luts[sel[j]], 0 ...) [B][1+k][N].  Needs no keys */
+int mkt_lut_many_testvector_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *atilde,
+                                  void *acc, size_t B, int mem);
+/* unit level: accs[j][v] = E_v(acc[j]); acc [B][1+k][N] -> accs [B][nout][1+k][N], which must not overlap acc.  Needs no keys */
+int mkt_lut_extract_batch(mkt_ctx *ctx, const void *acc, int nout, void *accs, size_t B, int mem);
+
 /* ---- unit-level entry points (parity tests, transform roofline) ----
  * On an MKT_ARITH_EXACT context a TransPoly is N residue pairs (x mod p1) | (x mod p2) << 32 (uint64, the same 8 N bytes as
  * M complex doubles), in the bit-reversed order the Cooley-Tukey network with psi_rev[m + i] leaves them; forward reads
@@ -336,6 +364,9 @@ int mkt_multi_mux_batch(mkt_multi *m, const uint32_t *s, const uint32_t *a, cons
 int mkt_multi_bootstrap_batch(mkt_multi *m, uint32_t *lwe, size_t B, int mem);
 /* mkt_lut_bootstrap_batch, sharded: lwe, out and sel are cut with the batch; every shard reads all of luts (in place, or staged per shard) */
 int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem);
+/* sharded as mkt_multi_lut_bootstrap_batch; out [B][nout][k*n+1] is cut at nout rows per input */
+int mkt_multi_lut_many_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out,
+                                       size_t B, int mem);
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem);
 int mkt_multi_blindrotate_batch(mkt_multi *m, const uint32_t *atilde, void *acc, size_t B, int mem);
 int mkt_multi_keyswitch_batch(mkt_multi *m, const void *acc, uint32_t *out, size_t B, int mem);

@@ -133,6 +133,7 @@ struct mkt_ctx {
     cplx *ws_lev = nullptr, *ws_scratch = nullptr;
     void *ws_fxacc = nullptr;    // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
     uint32_t *ws_ksd = nullptr; size_t ws_ksd_words = 0;   // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
+    void *ws_many = nullptr; size_t ws_many_accs = 0;      // many-table bootstrap: the nout extracted copies of a chunk's accumulators (first such call; at most CHUNK_GATES accumulators, ws_acc's full size)
     // timing
     bool timing = false;
     std::vector<TimedSpan> spans;
@@ -490,6 +491,39 @@ int lut_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, uint3
     return do_keyswitch(c, c->ws_acc, out, B);
 }
 
+// ---- many-table bootstrap (mktfhe.h): nout = 2^nu tables packed into one test vector, one rotation, nout key switches ----
+// nu = log2(nout) for nout in {1, 2, 4, 8} with nout <= N, else -1
+int many_nu(const mkt_ctx *c, int nout) {
+    for (int nu = 0; nu <= 3; nu++) if (nout == 1 << nu) return nout <= c->p.N ? nu : -1;
+    return -1;
+}
+
+// lut_rotate_chunk on the coarse grid: the switched mask words go to ws_lin (rows of lwe_len words; lin may BE ws_lin, the gather form), the
+// rotation then runs on pre-switched masks with the accumulator it is handed, as mkt_blindrotate_batch runs it
+int lut_many_rotate_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, int nu, size_t B) {
+    HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, t.luts, t.nluts, t.sel, lin, c->sh.lwe_len, c->logN, c->sh.kacc, nu, c->ws_lin, c->sh.lwe_len, c->ws_acc, B, c->stream));
+    return do_blindrotate(c, c->ws_lin, c->sh.lwe_len, 1, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B);
+}
+
+// the many-table bootstrap of a device-resident chunk of B <= CHUNK_GATES >> nu inputs: lin [B][len] -> out [B << nu][len], output v of
+// input j at row (j << nu) + v.  The copies X^-v acc live in ws_many, allocated by the first call that needs it (a context that never
+// makes one never pays for it); the unchanged key switch then extracts coefficient 0 of each.  out must not be lin when nu > 0
+int lut_many_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, int nu, uint32_t *out, size_t B) {
+    int r;
+    if ((r = lut_many_rotate_chunk(c, t, lin, nu, B))) return r;
+    if (!nu) return do_keyswitch(c, c->ws_acc, out, B);       // one table: X^0 acc is acc
+    const size_t accs = B << nu;
+    if (accs > c->ws_many_accs) {
+        if (c->ws_many) (void)hipFree(c->ws_many);
+        c->ws_many = nullptr; c->ws_many_accs = 0;
+        const hipError_t e = hipMalloc(&c->ws_many, accs * (size_t)(1 + c->sh.kacc) * poly_bytes(c));
+        if (e != hipSuccess) { c->ws_many = nullptr; return fail(c, e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP, std::string("many-table bootstrap: workspace for the extracted accumulators: ") + hipGetErrorString(e)); }
+        c->ws_many_accs = accs;
+    }
+    HIPCHK(c, mktd::launch_lut_extract(c->p.W, c->ws_acc, 1 << nu, c->logN, c->sh.kacc, c->ws_many, B, c->stream));
+    return do_keyswitch(c, c->ws_many, out, accs);
+}
+
 // staging helper for MKT_MEM_HOST callers
 struct Staged {
     mkt_ctx *c; void *dev = nullptr; void *host_out = nullptr; size_t bytes = 0; bool owned = false;
@@ -734,7 +768,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_fxacc, c->d_pm_stat};
+    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_many, c->ws_fxacc, c->d_pm_stat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
@@ -1248,10 +1282,13 @@ int mkt_lut_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const u
     return sc.out(acc);
 }
 
-// both programmable-bootstrap entry points share one body: the inputs in batch order (src: [B][len]), or built per gate from a pool
-// (src = pool [rows][len]; idx [B][4], wt [B][4], cst [B]) by lut_linear_kernel
+// all programmable-bootstrap entry points share one body: the inputs in batch order (src: [B][len]), or built per gate from a pool
+// (src = pool [rows][len]; idx [B][4], wt [B][4], cst [B]) by lut_linear_kernel.  nout 0: one table per rotation, out [B][len]; nout >= 1: the
+// many-table form, out [B][nout][len], in chunks of CHUNK_GATES / nout inputs so that a chunk's copies fit ws_many
 static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *src, size_t rows, const uint32_t *idx,
-                    const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem) {
+                    const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem) {
+    const int nu = nout ? many_nu(c, nout) : 0;   // (the many-table entry points have refused any other count)
+    const size_t per = nout ? (size_t)nout : 1, step = CHUNK_GATES / per;
     MKT_EXACT_GATE(c);
     int r;
     if ((r = check_ready(c, true, true))) return r;
@@ -1261,10 +1298,10 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
     const bool pool = idx != nullptr;
     StagedLuts t(c);
     Staged sv{c}, so{c}, si{c}, sw{c}, sk{c};
-    if ((r = t.in(c, who, luts, nluts, sel, B, mem)) || (r = sv.in(src, rows * len * 4, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
+    if ((r = t.in(c, who, luts, nluts, sel, B, mem)) || (r = sv.in(src, rows * len * 4, mem, true)) || (r = so.in(out, B * per * len * 4, mem, false))) return r;
     if (pool && ((r = si.in(idx, B * 16, mem, true)) || (r = sw.in(wt, B * 4, mem, true)) || (r = sk.in(cst, B * 4, mem, true)))) return r;
-    for (size_t off = 0; off < B; off += CHUNK_GATES) {
-        const size_t nb = std::min(CHUNK_GATES, B - off);
+    for (size_t off = 0; off < B; off += step) {
+        const size_t nb = std::min(step, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
         const uint32_t *lin = (const uint32_t *)sv.dev + off * len;
         if (pool) {
@@ -1272,7 +1309,8 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
                                               c->ws_lin, (int)len, nb, c->stream));
             lin = c->ws_lin;
         }
-        if ((r = lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, (uint32_t *)so.dev + off * len, nb))) return r;
+        uint32_t *dst = (uint32_t *)so.dev + off * per * len;
+        if ((r = nout ? lut_many_bootstrap_chunk(c, t.chunk(nluts, off), lin, nu, dst, nb) : lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, dst, nb))) return r;
     }
     return so.out(out);
 }
@@ -1280,7 +1318,7 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
 // out[j] = keyswitch!(blindrotate!((X^btilde(lwe[j]) * luts[sel[j]], 0 ...))): bootstrapping! with a caller's table; out may be lwe
 int mkt_lut_bootstrap_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem) {
     if (!c || !luts || !lwe || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    return lut_impl(c, "mkt_lut_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, out, B, mem);
+    return lut_impl(c, "mkt_lut_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, 0, out, B, mem);
 }
 
 // one circuit level of table lookups: gate j bootstraps cst[j] e_b + sum_t wt[j][t] pool[idx[j][t]] through luts[sel[j]]; out may be a later
@@ -1291,7 +1329,68 @@ int mkt_lut_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const uint3
     if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: gates over an empty pool");
     const uint32_t *iv[] = {idx};
     if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: operand index outside the pool");
-    return lut_impl(c, "mkt_lut_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, out, B, mem);
+    return lut_impl(c, "mkt_lut_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, 0, out, B, mem);
+}
+
+// ---- many-table bootstrap (mktfhe.h): nout tables per blind rotation ----
+static int bad_nout(mkt_ctx *c, const char *who, int nout) {
+    return fail(c, MKT_ERR_ARG, std::string(who) + ": nout = " + std::to_string(nout) + ", expected 1, 2, 4 or 8 and at most N = " + std::to_string(c->p.N));
+}
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+// unit level: the coarse-switched mask words atilde [B][k*n] and acc[j] = (X^btilde * luts[sel[j]], 0 ...) from the coarse btilde; no keys needed
+int mkt_lut_many_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *atilde, void *acc, size_t B, int mem) {
+    if (!c || !luts || !lwe || !atilde || !acc || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    const int nu = many_nu(c, nout);
+    if (nu < 0) return bad_nout(c, "mkt_lut_many_testvector_batch", nout);
+    DevGuard dg(c->device);
+    const size_t len = (size_t)c->sh.lwe_len, accb = (size_t)(1 + c->sh.kacc) * poly_bytes(c);
+    StagedLuts t(c);
+    Staged sx{c}, sa{c}, sc{c};
+    int r;
+    if ((r = t.in(c, "mkt_lut_many_testvector_batch", luts, nluts, sel, B, mem)) || (r = sx.in(lwe, B * len * 4, mem, true)) || (r = sa.in(atilde, B * (len - 1) * 4, mem, false)) ||
+        (r = sc.in(acc, B * accb, mem, false))) return r;
+    const LutArgs a = t.chunk(nluts, 0);
+    HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, a.luts, a.nluts, a.sel, (const uint32_t *)sx.dev, (int)len, c->logN, c->sh.kacc, nu, (uint32_t *)sa.dev, (int)len - 1, sc.dev, B, c->stream));
+    if ((r = sa.out(atilde))) return r;
+    return sc.out(acc);
+}
+
+// unit level: accs[j][v] = X^-v * acc[j], v < nout; acc [B][1+k][N] -> accs [B][nout][1+k][N]
+int mkt_lut_extract_batch(mkt_ctx *c, const void *acc, int nout, void *accs, size_t B, int mem) {
+    if (!c || !acc || !accs || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (many_nu(c, nout) < 0) return bad_nout(c, "mkt_lut_extract_batch", nout);
+    const size_t accb = (size_t)(1 + c->sh.kacc) * poly_bytes(c);
+    if (ranges_overlap(acc, B * accb, accs, B * nout * accb)) return fail(c, MKT_ERR_ARG, "mkt_lut_extract_batch: accs overlaps acc");
+    DevGuard dg(c->device);
+    Staged sc{c}, so{c};
+    int r;
+    if ((r = sc.in(acc, B * accb, mem, true)) || (r = so.in(accs, B * nout * accb, mem, false))) return r;
+    HIPCHK(c, mktd::launch_lut_extract(c->p.W, sc.dev, nout, c->logN, c->sh.kacc, so.dev, B, c->stream));
+    return so.out(accs);
+}
+
+// out[j][v] = keyswitch!(X^-v * blindrotate!(coarse atilde(lwe[j]), (X^btilde * luts[sel[j]], 0 ...))): nout tables in one rotation
+int mkt_lut_many_bootstrap_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !lwe || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (many_nu(c, nout) < 0) return bad_nout(c, "mkt_lut_many_bootstrap_batch", nout);
+    const size_t rb = (size_t)c->sh.lwe_len * 4;
+    if (nout > 1 && ranges_overlap(lwe, B * rb, out, B * (size_t)nout * rb)) return fail(c, MKT_ERR_ARG, "mkt_lut_many_bootstrap_batch: out overlaps lwe (nout > 1)");
+    return lut_impl(c, "mkt_lut_many_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, nout, out, B, mem);
+}
+
+// the linear front end of mkt_lut_batch_gather, then the many-table bootstrap; out [B][nout][len] may be a later region of the pool
+int mkt_lut_many_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
+                              const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !pool || !idx || !wt || !cst || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (many_nu(c, nout) < 0) return bad_nout(c, "mkt_lut_many_batch_gather", nout);
+    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_many_batch_gather: gates over an empty pool");
+    const uint32_t *iv[] = {idx};
+    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_many_batch_gather: operand index outside the pool");
+    return lut_impl(c, "mkt_lut_many_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, nout, out, B, mem);
 }
 
 int mkt_modswitch_batch(mkt_ctx *c, const uint32_t *lwe, uint32_t *atilde, uint32_t *btilde, size_t B, int mem) {

@@ -140,6 +140,14 @@ hipError_t launch_testvector(int W, const uint32_t *lin, int lwe_stride, int log
 // programmable bootstrap (lut.hip; mktfhe.h "programmable bootstrap"): acc[g] = (X^btilde(lin[g]) * luts[sel[g]], 0 ...), luts [nluts][N] ring
 // words, sel [B] or NULL (row 0), rows clamped to nluts - 1; acc [B][1+kacc][N]
 hipError_t launch_lut_testvector(int W, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lin, int lwe_stride, int logN, int kacc, void *acc, size_t B, hipStream_t s);
+// the many-table form (mktfhe.h "many-table bootstrap"), nu = log2(nout) in 0 .. 3: body and mask words go onto the grid 2^nu times coarser,
+// sw(w) = divbits(w, 32 - logN - 1 + nu) << nu.  acc as above from the coarse btilde; atilde (NULL: not wanted) receives the lwe_stride - 1
+// switched mask words of each ciphertext, rows of at_stride words -- it may be lin itself (every word is read and written by the same lane,
+// the b word is left alone).  nu = 0 with atilde NULL is launch_lut_testvector
+hipError_t launch_lut_many_testvector(int W, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lin, int lwe_stride, int logN, int kacc, int nu,
+                                      uint32_t *atilde, int at_stride, void *acc, size_t B, hipStream_t s);
+// accs[g][v] = X^-v * acc[g] for v < nout (1, 2, 4, 8; nout <= N): acc [B][1+kacc][N] -> accs [B][nout][1+kacc][N]; the two must not overlap
+hipError_t launch_lut_extract(int W, const void *acc, int nout, int logN, int kacc, void *accs, size_t B, hipStream_t s);
 // its gather front end: out[g] = cst[g] e_b + sum_{t<4} wt[g][t] pool[idx[g][t]] (int8 weights, 0 skips the term; rows clamped into the pool); out [B][len]
 hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s);
 hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);

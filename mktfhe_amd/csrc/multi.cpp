@@ -303,6 +303,25 @@ int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, 
     });
 }
 
+// the many-table bootstrap, sharded as mkt_multi_lut_bootstrap_batch: out is cut at nout rows per input.  nout is checked by every shard's
+// own call before it writes; the count that no shard could take is refused here, before any shard starts
+int mkt_multi_lut_many_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B, int mem) {
+    if (!m || !luts || !lwe || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
+    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: no lookup table");
+    if ((nout != 1 && nout != 2 && nout != 4 && nout != 8) || nout > m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: nout = " + std::to_string(nout) + ", expected 1, 2, 4 or 8 and at most N");
+    if (sel && mem == MKT_MEM_HOST) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: table selector outside the tables");   // before any shard writes
+    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);
+    if (nout > 1 && B) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(lwe), b0 = reinterpret_cast<uintptr_t>(out);
+        if (a0 < b0 + B * nout * rb && b0 < a0 + B * rb) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: out overlaps lwe (nout > 1)");
+    }
+    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb * (size_t)nout, false, true}};
+    if (sel) specs.push_back({sel, 4, true, false});
+    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
+        return mkt_lut_many_bootstrap_batch(c, a[0], nluts, sel ? (const uint32_t *)a[3] : nullptr, (const uint32_t *)a[1], nout, (uint32_t *)a[2], nb, mem);
+    });
+}
+
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem) {
     if (!m || !x) return mfail(m, MKT_ERR_ARG, "bad argument");
     const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4;

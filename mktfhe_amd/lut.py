@@ -90,6 +90,86 @@ def lut_gather(scheme, luts, sel, pool, idx, wt, cst, out):
                         _Buf(cst, np.uint32, B), scheme._ct(out, B, out=True))[-1]
 
 
+# ---- many-table bootstrap (include/mktfhe.h "many-table bootstrap"): nout functions of one input for one blind rotation ----
+NOUT = (1, 2, 4, 8)
+
+
+def _nout(nout, params):
+    if nout not in NOUT or nout > params.N:
+        raise ValueError(f"nout = {nout!r}: the table count must be 1, 2, 4 or 8 and at most N = {params.N}")
+    return int(nout)
+
+
+def lut_pack(tables, params: Params):
+    """the packed table of nout = len(tables) tables laid out as lut_poly does: U[nout * i + v] = tables[v][nout * i].  tables (nout, N) ring
+    words -> (N,) ring words; one table packs to itself"""
+    rd = np.dtype(params.ring_dtype)
+    t = np.asarray(tables)
+    if t.dtype.kind not in "iu" or t.dtype.itemsize != rd.itemsize:
+        raise ValueError(f"lookup tables of dtype {t.dtype}, expected {rd} (ring words)")
+    if t.ndim != 2 or t.shape[1] != params.N:
+        raise ValueError(f"tables of shape {t.shape}, expected (nout, {params.N})")
+    o = _nout(t.shape[0], params)
+    return np.ascontiguousarray(t.view(rd)[:, ::o].T).reshape(params.N)
+
+
+def _out_many(scheme, ctxt, nout, out):
+    """-> (B, out): out None = a new (..., nout, lwe_len) array where ctxt lives; a given out must hold exactly B * nout rows"""
+    shape = tuple(np.shape(ctxt))
+    B = _rows(shape)
+    if out is None:
+        out = _empty(ctxt, shape[:-1] + (nout, scheme.params.lwe_len), np.uint32)
+    return B, out
+
+
+def lut_many_testvector(scheme, luts, ctxt, nout, sel=None):
+    """mkt_lut_many_testvector_batch: what the many-table bootstrap hands to blindrotate! -> (atilde (..., k*n) uint32 on the grid nout times
+    coarser, acc (..., k + 1, N) ring words), living where ctxt lives.  luts: packed tables (lut_pack)"""
+    p = scheme.params
+    nout = _nout(nout, p)
+    shape = tuple(np.shape(ctxt))
+    B = _rows(shape)
+    tb, nluts = _tables(luts, p)
+    at = _empty(ctxt, shape[:-1] + (p.lwe_len - 1,), np.uint32)
+    acc = _empty(ctxt, shape[:-1] + (p.k + 1, p.N), p.ring_dtype, "int64" if p.W == 64 else "int32")
+    kept = scheme._call("lut_many_testvector_batch", B, tb, nluts, _sel(sel, B), scheme._ct(ctxt, B), nout, _Buf(at, np.uint32, B, p.lwe_len - 1, out=True),
+                        _Buf(acc, p.ring_dtype, B * (p.k + 1) * p.N, out=True))
+    return kept[-2], kept[-1]
+
+
+def lut_extract(scheme, acc, nout):
+    """mkt_lut_extract_batch: acc (..., k + 1, N) ring words -> (..., nout, k + 1, N), copy v = X^-v * acc (coefficient v moved to 0)"""
+    p = scheme.params
+    nout = _nout(nout, p)
+    shape = tuple(np.shape(acc))
+    if shape[-2:] != (p.k + 1, p.N):
+        raise ValueError(f"accumulator of shape {shape}, expected (..., {p.k + 1}, {p.N})")
+    B, words = int(np.prod(shape[:-2])), (p.k + 1) * p.N
+    accs = _empty(acc, shape[:-2] + (nout,) + shape[-2:], p.ring_dtype)
+    return scheme._call("lut_extract_batch", B, _Buf(acc, p.ring_dtype, B * words), nout, _Buf(accs, p.ring_dtype, B * nout * words, out=True))[-1]
+
+
+def lut_many_bootstrap(scheme, luts, ctxt, nout, sel=None, out=None):
+    """mkt_lut_many_bootstrap_batch (a Scheme) / mkt_multi_lut_many_bootstrap_batch (a MultiScheme): out[j][v] = the bootstrap of ctxt[j]
+    through table v of the packed table luts[sel[j]] (None: row 0), nout tables for ONE blind rotation.  The input's words are rounded to a
+    grid nout times coarser (noise).  out None = a new (..., nout, lwe_len) array where ctxt lives; out must not overlap ctxt
+    when nout > 1"""
+    nout = _nout(nout, scheme.params)
+    B, out = _out_many(scheme, ctxt, nout, out)
+    tb, nluts = _tables(luts, scheme.params)
+    return scheme._call("lut_many_bootstrap_batch", B, tb, nluts, _sel(sel, B), scheme._ct(ctxt, B), nout, scheme._ct(out, B * nout, out=True))[-1]
+
+
+def lut_many_gather(scheme, luts, sel, pool, idx, wt, cst, nout, out):
+    """one circuit level of many-table lookups (mkt_lut_many_batch_gather): the linear front end of lut_gather, then lut_many_bootstrap.
+    out: B * nout rows, output v of gate j at row j * nout + v; it may be a later region of the pool"""
+    nout = _nout(nout, scheme.params)
+    B, P = _count(cst), _rows(np.shape(pool))
+    tb, nluts = _tables(luts, scheme.params)
+    return scheme._call("lut_many_batch_gather", B, tb, nluts, _sel(sel, B), scheme._ct(pool, P), P, _Buf(idx, np.uint32, B, 4), _Buf(wt, np.int8, B, 4),
+                        _Buf(cst, np.uint32, B), nout, scheme._ct(out, B * nout, out=True))[-1]
+
+
 def lwe_encrypt_word(mu, i, key: PartyKeys, params: Params, deterministic_seed=None):
     """lwe_ith_encrypt (scheme.jl:370-386) of ANY message mu on the 32-bit torus under party i (single-key schemes: 0): a multi-valued input
     of a programmable bootstrap.  mu = +-2^29 with the same pinned seed gives the words of lwe_ith_encrypt"""
