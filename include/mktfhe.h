@@ -302,6 +302,38 @@ int mkt_lut_many_testvector_batch(mkt_ctx *ctx, const void *luts, size_t nluts, 
 /* unit level: accs[j][v] = E_v(acc[j]); acc [B][1+k][N] -> accs [B][nout][1+k][N], which must not overlap acc.  Needs no keys */
 int mkt_lut_extract_batch(mkt_ctx *ctx, const void *acc, int nout, void *accs, size_t B, int mem);
 
+/* ---- key switch at a coefficient; the bootstrap at a coefficient list: ncoef outputs of ONE blind rotation with no copy of the accumulator.
+ *      keyswitch! sample-extracts coefficient 0.  With E_v(acc) = X^-v * acc as defined above, keyswitch!(E_v(acc)) reads acc itself at
+ *      other places: the body word is acc.b[v] >> (W - 32), and word j of a mask component a is  a[v] >> (W - 32)  for j = 0,
+ *      -((-a[v - j]) >> (W - 32))  for 0 < j <= v (the inner negation at the ring's width, as E_v writes it: on the 32-bit ring this is
+ *      a[v - j]),  -(a[N + v - j] >> (W - 32))  for j > v.  Every output row g names its accumulator src[g] and its coefficient coef[g].
+ *      WHAT IT COMPUTES.  Coefficient v of X^phi * T is what a single-table bootstrap of T reads at phase phi - v: one rotation returns
+ *      f(m - w) for every shift w asked for, at the fine mod-switch (nu = 0).  E_v is a signed permutation, so the output noise is that of
+ *      one bootstrap and the input margin that of one lookup.  THERMOMETER.  With the sign table and coef[w] = w N / P,
+ *      output w of an input on window m of P (phase m / 2P + 1 / 4P) decrypts to [m >= w], for all w < P at once.
+ *      nu in 0 .. 3 with 2^nu <= N is the coarse mod-switch sw of the many-table block (nu = 0: mkt_modswitch_batch); 1 <= ncoef <= N and
+ *      coef[i] < N.  Word for word:  mkt_keyswitch_at_batch(src = coef = NULL) = mkt_keyswitch_batch;  mkt_lut_bootstrap_at_batch(nu = 0,
+ *      coef = {0}) = mkt_lut_bootstrap_batch;  (nu = log2 o, coef = {0 .. o-1}) on a packed table = mkt_lut_many_bootstrap_batch(nout = o).
+ *      src, coef and sel live where the ciphertexts live (`mem`).  Validation as mkt_gate_batch_gather: with MKT_MEM_HOST a src[g] >= nacc,
+ *      a coef >= N or a sel >= nluts is MKT_ERR_ARG and nothing is written; with MKT_MEM_DEVICE src is clamped to the last row and coef
+ *      read mod N -- never an out-of-bounds access.  nacc == 0 with B > 0, ncoef == 0 or > N, a bad nu, and src == NULL with nacc != B are
+ *      refused in either memory kind; B == 0 succeeds and writes nothing.  A call runs in chunks of max(1, 8192 / ncoef) inputs (8192 rows
+ *      for mkt_keyswitch_at_batch).  No buffer of extracted accumulators exists on this path: the key switch reads the rotated accumulators
+ *      in the workspace through a (row, coefficient) table of 8 bytes per output row.  Both arithmetic modes, every scheme; forks hold
+ *      their own workspace. ---- */
+/* out[g] = keyswitch!(E_{coef[g]}(acc[src[g]])); acc [nacc][1+k][N] ring words, out [B][k*n+1]; src [B] or NULL (= g; then nacc must
+ * equal B), coef [B] or NULL (= 0) */
+int mkt_keyswitch_at_batch(mkt_ctx *ctx, const void *acc, size_t nacc, const uint32_t *src, const uint32_t *coef, uint32_t *out, size_t B, int mem);
+/* one rotation per input, ncoef outputs: out[j][i] = keyswitch!(E_{coef[i]}(blindrotate!(sw_nu(a_j), (X^sw_nu(b_j) * luts[sel[j]], 0, ...))));
+ * coef [ncoef], shared by the batch; out [B][ncoef][k*n+1] must not overlap lwe when ncoef > 1 (MKT_ERR_ARG) */
+int mkt_lut_bootstrap_at_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu, const uint32_t *coef,
+                               size_t ncoef, uint32_t *out, size_t B, int mem);
+/* the linear front end of mkt_lut_batch_gather, then the above; out [B][ncoef][k*n+1] may be a later region of the pool that no gate of
+ * this call reads */
+int mkt_lut_batch_gather_at(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows,
+                            const uint32_t *idx, const int8_t *wt, const uint32_t *cst, int nu, const uint32_t *coef, size_t ncoef, uint32_t *out,
+                            size_t B, int mem);
+
 /* ---- unit-level entry points (parity tests, transform roofline) ----
  * On an MKT_ARITH_EXACT context a TransPoly is N residue pairs (x mod p1) | (x mod p2) << 32 (uint64, the same 8 N bytes as
  * M complex doubles), in the bit-reversed order the Cooley-Tukey network with psi_rev[m + i] leaves them; forward reads
@@ -367,6 +399,9 @@ int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, 
 /* sharded as mkt_multi_lut_bootstrap_batch; out [B][nout][k*n+1] is cut at nout rows per input */
 int mkt_multi_lut_many_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out,
                                        size_t B, int mem);
+/* mkt_lut_bootstrap_at_batch, sharded by input as the call above: out is cut at ncoef rows per input; coef reaches every shard as luts does */
+int mkt_multi_lut_bootstrap_at_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu,
+                                     const uint32_t *coef, size_t ncoef, uint32_t *out, size_t B, int mem);
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem);
 int mkt_multi_blindrotate_batch(mkt_multi *m, const uint32_t *atilde, void *acc, size_t B, int mem);
 int mkt_multi_keyswitch_batch(mkt_multi *m, const void *acc, uint32_t *out, size_t B, int mem);

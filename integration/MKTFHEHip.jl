@@ -169,6 +169,32 @@ function MKTFHE.keyswitch!(res::MKTFHE.LWE{UInt32}, acc::MKTFHE.RLWE{R}, s::HipS
     unflat!(res, out)
 end
 
+# key switch at a coefficient (mktfhe.h "key switch at a coefficient"): res = keyswitch!(X^-v * acc), acc read in place
+function keyswitch_at!(res::MKTFHE.LWE{UInt32}, acc::MKTFHE.RLWE{R}, v::Integer, s::HipScheme{R}) where R
+    out = Vector{UInt32}(undef, s.nparty * s.n + 1)
+    check(ccall((:mkt_keyswitch_at_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{R}, Csize_t, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Csize_t, Cint),
+                s.ctx, flat(acc), 1, C_NULL, UInt32[v], out, 1, HOST), s.ctx)
+    unflat!(res, out)
+end
+
+# bootstrap at a coefficient list: ONE blind rotation of ctxt through `lut`, one output per entry of coef (what a bootstrap of `lut` reads
+# at phase phi - coef[i]); nu = 0 is the fine mod-switch.  -> [kn+1] x length(coef), one output per column
+function lut_bootstrapping_at(ctxt::MKTFHE.LWE{UInt32}, lut::Vector{R}, coef::Vector{UInt32}, s::HipScheme; nu::Integer=0) where {R<:Unsigned}
+    v = flat(ctxt)
+    out = Matrix{UInt32}(undef, length(v), length(coef))
+    check(ccall((:mkt_lut_bootstrap_at_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{R}, Csize_t, Ptr{UInt32}, Ptr{UInt32}, Cint, Ptr{UInt32}, Csize_t, Ptr{UInt32}, Csize_t, Cint),
+                s.ctx, lut, 1, C_NULL, v, nu, coef, length(coef), out, 1, HOST), s.ctx)
+    out
+end
+
+# the same behind the linear front end of mkt_lut_batch_gather: pool [kn+1] x rows, idx 4 x B (0-based rows), wt 4 x B, cst B
+function lut_gather_at(lut::Vector{R}, pool::Matrix{UInt32}, idx::Matrix{UInt32}, wt::Matrix{Int8}, cst::Vector{UInt32}, coef::Vector{UInt32}, s::HipScheme; nu::Integer=0) where {R<:Unsigned}
+    out = Array{UInt32}(undef, size(pool, 1), length(coef), length(cst))
+    check(ccall((:mkt_lut_batch_gather_at, LIB), Cint, (Ptr{Cvoid}, Ptr{R}, Csize_t, Ptr{UInt32}, Ptr{UInt32}, Csize_t, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32}, Cint, Ptr{UInt32}, Csize_t,
+                 Ptr{UInt32}, Csize_t, Cint), s.ctx, lut, 1, C_NULL, pool, size(pool, 2), idx, wt, cst, nu, coef, length(coef), out, length(cst), HOST), s.ctx)
+    out
+end
+
 # gates (gate.jl:1-53): op = 0 NAND, 1 AND, 2 OR, 3 XOR, 4 XNOR, 5 NOR; vectors evaluate as ONE batch on the GPU
 function gate(op, c1::Vector{<:MKTFHE.LWE}, c2::Vector{<:MKTFHE.LWE}, s::HipScheme)
     x = reduce(hcat, flat.(c1)); y = reduce(hcat, flat.(c2)); out = similar(x)

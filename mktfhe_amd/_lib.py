@@ -68,6 +68,9 @@ SYMBOLS = {
     "mkt_lut_many_batch_gather": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _i]),
     "mkt_lut_many_testvector_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _i]),
     "mkt_lut_extract_batch": (_i, [_vp, _vp, _i, _vp, _sz, _i]),
+    "mkt_keyswitch_at_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _i]),
+    "mkt_lut_bootstrap_at_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _sz, _vp, _sz, _i]),
+    "mkt_lut_batch_gather_at": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _vp, _sz, _i]),
     "mkt_modswitch_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i]),
     "mkt_blindrotate_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mkt_keyswitch_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
@@ -99,6 +102,7 @@ SYMBOLS = {
     "mkt_multi_bootstrap_batch": (_i, [_vp, _vp, _sz, _i]),
     "mkt_multi_lut_bootstrap_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _i]),
     "mkt_multi_lut_many_bootstrap_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _sz, _i]),
+    "mkt_multi_lut_bootstrap_at_batch": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _sz, _vp, _sz, _i]),
     "mkt_multi_not_batch": (_i, [_vp, _vp, _sz, _i]),
     "mkt_multi_blindrotate_batch": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mkt_multi_keyswitch_batch": (_i, [_vp, _vp, _vp, _sz, _i]),

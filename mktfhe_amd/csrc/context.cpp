@@ -133,6 +133,7 @@ struct mkt_ctx {
     cplx *ws_lev = nullptr, *ws_scratch = nullptr;
     void *ws_fxacc = nullptr;    // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
     uint32_t *ws_ksd = nullptr; size_t ws_ksd_words = 0;   // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
+    uint32_t *ws_at = nullptr; size_t ws_at_rows = 0;      // bootstrap at a coefficient list: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call)
     void *ws_many = nullptr; size_t ws_many_accs = 0;      // many-table bootstrap: the nout extracted copies of a chunk's accumulators (first such call; at most CHUNK_GATES accumulators, ws_acc's full size)
     // timing
     bool timing = false;
@@ -437,9 +438,11 @@ int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const u
     return MKT_OK;
 }
 
-int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B) {
+// src / coef (device, [B]) / nacc: the key switch at a coefficient, out[g] = keyswitch!(E_coef[g](acc[src[g]])) (device_api.h KsArgs); both null = keyswitch!
+int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, const uint32_t *src = nullptr, const uint32_t *coef = nullptr, size_t nacc = 0) {
     const mkt_params &p = c->p;
     mktd::KsArgs a{};
+    a.src = src; a.coef = coef; a.nacc = nacc;
     a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->stride(T_KSK); a.n1p = c->ks->n1p;
     a.N = p.N; a.n = p.n; a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.kacc = c->sh.kacc;
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
@@ -522,6 +525,30 @@ int lut_many_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, 
     }
     HIPCHK(c, mktd::launch_lut_extract(c->p.W, c->ws_acc, 1 << nu, c->logN, c->sh.kacc, c->ws_many, B, c->stream));
     return do_keyswitch(c, c->ws_many, out, accs);
+}
+
+// ---- bootstrap at a coefficient list (mktfhe.h "key switch at a coefficient"): one rotation, ncoef key switches, no copy of the accumulators ----
+// where every output row of a chunk's key switch reads: row g = j * ncoef + i is accumulator j at coef[i].  Written once per call, for its
+// largest chunk (a shorter last chunk reads a prefix); coef [ncoef] on the device
+struct AtArgs { const uint32_t *coef; size_t ncoef; int nu; };
+int at_table(mkt_ctx *c, const AtArgs &at, size_t rows) {
+    if (rows > c->ws_at_rows) {
+        if (c->ws_at) (void)hipFree(c->ws_at);
+        c->ws_at = nullptr; c->ws_at_rows = 0;
+        HIPCHK(c, hipMalloc((void **)&c->ws_at, rows * 8));
+        c->ws_at_rows = rows;
+    }
+    HIPCHK(c, mktd::launch_ks_at_table(at.coef, at.ncoef, c->ws_at, c->ws_at + c->ws_at_rows, rows, c->stream));
+    return MKT_OK;
+}
+
+// a device-resident chunk of B inputs: lin [B][len] -> out [B * ncoef][len].  The rotation is the programmable bootstrap's (nu = 0) or the
+// many-table form's on the grid 2^nu times coarser; the key switch then reads the B rotated accumulators where they lie in ws_acc, every
+// output row at its own coefficient.  out must not be lin when ncoef > 1
+int lut_at_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, const AtArgs &at, uint32_t *out, size_t B) {
+    int r;
+    if ((r = at.nu ? lut_many_rotate_chunk(c, t, lin, at.nu, B) : lut_rotate_chunk(c, t, lin, B))) return r;
+    return do_keyswitch(c, c->ws_acc, out, B * at.ncoef, c->ws_at, c->ws_at + c->ws_at_rows, B);
 }
 
 // staging helper for MKT_MEM_HOST callers
@@ -768,7 +795,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_many, c->ws_fxacc, c->d_pm_stat};
+    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_many, c->ws_fxacc, c->d_pm_stat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
@@ -1284,11 +1311,13 @@ int mkt_lut_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const u
 
 // all programmable-bootstrap entry points share one body: the inputs in batch order (src: [B][len]), or built per gate from a pool
 // (src = pool [rows][len]; idx [B][4], wt [B][4], cst [B]) by lut_linear_kernel.  nout 0: one table per rotation, out [B][len]; nout >= 1: the
-// many-table form, out [B][nout][len], in chunks of CHUNK_GATES / nout inputs so that a chunk's copies fit ws_many
+// many-table form, out [B][nout][len], in chunks of CHUNK_GATES / nout inputs so that a chunk's copies fit ws_many.  coef (with nout 0): the
+// bootstrap at a coefficient list, out [B][ncoef][len], in chunks of max(1, CHUNK_GATES / ncoef) inputs so that a key switch sees at most
+// CHUNK_GATES rows (ncoef rows where one input has more); nu_at its mod-switch
 static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *src, size_t rows, const uint32_t *idx,
-                    const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem) {
+                    const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem, const uint32_t *coef = nullptr, size_t ncoef = 0, int nu_at = 0) {
     const int nu = nout ? many_nu(c, nout) : 0;   // (the many-table entry points have refused any other count)
-    const size_t per = nout ? (size_t)nout : 1, step = CHUNK_GATES / per;
+    const size_t per = coef ? ncoef : (nout ? (size_t)nout : 1), step = std::max<size_t>(1, CHUNK_GATES / per);
     MKT_EXACT_GATE(c);
     int r;
     if ((r = check_ready(c, true, true))) return r;
@@ -1297,7 +1326,11 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
     const size_t len = (size_t)c->sh.lwe_len;
     const bool pool = idx != nullptr;
     StagedLuts t(c);
-    Staged sv{c}, so{c}, si{c}, sw{c}, sk{c};
+    Staged sv{c}, so{c}, si{c}, sw{c}, sk{c}, sf{c};
+    if (coef && !B) return MKT_OK;
+    if (coef && (r = sf.in(coef, ncoef * 4, mem, true))) return r;
+    const AtArgs at{(const uint32_t *)sf.dev, ncoef, nu_at};
+    if (coef && (r = at_table(c, at, std::min(step, B) * ncoef))) return r;
     if ((r = t.in(c, who, luts, nluts, sel, B, mem)) || (r = sv.in(src, rows * len * 4, mem, true)) || (r = so.in(out, B * per * len * 4, mem, false))) return r;
     if (pool && ((r = si.in(idx, B * 16, mem, true)) || (r = sw.in(wt, B * 4, mem, true)) || (r = sk.in(cst, B * 4, mem, true)))) return r;
     for (size_t off = 0; off < B; off += step) {
@@ -1310,7 +1343,8 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
             lin = c->ws_lin;
         }
         uint32_t *dst = (uint32_t *)so.dev + off * per * len;
-        if ((r = nout ? lut_many_bootstrap_chunk(c, t.chunk(nluts, off), lin, nu, dst, nb) : lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, dst, nb))) return r;
+        if ((r = coef ? lut_at_bootstrap_chunk(c, t.chunk(nluts, off), lin, at, dst, nb)
+                      : (nout ? lut_many_bootstrap_chunk(c, t.chunk(nluts, off), lin, nu, dst, nb) : lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, dst, nb)))) return r;
     }
     return so.out(out);
 }
@@ -1393,6 +1427,38 @@ int mkt_lut_many_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const 
     return lut_impl(c, "mkt_lut_many_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, nout, out, B, mem);
 }
 
+// ---- key switch at a coefficient (mktfhe.h): the bootstrap at a coefficient list ----
+// what every such entry point refuses before anything is staged or written; coef on the host is checked against N here
+static int at_args_ok(mkt_ctx *c, const std::string &who, int nu, const uint32_t *coef, size_t ncoef, int mem) {
+    if (nu < 0 || nu > 3 || (1 << nu) > c->p.N) return fail(c, MKT_ERR_ARG, who + ": nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N = " + std::to_string(c->p.N));
+    if (ncoef < 1 || ncoef > (size_t)c->p.N) return fail(c, MKT_ERR_ARG, who + ": " + std::to_string(ncoef) + " coefficients, expected 1 .. N = " + std::to_string(c->p.N));
+    const uint32_t *iv[] = {coef};
+    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, ncoef, (size_t)c->p.N)) return fail(c, MKT_ERR_ARG, who + ": a coefficient is not below N");
+    return MKT_OK;
+}
+
+// out[j][i] = keyswitch!(E_coef[i](blindrotate!(sw_nu(a_j), (X^sw_nu(b_j) * luts[sel[j]], 0 ...)))): ncoef outputs of one rotation
+int mkt_lut_bootstrap_at_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu, const uint32_t *coef, size_t ncoef, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !lwe || !coef || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    int r;
+    if ((r = at_args_ok(c, "mkt_lut_bootstrap_at_batch", nu, coef, ncoef, mem))) return r;
+    const size_t rb = (size_t)c->sh.lwe_len * 4;
+    if (ncoef > 1 && ranges_overlap(lwe, B * rb, out, B * ncoef * rb)) return fail(c, MKT_ERR_ARG, "mkt_lut_bootstrap_at_batch: out overlaps lwe (ncoef > 1)");
+    return lut_impl(c, "mkt_lut_bootstrap_at_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, 0, out, B, mem, coef, ncoef, nu);
+}
+
+// the linear front end of mkt_lut_batch_gather, then the above; out [B][ncoef][len] may be a later region of the pool
+int mkt_lut_batch_gather_at(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
+                            const int8_t *wt, const uint32_t *cst, int nu, const uint32_t *coef, size_t ncoef, uint32_t *out, size_t B, int mem) {
+    if (!c || !luts || !pool || !idx || !wt || !cst || !coef || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    int r;
+    if ((r = at_args_ok(c, "mkt_lut_batch_gather_at", nu, coef, ncoef, mem))) return r;
+    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather_at: gates over an empty pool");
+    const uint32_t *iv[] = {idx};
+    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather_at: operand index outside the pool");
+    return lut_impl(c, "mkt_lut_batch_gather_at", luts, nluts, sel, pool, pool_rows, idx, wt, cst, 0, out, B, mem, coef, ncoef, nu);
+}
+
 int mkt_modswitch_batch(mkt_ctx *c, const uint32_t *lwe, uint32_t *atilde, uint32_t *btilde, size_t B, int mem) {
     if (!c || !lwe || !atilde || !btilde || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     DevGuard dg(c->device);
@@ -1464,6 +1530,34 @@ int mkt_keyswitch_batch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, in
     Staged sc{c}, so{c};
     if ((r = sc.in(acc, B * accb, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
     if ((r = do_keyswitch(c, sc.dev, (uint32_t *)so.dev, B))) return r;
+    return so.out(out);
+}
+
+// out[g] = keyswitch!(E_coef[g](acc[src[g]])); rows in chunks of CHUNK_GATES, each reading the whole of acc (src NULL: its own rows of it)
+int mkt_keyswitch_at_batch(mkt_ctx *c, const void *acc, size_t nacc, const uint32_t *src, const uint32_t *coef, uint32_t *out, size_t B, int mem) {
+    if (!c || !acc || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (B && !nacc) return fail(c, MKT_ERR_ARG, "mkt_keyswitch_at_batch: output rows over no accumulator");
+    if (!src && nacc != B) return fail(c, MKT_ERR_ARG, "mkt_keyswitch_at_batch: src NULL names accumulator g for row g: nacc must equal B");
+    if (mem == MKT_MEM_HOST) {
+        const uint32_t *is[] = {src}, *ic[] = {coef};
+        if (src && !in_pool_host(is, 1, B, nacc)) return fail(c, MKT_ERR_ARG, "mkt_keyswitch_at_batch: src names a row outside acc");
+        if (coef && !in_pool_host(ic, 1, B, (size_t)c->p.N)) return fail(c, MKT_ERR_ARG, "mkt_keyswitch_at_batch: a coefficient is not below N");
+    }
+    MKT_EXACT_GATE(c);
+    int r;
+    if ((r = check_ready(c, false, true))) return r;
+    if (!B) return MKT_OK;
+    DevGuard dg(c->device);
+    const size_t accb = (size_t)(1 + c->sh.kacc) * poly_bytes(c), len = (size_t)c->sh.lwe_len;
+    Staged sc{c}, so{c}, ss{c}, sf{c};
+    if ((r = sc.in(acc, nacc * accb, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
+    if (src && (r = ss.in(src, B * 4, mem, true))) return r;
+    if (coef && (r = sf.in(coef, B * 4, mem, true))) return r;
+    for (size_t off = 0; off < B; off += CHUNK_GATES) {
+        const size_t nb = std::min(CHUNK_GATES, B - off);
+        const void *a0 = src ? sc.dev : (const void *)((const char *)sc.dev + off * accb);
+        if ((r = do_keyswitch(c, a0, (uint32_t *)so.dev + off * len, nb, src ? (const uint32_t *)ss.dev + off : nullptr, coef ? (const uint32_t *)sf.dev + off : nullptr, src ? nacc : nb))) return r;
+    }
     return so.out(out);
 }
 

@@ -101,6 +101,11 @@ struct KsArgs {
     int lmss;                 // LMSS flavour of the copy rule (global coefficient index across components)
     uint32_t *digits;         // scratch of the digit-pair kernel (both or neither; sizes: ks_scratch_words): prepared digit words
     uint32_t *partial;        //   and the partial sums of every slab; null: the per-digit kernel with atomics
+    // key switch at a coefficient (mktfhe.h): out[g] = keyswitch!(E_coef[g](acc[src[g]])).  Both null = the plain key switch, which runs
+    // kernels of its own; else acc holds nacc rows, src [B] rows of acc (null: g; clamped to nacc - 1), coef [B] (null: 0; read mod N)
+    const uint32_t *src;
+    const uint32_t *coef;
+    size_t nacc;
 };
 // words of KsArgs::digits / KsArgs::partial for a batch of B ciphertexts (0, 0: this shape runs on the per-digit kernel)
 void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *partial_words);
@@ -148,6 +153,8 @@ hipError_t launch_lut_many_testvector(int W, const void *luts, size_t nluts, con
                                       uint32_t *atilde, int at_stride, void *acc, size_t B, hipStream_t s);
 // accs[g][v] = X^-v * acc[g] for v < nout (1, 2, 4, 8; nout <= N): acc [B][1+kacc][N] -> accs [B][nout][1+kacc][N]; the two must not overlap
 hipError_t launch_lut_extract(int W, const void *acc, int nout, int logN, int kacc, void *accs, size_t B, hipStream_t s);
+// the (src, coef) rows of a bootstrap with ncoef outputs per input (KsArgs): src[g] = g / ncoef, coef_rows[g] = coef[g % ncoef] for g < rows
+hipError_t launch_ks_at_table(const uint32_t *coef, size_t ncoef, uint32_t *src, uint32_t *coef_rows, size_t rows, hipStream_t s);
 // its gather front end: out[g] = cst[g] e_b + sum_{t<4} wt[g][t] pool[idx[g][t]] (int8 weights, 0 skips the term; rows clamped into the pool); out [B][len]
 hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s);
 hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);

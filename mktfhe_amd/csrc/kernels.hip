@@ -1172,10 +1172,39 @@ __device__ __forceinline__ uint32_t extract_word(const WORD *a, int j, int N) { 
     if (j == 0) return (uint32_t)(a[0] >> sh);
     return 0u - (uint32_t)(a[N - j] >> sh);
 }
+// the same word of E_v(a) = X^-v * a (mktfhe.h "key switch at a coefficient"): E_v(a)[0] = a[v]; E_v(a)[N - j] is a[N + v - j] for j > v
+// and -a[v - j], negated at the ring's width, for 0 < j <= v (the wrap of X^N = -1).  On the 64-bit ring the truncation comes after that
+// negation, as it does for the copy X^-v * acc the many-table route writes out: -((-a) >> 32) is (a >> 32) + 1 unless a's low half is 0.
+// v = 0 is the function above
+template <typename WORD>
+__device__ __forceinline__ uint32_t extract_word_at(const WORD *a, int j, int N, int v) {
+    constexpr int sh = WordTraits<WORD>::W - 32;
+    if (j == 0) return (uint32_t)(a[v] >> sh);
+    if (j <= v) return 0u - (uint32_t)((WORD)(0 - a[v - j]) >> sh);
+    return 0u - (uint32_t)(a[N + v - j] >> sh);
+}
+// AT: every output row g names its accumulator and its coefficient (KsArgs::src / ::coef; a null array = the identity / coefficient 0).
+// The row is clamped into [0, nacc) and the coefficient read mod N, so no device-side value reaches outside acc.  The plain key switch
+// (AT = false) is its own instantiation: it carries none of this
+template <bool AT>
+__device__ __forceinline__ size_t ks_row(const KsArgs &a, size_t g) {
+    if constexpr (!AT) return g;
+    else { const size_t r = a.src ? (size_t)a.src[g] : g; return r < a.nacc ? r : a.nacc - 1; }
+}
+template <bool AT>
+__device__ __forceinline__ int ks_coef(const KsArgs &a, size_t g) {
+    if constexpr (!AT) return 0;
+    else return a.coef ? (int)(a.coef[g] & (uint32_t)(a.N - 1)) : 0;
+}
+template <typename WORD, bool AT>
+__device__ __forceinline__ uint32_t ks_word(const WORD *poly, int j, int N, int v) {
+    if constexpr (!AT) return extract_word<WORD>(poly, j, N);
+    else return extract_word_at<WORD>(poly, j, N, v);
+}
 
 // out = 0 except: b = acc.b[0] >> (W-32) (:86 / :569) and, for the block schemes, the extracted words that are
 // copied instead of switched (:180-191, :676-679).  The key-switch kernel then accumulates with atomics.
-template <typename WORD>
+template <typename WORD, bool AT>
 __global__ void ks_init_kernel(const KsArgs a, size_t B) {
     constexpr int sh = WordTraits<WORD>::W - 32;
     const int nblocks_out = a.mk ? a.kacc : 1;
@@ -1183,12 +1212,13 @@ __global__ void ks_init_kernel(const KsArgs a, size_t B) {
     const size_t total = B * (size_t)lwe_len;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t g = i / lwe_len; const int q = (int)(i % lwe_len);
-        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + g * (size_t)(1 + a.kacc) * a.N;
+        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + ks_row<AT>(a, g) * (size_t)(1 + a.kacc) * a.N;
+        const int cf = ks_coef<AT>(a, g);
         uint32_t v = 0;
-        if (q == lwe_len - 1) v = (uint32_t)(accg[0] >> sh);
+        if (q == lwe_len - 1) v = (uint32_t)(accg[cf] >> sh);
         else if (a.balanced) {
-            if (a.lmss) { const int c = q / a.N, j = q % a.N; v = extract_word<WORD>(accg + (size_t)(1 + c) * a.N, j, a.N); }
-            else { const int c = q / a.n, j = q % a.n; v = extract_word<WORD>(accg + (size_t)(1 + c) * a.N, j, a.N); }
+            if (a.lmss) { const int c = q / a.N, j = q % a.N; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
+            else { const int c = q / a.n, j = q % a.n; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
         }
         a.out[i] = v;
     }
@@ -1210,7 +1240,7 @@ constexpr int KS_BATCH = 8;
 // have passed the barrier in between (a per-j parity would reuse stage 0 back to back when f is odd).
 // BAL: balanced (signed) digits of the block schemes -- a template flag so the unbalanced path carries none of the
 // sign handling on the scalar unit (one per CU, and the busiest unit of this kernel)
-template <typename WORD, int G, int WAVES, bool BAL>
+template <typename WORD, int G, int WAVES, bool BAL, bool AT>
 __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_mg_kernel(const KsArgs a, int B, int ngroups, int jslab) {
     // digit table: [stage][1 + drows (+ drows negated rows for balanced digits)][lane]
     uint4 *tabp = reinterpret_cast<uint4 *>(mkt_smem);
@@ -1256,8 +1286,9 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
 #pragma unroll
             for (int g = 0; g < G; g++) {
                 const int gi = g_base + g < B ? g_base + g : B - 1;
-                const WORD *ac = reinterpret_cast<const WORD *>(a.acc) + ((size_t)gi * (1 + a.kacc) + 1 + c) * N;
-                const uint32_t w = extract_word<WORD>(ac, j, N);
+                // (AT: the row and the coefficient of an output row are wave-uniform like gi itself, two more loads on the scalar path)
+                const WORD *ac = reinterpret_cast<const WORD *>(a.acc) + (ks_row<AT>(a, (size_t)gi) * (1 + a.kacc) + 1 + c) * N;
+                const uint32_t w = ks_word<WORD, AT>(ac, j, N, ks_coef<AT>(a, (size_t)gi));
                 tt[g] = BAL ? gb.prep(w) : divbits<uint32_t>(w, 32 - f * logD);   // gsw.jl:42-52 / :34-40
             }
             const uint32_t *rowj = ksk + (size_t)j * drows * f * n1p + q0;
@@ -1312,14 +1343,14 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
 // once per key switch: [component][group of 32 ciphertexts][j][32] so that a wave of the pair kernel reads the words of its 32
 // ciphertexts for one coefficient as 128 contiguous bytes.  Block = 32 ciphertexts x 8 coefficients: reads are one or two 64-byte
 // lines per ciphertext, writes 1 KiB contiguous.
-template <typename WORD, bool BAL>
+template <typename WORD, bool BAL, bool AT>
 __global__ __launch_bounds__(256) void ks_digits_kernel(const KsArgs a, int B, int ngroups) {
     const int g = threadIdx.x & 31, j = (int)blockIdx.x * 8 + (int)(threadIdx.x >> 5);
     if (j >= a.N) return;
     const int grp = blockIdx.y, c = blockIdx.z;
     const int gi = grp * 32 + g < B ? grp * 32 + g : B - 1;
-    const WORD *ac = reinterpret_cast<const WORD *>(a.acc) + ((size_t)gi * (1 + a.kacc) + 1 + c) * a.N;
-    const uint32_t w = extract_word<WORD>(ac, j, a.N);
+    const WORD *ac = reinterpret_cast<const WORD *>(a.acc) + (ks_row<AT>(a, (size_t)gi) * (1 + a.kacc) + 1 + c) * a.N;
+    const uint32_t w = ks_word<WORD, AT>(ac, j, a.N, ks_coef<AT>(a, (size_t)gi));
     const Gadget<uint32_t> gb(a.f, 2);
     a.digits[(((size_t)c * ngroups + grp) * a.N + j) * 32 + g] = BAL ? gb.prep(w) : divbits<uint32_t>(w, 32 - a.f * 2);
 }
@@ -1432,7 +1463,7 @@ __global__ __launch_bounds__(KS_LANES * WAVES, MKT_KSP_OCC) void keyswitch_pair_
 
 // out = what the key switch leaves alone (b, and for the block schemes the extracted words that are copied, :180-191 / :676-679:
 // ks_init_kernel's words) + the partial sums of every slab (and, for b, of every party).
-template <typename WORD>
+template <typename WORD, bool AT>
 __global__ void ks_reduce_kernel(const KsArgs a, size_t B, int slabs, int parties) {
     constexpr int sh = WordTraits<WORD>::W - 32;
     const int nblocks_out = a.mk ? a.kacc : 1;
@@ -1441,16 +1472,17 @@ __global__ void ks_reduce_kernel(const KsArgs a, size_t B, int slabs, int partie
     const size_t row = (size_t)a.n1p, slab_stride = (size_t)parties * B * row;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t g = i / lwe_len; const int q = (int)(i % lwe_len);
-        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + g * (size_t)(1 + a.kacc) * a.N;
+        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + ks_row<AT>(a, g) * (size_t)(1 + a.kacc) * a.N;
+        const int cf = ks_coef<AT>(a, g);
         uint32_t v = 0;
         if (q == lwe_len - 1) {
-            v = (uint32_t)(accg[0] >> sh);
+            v = (uint32_t)(accg[cf] >> sh);
             for (int sl = 0; sl < slabs; sl++)
                 for (int pt = 0; pt < parties; pt++) v += a.partial[sl * slab_stride + ((size_t)pt * B + g) * row + a.n];
         } else {
             if (a.balanced) {
-                if (a.lmss) { const int c = q / a.N, j = q % a.N; v = extract_word<WORD>(accg + (size_t)(1 + c) * a.N, j, a.N); }
-                else { const int c = q / a.n, j = q % a.n; v = extract_word<WORD>(accg + (size_t)(1 + c) * a.N, j, a.N); }
+                if (a.lmss) { const int c = q / a.N, j = q % a.N; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
+                else { const int c = q / a.n, j = q % a.n; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
             }
             const int pt = a.mk ? q / a.n : 0, w = a.mk ? q % a.n : q;
             const uint32_t *src = a.partial + ((size_t)pt * B + g) * row + w;
@@ -1891,8 +1923,9 @@ void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *pa
     *partial_words = q.pair ? (size_t)q.slabs * q.parties * B * (size_t)a.n1p : 0;                 // [slab][party][B][n1p]
 }
 
-hipError_t launch_keyswitch(int W, const KsArgs &a, size_t B, hipStream_t s) {
-    if (!B) return hipSuccess;
+// AT: the rows extract at a coefficient of a named accumulator (KsArgs::src / ::coef); the plain key switch keeps kernels of its own
+template <bool AT>
+static hipError_t launch_keyswitch_as(int W, const KsArgs &a, size_t B, hipStream_t s) {
     const KsPlan q = ks_plan(a, B, a.digits && a.partial);
     const int G = q.G, waves = q.waves, ngroups = q.ngroups, parties = q.parties, gblocks = q.gblocks, slabs = q.slabs, jslab = q.jslab;
     const bool pair = q.pair;
@@ -1905,35 +1938,42 @@ hipError_t launch_keyswitch(int W, const KsArgs &a, size_t B, hipStream_t s) {
         else if (waves == 2) hipLaunchKernelGGL((keyswitch_pair_kernel<WT, 32, 2, BV>), grid, dim3(KS_LANES * 2), ks_lds, s, a, (int)B, ngroups); \
         else hipLaunchKernelGGL((keyswitch_pair_kernel<WT, 32, 1, BV>), grid, dim3(KS_LANES), ks_lds, s, a, (int)B, ngroups); } while (0)
         const dim3 dgrid((unsigned)((a.N + 7) / 8), (unsigned)ngroups, (unsigned)a.kacc);
-#define MKT_KSD_LAUNCH(WT) do { if (a.balanced) hipLaunchKernelGGL((ks_digits_kernel<WT, true>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); \
-        else hipLaunchKernelGGL((ks_digits_kernel<WT, false>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); } while (0)
+#define MKT_KSD_LAUNCH(WT) do { if (a.balanced) hipLaunchKernelGGL((ks_digits_kernel<WT, true, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); \
+        else hipLaunchKernelGGL((ks_digits_kernel<WT, false, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); } while (0)
         if (W == 64) {
             MKT_KSD_LAUNCH(uint64_t);
             if (a.balanced) MKT_KSP_LAUNCH_B(uint64_t, true); else MKT_KSP_LAUNCH_B(uint64_t, false);
-            hipLaunchKernelGGL(ks_reduce_kernel<uint64_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
+            hipLaunchKernelGGL((ks_reduce_kernel<uint64_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
         } else {
             MKT_KSD_LAUNCH(uint32_t);
             if (a.balanced) MKT_KSP_LAUNCH_B(uint32_t, true); else MKT_KSP_LAUNCH_B(uint32_t, false);
-            hipLaunchKernelGGL(ks_reduce_kernel<uint32_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
+            hipLaunchKernelGGL((ks_reduce_kernel<uint32_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
         }
 #undef MKT_KSD_LAUNCH
 #undef MKT_KSP_LAUNCH_B
         return hipGetLastError();
     }
-#define MKT_KS_LAUNCH_B(WT, GV, BV) do { if (GV == 32 && waves == 4) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 4, BV>), grid, dim3(KS_LANES * 4), ks_lds, s, a, (int)B, ngroups, jslab); \
-        else if (GV == 32 && waves == 2) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 2, BV>), grid, dim3(KS_LANES * 2), ks_lds, s, a, (int)B, ngroups, jslab); \
-        else hipLaunchKernelGGL((keyswitch_mg_kernel<WT, GV, 1, BV>), grid, dim3(KS_LANES), ks_lds, s, a, (int)B, ngroups, jslab); } while (0)
+#define MKT_KS_LAUNCH_B(WT, GV, BV) do { if (GV == 32 && waves == 4) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 4, BV, AT>), grid, dim3(KS_LANES * 4), ks_lds, s, a, (int)B, ngroups, jslab); \
+        else if (GV == 32 && waves == 2) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 2, BV, AT>), grid, dim3(KS_LANES * 2), ks_lds, s, a, (int)B, ngroups, jslab); \
+        else hipLaunchKernelGGL((keyswitch_mg_kernel<WT, GV, 1, BV, AT>), grid, dim3(KS_LANES), ks_lds, s, a, (int)B, ngroups, jslab); } while (0)
 #define MKT_KS_LAUNCH(WT, GV) do { if (a.balanced) MKT_KS_LAUNCH_B(WT, GV, true); else MKT_KS_LAUNCH_B(WT, GV, false); } while (0)
     if (W == 64) {
-        hipLaunchKernelGGL(ks_init_kernel<uint64_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
+        hipLaunchKernelGGL((ks_init_kernel<uint64_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
         if (G == 8) MKT_KS_LAUNCH(uint64_t, 8); else if (G == 32) MKT_KS_LAUNCH(uint64_t, 32); else MKT_KS_LAUNCH(uint64_t, 16);
     } else {
-        hipLaunchKernelGGL(ks_init_kernel<uint32_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
+        hipLaunchKernelGGL((ks_init_kernel<uint32_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
         if (G == 8) MKT_KS_LAUNCH(uint32_t, 8); else if (G == 32) MKT_KS_LAUNCH(uint32_t, 32); else MKT_KS_LAUNCH(uint32_t, 16);
     }
 #undef MKT_KS_LAUNCH_B
 #undef MKT_KS_LAUNCH
     return hipGetLastError();
+}
+
+hipError_t launch_keyswitch(int W, const KsArgs &a, size_t B, hipStream_t s) {
+    if (!B) return hipSuccess;
+    if (!a.src && !a.coef) return launch_keyswitch_as<false>(W, a, B, s);
+    if (!a.nacc || a.N < 1 || (a.N & (a.N - 1))) return hipErrorInvalidValue;   // a row to clamp to; the coefficient is read mod N
+    return launch_keyswitch_as<true>(W, a, B, s);
 }
 #endif  // TU 0
 

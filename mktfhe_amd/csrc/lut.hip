@@ -2,6 +2,7 @@
 //   lut_testvector_kernel  acc = (X^btilde * T, 0 ...) for a caller-supplied test-vector polynomial T (bootstrapping.jl:11-23 builds this for
 //                          the constant -1/8 table only); for the many-table form btilde and the mask words go onto a coarser grid
 //   lut_extract_kernel     the many-table form behind the rotation: the nout copies X^-v * acc, v < nout, the key switch reads
+//   ks_at_table_kernel     the bootstrap at a coefficient list: which accumulator and which coefficient every output row of the key switch reads
 //   lut_linear_kernel      the gather front end of a circuit level: a weighted sum of up to four pool rows plus a constant on the b word
 // Neither does floating point.
 #include "kernel_common.h"
@@ -89,6 +90,16 @@ __global__ void __launch_bounds__(256) lut_extract_kernel(const WORD *__restrict
     }
 }
 
+// The rows of a key switch at a coefficient (device_api.h KsArgs::src / ::coef) for ncoef outputs per rotated accumulator: output row
+// g = j * ncoef + i reads accumulator j at coef[i].  The list is the caller's, as it is (the key switch reads it mod N)
+__global__ void __launch_bounds__(256) ks_at_table_kernel(const uint32_t *__restrict__ coef, uint32_t ncoef, uint32_t *__restrict__ src, uint32_t *__restrict__ coef_rows, size_t rows) {
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < rows; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = g / ncoef;
+        src[g] = (uint32_t)j;
+        coef_rows[g] = coef[g - j * ncoef];
+    }
+}
+
 // lin[g] = cst[g] e_b + sum_{t < 4} wt[g][t] pool[idx[g][t]]: one workgroup per gate (grid-stride over gates), shaped as gate3_linear_kernel --
 // the four row indices, weights and the constant are the same for the whole workgroup, the rows are streamed coalesced.  A weight of 0
 // skips its term (its row is not read); rows are clamped into the pool as everywhere (kernels.hip gate_linear_kernel).
@@ -162,6 +173,14 @@ hipError_t launch_lut_extract(int W, const void *acc, int nout, int logN, int ka
     if (!B) return hipSuccess;
     if (logN < 0 || logN > 12 || kacc < 0 || (nout != 1 && nout != 2 && nout != 4 && nout != 8) || nout > (1 << logN)) return hipErrorInvalidValue;
     return W == 64 ? launch_lut_ex<uint64_t>(acc, nout, logN, kacc, accs, B, s) : launch_lut_ex<uint32_t>(acc, nout, logN, kacc, accs, B, s);
+}
+
+hipError_t launch_ks_at_table(const uint32_t *coef, size_t ncoef, uint32_t *src, uint32_t *coef_rows, size_t rows, hipStream_t s) {
+    if (!rows) return hipSuccess;
+    if (!ncoef || ncoef > 0xffffffffull || rows / ncoef > 0xffffffffull) return hipErrorInvalidValue;
+    const size_t blocks = (rows + 255) / 256;
+    hipLaunchKernelGGL(ks_at_table_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, coef, (uint32_t)ncoef, src, coef_rows, rows);
+    return hipGetLastError();
 }
 
 hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s) {

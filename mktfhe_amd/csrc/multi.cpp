@@ -322,6 +322,30 @@ int mkt_multi_lut_many_bootstrap_batch(mkt_multi *m, const void *luts, size_t nl
     });
 }
 
+// the bootstrap at a coefficient list, sharded by input: out is cut at ncoef rows per input, coef travels whole to every shard as luts does.
+// What no shard could take (and, in host memory, any index outside its range) is refused here, before any shard starts
+int mkt_multi_lut_bootstrap_at_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu, const uint32_t *coef, size_t ncoef,
+                                     uint32_t *out, size_t B, int mem) {
+    if (!m || !luts || !lwe || !coef || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
+    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: no lookup table");
+    if (nu < 0 || nu > 3 || (1 << nu) > m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N");
+    if (ncoef < 1 || ncoef > (size_t)m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: " + std::to_string(ncoef) + " coefficients, expected 1 .. N");
+    if (mem == MKT_MEM_HOST) {
+        for (size_t i = 0; i < ncoef; i++) if (coef[i] >= (uint32_t)m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: a coefficient is not below N");
+        if (sel) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: table selector outside the tables");
+    }
+    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);
+    if (ncoef > 1 && B) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(lwe), b0 = reinterpret_cast<uintptr_t>(out);
+        if (a0 < b0 + B * ncoef * rb && b0 < a0 + B * rb) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: out overlaps lwe (ncoef > 1)");
+    }
+    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb * ncoef, false, true}, {coef, 4, true, false, ncoef}};
+    if (sel) specs.push_back({sel, 4, true, false});
+    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
+        return mkt_lut_bootstrap_at_batch(c, a[0], nluts, sel ? (const uint32_t *)a[4] : nullptr, (const uint32_t *)a[1], nu, (const uint32_t *)a[3], ncoef, (uint32_t *)a[2], nb, mem);
+    });
+}
+
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem) {
     if (!m || !x) return mfail(m, MKT_ERR_ARG, "bad argument");
     const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4;

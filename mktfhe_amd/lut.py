@@ -170,6 +170,75 @@ def lut_many_gather(scheme, luts, sel, pool, idx, wt, cst, nout, out):
                         _Buf(cst, np.uint32, B), nout, scheme._ct(out, B * nout, out=True))[-1]
 
 
+# ---- bootstrap at a coefficient list (include/mktfhe.h "key switch at a coefficient"): ncoef outputs of one blind rotation, no copy ----
+def lut_threshold_coefs(P, params: Params):
+    """the coefficients w * N / P, w < P: with sign_lut, output w of an input on window m of P (phase m / 2P + 1 / 4P) is + iff m >= w --
+    the thermometer bits of a P-valued message from ONE rotation.  P divides N"""
+    P = int(P)
+    if P < 1 or params.N % P:
+        raise ValueError(f"P = {P}: the window count must divide N = {params.N}")
+    return np.array([w * (params.N // P) for w in range(P)], dtype=np.uint32)
+
+
+def keyswitch_at(scheme, acc, src=None, coef=None):
+    """mkt_keyswitch_at_batch (a Scheme): out[g] = keyswitch!(X^-coef[g] * acc[src[g]]) -- the key switch extracting at coefficient coef[g]
+    of accumulator src[g], no rotated copy made.  acc: (..., k+1, N) ring words; src, coef: uint32 arrays (int32 tensors) of one shape living
+    where acc lives; src None = row g of acc (as many rows as accumulators), coef None = 0.  Both None is scheme.keyswitch(acc), word for
+    word.  -> (shape of src / coef / the accumulators, k*n+1) uint32 where acc lives"""
+    p = scheme.params
+    shape = tuple(np.shape(acc))
+    if shape[-2:] != (p.k + 1, p.N):
+        raise ValueError(f"accumulator of shape {shape}, expected (..., {p.k + 1}, {p.N})")
+    nacc = int(np.prod(shape[:-2]))
+    rows = shape[:-2] if src is None and coef is None else tuple(np.shape(coef if src is None else src))
+    if src is not None and coef is not None and tuple(np.shape(coef)) != rows:
+        raise ValueError(f"src of shape {rows} and coef of shape {tuple(np.shape(coef))}: one entry each per output row")
+    B = int(np.prod(rows))
+    out = _empty(acc, rows + (p.lwe_len,), np.uint32, "int32")
+    return scheme._call("keyswitch_at_batch", B, _Buf(acc, p.ring_dtype, nacc * (p.k + 1) * p.N), nacc, None if src is None else _Buf(src, np.uint32, B),
+                        None if coef is None else _Buf(coef, np.uint32, B), scheme._ct(out, B, out=True))[-1]
+
+
+def _coef(coef, params):
+    """-> the _Buf of a coefficient list and its length; a host list is checked here (1 .. N entries, each below N)"""
+    if not _is_torch(coef):
+        coef = np.ascontiguousarray(coef)
+        if coef.dtype.kind not in "iu" or coef.ndim != 1 or not 1 <= coef.size <= params.N or coef.min() < 0 or coef.max() >= params.N:
+            raise ValueError(f"coef: expected 1 .. {params.N} integers in [0, {params.N})")
+        coef = coef.astype(np.uint32)
+    n = _count(coef)
+    return _Buf(coef, np.uint32, n), n
+
+
+def _nu(nu, params):
+    if nu not in (0, 1, 2, 3) or (1 << nu) > params.N:
+        raise ValueError(f"nu = {nu!r}: the coarse mod-switch is 0 .. 3 with 2^nu at most N = {params.N}")
+    return int(nu)
+
+
+def lut_bootstrap_at(scheme, luts, ctxt, coef, nu=0, sel=None, out=None):
+    """mkt_lut_bootstrap_at_batch (a Scheme) / mkt_multi_lut_bootstrap_at_batch (a MultiScheme): ONE blind rotation of ctxt[j] through table
+    luts[sel[j]] (None: row 0), then out[j][i] = the key switch extracting at coefficient coef[i] -- what a bootstrap of the same table
+    reads at phase phi - coef[i], for every i, at the noise of one bootstrap.  nu: the coarse mod-switch of the many-table
+    form (0 = the fine one).  coef (ncoef,) lives where ctxt lives.  -> (..., ncoef, lwe_len); out must not overlap ctxt when ncoef > 1"""
+    nu = _nu(nu, scheme.params)
+    cb, ncoef = _coef(coef, scheme.params)
+    B, out = _out_many(scheme, ctxt, ncoef, out)
+    tb, nluts = _tables(luts, scheme.params)
+    return scheme._call("lut_bootstrap_at_batch", B, tb, nluts, _sel(sel, B), scheme._ct(ctxt, B), nu, cb, ncoef, scheme._ct(out, B * ncoef, out=True))[-1]
+
+
+def lut_gather_at(scheme, luts, sel, pool, idx, wt, cst, coef, out, nu=0):
+    """one circuit level of lookups at a coefficient list (mkt_lut_batch_gather_at): the linear front end of lut_gather, then
+    lut_bootstrap_at.  out: B * ncoef rows, output i of gate j at row j * ncoef + i; it may be a later region of the pool"""
+    nu = _nu(nu, scheme.params)
+    cb, ncoef = _coef(coef, scheme.params)
+    B, P = _count(cst), _rows(np.shape(pool))
+    tb, nluts = _tables(luts, scheme.params)
+    return scheme._call("lut_batch_gather_at", B, tb, nluts, _sel(sel, B), scheme._ct(pool, P), P, _Buf(idx, np.uint32, B, 4), _Buf(wt, np.int8, B, 4),
+                        _Buf(cst, np.uint32, B), nu, cb, ncoef, scheme._ct(out, B * ncoef, out=True))[-1]
+
+
 def lwe_encrypt_word(mu, i, key: PartyKeys, params: Params, deterministic_seed=None):
     """lwe_ith_encrypt (scheme.jl:370-386) of ANY message mu on the 32-bit torus under party i (single-key schemes: 0): a multi-valued input
     of a programmable bootstrap.  mu = +-2^29 with the same pinned seed gives the words of lwe_ith_encrypt"""
