@@ -459,6 +459,42 @@ int mkt_client_lwe_decrypt(const mkt_params *params, const mkt_client_party *con
  * that makes decryption a sum) that is b + sum_i <a_i, s_i> */
 int mkt_client_lwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const uint32_t *lwe, uint32_t *phase);
 
+/* ---- distributed decryption: every party opens its OWN block of the mask; nobody holds two secrets.  mkt_client_lwe_decrypt / _phase take
+ *      all k secret keys in one process (the reference's lwe_decrypt, scheme.jl:388-407, a test harness); the multi-key protocols
+ *      behind the CCS and KMS schemes (Chen, Chillotti, Song 2019; Kwak, Min, Song 2022) end instead with one share per party, blurred by
+ *      fresh noise, that anyone may add up.
+ *      LAYOUT.  Unchanged: a row is [a_0 (n words) .. a_{nparty-1} (n words), b], 32-bit words; nparty = k for the multi-key schemes and 1
+ *      for MKT_CGGI / MKT_LMSS whatever their RLWE length.
+ *      SHARE.  Party i's share of row j of a batch is  share_i[j] = sum_q a_i[q] * s_i[q] + e_i[j]  (mod 2^32): wrapping uint32_t arithmetic,
+ *      the key word multiplied (not assumed binary), as mkt_client_lwe_phase does.  Only block i of the row is read.
+ *      SMUDGING NOISE.  e_i[j] = (uint32_t) Rng(key, i, 9, lo32(row0 + j), hi32(row0 + j)).noise(sigma_smudge): the ChaCha20 streams of
+ *      every client call (256-bit `seed` as in the RANDOMNESS note above, NULL = fresh OS entropy per call), stream id 9, one stream per
+ *      row, its first Gaussian draw rounded.  sigma_smudge is a standard deviation in words of the 32-bit torus (the unit of sigma_lwe); it
+ *      must be finite with 0 <= sigma_smudge <= 2^31, anything else is MKT_ERR_ARG and no word is written.  row0 is the index of the
+ *      call's first row in a larger logical batch: a caller streams one batch in pieces under one seed without drawing a noise word twice.
+ *      A SEED MUST NEVER SERVE TWO DIFFERENT CIPHERTEXTS AT ONE ROW INDEX: the difference of the two shares is then noise-free.
+ *      MERGE.  phase[j] = b[j] + sum_i share_i[j]; the bit is what mkt_client_lwe_decrypt decides from that phase for the scheme.  With
+ *      sigma_smudge = 0 the merged phase is mkt_client_lwe_phase word for word.  Merging needs no key.
+ *      WHAT IS NOT CLAIMED.  No sigma_smudge is certified as simulation-secure: on a 32-bit torus with a decision margin of 1/8 the
+ *      flooding noise a statistical argument asks for does not fit.  The value is the deployment's choice (failure
+ *      predictions per shipped set). ---- */
+/* lwe [B][lwe_len] -> share_out [B]; keys = party `party`'s keys, made for these parameters and that party index.  B == 0 succeeds */
+int mkt_client_partial_decrypt(const mkt_params *params, const mkt_client_party *keys, int party, const uint32_t *lwe, double sigma_smudge,
+                               const uint8_t *seed, uint64_t row0, uint32_t *share_out, size_t B);
+/* shares [nparties][B] (party-major) -> phase_out [B] / bits_out [B] (0 / 1); nparties must be the scheme's party count (MKT_ERR_ARG) */
+int mkt_client_merge_phase(const mkt_params *params, const uint32_t *lwe, const uint32_t *shares, int nparties, uint32_t *phase_out, size_t B);
+int mkt_client_merge_decrypt(const mkt_params *params, const uint32_t *lwe, const uint32_t *shares, int nparties, uint8_t *bits_out, size_t B);
+/* the share on the GPU of `ctx`, for a party that opens many rows: the same words as mkt_client_partial_decrypt for the same seed and
+ * row0.  lwe and share_out live in `mem` (MKT_MEM_DEVICE / MKT_MEM_HOST); the call runs on the context's stream and needs NO evaluation
+ * key loaded (a context made by mkt_ctx_create alone serves).  It returns once the share is written and the key copy is wiped.
+ * TRUST: this call hands party `party`'s SECRET LWE key to the GPU of this context.  It is a party-local operation: a party runs it on
+ * its own machine / GPU and ships the shares to whoever merges.  An evaluator context that runs it for every party holds all k secrets
+ * -- acceptable only in tests and benchmarks.  The n key words are uploaded per call and zeroed on the device before they are freed, and
+ * the host-side copy of the stream key is wiped; the copy of that key carried in the kernel-argument segment of the launch lives in
+ * runtime-owned memory the library cannot erase (it is overwritten by later launches). */
+int mkt_partial_decrypt_batch(mkt_ctx *ctx, int party, const mkt_client_party *keys, const uint32_t *lwe, double sigma_smudge, const uint8_t *seed,
+                              uint64_t row0, uint32_t *share_out, size_t B, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,10 @@ SYMBOLS = {
     "mkt_client_lwe_encrypt_word": (_i, [_pp, _vp, _i, C.c_uint32, _dbl, _vp, _vp]),
     "mkt_client_lwe_phase": (_i, [_pp, C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint32)]),
     "mkt_client_lwe_decrypt": (_i, [_pp, C.POINTER(_vp), _i, _vp]),
+    "mkt_client_partial_decrypt": (_i, [_pp, _vp, _i, _vp, _dbl, _vp, _u64, _vp, _sz]),
+    "mkt_client_merge_phase": (_i, [_pp, _vp, _vp, _i, _vp, _sz]),
+    "mkt_client_merge_decrypt": (_i, [_pp, _vp, _vp, _i, _vp, _sz]),
+    "mkt_partial_decrypt_batch": (_i, [_vp, _i, _vp, _vp, _dbl, _vp, _u64, _vp, _sz, _i]),
 }
 
 _lib = None

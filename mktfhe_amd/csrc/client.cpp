@@ -39,10 +39,6 @@ int validate_params(const mkt_params &p, std::string &why) {
     return MKT_OK;
 }
 
-namespace {
-
-using mktrng::Rng;
-
 // 256-bit seed -> key words; NULL = fresh OS entropy (getrandom), never a fixed default
 int seed_to_key(const uint8_t *seed, uint32_t key[8]) {
     uint8_t tmp[32];
@@ -59,6 +55,10 @@ int seed_to_key(const uint8_t *seed, uint32_t key[8]) {
     explicit_bzero(tmp, sizeof tmp);
     return MKT_OK;
 }
+
+namespace {
+
+using mktrng::Rng;
 
 inline uint64_t wmask(int W) { return W == 64 ? ~0ull : ((1ull << W) - 1); }
 
@@ -388,6 +388,22 @@ int mkt_client_lwe_phase(const mkt_params *params, const mkt_client_party *const
     return MKT_OK;
 }
 
+// the bit a phase decides (scheme.jl:388-407 after the sum): shared by mkt_client_lwe_decrypt and mkt_client_merge_decrypt
+static int bit_of_phase(const mkt_params &p, uint32_t b) {
+    if (!is_mk(p.scheme)) {                       // divbits(phase, 29) == 1
+        uint32_t carry = (b << 3) >> 31;
+        return ((b >> 29) + carry) == 1 ? 1 : 0;
+    }
+    return b < (1u << 31) ? 1 : 0;
+}
+
+// b + the k shares of row j; shares [nparty][B]
+static uint32_t merged_phase(const Shape &sh, const uint32_t *lwe, const uint32_t *shares, size_t B, size_t j) {
+    uint32_t b = lwe[j * (size_t)sh.lwe_len + sh.lwe_len - 1];
+    for (int i = 0; i < sh.nparty; i++) b += shares[(size_t)i * B + j];
+    return b;
+}
+
 // scheme.jl:388-407
 int mkt_client_lwe_decrypt(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const uint32_t *lwe) {
     if (!params || !keys || !lwe) return MKT_ERR_ARG;
@@ -397,11 +413,47 @@ int mkt_client_lwe_decrypt(const mkt_params *params, const mkt_client_party *con
     uint32_t b = lwe[sh.lwe_len - 1];
     for (int i = 0; i < nparties; i++)
         for (int q = 0; q < p.n; q++) b += keys[i]->lwekey[q] * lwe[(size_t)i * p.n + q];
-    if (!is_mk(p.scheme)) {                       // divbits(phase, 29) == 1
-        uint32_t carry = (b << 3) >> 31;
-        return ((b >> 29) + carry) == 1 ? 1 : 0;
+    return bit_of_phase(p, b);
+}
+
+// ---- distributed decryption (mktfhe.h): a share per party from its own mask block, merged by anyone ----
+
+// share_i[j] = <a_i, s_i> + e_i[j], e_i[j] the smudging noise of row row0 + j (rng_chacha.h smudge_word)
+int mkt_client_partial_decrypt(const mkt_params *params, const mkt_client_party *K, int party, const uint32_t *lwe, double sigma_smudge,
+                               const uint8_t *seed, uint64_t row0, uint32_t *share_out, size_t B) {
+    if (!params || !K || !lwe || !share_out || !smudge_sigma_ok(sigma_smudge)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
+    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return MKT_ERR_ARG;   // keys made for other parameters / another party index (as mkt_keygen_device)
+    uint32_t key[8];
+    if (seed_to_key(seed, key)) return MKT_ERR_STATE;
+    for (size_t j = 0; j < B; j++) {
+        const uint32_t *a = lwe + j * (size_t)sh.lwe_len + (size_t)party * p.n;
+        uint32_t dot = 0;
+        for (int q = 0; q < p.n; q++) dot += a[q] * K->lwekey[q];
+        share_out[j] = dot + mktrng::smudge_word(key, (uint32_t)party, row0 + j, sigma_smudge);
     }
-    return b < (1u << 31) ? 1 : 0;
+    explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// phase[j] = b[j] + sum_i share_i[j]; shares [nparty][B]
+int mkt_client_merge_phase(const mkt_params *params, const uint32_t *lwe, const uint32_t *shares, int nparties, uint32_t *phase_out, size_t B) {
+    if (!params || !lwe || !shares || !phase_out) return MKT_ERR_ARG;
+    Shape sh = shape_of(*params);
+    if (nparties != sh.nparty) return MKT_ERR_ARG;
+    for (size_t j = 0; j < B; j++) phase_out[j] = merged_phase(sh, lwe, shares, B, j);
+    return MKT_OK;
+}
+
+// the bit mkt_client_lwe_decrypt decides from that phase
+int mkt_client_merge_decrypt(const mkt_params *params, const uint32_t *lwe, const uint32_t *shares, int nparties, uint8_t *bits_out, size_t B) {
+    if (!params || !lwe || !shares || !bits_out) return MKT_ERR_ARG;
+    Shape sh = shape_of(*params);
+    if (nparties != sh.nparty) return MKT_ERR_ARG;
+    for (size_t j = 0; j < B; j++) bits_out[j] = (uint8_t)bit_of_phase(*params, merged_phase(sh, lwe, shares, B, j));
+    return MKT_OK;
 }
 
 }  // extern "C"

@@ -1080,6 +1080,38 @@ int mkt_keygen_device_export(mkt_ctx *c, int party, const mkt_client_party *K, c
     return keygen_device_impl(c, party, K, crs, brk_out, ksk_out);
 }
 
+// Distributed decryption (mktfhe.h): party `party`'s shares of B rows on this context's device -- a party-local call like
+// mkt_keygen_device, on a context that needs no evaluation key.  The n key words are uploaded for the call and wiped before they are freed.
+int mkt_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const uint32_t *lwe, double sigma_smudge, const uint8_t *seed,
+                              uint64_t row0, uint32_t *share_out, size_t B, int mem) {
+    if (!c || !K || !lwe || !share_out || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::smudge_sigma_ok(sigma_smudge)) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: sigma_smudge must be finite, 0 <= sigma_smudge <= 2^31");
+    const mkt_params &p = c->p;
+    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
+    if (!B) return MKT_OK;
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    Staged sx{c}, so{c};
+    int r;
+    if ((r = sx.in(lwe, B * (size_t)c->sh.lwe_len * 4, mem, true)) || (r = so.in(share_out, B * 4, mem, false))) return r;
+    mktd::PartialDecryptArgs a{};
+    if (mkt::seed_to_key(seed, a.key)) return fail(c, MKT_ERR_STATE, "mkt_partial_decrypt_batch: no entropy from the OS");
+    uint32_t *d_key = nullptr;
+    hipError_t e = hipMalloc((void **)&d_key, (size_t)p.n * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_key, K->lwekey.data(), (size_t)p.n * 4, hipMemcpyHostToDevice, c->stream);
+    a.party = party; a.n = p.n; a.lwe_stride = c->sh.lwe_len; a.sigma = sigma_smudge; a.row0 = row0;
+    a.lwe = (const uint32_t *)sx.dev; a.lwekey = d_key; a.out = (uint32_t *)so.dev; a.B = B;
+    if (e == hipSuccess) e = mktd::launch_partial_decrypt(a, c->stream);
+    // the secret is wiped on the device before its buffer is released
+    if (d_key) (void)hipMemsetAsync(d_key, 0, (size_t)p.n * 4, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_key);
+    explicit_bzero(&a, sizeof a);            // the host copy of the stream key (the kernel-argument copy: see the TRUST note in mktfhe.h)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hipfail(c, e, "device partial decryption");
+    return so.out(share_out);
+}
+
 // debug / test read-back of a party's key-switching key in the host layout of mkt_load_ksk
 int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
     if (!c || !out_host || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");

@@ -127,6 +127,20 @@ struct KeygenArgs {
 hipError_t launch_keygen_brk(const KeygenArgs &a, int unienc, hipStream_t s);
 hipError_t launch_keygen_ksk(const KeygenArgs &a, uint32_t *ksk, int n1p, int kk, int dr, int is_block, hipStream_t s);
 
+// A party's decryption shares on the device (partial_decrypt.hip; mktfhe.h "distributed decryption"):
+// out[j] = <lwe[j] block `party`, lwekey> + smudge_word(key, party, row0 + j, sigma), j < B
+struct PartialDecryptArgs {
+    uint32_t key[8];             // 256-bit ChaCha20 key of the call's noise streams (rng_chacha.h)
+    int party, n, lwe_stride;    // party block, words per block, words per row
+    double sigma;
+    uint64_t row0;
+    const uint32_t *lwe;         // [B][lwe_stride]
+    const uint32_t *lwekey;      // [n]
+    uint32_t *out;               // [B]
+    size_t B;
+};
+hipError_t launch_partial_decrypt(const PartialDecryptArgs &a, hipStream_t s);
+
 hipError_t launch_transform_fwd(int logM, int W, TwPtrs tw, const void *p, cplx *t, size_t B, int dev_order, hipStream_t s);
 hipError_t launch_reorder(int logM, const cplx *in, cplx *out, size_t npolys, int to_device, int order, hipStream_t s);
 hipError_t launch_transform_inv(int logM, int W, TwPtrs tw, const cplx *t, void *p, size_t B, hipStream_t s);

@@ -127,4 +127,15 @@ struct Rng {
     MKT_HD uint64_t noise(double sigma) { return (uint64_t)(int64_t)__builtin_rint(sigma * gauss()); }
 };
 
+// Stream ids (the purpose field of the nonce) in use, each keyed by its caller's seed: 1 secret keys, 2 bootstrapping key, 3 public key,
+// 4 relinearisation key, 5 key-switching key, 7 encryption mask and noise (client.cpp, keygen.hip), 0xC125 the CRS (client.cpp).
+// 9: the smudging noise of a decryption share (mktfhe.h "distributed decryption"): one stream per batch row, the 64-bit row index in the
+// two index words of the nonce.
+constexpr uint32_t STREAM_SMUDGE = 9;
+// e of row `row` for party `party`: the first noise draw of that row's stream, on the 32-bit torus (client.cpp and partial_decrypt.hip)
+MKT_HD uint32_t smudge_word(const uint32_t key[8], uint32_t party, uint64_t row, double sigma) {
+    Rng r(key, party, STREAM_SMUDGE, (uint32_t)row, (uint32_t)(row >> 32));
+    return (uint32_t)r.noise(sigma);
+}
+
 }  // namespace mktrng

@@ -211,6 +211,17 @@ def predict(p):
     return math.sqrt(br), math.sqrt(ks), math.sqrt(br + ks)
 
 
+def smudged_failure(p, sigma_smudge, sigma_b=None):
+    """Gaussian prediction of a wrong bit when a gate output of set p is opened by distributed decryption (mktfhe.h): every one of the
+    nparty shares adds smudging noise of deviation sigma_smudge (words of the 32-bit torus, the unit of p.alpha), so the merged phase
+    carries the variance sigma_b^2 + nparty (sigma_smudge / 2^32)^2 against the margin 1/8 -> P(|error| > 1/8).  sigma_b: the output
+    phase error of the gate in torus units, by default predict(p)'s total (for the KMS sets that is a simulation: pass it in to reuse it)"""
+    if sigma_b is None:
+        sigma_b = predict(p)[2]
+    var = sigma_b ** 2 + p.nparty * (sigma_smudge / 2.0 ** 32) ** 2
+    return math.erfc(0.125 / math.sqrt(2.0 * var)) if var > 0.0 else 0.0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("names", nargs="*")
