@@ -286,8 +286,8 @@ int mkt_lut_batch_gather(mkt_ctx *ctx, const void *luts, size_t nluts, const uin
  *      EXTRACTION AT COEFFICIENT v.  E_v(acc) = X^-v * acc on every one of the 1 + k polynomials: E_v(acc)[c][i] = acc[c][i + v] for
  *      i + v < N, -acc[c][i + v - N] otherwise.  Output v of input j is keyswitch!(E_v(blindrotate!(sw(a), (X^sw(b) * U, 0, ...)))).
  *      nout = 1 returns the words of mkt_lut_bootstrap_batch.  The output noise is that of any bootstrap; the INPUT's mod-switch error
- *      grows nout-fold.  The nout rotated copies of a chunk live in a buffer of the accumulator workspace's size that a
- *      context allocates at its first such call (MKT_ERR_NOMEM / MKT_ERR_HIP from that call if it cannot; forks hold their own).
+ *      grows nout-fold.  No copy E_v(acc) is made: the key switch reads coefficient v of the rotated accumulator where it
+ *      lies, as the bootstrap at the coefficient list 0 .. nout - 1 does (next block); mkt_lut_extract_batch is the definition as a unit call.
  *      Validation of luts, sel, pool indices: as in the programmable-bootstrap block.  Both arithmetic modes, every scheme. ---- */
 /* out [B][nout][k*n+1]: output v of input j at row j * nout + v.  out must not overlap lwe when nout > 1 (MKT_ERR_ARG) */
 int mkt_lut_many_bootstrap_batch(mkt_ctx *ctx, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B,
@@ -318,7 +318,7 @@ int mkt_lut_extract_batch(mkt_ctx *ctx, const void *acc, int nout, void *accs, s
  *      a coef >= N or a sel >= nluts is MKT_ERR_ARG and nothing is written; with MKT_MEM_DEVICE src is clamped to the last row and coef
  *      read mod N -- never an out-of-bounds access.  nacc == 0 with B > 0, ncoef == 0 or > N, a bad nu, and src == NULL with nacc != B are
  *      refused in either memory kind; B == 0 succeeds and writes nothing.  A call runs in chunks of max(1, 8192 / ncoef) inputs (8192 rows
- *      for mkt_keyswitch_at_batch).  No buffer of extracted accumulators exists on this path: the key switch reads the rotated accumulators
+ *      for mkt_keyswitch_at_batch).  No buffer of extracted accumulators exists: the key switch reads the rotated accumulators
  *      in the workspace through a (row, coefficient) table of 8 bytes per output row.  Both arithmetic modes, every scheme; forks hold
  *      their own workspace. ---- */
 /* out[g] = keyswitch!(E_{coef[g]}(acc[src[g]])); acc [nacc][1+k][N] ring words, out [B][k*n+1]; src [B] or NULL (= g; then nacc must

@@ -133,8 +133,7 @@ struct mkt_ctx {
     cplx *ws_lev = nullptr, *ws_scratch = nullptr;
     void *ws_fxacc = nullptr;    // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
     uint32_t *ws_ksd = nullptr; size_t ws_ksd_words = 0;   // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
-    uint32_t *ws_at = nullptr; size_t ws_at_rows = 0;      // bootstrap at a coefficient list: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call)
-    void *ws_many = nullptr; size_t ws_many_accs = 0;      // many-table bootstrap: the nout extracted copies of a chunk's accumulators (first such call; at most CHUNK_GATES accumulators, ws_acc's full size)
+    uint32_t *ws_at = nullptr; size_t ws_at_rows = 0;      // lookup-table bootstrap with more than one output per input: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call)
     // timing
     bool timing = false;
     std::vector<TimedSpan> spans;
@@ -480,75 +479,39 @@ int bootstrap_chunk(mkt_ctx *c, const uint32_t *lin, uint32_t *out, size_t B) {
 // A caller's lookup tables on the device: luts [nluts][N] ring words, sel [B] rows or nullptr (row 0)
 struct LutArgs { const void *luts; size_t nluts; const uint32_t *sel; };
 
-// rotate_chunk with the test vector of a caller's table (mktfhe.h "programmable bootstrap"): ws_acc <- blindrotate!((X^btilde T, 0 ...)).
-// Every route takes the accumulator it is handed (the multi-key phase 2 with lin_for_tv == nullptr, as mkt_blindrotate_batch runs it)
-int lut_rotate_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, size_t B) {
-    HIPCHK(c, mktd::launch_lut_testvector(c->p.W, t.luts, t.nluts, t.sel, lin, c->sh.lwe_len, c->logN, c->sh.kacc, c->ws_acc, B, c->stream));
-    return do_blindrotate(c, lin, c->sh.lwe_len, 0, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B);
-}
+// ---- lookup-table bootstrap (mktfhe.h "programmable bootstrap", "many-table bootstrap", "key switch at a coefficient") ----
+// One chunk of any of them: the tables, the mod-switch exponent nu (0: the caller's words as they are; 1 .. 3: the grid 2^nu times coarser),
+// `per` outputs per input, and where the key switch reads.  at: output row j * per + i is accumulator j at coef[i] (coef [per] on the device;
+// nullptr = the list 0 .. per - 1, the many-table form), through the context's (row, coefficient) table ws_at.  Not at (per == 1): the plain
+// key switch, coefficient 0 of every accumulator
+struct LutChunk { LutArgs t; int nu; size_t per; bool at; const uint32_t *coef; };
 
-// the programmable bootstrap of a device-resident chunk: lin -> out (out may be lin: the masks and b are read before the key switch writes)
-int lut_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, uint32_t *out, size_t B) {
-    int r;
-    if ((r = lut_rotate_chunk(c, t, lin, B))) return r;
-    return do_keyswitch(c, c->ws_acc, out, B);
-}
-
-// ---- many-table bootstrap (mktfhe.h): nout = 2^nu tables packed into one test vector, one rotation, nout key switches ----
-// nu = log2(nout) for nout in {1, 2, 4, 8} with nout <= N, else -1
-int many_nu(const mkt_ctx *c, int nout) {
-    for (int nu = 0; nu <= 3; nu++) if (nout == 1 << nu) return nout <= c->p.N ? nu : -1;
-    return -1;
-}
-
-// lut_rotate_chunk on the coarse grid: the switched mask words go to ws_lin (rows of lwe_len words; lin may BE ws_lin, the gather form), the
-// rotation then runs on pre-switched masks with the accumulator it is handed, as mkt_blindrotate_batch runs it
-int lut_many_rotate_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, int nu, size_t B) {
-    HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, t.luts, t.nluts, t.sel, lin, c->sh.lwe_len, c->logN, c->sh.kacc, nu, c->ws_lin, c->sh.lwe_len, c->ws_acc, B, c->stream));
-    return do_blindrotate(c, c->ws_lin, c->sh.lwe_len, 1, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B);
-}
-
-// the many-table bootstrap of a device-resident chunk of B <= CHUNK_GATES >> nu inputs: lin [B][len] -> out [B << nu][len], output v of
-// input j at row (j << nu) + v.  The copies X^-v acc live in ws_many, allocated by the first call that needs it (a context that never
-// makes one never pays for it); the unchanged key switch then extracts coefficient 0 of each.  out must not be lin when nu > 0
-int lut_many_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, int nu, uint32_t *out, size_t B) {
-    int r;
-    if ((r = lut_many_rotate_chunk(c, t, lin, nu, B))) return r;
-    if (!nu) return do_keyswitch(c, c->ws_acc, out, B);       // one table: X^0 acc is acc
-    const size_t accs = B << nu;
-    if (accs > c->ws_many_accs) {
-        if (c->ws_many) (void)hipFree(c->ws_many);
-        c->ws_many = nullptr; c->ws_many_accs = 0;
-        const hipError_t e = hipMalloc(&c->ws_many, accs * (size_t)(1 + c->sh.kacc) * poly_bytes(c));
-        if (e != hipSuccess) { c->ws_many = nullptr; return fail(c, e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP, std::string("many-table bootstrap: workspace for the extracted accumulators: ") + hipGetErrorString(e)); }
-        c->ws_many_accs = accs;
-    }
-    HIPCHK(c, mktd::launch_lut_extract(c->p.W, c->ws_acc, 1 << nu, c->logN, c->sh.kacc, c->ws_many, B, c->stream));
-    return do_keyswitch(c, c->ws_many, out, accs);
-}
-
-// ---- bootstrap at a coefficient list (mktfhe.h "key switch at a coefficient"): one rotation, ncoef key switches, no copy of the accumulators ----
-// where every output row of a chunk's key switch reads: row g = j * ncoef + i is accumulator j at coef[i].  Written once per call, for its
-// largest chunk (a shorter last chunk reads a prefix); coef [ncoef] on the device
-struct AtArgs { const uint32_t *coef; size_t ncoef; int nu; };
-int at_table(mkt_ctx *c, const AtArgs &at, size_t rows) {
+// ws_at <- where every output row of a chunk's key switch reads.  Written once per call, for its largest chunk (a shorter last chunk reads
+// a prefix), 8 bytes per output row
+int at_table(mkt_ctx *c, const LutChunk &k, size_t rows) {
     if (rows > c->ws_at_rows) {
         if (c->ws_at) (void)hipFree(c->ws_at);
         c->ws_at = nullptr; c->ws_at_rows = 0;
         HIPCHK(c, hipMalloc((void **)&c->ws_at, rows * 8));
         c->ws_at_rows = rows;
     }
-    HIPCHK(c, mktd::launch_ks_at_table(at.coef, at.ncoef, c->ws_at, c->ws_at + c->ws_at_rows, rows, c->stream));
+    HIPCHK(c, mktd::launch_ks_at_table(k.coef, k.per, c->ws_at, c->ws_at + c->ws_at_rows, rows, c->stream));
     return MKT_OK;
 }
 
-// a device-resident chunk of B inputs: lin [B][len] -> out [B * ncoef][len].  The rotation is the programmable bootstrap's (nu = 0) or the
-// many-table form's on the grid 2^nu times coarser; the key switch then reads the B rotated accumulators where they lie in ws_acc, every
-// output row at its own coefficient.  out must not be lin when ncoef > 1
-int lut_at_bootstrap_chunk(mkt_ctx *c, const LutArgs &t, const uint32_t *lin, const AtArgs &at, uint32_t *out, size_t B) {
+// a device-resident chunk of B inputs: lin [B][len] -> out [B * per][len] (out may be lin when per == 1: the masks and b are read before the
+// key switch writes).  ws_acc <- (X^btilde T, 0 ...) for the caller's table, then blindrotate! with the accumulator it is handed (the multi-key
+// phase 2 with lin_for_tv == nullptr, as mkt_blindrotate_batch runs it): on the caller's masks for nu = 0, else on the coarse-switched mask
+// words, which go to ws_lin (rows of lwe_len words; lin may BE ws_lin, the gather form).  The key switch reads the B rotated accumulators
+// where they lie in ws_acc
+int lut_chunk(mkt_ctx *c, const LutChunk &k, const uint32_t *lin, uint32_t *out, size_t B) {
+    const int len = c->sh.lwe_len;
     int r;
-    if ((r = at.nu ? lut_many_rotate_chunk(c, t, lin, at.nu, B) : lut_rotate_chunk(c, t, lin, B))) return r;
-    return do_keyswitch(c, c->ws_acc, out, B * at.ncoef, c->ws_at, c->ws_at + c->ws_at_rows, B);
+    if (!k.nu) HIPCHK(c, mktd::launch_lut_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, c->ws_acc, B, c->stream));
+    else HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, k.nu, c->ws_lin, len, c->ws_acc, B, c->stream));
+    if ((r = do_blindrotate(c, k.nu ? c->ws_lin : lin, len, k.nu ? 1 : 0, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B))) return r;
+    if (!k.at) return do_keyswitch(c, c->ws_acc, out, B);
+    return do_keyswitch(c, c->ws_acc, out, B * k.per, c->ws_at, c->ws_at + c->ws_at_rows, B);
 }
 
 // staging helper for MKT_MEM_HOST callers
@@ -795,7 +758,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_many, c->ws_fxacc, c->d_pm_stat};
+    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_fxacc, c->d_pm_stat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
@@ -1318,8 +1281,7 @@ struct StagedLuts {
     explicit StagedLuts(mkt_ctx *c) : luts{c}, sel{c} {}
     int in(mkt_ctx *c, const char *who, const void *l, size_t nluts, const uint32_t *s, size_t B, int mem) {
         if (!nluts) return fail(c, MKT_ERR_ARG, std::string(who) + ": no lookup table");
-        const uint32_t *iv[] = {s};
-        if (s && mem == MKT_MEM_HOST && !in_pool_host(iv, 1, B, nluts)) return fail(c, MKT_ERR_ARG, std::string(who) + ": table selector outside the tables");
+        if (s && mem == MKT_MEM_HOST && !mkt::host_below(s, B, nluts)) return fail(c, MKT_ERR_ARG, std::string(who) + ": table selector outside the tables");
         int r;
         if ((r = luts.in(l, nluts * poly_bytes(c), mem, true))) return r;
         return s ? sel.in(s, B * 4, mem, true) : MKT_OK;
@@ -1341,42 +1303,48 @@ int mkt_lut_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const u
     return sc.out(acc);
 }
 
-// all programmable-bootstrap entry points share one body: the inputs in batch order (src: [B][len]), or built per gate from a pool
-// (src = pool [rows][len]; idx [B][4], wt [B][4], cst [B]) by lut_linear_kernel.  nout 0: one table per rotation, out [B][len]; nout >= 1: the
-// many-table form, out [B][nout][len], in chunks of CHUNK_GATES / nout inputs so that a chunk's copies fit ws_many.  coef (with nout 0): the
-// bootstrap at a coefficient list, out [B][ncoef][len], in chunks of max(1, CHUNK_GATES / ncoef) inputs so that a key switch sees at most
-// CHUNK_GATES rows (ncoef rows where one input has more); nu_at its mod-switch
-static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *src, size_t rows, const uint32_t *idx,
-                    const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem, const uint32_t *coef = nullptr, size_t ncoef = 0, int nu_at = 0) {
-    const int nu = nout ? many_nu(c, nout) : 0;   // (the many-table entry points have refused any other count)
-    const size_t per = coef ? ncoef : (nout ? (size_t)nout : 1), step = std::max<size_t>(1, CHUNK_GATES / per);
+// the gather front end of a circuit level: gate j's input is cst[j] e_b + sum_t wt[j][t] pool[idx[j][t]] (lut_linear_kernel); idx [B][4], wt [B][4], cst [B]
+struct LutGather {
+    const uint32_t *pool; size_t rows; const uint32_t *idx; const int8_t *wt; const uint32_t *cst;
+    bool null() const { return !pool || !idx || !wt || !cst; }
+};
+// what every gather entry point refuses before anything is staged or written; validation as mkt_gate_batch_gather
+static int gather_ok(mkt_ctx *c, const std::string &who, const LutGather &g, size_t B, int mem) {
+    if (B && !g.rows) return fail(c, MKT_ERR_ARG, who + ": gates over an empty pool");
+    if (mem == MKT_MEM_HOST && !mkt::host_below(g.idx, 4 * B, g.rows)) return fail(c, MKT_ERR_ARG, who + ": operand index outside the pool");
+    return MKT_OK;
+}
+
+// all lookup-table bootstraps share one body.  k describes the call in the caller's memory (tables, selectors and coef are staged here); the
+// inputs are lwe [B][len] in batch order, or built per gate from g's pool.  out [B][k.per][len], in chunks of max(1, CHUNK_GATES / k.per)
+// inputs so that a key switch sees at most CHUNK_GATES rows (k.per rows where one input has more)
+static int lut_impl(mkt_ctx *c, const char *who, LutChunk k, const uint32_t *lwe, const LutGather *g, uint32_t *out, size_t B, int mem) {
+    const size_t step = std::max<size_t>(1, CHUNK_GATES / k.per), nluts = k.t.nluts;
     MKT_EXACT_GATE(c);
     int r;
     if ((r = check_ready(c, true, true))) return r;
     DevGuard dg(c->device);
     Timer whole(c, 0);
-    const size_t len = (size_t)c->sh.lwe_len;
-    const bool pool = idx != nullptr;
+    const size_t len = (size_t)c->sh.lwe_len, rows = g ? g->rows : B;
     StagedLuts t(c);
     Staged sv{c}, so{c}, si{c}, sw{c}, sk{c}, sf{c};
-    if (coef && !B) return MKT_OK;
-    if (coef && (r = sf.in(coef, ncoef * 4, mem, true))) return r;
-    const AtArgs at{(const uint32_t *)sf.dev, ncoef, nu_at};
-    if (coef && (r = at_table(c, at, std::min(step, B) * ncoef))) return r;
-    if ((r = t.in(c, who, luts, nluts, sel, B, mem)) || (r = sv.in(src, rows * len * 4, mem, true)) || (r = so.in(out, B * per * len * 4, mem, false))) return r;
-    if (pool && ((r = si.in(idx, B * 16, mem, true)) || (r = sw.in(wt, B * 4, mem, true)) || (r = sk.in(cst, B * 4, mem, true)))) return r;
+    if (k.coef && !B) return MKT_OK;
+    if (k.coef && (r = sf.in(k.coef, k.per * 4, mem, true))) return r;
+    k.coef = (const uint32_t *)sf.dev;
+    if (k.at && (r = at_table(c, k, std::min(step, B) * k.per))) return r;
+    if ((r = t.in(c, who, k.t.luts, nluts, k.t.sel, B, mem)) || (r = sv.in(g ? g->pool : lwe, rows * len * 4, mem, true)) || (r = so.in(out, B * k.per * len * 4, mem, false))) return r;
+    if (g && ((r = si.in(g->idx, B * 16, mem, true)) || (r = sw.in(g->wt, B * 4, mem, true)) || (r = sk.in(g->cst, B * 4, mem, true)))) return r;
     for (size_t off = 0; off < B; off += step) {
         const size_t nb = std::min(step, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
         const uint32_t *lin = (const uint32_t *)sv.dev + off * len;
-        if (pool) {
+        if (g) {
             HIPCHK(c, mktd::launch_lut_linear((const uint32_t *)sv.dev, rows, (const uint32_t *)si.dev + off * 4, (const int8_t *)sw.dev + off * 4, (const uint32_t *)sk.dev + off,
                                               c->ws_lin, (int)len, nb, c->stream));
             lin = c->ws_lin;
         }
-        uint32_t *dst = (uint32_t *)so.dev + off * per * len;
-        if ((r = coef ? lut_at_bootstrap_chunk(c, t.chunk(nluts, off), lin, at, dst, nb)
-                      : (nout ? lut_many_bootstrap_chunk(c, t.chunk(nluts, off), lin, nu, dst, nb) : lut_bootstrap_chunk(c, t.chunk(nluts, off), lin, dst, nb)))) return r;
+        k.t = t.chunk(nluts, off);
+        if ((r = lut_chunk(c, k, lin, (uint32_t *)so.dev + off * k.per * len, nb))) return r;
     }
     return so.out(out);
 }
@@ -1384,28 +1352,26 @@ static int lut_impl(mkt_ctx *c, const char *who, const void *luts, size_t nluts,
 // out[j] = keyswitch!(blindrotate!((X^btilde(lwe[j]) * luts[sel[j]], 0 ...))): bootstrapping! with a caller's table; out may be lwe
 int mkt_lut_bootstrap_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem) {
     if (!c || !luts || !lwe || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    return lut_impl(c, "mkt_lut_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, 0, out, B, mem);
+    return lut_impl(c, "mkt_lut_bootstrap_batch", LutChunk{{luts, nluts, sel}, 0, 1, false, nullptr}, lwe, nullptr, out, B, mem);
 }
 
 // one circuit level of table lookups: gate j bootstraps cst[j] e_b + sum_t wt[j][t] pool[idx[j][t]] through luts[sel[j]]; out may be a later
-// region of the pool that no gate of this call reads.  Validation as mkt_gate_batch_gather
+// region of the pool that no gate of this call reads
 int mkt_lut_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
                          const int8_t *wt, const uint32_t *cst, uint32_t *out, size_t B, int mem) {
-    if (!c || !luts || !pool || !idx || !wt || !cst || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: gates over an empty pool");
-    const uint32_t *iv[] = {idx};
-    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather: operand index outside the pool");
-    return lut_impl(c, "mkt_lut_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, 0, out, B, mem);
+    const LutGather g{pool, pool_rows, idx, wt, cst};
+    if (!c || !luts || g.null() || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = gather_ok(c, "mkt_lut_batch_gather", g, B, mem)) return r;
+    return lut_impl(c, "mkt_lut_batch_gather", LutChunk{{luts, nluts, sel}, 0, 1, false, nullptr}, nullptr, &g, out, B, mem);
 }
 
 // ---- many-table bootstrap (mktfhe.h): nout tables per blind rotation ----
+// nu = log2(nout) for a table count the library takes, else -1
+static int many_nu(const mkt_ctx *c, int nout) { return mkt::lut_nout_ok(nout, c->p.N) ? __builtin_ctz((unsigned)nout) : -1; }
 static int bad_nout(mkt_ctx *c, const char *who, int nout) {
     return fail(c, MKT_ERR_ARG, std::string(who) + ": nout = " + std::to_string(nout) + ", expected 1, 2, 4 or 8 and at most N = " + std::to_string(c->p.N));
 }
-static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
+using mkt::ranges_overlap;
 
 // unit level: the coarse-switched mask words atilde [B][k*n] and acc[j] = (X^btilde * luts[sel[j]], 0 ...) from the coarse btilde; no keys needed
 int mkt_lut_many_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *atilde, void *acc, size_t B, int mem) {
@@ -1439,56 +1405,57 @@ int mkt_lut_extract_batch(mkt_ctx *c, const void *acc, int nout, void *accs, siz
     return so.out(accs);
 }
 
-// out[j][v] = keyswitch!(X^-v * blindrotate!(coarse atilde(lwe[j]), (X^btilde * luts[sel[j]], 0 ...))): nout tables in one rotation
+// out[j][v] = keyswitch!(E_v(blindrotate!(coarse atilde(lwe[j]), (X^btilde * luts[sel[j]], 0 ...)))): nout tables in one rotation, the key switch
+// at the coefficient list 0 .. nout - 1 (nout = 1: the plain key switch)
+static LutChunk many_chunk(const void *luts, size_t nluts, const uint32_t *sel, int nu) { return LutChunk{{luts, nluts, sel}, nu, (size_t)1 << nu, nu > 0, nullptr}; }
+
 int mkt_lut_many_bootstrap_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B, int mem) {
     if (!c || !luts || !lwe || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (many_nu(c, nout) < 0) return bad_nout(c, "mkt_lut_many_bootstrap_batch", nout);
+    const int nu = many_nu(c, nout);
+    if (nu < 0) return bad_nout(c, "mkt_lut_many_bootstrap_batch", nout);
     const size_t rb = (size_t)c->sh.lwe_len * 4;
     if (nout > 1 && ranges_overlap(lwe, B * rb, out, B * (size_t)nout * rb)) return fail(c, MKT_ERR_ARG, "mkt_lut_many_bootstrap_batch: out overlaps lwe (nout > 1)");
-    return lut_impl(c, "mkt_lut_many_bootstrap_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, nout, out, B, mem);
+    return lut_impl(c, "mkt_lut_many_bootstrap_batch", many_chunk(luts, nluts, sel, nu), lwe, nullptr, out, B, mem);
 }
 
 // the linear front end of mkt_lut_batch_gather, then the many-table bootstrap; out [B][nout][len] may be a later region of the pool
 int mkt_lut_many_batch_gather(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
                               const int8_t *wt, const uint32_t *cst, int nout, uint32_t *out, size_t B, int mem) {
-    if (!c || !luts || !pool || !idx || !wt || !cst || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (many_nu(c, nout) < 0) return bad_nout(c, "mkt_lut_many_batch_gather", nout);
-    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_many_batch_gather: gates over an empty pool");
-    const uint32_t *iv[] = {idx};
-    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_many_batch_gather: operand index outside the pool");
-    return lut_impl(c, "mkt_lut_many_batch_gather", luts, nluts, sel, pool, pool_rows, idx, wt, cst, nout, out, B, mem);
+    const LutGather g{pool, pool_rows, idx, wt, cst};
+    if (!c || !luts || g.null() || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    const int nu = many_nu(c, nout);
+    if (nu < 0) return bad_nout(c, "mkt_lut_many_batch_gather", nout);
+    if (int r = gather_ok(c, "mkt_lut_many_batch_gather", g, B, mem)) return r;
+    return lut_impl(c, "mkt_lut_many_batch_gather", many_chunk(luts, nluts, sel, nu), nullptr, &g, out, B, mem);
 }
 
 // ---- key switch at a coefficient (mktfhe.h): the bootstrap at a coefficient list ----
 // what every such entry point refuses before anything is staged or written; coef on the host is checked against N here
 static int at_args_ok(mkt_ctx *c, const std::string &who, int nu, const uint32_t *coef, size_t ncoef, int mem) {
-    if (nu < 0 || nu > 3 || (1 << nu) > c->p.N) return fail(c, MKT_ERR_ARG, who + ": nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N = " + std::to_string(c->p.N));
-    if (ncoef < 1 || ncoef > (size_t)c->p.N) return fail(c, MKT_ERR_ARG, who + ": " + std::to_string(ncoef) + " coefficients, expected 1 .. N = " + std::to_string(c->p.N));
-    const uint32_t *iv[] = {coef};
-    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, ncoef, (size_t)c->p.N)) return fail(c, MKT_ERR_ARG, who + ": a coefficient is not below N");
+    const int N = c->p.N;
+    if (!mkt::lut_nu_ok(nu, N)) return fail(c, MKT_ERR_ARG, who + ": nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N = " + std::to_string(N));
+    if (!mkt::lut_ncoef_ok(ncoef, N)) return fail(c, MKT_ERR_ARG, who + ": " + std::to_string(ncoef) + " coefficients, expected 1 .. N = " + std::to_string(N));
+    if (mem == MKT_MEM_HOST && !mkt::host_below(coef, ncoef, (size_t)N)) return fail(c, MKT_ERR_ARG, who + ": a coefficient is not below N");
     return MKT_OK;
 }
 
 // out[j][i] = keyswitch!(E_coef[i](blindrotate!(sw_nu(a_j), (X^sw_nu(b_j) * luts[sel[j]], 0 ...)))): ncoef outputs of one rotation
 int mkt_lut_bootstrap_at_batch(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu, const uint32_t *coef, size_t ncoef, uint32_t *out, size_t B, int mem) {
     if (!c || !luts || !lwe || !coef || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
-    int r;
-    if ((r = at_args_ok(c, "mkt_lut_bootstrap_at_batch", nu, coef, ncoef, mem))) return r;
+    if (int r = at_args_ok(c, "mkt_lut_bootstrap_at_batch", nu, coef, ncoef, mem)) return r;
     const size_t rb = (size_t)c->sh.lwe_len * 4;
     if (ncoef > 1 && ranges_overlap(lwe, B * rb, out, B * ncoef * rb)) return fail(c, MKT_ERR_ARG, "mkt_lut_bootstrap_at_batch: out overlaps lwe (ncoef > 1)");
-    return lut_impl(c, "mkt_lut_bootstrap_at_batch", luts, nluts, sel, lwe, B, nullptr, nullptr, nullptr, 0, out, B, mem, coef, ncoef, nu);
+    return lut_impl(c, "mkt_lut_bootstrap_at_batch", LutChunk{{luts, nluts, sel}, nu, ncoef, true, coef}, lwe, nullptr, out, B, mem);
 }
 
 // the linear front end of mkt_lut_batch_gather, then the above; out [B][ncoef][len] may be a later region of the pool
 int mkt_lut_batch_gather_at(mkt_ctx *c, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *pool, size_t pool_rows, const uint32_t *idx,
                             const int8_t *wt, const uint32_t *cst, int nu, const uint32_t *coef, size_t ncoef, uint32_t *out, size_t B, int mem) {
-    if (!c || !luts || !pool || !idx || !wt || !cst || !coef || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    const LutGather g{pool, pool_rows, idx, wt, cst};
+    if (!c || !luts || g.null() || !coef || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     int r;
-    if ((r = at_args_ok(c, "mkt_lut_batch_gather_at", nu, coef, ncoef, mem))) return r;
-    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather_at: gates over an empty pool");
-    const uint32_t *iv[] = {idx};
-    if (mem == MKT_MEM_HOST && !in_pool_host(iv, 1, 4 * B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_lut_batch_gather_at: operand index outside the pool");
-    return lut_impl(c, "mkt_lut_batch_gather_at", luts, nluts, sel, pool, pool_rows, idx, wt, cst, 0, out, B, mem, coef, ncoef, nu);
+    if ((r = at_args_ok(c, "mkt_lut_batch_gather_at", nu, coef, ncoef, mem)) || (r = gather_ok(c, "mkt_lut_batch_gather_at", g, B, mem))) return r;
+    return lut_impl(c, "mkt_lut_batch_gather_at", LutChunk{{luts, nluts, sel}, nu, ncoef, true, coef}, nullptr, &g, out, B, mem);
 }
 
 int mkt_modswitch_batch(mkt_ctx *c, const uint32_t *lwe, uint32_t *atilde, uint32_t *btilde, size_t B, int mem) {

@@ -167,7 +167,7 @@ hipError_t launch_lut_many_testvector(int W, const void *luts, size_t nluts, con
                                       uint32_t *atilde, int at_stride, void *acc, size_t B, hipStream_t s);
 // accs[g][v] = X^-v * acc[g] for v < nout (1, 2, 4, 8; nout <= N): acc [B][1+kacc][N] -> accs [B][nout][1+kacc][N]; the two must not overlap
 hipError_t launch_lut_extract(int W, const void *acc, int nout, int logN, int kacc, void *accs, size_t B, hipStream_t s);
-// the (src, coef) rows of a bootstrap with ncoef outputs per input (KsArgs): src[g] = g / ncoef, coef_rows[g] = coef[g % ncoef] for g < rows
+// the (src, coef) rows of a bootstrap with ncoef outputs per input (KsArgs): src[g] = g / ncoef, coef_rows[g] = coef[g % ncoef] (coef NULL: g % ncoef) for g < rows
 hipError_t launch_ks_at_table(const uint32_t *coef, size_t ncoef, uint32_t *src, uint32_t *coef_rows, size_t rows, hipStream_t s);
 // its gather front end: out[g] = cst[g] e_b + sum_{t<4} wt[g][t] pool[idx[g][t]] (int8 weights, 0 skips the term; rows clamped into the pool); out [B][len]
 hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s);

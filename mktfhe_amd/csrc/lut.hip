@@ -1,8 +1,10 @@
 // Programmable bootstrap (include/mktfhe.h "programmable bootstrap", "many-table bootstrap"): the small kernels around the blind rotation, for gfx950.
 //   lut_testvector_kernel  acc = (X^btilde * T, 0 ...) for a caller-supplied test-vector polynomial T (bootstrapping.jl:11-23 builds this for
 //                          the constant -1/8 table only); for the many-table form btilde and the mask words go onto a coarser grid
-//   lut_extract_kernel     the many-table form behind the rotation: the nout copies X^-v * acc, v < nout, the key switch reads
-//   ks_at_table_kernel     the bootstrap at a coefficient list: which accumulator and which coefficient every output row of the key switch reads
+//   lut_extract_kernel     the many-table form's extraction as a unit call (mkt_lut_extract_batch): the nout copies X^-v * acc, v < nout; no
+//                          bootstrap runs it -- with the plain key switch it is the composition the many-table bootstrap is tested against
+//   ks_at_table_kernel     every bootstrap with more than one output per input (many-table, coefficient list): which accumulator and which
+//                          coefficient every output row of the key switch reads
 //   lut_linear_kernel      the gather front end of a circuit level: a weighted sum of up to four pool rows plus a constant on the b word
 // Neither does floating point.
 #include "kernel_common.h"
@@ -91,12 +93,14 @@ __global__ void __launch_bounds__(256) lut_extract_kernel(const WORD *__restrict
 }
 
 // The rows of a key switch at a coefficient (device_api.h KsArgs::src / ::coef) for ncoef outputs per rotated accumulator: output row
-// g = j * ncoef + i reads accumulator j at coef[i].  The list is the caller's, as it is (the key switch reads it mod N)
+// g = j * ncoef + i reads accumulator j at coef[i].  The list is the caller's, as it is (the key switch reads it mod N); coef NULL = the list
+// 0 .. ncoef - 1, the many-table bootstrap's
 __global__ void __launch_bounds__(256) ks_at_table_kernel(const uint32_t *__restrict__ coef, uint32_t ncoef, uint32_t *__restrict__ src, uint32_t *__restrict__ coef_rows, size_t rows) {
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < rows; g += (size_t)gridDim.x * blockDim.x) {
         const size_t j = g / ncoef;
         src[g] = (uint32_t)j;
-        coef_rows[g] = coef[g - j * ncoef];
+        const size_t i = g - j * ncoef;
+        coef_rows[g] = coef ? coef[i] : (uint32_t)i;
     }
 }
 

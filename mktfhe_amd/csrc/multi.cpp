@@ -171,6 +171,28 @@ int sharded_call(mkt_multi *m, size_t B, int mem, const std::vector<ArgSpec> &sp
     });
 }
 
+// the lookup-table bootstraps, sharded by input: the batch (lwe, out, sel) is cut as everywhere, out at `per` rows per input; every shard
+// reads the WHOLE of luts and of coef ([per], or nullptr: the call has none) -- in place where it can (host memory, or its own device),
+// through its staging buffer otherwise.  Every shard's own call checks its arguments before it writes; what no shard could take (`refused`:
+// the wrapper's verdict on its counts, empty = fine; in host memory any selector outside the tables) is refused here, before any shard starts
+using LutShardCall = std::function<int(mkt_ctx *, const void *luts, const uint32_t *sel, const uint32_t *lwe, const uint32_t *coef, uint32_t *out, size_t nb)>;
+int sharded_lut(mkt_multi *m, const std::string &who, const std::string &refused, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, size_t per,
+                const uint32_t *coef, uint32_t *out, size_t B, int mem, const LutShardCall &call) {
+    if (!nluts) return mfail(m, MKT_ERR_ARG, who + ": no lookup table");
+    if (!refused.empty()) return mfail(m, MKT_ERR_ARG, who + ": " + refused);
+    if (sel && mem == MKT_MEM_HOST && !mkt::host_below(sel, B, nluts)) return mfail(m, MKT_ERR_ARG, who + ": table selector outside the tables");
+    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);   // one table: N ring words
+    if (per > 1 && mkt::ranges_overlap(lwe, B * rb, out, B * per * rb)) return mfail(m, MKT_ERR_ARG, who + ": out overlaps lwe (" + (coef ? "ncoef" : "nout") + " > 1)");
+    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb * per, false, true}};
+    const int icoef = coef ? (int)specs.size() : -1;
+    if (coef) specs.push_back({coef, 4, true, false, per});
+    const int isel = sel ? (int)specs.size() : -1;
+    if (sel) specs.push_back({sel, 4, true, false});
+    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
+        return call(c, a[0], sel ? (const uint32_t *)a[isel] : nullptr, (const uint32_t *)a[1], coef ? (const uint32_t *)a[icoef] : nullptr, (uint32_t *)a[2], nb);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -289,61 +311,29 @@ int mkt_multi_bootstrap_batch(mkt_multi *m, uint32_t *lwe, size_t B, int mem) {
     return sharded_call(m, B, mem, {{lwe, rb, true, true}}, [&](mkt_ctx *c, void **a, size_t nb) { return mkt_bootstrap_batch(c, (uint32_t *)a[0], nb, mem); });
 }
 
-// the programmable bootstrap, sharded: the batch (lwe, out, sel) is cut as everywhere, every shard reads the WHOLE of luts -- in place
-// where it can (host memory, or its own device), through its staging buffer otherwise
+// the three lookup-table bootstraps over sharded_lut: out is cut at 1, nout or ncoef rows per input
 int mkt_multi_lut_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, uint32_t *out, size_t B, int mem) {
     if (!m || !luts || !lwe || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
-    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_batch: no lookup table");
-    if (sel && mem == MKT_MEM_HOST) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_batch: table selector outside the tables");   // before any shard writes
-    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);   // one table: N ring words
-    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb, false, true}};
-    if (sel) specs.push_back({sel, 4, true, false});
-    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
-        return mkt_lut_bootstrap_batch(c, a[0], nluts, sel ? (const uint32_t *)a[3] : nullptr, (const uint32_t *)a[1], (uint32_t *)a[2], nb, mem);
-    });
+    return sharded_lut(m, "mkt_multi_lut_bootstrap_batch", "", luts, nluts, sel, lwe, 1, nullptr, out, B, mem,
+                       [&](mkt_ctx *c, const void *l, const uint32_t *s, const uint32_t *x, const uint32_t *, uint32_t *o, size_t nb) { return mkt_lut_bootstrap_batch(c, l, nluts, s, x, o, nb, mem); });
 }
 
-// the many-table bootstrap, sharded as mkt_multi_lut_bootstrap_batch: out is cut at nout rows per input.  nout is checked by every shard's
-// own call before it writes; the count that no shard could take is refused here, before any shard starts
 int mkt_multi_lut_many_bootstrap_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nout, uint32_t *out, size_t B, int mem) {
     if (!m || !luts || !lwe || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
-    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: no lookup table");
-    if ((nout != 1 && nout != 2 && nout != 4 && nout != 8) || nout > m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: nout = " + std::to_string(nout) + ", expected 1, 2, 4 or 8 and at most N");
-    if (sel && mem == MKT_MEM_HOST) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: table selector outside the tables");   // before any shard writes
-    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);
-    if (nout > 1 && B) {
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(lwe), b0 = reinterpret_cast<uintptr_t>(out);
-        if (a0 < b0 + B * nout * rb && b0 < a0 + B * rb) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_many_bootstrap_batch: out overlaps lwe (nout > 1)");
-    }
-    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb * (size_t)nout, false, true}};
-    if (sel) specs.push_back({sel, 4, true, false});
-    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
-        return mkt_lut_many_bootstrap_batch(c, a[0], nluts, sel ? (const uint32_t *)a[3] : nullptr, (const uint32_t *)a[1], nout, (uint32_t *)a[2], nb, mem);
-    });
+    const std::string refused = mkt::lut_nout_ok(nout, m->p.N) ? "" : "nout = " + std::to_string(nout) + ", expected 1, 2, 4 or 8 and at most N";
+    return sharded_lut(m, "mkt_multi_lut_many_bootstrap_batch", refused, luts, nluts, sel, lwe, (size_t)nout, nullptr, out, B, mem,
+                       [&](mkt_ctx *c, const void *l, const uint32_t *s, const uint32_t *x, const uint32_t *, uint32_t *o, size_t nb) { return mkt_lut_many_bootstrap_batch(c, l, nluts, s, x, nout, o, nb, mem); });
 }
 
-// the bootstrap at a coefficient list, sharded by input: out is cut at ncoef rows per input, coef travels whole to every shard as luts does.
-// What no shard could take (and, in host memory, any index outside its range) is refused here, before any shard starts
 int mkt_multi_lut_bootstrap_at_batch(mkt_multi *m, const void *luts, size_t nluts, const uint32_t *sel, const uint32_t *lwe, int nu, const uint32_t *coef, size_t ncoef,
                                      uint32_t *out, size_t B, int mem) {
     if (!m || !luts || !lwe || !coef || !out) return mfail(m, MKT_ERR_ARG, "bad argument");
-    if (!nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: no lookup table");
-    if (nu < 0 || nu > 3 || (1 << nu) > m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N");
-    if (ncoef < 1 || ncoef > (size_t)m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: " + std::to_string(ncoef) + " coefficients, expected 1 .. N");
-    if (mem == MKT_MEM_HOST) {
-        for (size_t i = 0; i < ncoef; i++) if (coef[i] >= (uint32_t)m->p.N) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: a coefficient is not below N");
-        if (sel) for (size_t j = 0; j < B; j++) if (sel[j] >= nluts) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: table selector outside the tables");
-    }
-    const size_t rb = mkt_internal_lwe_len(m->ctx[0]) * 4, tb = (size_t)m->p.N * (size_t)(m->p.W / 8);
-    if (ncoef > 1 && B) {
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(lwe), b0 = reinterpret_cast<uintptr_t>(out);
-        if (a0 < b0 + B * ncoef * rb && b0 < a0 + B * rb) return mfail(m, MKT_ERR_ARG, "mkt_multi_lut_bootstrap_at_batch: out overlaps lwe (ncoef > 1)");
-    }
-    std::vector<ArgSpec> specs = {{luts, tb, true, false, nluts}, {lwe, rb, true, false}, {out, rb * ncoef, false, true}, {coef, 4, true, false, ncoef}};
-    if (sel) specs.push_back({sel, 4, true, false});
-    return sharded_call(m, B, mem, specs, [&](mkt_ctx *c, void **a, size_t nb) {
-        return mkt_lut_bootstrap_at_batch(c, a[0], nluts, sel ? (const uint32_t *)a[4] : nullptr, (const uint32_t *)a[1], nu, (const uint32_t *)a[3], ncoef, (uint32_t *)a[2], nb, mem);
-    });
+    const int N = m->p.N;
+    const std::string refused = !mkt::lut_nu_ok(nu, N) ? "nu = " + std::to_string(nu) + ", expected 0 .. 3 with 2^nu at most N"
+                              : !mkt::lut_ncoef_ok(ncoef, N) ? std::to_string(ncoef) + " coefficients, expected 1 .. N"
+                              : mem == MKT_MEM_HOST && !mkt::host_below(coef, ncoef, (size_t)N) ? "a coefficient is not below N" : "";
+    return sharded_lut(m, "mkt_multi_lut_bootstrap_at_batch", refused, luts, nluts, sel, lwe, ncoef, coef, out, B, mem,
+                       [&](mkt_ctx *c, const void *l, const uint32_t *s, const uint32_t *x, const uint32_t *cf, uint32_t *o, size_t nb) { return mkt_lut_bootstrap_at_batch(c, l, nluts, s, x, nu, cf, ncoef, o, nb, mem); });
 }
 
 int mkt_multi_not_batch(mkt_multi *m, uint32_t *x, size_t B, int mem) {

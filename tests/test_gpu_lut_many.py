@@ -1,7 +1,10 @@
 """Many-table bootstrap on the GPU (mktfhe.h "many-table bootstrap", mktfhe_amd/lut.py), word for word (tolerance 0) unless a
 test says otherwise: the coarse switch and table step and the extraction against their numpy restatements (tests/ref_lut_many.py), the
 whole call against the unit calls composed and against the CPU checker's chain, every scheme and both arithmetic modes, forced kernels,
-the chunk boundary, the gather front end, logical shards, recipe (a) and the argument edges."""
+the chunk boundary, the gather front end, logical shards, recipe (a), the argument edges, and the context's (row, coefficient) table across
+calls and forks.  The bootstrap makes no copies E_v(acc): the composition of the unit calls (lut_many_testvector, blindrotate_, lut_extract,
+the plain keyswitch) is its independent check -- test_small_sets_equal_the_composed_calls_and_the_checker reaches o = 2, 4, 8 on the 32-bit
+ring (SMALL[0], [1], [2]) and on the 64-bit ring (SMALL[3], [4], [5]), where E_v negates the wrapped words before the truncation."""
 import threading
 
 import numpy as np
@@ -329,7 +332,7 @@ def test_empty_invalid_count_overlap_and_forks(require_gpu):
     assert np.array_equal(_host(buf[:B], np.uint32), c) and not _host(buf[B:], np.uint32).any()
     mk.lut_many_bootstrap(sg, dU, buf[:B], o, dsel, out=buf[B:])               # adjacent, not overlapping: served
     assert np.array_equal(_host(buf[B:], np.uint32).reshape(want.shape), want)
-    # a fork runs the call while its parent does: each holds its own buffer of extracted accumulators
+    # a fork runs the call while its parent does: each holds its own workspace
     f = sg.fork()
     got = {}
 
@@ -343,3 +346,81 @@ def test_empty_invalid_count_overlap_and_forks(require_gpu):
         t.join()
     assert all(np.array_equal(w, want) for name in ("parent", "fork") for w in got[name]) and len(got) == 2
     f.close(); sg.close()
+
+
+# ---- 11: one (row, coefficient) table per context, shared with the bootstrap at a coefficient list ----
+TABLE_SETS = [mk.CGGIparam.scaled(n=8, N=64), mk.KMS2party.scaled(n=16, N=256)]
+
+
+def _table_case(p):
+    """-> (crs, keys, the named calls of one context in the order the tests make them); B = 3 host inputs"""
+    crs, keys = _keys(p)
+    rng = np.random.default_rng(71)
+    c = _inputs(p, keys, 3, rng)
+    T = _tables(p, 2, rng)
+    U = {o: _packed(p, 2, o, rng)[1] for o in (2, 4, 8)}
+    sel = np.array([1, 0, 1], dtype=np.uint32)
+    coef11 = np.array([p.N - 1, 0, 17, 5, 40, 1, p.N - 2, 33, 8, 21, 2], dtype=np.uint32)       # unsorted, both ends of the polynomial
+    coef3 = np.array([9, p.N - 1, 4], dtype=np.uint32)
+    calls = {"at, 11 coefficients": lambda s: mk.lut_bootstrap_at(s, T, c, coef11, 0, sel),
+             "many, o = 2": lambda s: mk.lut_many_bootstrap(s, U[2], c, 2, sel),
+             "at, 3 coefficients": lambda s: mk.lut_bootstrap_at(s, T, c, coef3, 2, sel),
+             "many, o = 8": lambda s: mk.lut_many_bootstrap(s, U[8], c, 8, sel),
+             "one table": lambda s: mk.lut_bootstrap(s, T, c, sel),
+             "many, o = 1": lambda s: mk.lut_many_bootstrap(s, T, c, 1, sel),
+             "many, o = 4": lambda s: mk.lut_many_bootstrap(s, U[4], c, 4, sel)}
+    return crs, keys, calls
+
+
+def _fresh(p, crs, keys, call):
+    """the call on a context that has made no other"""
+    s = gpu_scheme(p, crs, keys)
+    out = call(s)
+    s.close()
+    return out
+
+
+@pytest.mark.parametrize("p", TABLE_SETS, ids=_sid)
+def test_shared_table_holds_no_stale_rows(require_gpu, p):
+    """the many-table bootstrap and the bootstrap at a coefficient list write the same table of the context: one left from a longer list, or
+    laid out for another count per input, must not reach the next call.  Every call equals itself on a freshly created context"""
+    crs, keys, calls = _table_case(p)
+    sg = gpu_scheme(p, crs, keys)
+    for name in ("at, 11 coefficients", "many, o = 2", "at, 3 coefficients", "many, o = 8", "one table"):
+        got = calls[name](sg)
+        assert np.array_equal(got, _fresh(p, crs, keys, calls[name])), (name, _sid(p))
+    sg.close()
+
+
+@pytest.mark.parametrize("p", TABLE_SETS, ids=_sid)
+def test_one_table_takes_no_table_and_leaves_the_context_usable(require_gpu, p):
+    """nout = 1 is the plain key switch (no coefficient table) beside nout > 1 (through the table), in either order on one context"""
+    crs, keys, calls = _table_case(p)
+    sg = gpu_scheme(p, crs, keys)
+    one, four = calls["one table"](sg), _fresh(p, crs, keys, calls["many, o = 4"])
+    for name, want in (("many, o = 1", one[:, None]), ("many, o = 4", four), ("many, o = 1", one[:, None])):
+        assert np.array_equal(calls[name](sg), want), (name, _sid(p))
+    sg.close()
+
+
+@pytest.mark.parametrize("p", TABLE_SETS, ids=_sid)
+def test_forks_hold_their_own_table(require_gpu, p):
+    """two forks run o = 2 and o = 8 at once, each on its own stream: the parent's words"""
+    crs, keys, calls = _table_case(p)
+    sg = gpu_scheme(p, crs, keys)
+    want = {name: calls[name](sg) for name in ("many, o = 2", "many, o = 8")}
+    forks = {name: sg.fork() for name in want}
+    got = {}
+
+    def run(name):
+        got[name] = [calls[name](forks[name]) for _ in range(3)]
+
+    threads = [threading.Thread(target=run, args=(name,)) for name in want]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert len(got) == 2 and all(np.array_equal(w, want[name]) for name in want for w in got[name])
+    for f in forks.values():
+        f.close()
+    sg.close()
