@@ -495,6 +495,49 @@ int mkt_client_merge_decrypt(const mkt_params *params, const uint32_t *lwe, cons
 int mkt_partial_decrypt_batch(mkt_ctx *ctx, int party, const mkt_client_party *keys, const uint32_t *lwe, double sigma_smudge, const uint8_t *seed,
                               uint64_t row0, uint32_t *share_out, size_t B, int mem);
 
+/* ---- seeded ciphertexts: a fresh ciphertext of party i is (k-1) n zero words, n uniform mask words that say nothing about the message, and
+ *      one body word.  A party therefore sends a PUBLIC 256-bit mask seed and one body word per ciphertext, and whoever holds the seed
+ *      regenerates the rows -- on the evaluator's GPU, where they are needed.  A SEEDED BATCH of party i is (mask_seed[32], row0, i,
+ *      body[B]); row0 is the index of its first row in a larger logical batch, as for a decryption share above.
+ *      LAYOUT.  Unchanged: an expanded row is an ordinary ciphertext [a_0 .. a_{nparty-1}, b] that every call of this header accepts.
+ *      MASK.  Word q < n of row j is 32-bit word (q & 15) of chacha20_block(key(mask_seed), q >> 4, nonce), nonce the one of
+ *      Rng(key, i, 10, lo32(row0 + j), hi32(row0 + j)): stream id 10, one stream per row, RFC 8439 block function with the block counter
+ *      starting at 0.  Every keystream word is used (the 64-bit draws of the other streams keep one word in two); the surplus words of a
+ *      row's last block are dropped.  key(seed) = the 32 bytes as eight little-endian words, as for every seed of this header.
+ *      NOISE.  e[j] = (uint32_t) Rng(key(noise_seed), i, 11, lo32(row0 + j), hi32(row0 + j)).noise(sigma_lwe): stream id 11, the first
+ *      Gaussian draw of the row's stream, rounded.  noise_seed is SECRET; NULL -- what a caller should pass -- is fresh OS entropy per call.
+ *      BODY.  body[j] = e[j] - sum_q a[j][q] * s_i[q] + mu[j]  (mod 2^32): wrapping uint32_t arithmetic, the key word multiplied (not
+ *      assumed binary), as mkt_client_lwe_encrypt_word does.  mu is any word of the 32-bit torus; a bit is mu = +-2^29.
+ *      EXPANSION.  Row j is all zeros except block i, which holds the mask, and the last word, which holds body[j]; so
+ *      mkt_client_lwe_phase(expand(...)) == mu + e word for word.  Expansion needs no key.
+ *      REFUSALS (MKT_ERR_ARG, no word written): mask_seed NULL; noise_seed given and bytewise equal to mask_seed (publishing the one would
+ *      publish the noise); party out of range; keys made for other parameters or another party index; sigma_lwe not finite, negative or
+ *      above 2^31; an unknown `mem`.  B == 0 succeeds and writes nothing.
+ *      A (mask_seed, party, row index) MUST NEVER SERVE TWO ENCRYPTIONS: the two rows then share their mask, and the difference of the two
+ *      bodies is the difference of the messages plus two noise words.  Draw a fresh mask seed (mkt_client_random_seed) per batch, or
+ *      continue one batch under its seed with row0.
+ *      mkt_client_lwe_encrypt(_word) and its stream 7 are unchanged; their rows cannot be compressed this way. ---- */
+/* mu [B] -> body_out [B]; keys = party `party`'s keys, made for these parameters and that party index */
+int mkt_client_seeded_encrypt(const mkt_params *params, const mkt_client_party *keys, int party, const uint32_t *mu, double sigma_lwe,
+                              const uint8_t *mask_seed, const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B);
+/* body [B] -> out [B][k*n+1] */
+int mkt_client_seeded_expand(const mkt_params *params, int party, const uint8_t *mask_seed, uint64_t row0, const uint32_t *body, uint32_t *out,
+                             size_t B);
+/* the evaluator's call: the rows of mkt_client_seeded_expand written on the GPU of `ctx`, word for word.  body and out live in `mem`
+ * (MKT_MEM_DEVICE / MKT_MEM_HOST); the call runs on the context's stream and needs NO evaluation key loaded (a context made by
+ * mkt_ctx_create alone serves).  It reads B words and writes B * (k*n+1); nothing it touches is secret. */
+int mkt_seeded_expand_batch(mkt_ctx *ctx, int party, const uint8_t *mask_seed, uint64_t row0, const uint32_t *body, uint32_t *out, size_t B, int mem);
+/* the party's call on its OWN GPU: the words of mkt_client_seeded_encrypt for the same seeds and row0.  mu and body_out live in `mem`; the
+ * call runs on the context's stream, needs no evaluation key and returns once the bodies are written and the key copy is wiped.  The mask
+ * words are never written to device memory.
+ * TRUST: as mkt_partial_decrypt_batch, this call hands party `party`'s SECRET LWE key and the noise seed to the GPU of this context.  It is
+ * a party-local operation; an evaluator context that runs it for every party holds all k secrets -- acceptable only in tests and
+ * benchmarks.  The n key words are uploaded per call and zeroed on the device before they are freed, and the host-side copy of the noise
+ * stream key is wiped; the copy of that key carried in the kernel-argument segment of the launch lives in runtime-owned memory the
+ * library cannot erase (it is overwritten by later launches). */
+int mkt_seeded_encrypt_batch(mkt_ctx *ctx, int party, const mkt_client_party *keys, const uint32_t *mu, double sigma_lwe, const uint8_t *mask_seed,
+                             const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B, int mem);
+
 #ifdef __cplusplus
 }
 #endif

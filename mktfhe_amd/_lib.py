@@ -129,6 +129,10 @@ SYMBOLS = {
     "mkt_client_merge_phase": (_i, [_pp, _vp, _vp, _i, _vp, _sz]),
     "mkt_client_merge_decrypt": (_i, [_pp, _vp, _vp, _i, _vp, _sz]),
     "mkt_partial_decrypt_batch": (_i, [_vp, _i, _vp, _vp, _dbl, _vp, _u64, _vp, _sz, _i]),
+    "mkt_client_seeded_encrypt": (_i, [_pp, _vp, _i, _vp, _dbl, _vp, _vp, _u64, _vp, _sz]),
+    "mkt_client_seeded_expand": (_i, [_pp, _i, _vp, _u64, _vp, _vp, _sz]),
+    "mkt_seeded_expand_batch": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _sz, _i]),
+    "mkt_seeded_encrypt_batch": (_i, [_vp, _i, _vp, _vp, _dbl, _vp, _vp, _u64, _vp, _sz, _i]),
 }
 
 _lib = None

@@ -456,4 +456,54 @@ int mkt_client_merge_decrypt(const mkt_params *params, const uint32_t *lwe, cons
     return MKT_OK;
 }
 
+// ---- seeded ciphertexts (mktfhe.h): a public mask seed and one body word per row; these two functions are the definition ----
+
+// body[j] = e[j] - <a[j], s> + mu[j], a[j] the n mask words of row row0 + j (rng_chacha.h mask_block), e[j] its noise word on stream 11
+int mkt_client_seeded_encrypt(const mkt_params *params, const mkt_client_party *K, int party, const uint32_t *mu, double sigma_lwe,
+                              const uint8_t *mask_seed, const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B) {
+    if (!params || !K || !mask_seed || !smudge_sigma_ok(sigma_lwe)) return MKT_ERR_ARG;
+    if (noise_seed && std::memcmp(noise_seed, mask_seed, 32) == 0) return MKT_ERR_ARG;    // the mask seed is published: the noise would be too
+    const mkt_params &p = *params;
+    Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
+    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return MKT_ERR_ARG;   // as mkt_client_partial_decrypt
+    if (!B) return MKT_OK;
+    if (!mu || !body_out) return MKT_ERR_ARG;
+    uint32_t mkey[8], nkey[8];
+    seed_to_key(mask_seed, mkey);
+    if (seed_to_key(noise_seed, nkey)) return MKT_ERR_STATE;
+    for (size_t j = 0; j < B; j++) {
+        uint32_t dot = 0, a[16];
+        for (int q0 = 0; q0 < p.n; q0 += 16) {
+            mktrng::mask_block(mkey, (uint32_t)party, row0 + j, (uint32_t)(q0 >> 4), a);
+            for (int i = 0; i < 16 && q0 + i < p.n; i++) dot += a[i] * K->lwekey[q0 + i];
+        }
+        body_out[j] = mktrng::row_noise_word(nkey, (uint32_t)party, mktrng::STREAM_ENC_NOISE, row0 + j, sigma_lwe) + (0u - dot + mu[j]);
+    }
+    explicit_bzero(nkey, sizeof nkey);
+    return MKT_OK;
+}
+
+// row j = zeros, the mask of row row0 + j in block `party`, body[j] last: an ordinary ciphertext; needs no key
+int mkt_client_seeded_expand(const mkt_params *params, int party, const uint8_t *mask_seed, uint64_t row0, const uint32_t *body, uint32_t *out, size_t B) {
+    if (!params || !mask_seed) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    Shape sh = shape_of(p);
+    if (p.n < 1 || party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
+    if (!B) return MKT_OK;
+    if (!body || !out) return MKT_ERR_ARG;
+    uint32_t mkey[8];
+    seed_to_key(mask_seed, mkey);
+    for (size_t j = 0; j < B; j++) {
+        uint32_t *row = out + j * (size_t)sh.lwe_len, a[16];
+        std::memset(row, 0, sizeof(uint32_t) * (size_t)sh.lwe_len);
+        for (int q0 = 0; q0 < p.n; q0 += 16) {
+            mktrng::mask_block(mkey, (uint32_t)party, row0 + j, (uint32_t)(q0 >> 4), a);
+            for (int i = 0; i < 16 && q0 + i < p.n; i++) row[(size_t)party * p.n + q0 + i] = a[i];
+        }
+        row[sh.lwe_len - 1] = body[j];
+    }
+    return MKT_OK;
+}
+
 }  // extern "C"

@@ -1075,6 +1075,58 @@ int mkt_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, 
     return so.out(share_out);
 }
 
+// Seeded ciphertexts (mktfhe.h): the evaluator's call -- a public seed and B body words in, B ordinary rows out.  No key of any kind.
+int mkt_seeded_expand_batch(mkt_ctx *c, int party, const uint8_t *mask_seed, uint64_t row0, const uint32_t *body, uint32_t *out, size_t B, int mem) {
+    if (!c || !mask_seed || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!B) return MKT_OK;
+    if (!body || !out) return fail(c, MKT_ERR_ARG, "bad argument");
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    Staged sb{c}, so{c};
+    int r;
+    if ((r = sb.in(body, B * 4, mem, true)) || (r = so.in(out, B * (size_t)c->sh.lwe_len * 4, mem, false))) return r;
+    mktd::SeededArgs a{};
+    mkt::seed_to_key(mask_seed, a.mkey);
+    a.party = party; a.n = c->p.n; a.lwe_len = c->sh.lwe_len; a.row0 = row0;
+    a.in = (const uint32_t *)sb.dev; a.out = (uint32_t *)so.dev; a.B = B;
+    HIPCHK(c, mktd::launch_seeded_expand(a, c->stream));
+    return so.out(out);
+}
+
+// the party's call, party-local like mkt_partial_decrypt_batch: the n key words are uploaded for the call and wiped before they are freed
+int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const uint32_t *mu, double sigma_lwe, const uint8_t *mask_seed,
+                             const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B, int mem) {
+    if (!c || !K || !mask_seed || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::smudge_sigma_ok(sigma_lwe)) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: sigma_lwe must be finite, 0 <= sigma_lwe <= 2^31");
+    if (noise_seed && std::memcmp(noise_seed, mask_seed, 32) == 0) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the noise seed is the public mask seed");
+    const mkt_params &p = c->p;
+    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the party's keys were made for other parameters / another party index");
+    if (!B) return MKT_OK;
+    if (!mu || !body_out) return fail(c, MKT_ERR_ARG, "bad argument");
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    Staged sx{c}, so{c};
+    int r;
+    if ((r = sx.in(mu, B * 4, mem, true)) || (r = so.in(body_out, B * 4, mem, false))) return r;
+    mktd::SeededArgs a{};
+    mkt::seed_to_key(mask_seed, a.mkey);
+    if (mkt::seed_to_key(noise_seed, a.nkey)) return fail(c, MKT_ERR_STATE, "mkt_seeded_encrypt_batch: no entropy from the OS");
+    uint32_t *d_key = nullptr;
+    hipError_t e = hipMalloc((void **)&d_key, (size_t)p.n * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_key, K->lwekey.data(), (size_t)p.n * 4, hipMemcpyHostToDevice, c->stream);
+    a.party = party; a.n = p.n; a.lwe_len = c->sh.lwe_len; a.sigma = sigma_lwe; a.row0 = row0;
+    a.in = (const uint32_t *)sx.dev; a.lwekey = d_key; a.out = (uint32_t *)so.dev; a.B = B;
+    if (e == hipSuccess) e = mktd::launch_seeded_encrypt(a, c->stream);
+    // the secret is wiped on the device before its buffer is released
+    if (d_key) (void)hipMemsetAsync(d_key, 0, (size_t)p.n * 4, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_key);
+    explicit_bzero(&a, sizeof a);            // the host copy of the noise stream key (the kernel-argument copy: see the TRUST note in mktfhe.h)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hipfail(c, e, "device seeded encryption");
+    return so.out(body_out);
+}
+
 // debug / test read-back of a party's key-switching key in the host layout of mkt_load_ksk
 int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
     if (!c || !out_host || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");

@@ -141,6 +141,30 @@ struct PartialDecryptArgs {
 };
 hipError_t launch_partial_decrypt(const PartialDecryptArgs &a, hipStream_t s);
 
+// Seeded ciphertexts on the device (seeded.hip; mktfhe.h "seeded ciphertexts"), the words of mkt_client_seeded_expand / _encrypt:
+// expand:  out[j] = zeros, mask_block words of row row0 + j in block `party`, in[j] last     (in = body [B], out [B][lwe_len], dense)
+// encrypt: out[j] = row_noise_word(nkey, party, 11, row0 + j, sigma) - <mask of row row0 + j, lwekey> + in[j]     (in = mu [B], out = body [B])
+struct SeededArgs {
+    uint32_t mkey[8];            // ChaCha20 key of the mask streams: the PUBLIC mask seed
+    uint32_t nkey[8];            // encrypt: key of the noise streams (secret)
+    int party, n, lwe_len;
+    int tile_words;              // expand: words of the output span per tile (set by the launcher)
+    int width;                   // encrypt: lanes that share a row's keystream blocks, a power of two in 4 .. 64 (set by the launcher)
+    double sigma;                // encrypt
+    uint64_t row0;
+    const uint32_t *lwekey;      // encrypt: [n]
+    const uint32_t *in;          // [B]
+    uint32_t *out;
+    size_t B;
+};
+hipError_t launch_seeded_expand(SeededArgs a, hipStream_t s);
+hipError_t launch_seeded_encrypt(SeededArgs a, hipStream_t s);
+// workgroups of one launch of either kernel, more tiles than that run grid-stride; rows per tile of the encrypt kernel; the words per tile
+// the expand launcher picks for a shape (what the tests size their grid-stride case by)
+constexpr unsigned SEEDED_MAX_GRID = 2048;
+constexpr int SEEDED_ENC_TILE = 64;
+int seeded_expand_tile_words(int n, int lwe_len);
+
 hipError_t launch_transform_fwd(int logM, int W, TwPtrs tw, const void *p, cplx *t, size_t B, int dev_order, hipStream_t s);
 hipError_t launch_reorder(int logM, const cplx *in, cplx *out, size_t npolys, int to_device, int order, hipStream_t s);
 hipError_t launch_transform_inv(int logM, int W, TwPtrs tw, const cplx *t, void *p, size_t B, hipStream_t s);

@@ -132,10 +132,24 @@ struct Rng {
 // 9: the smudging noise of a decryption share (mktfhe.h "distributed decryption"): one stream per batch row, the 64-bit row index in the
 // two index words of the nonce.
 constexpr uint32_t STREAM_SMUDGE = 9;
-// e of row `row` for party `party`: the first noise draw of that row's stream, on the 32-bit torus (client.cpp and partial_decrypt.hip)
-MKT_HD uint32_t smudge_word(const uint32_t key[8], uint32_t party, uint64_t row, double sigma) {
-    Rng r(key, party, STREAM_SMUDGE, (uint32_t)row, (uint32_t)(row >> 32));
+// 10, 11: the mask and the noise of a seeded ciphertext (mktfhe.h "seeded ciphertexts"), one stream per batch row like 9.  10 is keyed by the
+// PUBLIC mask seed and read as 32-bit words, every keystream word used (mask_block); 11 is keyed by the secret noise seed.
+constexpr uint32_t STREAM_ENC_MASK = 10;
+constexpr uint32_t STREAM_ENC_NOISE = 11;
+// the noise word of row `row` on stream `stream` for party `party`: the first noise draw of that row's stream, on the 32-bit torus
+MKT_HD uint32_t row_noise_word(const uint32_t key[8], uint32_t party, uint32_t stream, uint64_t row, double sigma) {
+    Rng r(key, party, stream, (uint32_t)row, (uint32_t)(row >> 32));
     return (uint32_t)r.noise(sigma);
+}
+// e of row `row` for party `party` (client.cpp and partial_decrypt.hip)
+MKT_HD uint32_t smudge_word(const uint32_t key[8], uint32_t party, uint64_t row, double sigma) {
+    return row_noise_word(key, party, STREAM_SMUDGE, row, sigma);
+}
+// mask words 16 blk .. 16 blk + 15 of row `row` of party `party`'s seeded batch: keystream block `blk` of the row's stream, whole
+// (client.cpp and seeded.hip; a row uses the first n words of its blocks and drops the rest of the last one)
+MKT_HD void mask_block(const uint32_t key[8], uint32_t party, uint64_t row, uint32_t blk, uint32_t out[16]) {
+    const uint32_t nonce[3] = {STREAM_ENC_MASK | (party << 16), (uint32_t)row, (uint32_t)(row >> 32)};
+    chacha20_block(key, blk, nonce, out);
 }
 
 }  // namespace mktrng
