@@ -87,6 +87,23 @@ KS_CHILD_SETS = [mk.CGGIparam.scaled(n=20, N=256), mk.KMS2party.scaled(n=12, N=2
                  mk.Blockparam.scaled(n=30, N=256, blk_d=10), mk.KMS2partyblock.scaled(n=24, N=256, blk_d=8),
                  mk.CGGIparam.scaled(n=20, N=256, f=5, logD=3)]
 
+# key switch at a coefficient (keyswitch_pair_kernel, ks_digits_kernel, keyswitch_mg_kernel, ks_init_kernel / ks_reduce_kernel with AT = true,
+# extract_word_at; tests/test_gpu_keyswitch_at.py runs the launcher switches in child processes): the same sets, the accumulators rotated
+# by X^v so that the extraction at v meets the same words.  The four full-length sets: one batch of 33 over v in {0, 1, N - 1}
+KS_AT_SETS = KS_SETS
+KS_AT_FULL = KS_SETS[:4]
+KS_AT_FULL_BATCHES = (33,)
+
+
+def KS_AT_COEFS(p):
+    """the sign boundary j = v at both ends, the first and last word, the block schemes' copy / switch border n, the middle"""
+    return sorted({v for v in (0, 1, p.n - 1, p.n, p.n + 1, p.N // 2, p.N - 1) if 0 <= v < p.N})
+
+
+def KS_AT_FULL_COEFS(p):
+    return [0, 1, p.N - 1]
+
+
 # whole bootstraps on crafted rows: one representative set per kernel (the fused mod switch / test vector is per kernel)
 BOOT_CASES = [
     (_CG, {"rot_wide": 1}, "blindrotate_k1_kernel"),
@@ -104,11 +121,21 @@ GATE_CASES = BOOT_CASES
 GATE_SETS = [_CG, _BL3, _CC2, _K2, _KB]          # one per scheme: the oracle-only identities of tests/test_edges_cpu.py
 EXACT_BOOT_CASES = [c[:3] for c in EXACT_CASES]
 
+# the one lookup-table route (context.cpp lut_chunk: lut_testvector_kernel with its own mod switch -- nu = 0 the plain one, nu > 0 the coarse
+# switch whose words the rotation reads pre-switched from ws_lin --, the rotation, ks_at_table_kernel and the key switch at a coefficient)
+# on crafted rows and tables: one line per rotation kernel (and the 64-bit ring's two), then MKT_ARITH_EXACT, one line per kernel.
+# (parameter set, options, kernel, EXACT context)
+LUT_BOOT_CASES = [c + (False,) for c in (BOOT_CASES[0], BOOT_CASES[1], BOOT_CASES[2], BOOT_CASES[3], BOOT_CASES[4], BOOT_CASES[6], BOOT_CASES[8], BOOT_CASES[9],
+                                          BOOT_CASES[10], BOOT_CASES[13])] + \
+                 [EXACT_CASES[i][:3] + (True,) for i in (0, 1, 2, 3, 5, 7, 8, 12, 14)]
+LUT_NOUTS = (2, 4, 8)
+
 
 def all_rotation_sets():
     seen, out = set(), []
-    for p in [c[0] for c in ROT_CASES + EXACT_CASES + BOOT_CASES + GATE_CASES] + EXACT_PAIR_SETS + GATE_SETS:
-        if p not in seen:
-            seen.add(p)
+    for p in [c[0] for c in ROT_CASES + EXACT_CASES + BOOT_CASES + GATE_CASES + LUT_BOOT_CASES] + EXACT_PAIR_SETS + GATE_SETS + KS_AT_SETS:
+        key = p.scaled(f=8, logD=2)          # (the key-switch gadget plays no part in a rotation: such twins would only repeat a case)
+        if key not in seen:
+            seen.add(key)
             out.append(p)
     return out

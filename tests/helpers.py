@@ -145,33 +145,46 @@ def kat_decrypt(p, d, ct):
 BT_TARGETS = ("0", "1", "N-1", "N", "N+1", "2N-1", "2N")
 
 
-def modswitch_words(N):
-    """name -> 32-bit word at a boundary of divbits(w, 32 - logN - 1) (bootstrapping.jl:8-9, arithmetic.jl:23-27)"""
-    s = 32 - (N.bit_length() - 1) - 1
+def _nu(nout):
+    assert nout in (1, 2, 4, 8)
+    return nout.bit_length() - 1
+
+
+def modswitch_words(N, nout=1):
+    """name -> 32-bit word at a boundary of divbits(w, 32 - logN - 1) (bootstrapping.jl:8-9, arithmetic.jl:23-27).  nout = 2^nu > 1: of the
+    coarse switch sw_nu(w) = divbits(w, 32 - logN - 1 + nu) << nu (tests/ref_lut_many.py): read 1, N-1, N+1, 2N-1 in the names as nout,
+    N - nout, N + nout, 2N - nout"""
+    s = 32 - (N.bit_length() - 1) - 1 + _nu(nout)
     h = 1 << (s - 1)
     return {"zero": 0, "max->0": h - 1, "tie->1": h, "->N-1": 2**31 - h - 1, "tie->N": 2**31 - h, "->N": 2**31, "max->N": 2**31 + h - 1,
             "tie->N+1": 2**31 + h, "->2N-1": 2**32 - h - 1, "min->2N": 2**32 - h, "ones->2N": 2**32 - 1}
 
 
-def btilde_words(N):
-    """BT_TARGETS name -> (smallest, largest) 32-bit word that the mod switch rounds to it"""
-    s = 32 - (N.bit_length() - 1) - 1
+def bt_values(N, nout=1):
+    """BT_TARGETS name -> the switched value: 0, nout, N - nout, N, N + nout, 2N - nout, 2N"""
+    return {"0": 0, "1": nout, "N-1": N - nout, "N": N, "N+1": N + nout, "2N-1": 2 * N - nout, "2N": 2 * N}
+
+
+def btilde_words(N, nout=1):
+    """BT_TARGETS name -> (smallest, largest) 32-bit word that the mod switch (nout > 1: the coarse switch sw_nu) rounds to it"""
+    s = 32 - (N.bit_length() - 1) - 1 + _nu(nout)
     T, h = 1 << s, 1 << (s - 1)
-    val = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
-    return {k: (max(v * T - h, 0), min(v * T + h - 1, 2**32 - 1)) for k, v in val.items()}
+    return {k: (max(v // nout * T - h, 0), min(v // nout * T + h - 1, 2**32 - 1)) for k, v in bt_values(N, nout).items()}
 
 
-def lwe_edge_rows(p, rng, even=False):
+def lwe_edge_rows(p, rng, even=False, nout=1):
     """LWE rows (not encryptions) on the boundaries of the mod switch -> (rows uint32 [R][lwe_len], kinds [R]).
     kinds: "zero" mask of zero words; "skip" every mask word non-zero but rounding to 0; "dense" random words with the boundary words
     at the first / last position and on both sides of every block and party border; "blocks" whole blocks (block length, or single
     words) of non-zero words that round to 0 next to blocks of boundary words that do not; "party" (multi-key) one party's block all
     rounding to 0, the others dense.  Every kind meets every btilde of BT_TARGETS, through the smallest or the largest word that
-    rounds to it.  even: bit 0 of every word cleared -- the words a XOR / XNOR linear part 2 (x + y) can take (gate.jl:28-44)."""
+    rounds to it.  even: bit 0 of every word cleared -- the words a XOR / XNOR linear part 2 (x + y) can take (gate.jl:28-44).
+    nout = 2, 4, 8: the same rows on the boundaries of the coarse switch sw_nu of the many-table bootstrap (tests/ref_lut_many.py), the
+    btilde targets 0, nout, N - nout, N, N + nout, 2N - nout, 2N."""
     N, n, nm = p.N, p.n, p.lwe_len - 1
-    s = 32 - (N.bit_length() - 1) - 1
+    s = 32 - (N.bit_length() - 1) - 1 + _nu(nout)
     h = 1 << (s - 1)
-    mw = modswitch_words(N)
+    mw = modswitch_words(N, nout)
     live = [v for k, v in mw.items() if k not in ("zero", "max->0")]           # boundary words that do not round to 0
     L = p.blk_len if p.blk_len > 1 else 1
     borders = {0, nm - 1} | {b for i in range(1, p.nparty) for b in (i * n - 1, i * n)}
@@ -199,7 +212,7 @@ def lwe_edge_rows(p, rng, even=False):
                 for b0 in range(0, nm, L):
                     blk = (b0 // L + ti) % 2
                     row[b0:b0 + L] = skipw(min(L, nm - b0)) if blk else [live[(b0 + j + r) % len(live)] for j in range(min(L, nm - b0))]
-            lo, hi = btilde_words(N)[t]
+            lo, hi = btilde_words(N, nout)[t]
             row[nm] = hi if (ti + len(rows)) % 2 else lo
             rows.append(row)
             kinds.append(kind)
@@ -305,20 +318,25 @@ def extract_words(p, poly):
     return np.concatenate([a[:1], out[:-1]])
 
 
+KS_LOW_HALVES = (0xFFFFFFFF, 0x80000000, 0x7FFFFFFF, 0, 1)          # of a crafted 64-bit accumulator word (ks_edge_acc)
+KS_BORROW_WORDS = ("u-tie", "u-tie-1", "u-carry", "u-carry-1", "b-tie", "b-tie-1")
+
+
 def ks_edge_acc(p, rng, B):
     """accumulators [B][1 + k][N] whose EXTRACTED words sit on the key-switch gadget's boundaries: in every ciphertext and component
     the ks_words at ks_positions (j = 0 is not negated, j = N - 1 reads a[1]; both sides of the copied / switched border), rotated
     from ciphertext to ciphertext, and the whole list from the first switched coefficient on.  64-bit ring: the low half of those
-    words is all ones or the top bit alone -- it is cut off, never rounded into the word"""
+    words is all ones, the top bit alone or all ones below it -- it is cut off, never rounded into the word -- and, in the list, also 0 and 1:
+    where X^v wraps such a word (ks_edge_acc_at) its 64-bit negation borrows from the high half, or does not"""
     N, W, sh = p.N, p.W, p.W - 32
     S = list(ks_words(p.f, p.logD).values())
     acc = rng.integers(0, 2**63, (B, 1 + p.k, N), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (B, 1 + p.k, N), dtype=np.uint64)
     acc &= np.uint64((1 << W) - 1)
 
-    def put(b, c, j, w, t):
+    def put(b, c, j, w, t, lows=KS_LOW_HALVES[:3]):
         v = (w if j == 0 else (-w) & 0xFFFFFFFF) << sh
         if sh:
-            v |= (0xFFFFFFFF, 0x80000000, 0x7FFFFFFF)[t % 3]
+            v |= lows[t % len(lows)]
         acc[b, 1 + c, 0 if j == 0 else N - j] = v
 
     for b in range(B):
@@ -329,10 +347,91 @@ def ks_edge_acc(p, rng, B):
                 for i, w in enumerate(S):
                     j = j0 + 2 + i
                     if j < N - 1:
-                        put(b, c, j, S[(i + b) % len(S)], i + b)
+                        put(b, c, j, S[(i + b) % len(S)], i + b, KS_LOW_HALVES)
             for i, j in enumerate(ks_positions(p, c)):
                 put(b, c, j, S[(i + b + c) % len(S)], i + b)
     return acc
+
+
+def ks_borrow_decides(p, c, j, word64):
+    """64-bit ring: does moving the negation of accumulator word a[N - j] (j >= 1) across the truncation change an output word?  The
+    extracted word is w = -trunc(a); trunc(-a) is w - 1 where a's low half is not 0.  A copied word (j below the border) IS an output;
+    a switched one changes the output where w and w - 1 differ in a digit (w a tie or a carry: w - 1 is the word one below)"""
+    if not int(word64) & 0xFFFFFFFF:
+        return False
+    if j < ks_border(p, c):
+        return True
+    w = (-(int(word64) >> 32)) & 0xFFFFFFFF
+    if p.scheme in (mk.LMSS, mk.KMS_BLOCK):
+        return list(O.decomp_word(w, p.f, p.logD, 32)) != list(O.decomp_word((w - 1) & 0xFFFFFFFF, p.f, p.logD, 32))
+    return list(O.unbalanced_decomp_word(w, p.f, p.logD, 32)) != list(O.unbalanced_decomp_word((w - 1) & 0xFFFFFFFF, p.f, p.logD, 32))
+
+
+def ks_edge_acc_at(p, rng, B, v):
+    """X^v * ks_edge_acc(p, rng, B) on W-bit words: out[i] = a[i - v] for i >= v, -a[N + i - v] mod 2^W otherwise, so that the extraction
+    at coefficient v (ref_lut_many.extract(out, v, W)) is the v = 0 accumulator exactly and every class of ks_edge_acc carries over.
+    64-bit ring: the wrapped words (extracted coefficients 1 <= j <= v) were negated at 64 bits, and the key switch truncates and negates
+    them at 32 bits: its word is trunc(out[v - j]) + (low half != 0).  That + 1 decides a digit only where the truncated word sits one
+    below a tie or a carry, so on each side of j = v (wrapped: 1 <= j <= v, not wrapped: j > v) every ciphertext gets the ks_words
+    u-tie, u-carry, b-tie and the words one below them over a non-zero low half: the list words of those classes that lie there
+    are given one, and the same words are placed at the free positions next to j = v (at position v or v + 1 itself where a side holds
+    nothing else)"""
+    N, W, sh = p.N, p.W, p.W - 32
+    a = ks_edge_acc(p, rng, B)
+    if sh and p.f * p.logD < 32:
+        kw = ks_words(p.f, p.logD)
+        D = [kw[k] for k in KS_BORROW_WORDS]
+        lows = [h for h in KS_LOW_HALVES if h]
+        for b in range(B):
+            for c in range(p.k):
+                j0 = ks_border(p, c)
+                taken = set(ks_positions(p, c)) | set(range(j0 + 2, j0 + 2 + len(kw)))
+                for side in (range(v, 0, -1), range(v + 1, N)):
+                    if not len(side):
+                        continue
+                    for j in side:                                  # list words of these classes: a low half that borrows
+                        x = int(a[b, 1 + c, N - j])
+                        if (-(x >> 32)) & 0xFFFFFFFF in D and not x & 0xFFFFFFFF:
+                            a[b, 1 + c, N - j] = x | lows[(j + b) % len(lows)]
+                    free = [j for j in side if j not in taken and j >= j0][:len(D)] or [j for j in side if j not in taken][:len(D)] or [side[0]]
+                    for i, j in enumerate(free):                    # (a single position: a tie or a carry itself, never the word one below)
+                        w = D[(i + b) % len(D)] if len(free) > 1 else D[2 * (b % 3)]
+                        a[b, 1 + c, N - j] = (((-w) & 0xFFFFFFFF) << 32) | lows[(i + b + c) % len(lows)]
+    m = np.uint64((1 << W) - 1)
+    out = np.roll(a, v, axis=-1)
+    if v:
+        out[..., :v] = (np.uint64(0) - out[..., :v]) & m
+    return out
+
+
+def lut_edge_tables(p, o, nluts=2, seed=0):
+    """lookup tables (nluts, N) ring words on the digit boundaries of the gadget that decomposes them in the first CMux (rot_gadgets(p)[0];
+    the constant test vector +-2^(W-3) reaches none): its gadget_words and their negatives (the table step negates the wrapped part and,
+    above N, the rest) at edge_positions(N) -- the four corners 0, M - 1, M, N - 1, then the whole list twice at the pairs (i, i + M) --
+    with helpers.edge_words elsewhere, the list rotated from row to row.  o > 1: each row is the PACKED table of o tables T_v (mk.lut_pack:
+    U[o i + v] = T_v[o i]) chosen so that the packed row is the one described"""
+    N, W = p.N, p.W
+    l, logB = rot_gadgets(p)[0]
+    rng = np.random.default_rng([seed, N, W, o, l, logB])
+    S = list(gadget_words(l, logB, W).values())
+    S += [(-w) & ((1 << W) - 1) for w in S]
+    pos = edge_positions(N)
+    assert 4 + 4 * len(S) <= len(pos), "the list fits twice"
+    rows = []
+    for r in range(nluts):
+        U = edge_words(W, N, rng)
+        for i in range(4 + 4 * len(S)):
+            U[pos[i]] = S[(5 * r + (i if i < 4 else (i - 4) // 2)) % len(S)]
+        if o > 1:
+            T = np.stack([edge_words(W, N, rng) for _ in range(o)])
+            for t in range(o):
+                T[t, ::o] = U[t::o]
+            packed = mk.lut_pack(T.astype(p.ring_dtype), p)
+            assert np.array_equal(packed.astype(np.uint64), U)
+            rows.append(packed)
+        else:
+            rows.append(U.astype(p.ring_dtype))
+    return np.stack(rows)
 
 
 _GATE_CONST = {0: 1 << 29, 1: 7 << 29, 2: 1 << 29, 3: 1 << 30, 4: 3 << 30, 5: 7 << 29}
@@ -357,4 +456,38 @@ def ks_edge_check(p, so, sg, rng, batches):
         for j in range(B):
             assert np.array_equal(out[j], so.keyswitch(acc[j])), ("keyswitch (edge words)", p.name, p.n, p.f, p.logD, B, j)
             checks += 1
+    return checks
+
+
+def ks_at_rows(p, rng, B, coefs):
+    """-> (src, coef) of B output rows over B accumulators: src unsorted with one repeat, coef cycling through coefs"""
+    src = rng.permutation(B).astype(np.uint32)
+    if B >= 3:
+        src[-1] = src[0]
+    return src, np.array([coefs[(g + 1) % len(coefs)] for g in range(B)], dtype=np.uint32)
+
+
+def ks_at_edge_check(p, so, sg, rng, batches, coefs, device=True):
+    """mk.keyswitch_at(sg, ks_edge_acc_at(v), src, coef) == the oracle's keyswitch! of the numpy extraction (ref_lut_many.extract) for
+    EVERY row, for every v of coefs and every batch size: coef cycling through coefs (one call mixes coefficients) and coef = v throughout
+    (every row on the crafted boundaries), in host and in device memory -> number of ciphertexts compared (each in both memories)"""
+    import ref_lut_many as RM
+    checks = 0
+    for v in coefs:
+        for B in batches:
+            acc = ks_edge_acc_at(p, rng, B, v)
+            a = acc.astype(p.ring_dtype)
+            src, cyc = ks_at_rows(p, rng, B, coefs)
+            for coef in (cyc, np.full(B, v, dtype=np.uint32)):
+                want = np.stack([so.keyswitch(RM.extract(acc[int(src[g])], int(coef[g]), p.W)) for g in range(B)])
+                got = mk.keyswitch_at(sg, a, src, coef)
+                bad = np.nonzero((got != want).any(axis=1))[0]
+                assert not len(bad), ("keyswitch_at (edge words), host memory", p.name, p.n, p.f, p.logD, v, B, bad[:4], src[bad[:4]], coef[bad[:4]])
+                if device:
+                    import torch
+                    t = lambda x: torch.from_numpy(np.ascontiguousarray(x).view({4: np.int32, 8: np.int64}[x.dtype.itemsize])).cuda()      # noqa: E731
+                    got = mk.keyswitch_at(sg, t(a), t(src), t(coef)).cpu().numpy().view(np.uint32)
+                    bad = np.nonzero((got != want).any(axis=1))[0]
+                    assert not len(bad), ("keyswitch_at (edge words), device memory", p.name, p.n, p.f, p.logD, v, B, bad[:4])
+                checks += B
     return checks

@@ -6,28 +6,47 @@ import numpy as np
 import pytest
 
 import edge_cases as EC
-from helpers import (BT_TARGETS, O, acc_edge, btilde_words, extract_words, gadget_words, gate_input, keygen, ks_border, ks_edge_acc,
-                     ks_words, lwe_edge_rows, mk, modswitch_words, oracle_scheme, rot_gadgets)
+import ref_lut as R
+import ref_lut_many as RM
+from helpers import (BT_TARGETS, KS_LOW_HALVES, O, acc_edge, bt_values, btilde_words, extract_words, gadget_words, gate_input, keygen, ks_border,
+                     ks_borrow_decides, ks_edge_acc, ks_edge_acc_at, ks_words, lut_edge_tables, lwe_edge_rows, mk, modswitch_words, oracle_scheme,
+                     rot_gadgets)
 
 
 def _switch(w, N):
     return O.divbits(int(w), 32 - (N.bit_length() - 1) - 1, 32)
 
 
-def _sw_row(row, N):
-    return np.array([_switch(w, N) for w in row], dtype=np.int64)
+def _sw_row(row, N, nout=1):
+    return np.array([RM.sw(w, N, nout) for w in row], dtype=np.int64)
 
 
 # ---------------------------------------------------------------- 1. class counts
 @pytest.mark.parametrize("even", [False, True], ids=["any", "even"])
 @pytest.mark.parametrize("p", EC.all_rotation_sets(), ids=EC.sid)
 def test_lwe_edge_rows_hold_every_class(p, even):
+    _rows_hold_every_class(p, even, 1)
+
+
+@pytest.mark.parametrize("nout", EC.LUT_NOUTS)
+@pytest.mark.parametrize("p", list(dict.fromkeys(c[0] for c in EC.LUT_BOOT_CASES)), ids=EC.sid)
+def test_lwe_edge_rows_hold_every_class_on_the_coarse_grid(p, nout):
+    """the rows of the many-table / coefficient-list bootstraps: every kind meets every target 0, nout, N - nout, N, N + nout, 2N - nout, 2N
+    of sw_nu (tests/ref_lut_many.py), ties and words that round to 0 included"""
+    assert RM.sw(1 << 31, p.N, nout) == p.N and {RM.sw(w, p.N, nout) for w in RM.sw_edge_words(p.N, nout)} >= {0, nout, p.N, 2 * p.N - nout, 2 * p.N}
+    _rows_hold_every_class(p, False, nout)
+
+
+def _rows_hold_every_class(p, even, nout):
     N, n, nm = p.N, p.n, p.lwe_len - 1
-    rows, kinds = lwe_edge_rows(p, np.random.default_rng(1), even=even)
+    rows, kinds = lwe_edge_rows(p, np.random.default_rng(1), even=even, nout=nout)
     if even:
         assert not (rows & 1).any()
-    want = {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
-    sw = np.stack([_sw_row(r, N) for r in rows])
+    want = bt_values(N, nout)
+    assert nout > 1 or want == {"0": 0, "1": 1, "N-1": N - 1, "N": N, "N+1": N + 1, "2N-1": 2 * N - 1, "2N": 2 * N}
+    sw = np.stack([_sw_row(r, N, nout) for r in rows])
+    if nout == 1:
+        assert all(int(v) == _switch(w, N) for v, w in zip(sw[0], rows[0]))
     for kind in ("zero", "skip", "dense", "blocks") + (("party",) if p.multikey else ()):
         sel = [i for i, k in enumerate(kinds) if k == kind]
         assert {int(sw[i, nm]) for i in sel} >= set(want.values()), (kind, "btilde")                    # every btilde in every kind
@@ -56,7 +75,7 @@ def test_lwe_edge_rows_hold_every_class(p, even):
     mask_sw = sw[:, :nm]
     counts = {k: int((mask_sw == v).sum()) for k, v in want.items()}
     counts["raw != 0 -> 0"] = int(((mask_sw == 0) & (rows[:, :nm] != 0)).sum())
-    h = 1 << (32 - (N.bit_length() - 1) - 2)
+    h = (1 << (32 - (N.bit_length() - 1) - 2)) * nout
     counts["tie"] = int(((rows[:, :nm] & np.uint32(2 * h - 1)) == h).sum())
     assert all(c > 0 for c in counts.values()), counts
 
@@ -108,10 +127,13 @@ def test_acc_edge_holds_every_class_for_every_gadget(p):
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("p", EC.KS_SETS + EC.KS_CHILD_SETS, ids=EC.sid)
 def test_ks_edge_acc_holds_every_class(p, B):
+    _ks_acc_holds_every_class(p, ks_edge_acc(p, np.random.default_rng(3), B), B)
+
+
+def _ks_acc_holds_every_class(p, acc, B):
     N, f, logD = p.N, p.f, p.logD
     Lb, bit, D = f * logD, 32 - f * logD, 1 << logD
     balanced = p.scheme in (mk.LMSS, mk.KMS_BLOCK)
-    acc = ks_edge_acc(p, np.random.default_rng(3), B)
     special_words = set(ks_words(f, logD).values())
     counts = {}
     for b in range(B):
@@ -124,7 +146,7 @@ def test_ks_edge_acc_holds_every_class(p, B):
                     continue                                                  # this component has no copied / switched border
                 here = int(w[j]) in special_words
                 if p.W == 64:                                                 # ... over one of the crafted low halves (cut off, never rounded in)
-                    here = here and int(src[0 if j == 0 else N - j]) & 0xFFFFFFFF in (0xFFFFFFFF, 0x80000000, 0x7FFFFFFF)
+                    here = here and int(src[0 if j == 0 else N - j]) & 0xFFFFFFFF in KS_LOW_HALVES
                 counts["a boundary word at j = " + name] = counts.get("a boundary word at j = " + name, 0) + here
             sw = w[j0:]                                                       # the switched words
             if not len(sw):
@@ -154,6 +176,88 @@ def test_ks_edge_acc_holds_every_class(p, B):
     if p.W == 64:
         low = acc[:, 1:] & np.uint64(0xFFFFFFFF)
         assert (low == 0xFFFFFFFF).any() and (low == 0x80000000).any()
+        cut = N - np.arange(N - 1, 0, -1)[None, None, :] >= np.array([ks_border(p, c) for c in range(p.k)])[None, :, None]      # a[N - j], j switched
+        for h in (0, 1):                                                      # a wrapped word with and without a borrow from the high half
+            assert ((low[:, :, 1:] == h) & cut).any(), ("low half", h)
+
+
+def _at_sets():
+    return list(dict.fromkeys(EC.KS_AT_SETS + EC.KS_CHILD_SETS))
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("p", _at_sets(), ids=EC.sid)
+def test_ks_edge_acc_at_holds_every_class_at_every_coefficient(p, B):
+    """X^v * ks_edge_acc: the extraction at v is an accumulator that the assertion above accepts -- every class at every position class --
+    and, 64-bit ring, on each side of j = v that exists every ciphertext holds a word over a non-zero low half where moving the negation
+    across the truncation changes an output word (ks_borrow_decides)"""
+    N = p.N
+    for v in EC.KS_AT_COEFS(p):
+        acc = ks_edge_acc_at(p, np.random.default_rng(3), B, v)
+        assert acc.dtype == np.uint64 and acc.shape == (B, 1 + p.k, N) and not (acc >> np.uint64(p.W - 1) >> np.uint64(1)).any()
+        base = RM.extract(acc, v, p.W)
+        for b in range(B):                                                    # the rotation itself, restated: out[i] = a[i - v], -a[N + i - v]
+            for c in range(1 + p.k):
+                assert np.array_equal(acc[b, c], R.rotate(base[b, c], v, p.W)), (v, b, c)
+        _ks_acc_holds_every_class(p, base, B)
+        if p.W == 64 and p.f * p.logD < 32:
+            for b in range(B):
+                for name, side in (("wrapped", range(1, v + 1)), ("not wrapped", range(v + 1, N))):
+                    if len(side):
+                        assert any(ks_borrow_decides(p, c, j, base[b, 1 + c, N - j]) for c in range(p.k) for j in side), (v, b, name)
+    assert set(EC.KS_AT_FULL_COEFS(p)) <= set(EC.KS_AT_COEFS(p))
+
+
+def _mutant_base(acc, v):
+    """the v = 0 accumulators whose key switch is what a kernel gives that takes -trunc(x) for trunc(-x) at the wrapped positions
+    1 <= j <= v of a 64-bit accumulator: its word there is trunc(acc[v - j]), without the + 1 of a non-zero low half"""
+    N = acc.shape[-1]
+    base = RM.extract(acc, v, 64)
+    for j in range(1, v + 1):
+        base[..., 1:, N - j] = ((np.uint64(0) - (acc[..., 1:, v - j] >> np.uint64(32))) & np.uint64(0xFFFFFFFF)) << np.uint64(32)
+    return base
+
+
+@pytest.mark.parametrize("p", [p for p in _at_sets() if p.W == 64], ids=EC.sid)
+def test_the_borrow_class_separates_the_oracle_from_a_negation_moved_across_the_truncation(p):
+    """the mutant changes an output word of the oracle's key switch for every v >= 1, in every ciphertext: the GPU comparison at these
+    accumulators sees a kernel that drops the + 1"""
+    crs, keys = keygen(p, 12)
+    so = oracle_scheme(p, crs, keys)
+    B = 2
+    for v in (EC.KS_AT_FULL_COEFS(p) if p in EC.KS_AT_FULL else EC.KS_AT_COEFS(p)):
+        acc = ks_edge_acc_at(p, np.random.default_rng(4), B, v)
+        good, bad = RM.extract(acc, v, 64), _mutant_base(acc, v)
+        if v == 0:
+            assert np.array_equal(good, bad)
+            continue
+        for b in range(B):
+            assert not np.array_equal(so.keyswitch(good[b]), so.keyswitch(bad[b])), (v, b)
+    # and the restatement is the mutant: where the low half is 0 it is the right word
+    x = np.zeros((1, 2, 8), dtype=np.uint64)
+    x[0, 1, :3] = [5 << 32, (5 << 32) | 1, (1 << 64) - 1]
+    g, m = RM.extract(x, 4, 64), _mutant_base(x, 4)
+    assert np.array_equal((g[0, 1, 4:7] >> np.uint64(32)) == (m[0, 1, 4:7] >> np.uint64(32)), [True, False, False])
+
+
+@pytest.mark.parametrize("o", [1, 2, 8])
+@pytest.mark.parametrize("p", list(dict.fromkeys(c[0] for c in EC.LUT_BOOT_CASES)), ids=EC.sid)
+def test_lut_edge_tables_hold_every_class_after_every_rotation(p, o):
+    """whatever target btilde rotates the table, the polynomial that the first CMux decomposes holds a boundary word of every class of its
+    gadget in both halves; a packed row is the packing of o tables"""
+    N, M, W = p.N, p.N // 2, p.W
+    l, logB = rot_gadgets(p)[0]
+    luts = lut_edge_tables(p, o)
+    assert luts.shape == (2, N) and luts.dtype == np.dtype(p.ring_dtype) and not np.array_equal(luts[0], luts[1])
+    for T in luts:
+        for bt in sorted(set(bt_values(N, o).values()) | set(bt_values(N, 1).values())):
+            tv = R.testvector(T, bt, W, p.k)
+            assert not tv[1:].any()
+            for k, m in _digit_classes(tv[0], l, logB, W).items():
+                assert m[:M].any() and m[M:].any(), (k, bt, "both halves")
+            if W == 64 and W - l * logB > 32:
+                low = tv[0] & np.uint64(0xFFFFFFFF)
+                assert (low == 0xFFFFFFFF).any() and (low == 0x80000000).any()
 
 
 # ---------------------------------------------------------------- 2. the oracle's composition identity on the crafted rows

@@ -3,7 +3,8 @@
 The standalone kernels (mkt_transform_*_batch, mkt_decompose_batch) see boundary words in tests/test_gpu_parity.py; the gate path
 calls neither.  Fresh encryptions, the test-vector accumulator (b = +-2^(W-3), every a polynomial zero) and uniformly random key-switch
 accumulators do not reach the boundaries below by construction, so these tests start the kernels from crafted valid inputs
-(helpers.lwe_edge_rows, acc_edge, ks_edge_acc; tests/test_edges_cpu.py proves every class is in them for every set used here) and
+(helpers.lwe_edge_rows, acc_edge, ks_edge_acc, ks_edge_acc_at, lut_edge_tables; tests/test_edges_cpu.py proves every class is in them for
+every set used here) and
 compare EVERY ciphertext with the oracle / tests/ref_exact.py.  Every rotation case asserts the kernel it reached.
 
 | step | fused copies (not the standalone kernel) | boundary classes |
@@ -12,6 +13,8 @@ compare EVERY ciphertext with the oracle / tests/ref_exact.py.  Every rotation c
 | test vector from btilde | launch_testvector, inline in kms_phase2_kernel / exact_kms_phase2_kernel (`if (a.lin) { ... if (tb > N) ... }`) | btilde in {0, 1, N-1, N, N+1, 2N-1, 2N}, each through the smallest and the largest word that rounds to it |
 | gadget digits Gadget::prep / digit_points | every rotation kernel, KMS phase 2 (LEV and UniEnc gadgets), CCS | ties of divbits(x, W - l logB), one below / above; the rounding carry out of the top digit; the carry of the prepared value (all digits -B/2); all digits B/2-1; 2^(W-1); W = 64: the same high parts over a low half of all ones / the top bit alone; index i and i + M, indices 0, M-1, M, N-1; non-zero acc.a on entry (KMS overwrites it, bootstrapping.jl:553-556) |
 | key-switch digits | keyswitch_mg_kernel (`divbits(w, 32-f logD)` / gb.prep), ks_digits_kernel + keyswitch_pair_kernel, extract_word, ks_init_kernel | the carry that leaves the f logD-bit field, ties, all digits D-1 / -D/2 / D/2-1, zero, 0x80000000 at a negated position, j = 0 / 1 / N-1, both sides of the copied / switched border (n < N, n > N), W = 64: the low half cut off, ragged groups of 32 |
+| key-switch digits at a coefficient | the `AT = true` instantiations of keyswitch_mg_kernel, ks_digits_kernel (+ keyswitch_pair_kernel), ks_init_kernel / ks_reduce_kernel; extract_word_at; ks_at_table_kernel (the coefficient list, NULL = 0 .. o-1) | the classes of the line above in X^v times the same accumulators, v in {0, 1, n-1, n, n+1, N/2, N-1}, rows and coefficients mixed in one call; W = 64, the borrow: a word wrapped by X^v was negated at 64 bits and is truncated and negated again at 32, so the extracted word is trunc(a) + (low half != 0) -- low halves 0 and 1, and a tie / carry (and the word one below) over a non-zero low half on both sides of j = v |
+| lookup-table route (context.cpp lut_chunk) | lut_testvector_kernel: `divbits(w, 32-logN-1+nu) << nu` on b and (nu > 0) on the mask words, which the rotation reads pre-switched; the caller's table rotated into acc.b | the mod-switch classes of the first line on the plain (nu = 0) and the coarse grid (targets 0, nout, N-nout, N, N+nout, 2N-nout, 2N); tables whose words sit on the first CMux's gadget boundaries (and their negatives: the table step negates) at 0, M-1, M, N-1 and pairs (i, i + M) |
 
 A kernel that gets its own copy of one of these steps gets a line in tests/edge_cases.py.
 
@@ -22,8 +25,12 @@ import numpy as np
 import pytest
 
 import edge_cases as EC
-from helpers import (O, acc_edge, gate_input, gpu_scheme, keygen, ks_edge_check, lwe_edge_rows, mk, oracle_scheme, rot_gadgets)
+import ref_lut as R
+import ref_lut_many as RM
+from helpers import (O, acc_edge, gate_input, gpu_scheme, keygen, ks_at_edge_check, ks_edge_check, lut_edge_tables, lwe_edge_rows, mk, oracle_scheme,
+                     rot_gadgets)
 from ref_gate3 import linear3
+from test_keyswitch_at_cpu import checker_at
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +137,13 @@ def test_exact_implementations_agree_on_edge_accumulators(require_gpu, p):
 def test_keyswitch_at_digit_boundaries(require_gpu, p):
     crs, keys, so, sg = _engines(p, 27, {})
     assert ks_edge_check(p, so, sg, np.random.default_rng(28), EC.KS_BATCHES) == sum(EC.KS_BATCHES)
+    # ... and at a coefficient: X^v times the same accumulators, read back at v (and, rows mixed, at every other coefficient of the list)
+    assert p in EC.KS_AT_SETS
+    full = p in EC.KS_AT_FULL
+    batches, coefs = (EC.KS_AT_FULL_BATCHES, EC.KS_AT_FULL_COEFS(p)) if full else (EC.KS_BATCHES, EC.KS_AT_COEFS(p))
+    n = ks_at_edge_check(p, so, sg, np.random.default_rng(35), batches, coefs)
+    assert n == 2 * len(coefs) * sum(batches)
+    print(f"{EC.sid(p)}: {sum(EC.KS_BATCHES)} + {n} ciphertexts compared (the latter in host and in device memory)")
     sg.close()
 
 
@@ -227,4 +241,95 @@ def test_gate_entry_points_on_edge_rows(require_gpu, p, opts, kernel):
     got = reached(sg.mux(zero, a, b))
     for j in range(B):
         assert np.array_equal(got[j], _oracle_mux(p, so, zero[j], a[j], b[j])), ("mux", j)
+    sg.close()
+
+
+# ---------------------------------------------------------------- 4. the lookup-table route: crafted rows through crafted tables
+def _t(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize])).cuda()
+
+
+def _lut_inputs(p, rng, nout):
+    """lwe_edge_rows on the grid of nout and one or two random rows (an odd batch), a table row per input"""
+    rows, kinds = lwe_edge_rows(p, rng, nout=nout)
+    more = 1 + len(rows) % 2
+    rows = np.concatenate([rows, rng.integers(0, 1 << 32, (more, p.lwe_len), dtype=np.uint64).astype(np.uint32)])
+    assert len(rows) % 2 == 1
+    sel = (np.arange(len(rows)) % 2).astype(np.uint32)[::-1].copy()
+    return rows, kinds + ["random"] * more, sel
+
+
+def _lut_calls(p):
+    """(name, nout of the input grid, table count packed into a row, call, checker of one ciphertext)"""
+    N = p.N
+    at0, at1 = np.array([N - 1, 0, 1], dtype=np.uint32), np.array([0, 1], dtype=np.uint32)
+    return [
+        ("lut_bootstrap", 1, 1, lambda s, T, c, sel: mk.lut_bootstrap(s, T, c, sel)[:, None], None),
+        ("lut_many_bootstrap o=2", 2, 2, lambda s, T, c, sel: mk.lut_many_bootstrap(s, T, c, 2, sel), None),
+        ("lut_many_bootstrap o=8", 8, 8, lambda s, T, c, sel: mk.lut_many_bootstrap(s, T, c, 8, sel), None),
+        ("lut_bootstrap_at nu=0", 1, 1, lambda s, T, c, sel: mk.lut_bootstrap_at(s, T, c, _like(c, at0), nu=0, sel=sel), at0),
+        ("lut_bootstrap_at nu=1", 2, 2, lambda s, T, c, sel: mk.lut_bootstrap_at(s, T, c, _like(c, at1), nu=1, sel=sel), at1),
+    ]
+
+
+def _like(c, a):
+    return a if isinstance(c, np.ndarray) else _t(a)
+
+
+def _lut_reference(p, so, name, nout, T, row, coef):
+    if name == "lut_bootstrap":
+        return R.checker_bootstrap(so, T, row, p.W)[None]
+    if coef is None:
+        return RM.checker_many(so, T, row, nout, p.W)
+    return checker_at(so, T, row, coef, p.W, nout)
+
+
+def _lut_composed(sx, p, name, nout, luts, c, sel, coef):
+    """MKT_ARITH_EXACT: the unit calls composed, none of them a key switch at a coefficient -- the table step on the grid of nout, the rotation,
+    the extraction (mkt_lut_extract_batch for the many-table form, numpy for a coefficient list), the plain key switch"""
+    at, acc = mk.lut_many_testvector(sx, luts, c, nout, sel)
+    acc = sx.blindrotate_(at, acc)
+    if name == "lut_bootstrap":
+        return sx.keyswitch(acc)[:, None]
+    if coef is None:
+        return sx.keyswitch(mk.lut_extract(sx, acc, nout))
+    accs = np.stack([RM.extract(acc, int(v), p.W) for v in coef], axis=1).astype(p.ring_dtype)
+    return sx.keyswitch(accs)
+
+
+@pytest.mark.parametrize("p,opts,kernel,exact", EC.LUT_BOOT_CASES, ids=_cid)
+def test_table_bootstraps_on_edge_rows(require_gpu, p, opts, kernel, exact):
+    """every lookup-table bootstrap (one route: table step, rotation, key switch -- at a coefficient for more than one output) on rows on the
+    mod-switch boundaries of its grid through tables on the first CMux's digit boundaries, every ciphertext, host and device memory.
+    Float64 mode: against the CPU checker's chains; EXACT: against the unit calls composed, both implementations where the other is offered"""
+    crs, keys, so, sg = _engines(p, 37, opts, exact=exact)
+    rng = np.random.default_rng(38)
+    checks = 0
+    for name, nout, o, call, coef in _lut_calls(p):
+        rows, kinds, sel = _lut_inputs(p, rng, nout)
+        luts = lut_edge_tables(p, o)
+        got = call(sg, luts, rows, sel)
+        assert sg.last_kernel_name() == kernel, (name, sg.last_kernel_name())
+        if exact:
+            want = _lut_composed(sg, p, name, nout, luts, rows, sel, coef)
+            assert sg.last_kernel_name() == kernel, (name, sg.last_kernel_name())
+        else:
+            want = np.stack([_lut_reference(p, so, name, nout, luts[sel[j]], rows[j], coef) for j in range(len(rows))])
+        assert got.shape == want.shape
+        for j in range(len(rows)):
+            assert np.array_equal(got[j], want[j]), (name, "host memory", j, kinds[j])
+        dev = call(sg, _t(luts), _t(rows), _t(sel)).cpu().numpy().view(np.uint32).reshape(want.shape)
+        for j in range(len(rows)):
+            assert np.array_equal(dev[j], want[j]), (name, "device memory", j, kinds[j])
+        if exact and "exact_impl" in opts:
+            sg.set_option("exact_impl", 1 - opts["exact_impl"])
+            other = call(sg, luts, rows, sel)
+            fx = opts["exact_impl"] == 0 and sg.get_metric("fx_available") == 1.0 and not opts.get("exact_kany")      # (exact_kany forces the integer kernel)
+            assert ("fx_" in sg.last_kernel_name()) == fx, sg.last_kernel_name()
+            assert np.array_equal(other, want), (name, "the other exact_impl", sg.last_kernel_name())
+            sg.set_option("exact_impl", opts["exact_impl"])
+        checks += want.shape[0] * want.shape[1]
+    print(f"{EC.sid(p)} {kernel}: {checks} ciphertexts compared (each in host and in device memory)")
     sg.close()

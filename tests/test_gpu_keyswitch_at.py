@@ -15,7 +15,8 @@ if __name__ == "__main__":
 
 import ref_lut as R
 import ref_lut_many as RM
-from helpers import ROOT, edge_words, gpu_scheme, keygen, mk, oracle_scheme
+import edge_cases as EC
+from helpers import ROOT, edge_words, gpu_scheme, keygen, ks_at_edge_check, mk, oracle_scheme
 from test_gpu_lut import _dk, _exact_scheme, _gpu, _host, _inputs, _keys, _sid, _tables
 from test_gpu_parity import SMALL
 from test_keyswitch_at_cpu import checker_at, thermometer_bits, thermometer_case, thermometer_coefs
@@ -116,7 +117,11 @@ def _child():
     for p in CHILD_SETS:
         crs, keys = keygen(p, 92)
         sg = gpu_scheme(p, crs, keys)
-        checks += _unit_check(p, oracle_scheme(p, crs, keys), sg, rng, batches=(1, 33, 70))
+        so = oracle_scheme(p, crs, keys)
+        checks += _unit_check(p, so, sg, rng, batches=(1, 33, 70))
+        # the accumulators of tests/test_gpu_edges.py on the key-switch digits' boundaries, rotated by X^v and read back at v
+        assert p in EC.KS_CHILD_SETS                                           # (tests/test_edges_cpu.py proves their classes for these sets)
+        checks += ks_at_edge_check(p, so, sg, rng, EC.KS_BATCHES, EC.KS_AT_COEFS(p))
         sg.close()
     return checks
 
