@@ -406,14 +406,9 @@ static uint32_t merged_phase(const Shape &sh, const uint32_t *lwe, const uint32_
 
 // scheme.jl:388-407
 int mkt_client_lwe_decrypt(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const uint32_t *lwe) {
-    if (!params || !keys || !lwe) return MKT_ERR_ARG;
-    const mkt_params &p = *params;
-    Shape sh = shape_of(p);
-    if (nparties != sh.nparty) return MKT_ERR_ARG;
-    uint32_t b = lwe[sh.lwe_len - 1];
-    for (int i = 0; i < nparties; i++)
-        for (int q = 0; q < p.n; q++) b += keys[i]->lwekey[q] * lwe[(size_t)i * p.n + q];
-    return bit_of_phase(p, b);
+    uint32_t b;
+    if (int r = mkt_client_lwe_phase(params, keys, nparties, lwe, &b)) return r;
+    return bit_of_phase(*params, b);
 }
 
 // ---- distributed decryption (mktfhe.h): a share per party from its own mask block, merged by anyone ----
@@ -425,7 +420,7 @@ int mkt_client_partial_decrypt(const mkt_params *params, const mkt_client_party 
     const mkt_params &p = *params;
     Shape sh = shape_of(p);
     if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
-    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return MKT_ERR_ARG;   // keys made for other parameters / another party index (as mkt_keygen_device)
+    if (!party_keys_match(K, p, party)) return MKT_ERR_ARG;   // (as mkt_keygen_device)
     uint32_t key[8];
     if (seed_to_key(seed, key)) return MKT_ERR_STATE;
     for (size_t j = 0; j < B; j++) {
@@ -466,7 +461,7 @@ int mkt_client_seeded_encrypt(const mkt_params *params, const mkt_client_party *
     const mkt_params &p = *params;
     Shape sh = shape_of(p);
     if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
-    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return MKT_ERR_ARG;   // as mkt_client_partial_decrypt
+    if (!party_keys_match(K, p, party)) return MKT_ERR_ARG;
     if (!B) return MKT_OK;
     if (!mu || !body_out) return MKT_ERR_ARG;
     uint32_t mkey[8], nkey[8];

@@ -536,6 +536,29 @@ struct Staged {
     ~Staged() { if (owned && dev) { (void)hipStreamSynchronize(c->stream); (void)hipFree(dev); } }
 };
 
+// A secret on the device for the length of one scope (the TRUST note in mktfhe.h): uploaded on the context's stream; zeroed on that stream and
+// the stream drained before the buffer is freed, by whatever path the scope is left.  Declared AFTER a call's Staged objects: its wipe is drained before they free
+struct DeviceSecret {
+    mkt_ctx *c; void *dev = nullptr; size_t bytes = 0;
+    DeviceSecret(const DeviceSecret &) = delete;
+    hipError_t alloc(size_t nbytes) { bytes = nbytes; const hipError_t e = hipMalloc(&dev, nbytes ? nbytes : 1); if (e != hipSuccess) dev = nullptr; return e; }
+    hipError_t in(const void *host, size_t nbytes) { const hipError_t e = alloc(nbytes); return e != hipSuccess ? e : hipMemcpyAsync(dev, host, nbytes, hipMemcpyHostToDevice, c->stream); }
+    hipError_t wipe_now() {   // behind everything enqueued so far; the result of draining the stream
+        if (!dev) return hipSuccess;
+        (void)hipMemsetAsync(dev, 0, bytes, c->stream);
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        (void)hipFree(dev); dev = nullptr;
+        return e;
+    }
+    ~DeviceSecret() { (void)wipe_now(); }
+};
+// the end of a party-local call: the secret wiped, and the host copy of the stream key in the argument struct (the kernel-argument copy: TRUST note in mktfhe.h)
+template <class Args> hipError_t wipe_secrets(hipError_t e, DeviceSecret &secret, Args &a) {
+    const hipError_t es = secret.wipe_now();
+    explicit_bzero(&a, sizeof a);
+    return e != hipSuccess ? e : es;   // the call's status so far, else that of the drain
+}
+struct DevBuf { void *p = nullptr; ~DevBuf() { (void)hipFree(p); } };   // a call's own device buffer that holds no secret
 bool mem_ok(int mem) { return mem == MKT_MEM_DEVICE || mem == MKT_MEM_HOST; }
 
 // ---- MKT_ARITH_EXACT: tables of the two-prime negacyclic NTT (ntt_exact.hip), computed on the host, uploaded once ----
@@ -986,44 +1009,35 @@ static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, 
     MKT_EXACT_GATE(c);
     if (int w = keys_writable(c)) return w;
     const mkt_params &p = c->p;
-    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: the party's keys were made for other parameters / another party index");
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: the party's keys were made for other parameters / another party index");
     const bool unienc = p.scheme == MKT_CCS;
     if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: CCS needs the integer CRS");
     DevGuard dg(c->device);
     const int N = p.N, nz = (int)K->zring.size();
-    uint32_t *d_lwe = nullptr; int8_t *d_z = nullptr; void *d_crs_int = nullptr, *d_out = nullptr;
     const size_t brk_polys_total = (size_t)p.n * c->sh.brk_polys;
-    // the secrets are wiped on the device before their buffers are released
-    auto cleanup = [&] {
-        if (d_lwe) (void)hipMemsetAsync(d_lwe, 0, (size_t)p.n * 4, c->stream);
-        if (d_z) (void)hipMemsetAsync(d_z, 0, (size_t)nz * N, c->stream);
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(d_lwe); (void)hipFree(d_z); (void)hipFree(d_crs_int); (void)hipFree(d_out);
-    };
-    hipError_t e = hipMalloc((void **)&d_lwe, (size_t)p.n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_z, (size_t)nz * N);
-    if (e == hipSuccess) e = hipMalloc(&d_out, brk_polys_total * poly_bytes(c));
-    if (e == hipSuccess && unienc) e = hipMalloc(&d_crs_int, (size_t)p.l_uni * poly_bytes(c));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lwe, K->lwekey.data(), (size_t)p.n * 4, hipMemcpyHostToDevice, c->stream);
-    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync(d_z + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && unienc) e = hipMemcpyAsync(d_crs_int, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { cleanup(); return hipfail(c, e, "device keygen setup"); }
+    DevBuf out, crs_int;                      // freed behind the secrets' drain of the stream
+    DeviceSecret lwe{c}, z{c};
+    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
+    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
+    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync((int8_t *)z.dev + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMalloc(&out.p, brk_polys_total * poly_bytes(c));
+    if (e == hipSuccess && unienc) e = hipMalloc(&crs_int.p, (size_t)p.l_uni * poly_bytes(c));
+    if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hipfail(c, e, "device keygen setup");
     mktd::KeygenArgs a{};
     std::memcpy(a.key, K->key, sizeof a.key); a.party = K->party; a.N = N; a.n = p.n; a.W = p.W; a.f = p.f; a.logD = p.logD;
     a.sigma_ring = K->sigma_ring; a.sigma_lwe = K->sigma_lwe;
-    a.lwekey = d_lwe; a.zring = d_z; a.crs = d_crs_int; a.out = d_out;
+    a.lwekey = (const uint32_t *)lwe.dev; a.zring = (const int8_t *)z.dev; a.crs = crs_int.p; a.out = out.p;
     if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; a.zoff = 0; }
     else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; a.zoff = 0; }
     e = mktd::launch_keygen_brk(a, unienc ? 1 : 0, c->stream);
-    if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, d_out, brk_polys_total * poly_bytes(c), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = to_resident(c, d_out, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
+    if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, out.p, brk_polys_total * poly_bytes(c), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = to_resident(c, out.p, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
     uint32_t *ksk = c->ks->party<uint32_t>(T_KSK, party);
     if (e == hipSuccess) e = hipMemsetAsync(ksk, 0, c->ks->stride(T_KSK) * sizeof(uint32_t), c->stream);
     a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
     if (e == hipSuccess) e = mktd::launch_keygen_ksk(a, ksk, c->ks->n1p, c->sh.ksk_kr, c->sh.ksk_drows, mkt::is_block(p.scheme) ? 1 : 0, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
-    explicit_bzero(&a, sizeof a);            // the host copy of the party's stream key (the kernel-argument copy: see the TRUST note in mktfhe.h)
+    e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);
     if (e != hipSuccess) return hipfail(c, e, "device keygen");
     c->ks->brk_loaded[party] = 1; c->ks->ksk_loaded[party] = 1;
     if (c->ks->d_fx_brk) { int r = fx_after_key_load(c); if (r) return r; }
@@ -1050,27 +1064,21 @@ int mkt_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, 
     if (!c || !K || !lwe || !share_out || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
     if (!mkt::smudge_sigma_ok(sigma_smudge)) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: sigma_smudge must be finite, 0 <= sigma_smudge <= 2^31");
     const mkt_params &p = c->p;
-    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
     if (!B) return MKT_OK;
     DevGuard dg(c->device);
     Timer whole(c, 0);
     Staged sx{c}, so{c};
+    DeviceSecret key{c};
     int r;
     if ((r = sx.in(lwe, B * (size_t)c->sh.lwe_len * 4, mem, true)) || (r = so.in(share_out, B * 4, mem, false))) return r;
     mktd::PartialDecryptArgs a{};
     if (mkt::seed_to_key(seed, a.key)) return fail(c, MKT_ERR_STATE, "mkt_partial_decrypt_batch: no entropy from the OS");
-    uint32_t *d_key = nullptr;
-    hipError_t e = hipMalloc((void **)&d_key, (size_t)p.n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_key, K->lwekey.data(), (size_t)p.n * 4, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = key.in(K->lwekey.data(), (size_t)p.n * 4);
     a.party = party; a.n = p.n; a.lwe_stride = c->sh.lwe_len; a.sigma = sigma_smudge; a.row0 = row0;
-    a.lwe = (const uint32_t *)sx.dev; a.lwekey = d_key; a.out = (uint32_t *)so.dev; a.B = B;
+    a.lwe = (const uint32_t *)sx.dev; a.lwekey = (const uint32_t *)key.dev; a.out = (uint32_t *)so.dev; a.B = B;
     if (e == hipSuccess) e = mktd::launch_partial_decrypt(a, c->stream);
-    // the secret is wiped on the device before its buffer is released
-    if (d_key) (void)hipMemsetAsync(d_key, 0, (size_t)p.n * 4, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_key);
-    explicit_bzero(&a, sizeof a);            // the host copy of the stream key (the kernel-argument copy: see the TRUST note in mktfhe.h)
-    if (e == hipSuccess) e = es;
+    e = wipe_secrets(e, key, a);
     if (e != hipSuccess) return hipfail(c, e, "device partial decryption");
     return so.out(share_out);
 }
@@ -1100,29 +1108,23 @@ int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, c
     if (!mkt::smudge_sigma_ok(sigma_lwe)) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: sigma_lwe must be finite, 0 <= sigma_lwe <= 2^31");
     if (noise_seed && std::memcmp(noise_seed, mask_seed, 32) == 0) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the noise seed is the public mask seed");
     const mkt_params &p = c->p;
-    if (std::memcmp(&K->p, &p, sizeof(mkt_params)) != 0 || K->party != party) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the party's keys were made for other parameters / another party index");
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the party's keys were made for other parameters / another party index");
     if (!B) return MKT_OK;
     if (!mu || !body_out) return fail(c, MKT_ERR_ARG, "bad argument");
     DevGuard dg(c->device);
     Timer whole(c, 0);
     Staged sx{c}, so{c};
+    DeviceSecret key{c};
     int r;
     if ((r = sx.in(mu, B * 4, mem, true)) || (r = so.in(body_out, B * 4, mem, false))) return r;
     mktd::SeededArgs a{};
     mkt::seed_to_key(mask_seed, a.mkey);
     if (mkt::seed_to_key(noise_seed, a.nkey)) return fail(c, MKT_ERR_STATE, "mkt_seeded_encrypt_batch: no entropy from the OS");
-    uint32_t *d_key = nullptr;
-    hipError_t e = hipMalloc((void **)&d_key, (size_t)p.n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_key, K->lwekey.data(), (size_t)p.n * 4, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = key.in(K->lwekey.data(), (size_t)p.n * 4);
     a.party = party; a.n = p.n; a.lwe_len = c->sh.lwe_len; a.sigma = sigma_lwe; a.row0 = row0;
-    a.in = (const uint32_t *)sx.dev; a.lwekey = d_key; a.out = (uint32_t *)so.dev; a.B = B;
+    a.in = (const uint32_t *)sx.dev; a.lwekey = (const uint32_t *)key.dev; a.out = (uint32_t *)so.dev; a.B = B;
     if (e == hipSuccess) e = mktd::launch_seeded_encrypt(a, c->stream);
-    // the secret is wiped on the device before its buffer is released
-    if (d_key) (void)hipMemsetAsync(d_key, 0, (size_t)p.n * 4, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_key);
-    explicit_bzero(&a, sizeof a);            // the host copy of the noise stream key (the kernel-argument copy: see the TRUST note in mktfhe.h)
-    if (e == hipSuccess) e = es;
+    e = wipe_secrets(e, key, a);
     if (e != hipSuccess) return hipfail(c, e, "device seeded encryption");
     return so.out(body_out);
 }

@@ -159,10 +159,8 @@ struct SeededArgs {
 };
 hipError_t launch_seeded_expand(SeededArgs a, hipStream_t s);
 hipError_t launch_seeded_encrypt(SeededArgs a, hipStream_t s);
-// workgroups of one launch of either kernel, more tiles than that run grid-stride; rows per tile of the encrypt kernel; the words per tile
-// the expand launcher picks for a shape (what the tests size their grid-stride case by)
-constexpr unsigned SEEDED_MAX_GRID = 2048;
-constexpr int SEEDED_ENC_TILE = 64;
+// the words per tile the expand launcher picks for a shape (what the tests size their grid-stride case by; the workgroup cap of a launch
+// and the encrypt kernel's rows per tile: party_rows.h)
 int seeded_expand_tile_words(int n, int lwe_len);
 
 hipError_t launch_transform_fwd(int logM, int W, TwPtrs tw, const void *p, cplx *t, size_t B, int dev_order, hipStream_t s);

@@ -21,15 +21,14 @@
 //      launcher lowers it until at most SE_SLOTS = 256 blocks can begin in T + 15 words, one per lane of the 256-thread workgroup
 //      (seeded_expand_tile_words).  By count a block is ~1000 vector instructions per 64 bytes, so single-party sets are bound by the
 //      cipher and sets of k >= 2 parties approach the write stream; measured figures: DESIGN.md 1f.
-//   4. At most SEEDED_MAX_GRID workgroups per launch, grid-stride beyond.
-// ENCRYPT.  body[j] = e[j] - <a[j], s> + mu[j].  The mask never leaves registers: a lane multiplies its 16 words with the key words at
-// the same offsets, staged once per workgroup in LDS (zero-padded to whole blocks, read as four 16-byte words), and the row's sum is
-// gathered with lane exchanges.  A workgroup takes tiles of 64 consecutive rows and has five waves, as partial_decrypt.hip: waves 0 .. 3 take
-// 16 rows each while wave 4 draws the tile's 64 noise words, one row per lane, beside them -- never a cipher with one live lane -- and after
-// one barrier adds noise, message and dot product and stores 64 consecutive words.  `width` lanes share a row (SeededArgs::width, a power
-// of two, 4 .. 64): lane i of them takes blocks i, i + width, ...; 64 / width rows are in flight per wave, log2(width) exchanges per row.
-// The launcher picks the largest width that idles at most one lane-pass in eight (n = 560: 35 blocks on 4 lanes, 9 passes, 35 / 36 busy).
-#include "kernel_common.h"
+//   4. At most PR_MAX_GRID workgroups per launch, grid-stride beyond.
+// ENCRYPT.  body[j] = e[j] - <a[j], s> + mu[j], on the five-wave tile of party_rows.h: the dot step stores the NEGATED sum and the noise step
+// adds the message, so the frame's one addition gives the body.  The mask never leaves registers: a lane multiplies its 16 words with the
+// key words at the same offsets, staged in LDS zero-padded to whole blocks and read as four 16-byte words, and the row's sum is gathered
+// with lane exchanges.  `width` lanes share a row (SeededArgs::width, a power of two, 4 .. 64): lane i of them takes blocks i, i + width, ...;
+// 64 / width rows are in flight per wave, log2(width) exchanges per row.  The launcher picks the largest width that idles at most one
+// lane-pass in eight (n = 560: 35 blocks on 4 lanes, 9 passes, 35 / 36 busy).
+#include "party_rows.h"
 #include "rng_chacha.h"
 
 namespace mktd {
@@ -39,9 +38,6 @@ constexpr int SE_THREADS = 256;
 constexpr int SE_SLOTS = 256;                       // keystream blocks that may begin in one tile = rows of the LDS image
 constexpr int SE_PITCH = 17;                        // words per LDS row
 constexpr int SE_TILE_WORDS = 4096;
-constexpr int SQ_DOT_WAVES = 4;
-constexpr int SQ_ROWS = SEEDED_ENC_TILE / SQ_DOT_WAVES;
-constexpr int SQ_THREADS = 64 * (SQ_DOT_WAVES + 1);
 
 // the keystream block both kernels are built on: mask words 16 blk .. 16 blk + 15 of row `row`, in this lane's registers
 __device__ __forceinline__ void lane_block(const SeededArgs &a, uint64_t row, uint32_t blk, uint32_t (&x)[16]) {
@@ -124,50 +120,35 @@ __global__ void __launch_bounds__(SE_THREADS) seeded_expand_kernel(SeededArgs a)
     }
 }
 
-__global__ void __launch_bounds__(SQ_THREADS) seeded_encrypt_kernel(SeededArgs a) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n = a.n, nb = (n + 15) >> 4;
-    uint32_t *ks = reinterpret_cast<uint32_t *>(mkt_smem);   // [16 nb] the party's key, zeros behind word n
-    uint32_t *dots = ks + 16 * nb;                           // [2][64] the tile's dot products, double-buffered: one barrier per tile
-    for (int q = t; q < 16 * nb; q += SQ_THREADS) ks[q] = q < n ? a.lwekey[q] : 0u;
-    __syncthreads();
+__global__ void __launch_bounds__(PR_THREADS) seeded_encrypt_kernel(SeededArgs a) {
+    const int lane = threadIdx.x & 63, nb = (a.n + 15) >> 4;
+    uint32_t *ks = reinterpret_cast<uint32_t *>(mkt_smem), *dots = ks + 16 * nb;   // [16 nb] the party's key, zeros behind word n; [2][PR_TILE] the frame's dot products
+    stage_key(ks, a.lwekey, a.n, 16 * nb);
     const int width = a.width, sub = lane & (width - 1), rsub = lane / width, per_pass = 64 / width;
-    const size_t tiles = (a.B + SEEDED_ENC_TILE - 1) / SEEDED_ENC_TILE;
-    int buf = 0;
-    for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x, buf ^= 1) {
-        uint32_t e = 0;
-        if (wave == SQ_DOT_WAVES) {
-            const size_t r = tile * SEEDED_ENC_TILE + lane;
-            if (r < a.B) e = mktrng::row_noise_word(a.nkey, (uint32_t)a.party, mktrng::STREAM_ENC_NOISE, a.row0 + r, a.sigma) + a.in[r];
-        } else {
+    const auto dot = [&](int wave, size_t tile, uint32_t *d) {
 #pragma unroll 1
-            for (int rp = 0; rp < SQ_ROWS; rp += per_pass) {
-                const int rt = wave * SQ_ROWS + rp + rsub;   // row of the tile; rsub < per_pass <= SQ_ROWS
-                const size_t r = tile * SEEDED_ENC_TILE + rt;
-                uint32_t acc = 0;
-                if (r < a.B) {
+        for (int rp = 0; rp < PR_ROWS; rp += per_pass) {
+            const int rt = wave * PR_ROWS + rp + rsub;   // row of the tile; rsub < per_pass <= PR_ROWS
+            const size_t r = tile * PR_TILE + rt;
+            uint32_t acc = 0;
+            if (r < a.B) {
 #pragma unroll 1
-                    for (int bq = sub; bq < nb; bq += width) {
-                        uint32_t x[16];
-                        lane_block(a, r, (uint32_t)bq, x);
-                        const uint4 *kk = reinterpret_cast<const uint4 *>(ks + 16 * bq);
+                for (int bq = sub; bq < nb; bq += width) {
+                    uint32_t x[16];
+                    lane_block(a, r, (uint32_t)bq, x);
+                    const uint4 *kk = reinterpret_cast<const uint4 *>(ks + 16 * bq);
 #pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            const uint4 k4 = kk[i];
-                            acc += x[4 * i] * k4.x + x[4 * i + 1] * k4.y + x[4 * i + 2] * k4.z + x[4 * i + 3] * k4.w;
-                        }
+                    for (int i = 0; i < 4; i++) {
+                        const uint4 k4 = kk[i];
+                        acc += x[4 * i] * k4.x + x[4 * i + 1] * k4.y + x[4 * i + 2] * k4.z + x[4 * i + 3] * k4.w;
                     }
                 }
-                for (int o = width >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-                if (sub == 0) dots[buf * SEEDED_ENC_TILE + rt] = acc;
             }
+            acc = lanes_sum(acc, width);
+            if (sub == 0) d[rt] = 0u - acc;
         }
-        __syncthreads();
-        // (the other waves go on to the next tile and write the other buffer; they meet this wave again at that tile's barrier)
-        if (wave == SQ_DOT_WAVES) {
-            const size_t r = tile * SEEDED_ENC_TILE + lane;
-            if (r < a.B) a.out[r] = e - dots[buf * SEEDED_ENC_TILE + lane];
-        }
-    }
+    };
+    party_rows_tiles(dots, a.B, a.out, dot, [&](size_t r) { return mktrng::row_noise_word(a.nkey, (uint32_t)a.party, mktrng::STREAM_ENC_NOISE, a.row0 + r, a.sigma) + a.in[r]; });
 }
 
 // most keystream blocks that begin in any window of L consecutive words of the span: the begins repeat with the row length, nb per row,
@@ -193,7 +174,7 @@ hipError_t launch_seeded_expand(SeededArgs a, hipStream_t s) {
     if (a.tile_words < 32) return hipErrorInvalidValue;                                               // a block never spans two boundaries
     const uint64_t total = (uint64_t)a.B * (uint64_t)a.lwe_len;
     const uint64_t tiles = (total + a.tile_words - 1) / a.tile_words;
-    const unsigned grid = (unsigned)(tiles < SEEDED_MAX_GRID ? tiles : SEEDED_MAX_GRID);
+    const unsigned grid = (unsigned)(tiles < PR_MAX_GRID ? tiles : PR_MAX_GRID);
     const size_t lds = 2 * (size_t)SE_SLOTS * SE_PITCH * sizeof(uint32_t);
     hipLaunchKernelGGL(seeded_expand_kernel, dim3(grid), dim3(SE_THREADS), lds, s, a);
     return hipGetLastError();
@@ -206,13 +187,7 @@ hipError_t launch_seeded_encrypt(SeededArgs a, hipStream_t s) {
     a.width = 4;
     for (int w = 64; w > 4; w >>= 1)
         if (((nb + w - 1) / w * w - nb) * 8 <= nb) { a.width = w; break; }
-    const size_t tiles = (a.B + SEEDED_ENC_TILE - 1) / SEEDED_ENC_TILE;
-    const unsigned grid = (unsigned)(tiles < SEEDED_MAX_GRID ? tiles : SEEDED_MAX_GRID);
-    const size_t lds = ((size_t)16 * nb + 2 * SEEDED_ENC_TILE) * sizeof(uint32_t);
-    hipError_t e = set_lds(seeded_encrypt_kernel, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(seeded_encrypt_kernel, dim3(grid), dim3(SQ_THREADS), lds, s, a);
-    return hipGetLastError();
+    return launch_party_rows(seeded_encrypt_kernel, a, a.B, (size_t)16 * nb, s);
 }
 
 }  // namespace mktd

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .params import Params
-from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _rows, _seed_arg
+from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _row0, _rows, _seed_arg
 
 
 def _batch_shape(shape, params):
@@ -44,9 +44,7 @@ def partial_decrypt(ctxt, key: PartyKeys, params: Params, party, sigma_smudge, s
     The noise comes from fresh OS randomness per call; deterministic_seed (tests only) pins it, and row0 is then the index of this call's
     first row in a larger batch opened in pieces under that one seed (row j draws the noise of row row0 + j)."""
     sp, _keep = _seed_arg(deterministic_seed)
-    row0 = int(row0)
-    if not 0 <= row0 < 2**64:
-        raise ValueError("row0 must fit 64 bits")
+    row0 = _row0(row0)
     if scheme is not None:
         shape = _batch_shape(tuple(ctxt.shape) if _is_torch(ctxt) else np.shape(ctxt), params)
         B = int(np.prod(shape))

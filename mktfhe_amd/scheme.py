@@ -106,6 +106,14 @@ def _seed_arg(deterministic_seed):
     return C.cast(buf, C.c_void_p), buf
 
 
+def _row0(row0):
+    """the index of a call's first row in a larger batch under one seed, as the library takes it: 64 bits"""
+    row0 = int(row0)
+    if not 0 <= row0 < 2**64:
+        raise ValueError("row0 must fit 64 bits")
+    return row0
+
+
 def CRS(params: Params, deterministic_seed=None):
     """scheme.jl:409-410 CRS(params): l_uni uniform ring polynomials -> (l_uni, N) ring words.
     Fresh OS randomness unless `deterministic_seed` (tests / benchmarks only) pins it."""

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .params import Params
-from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _seed_arg
+from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _row0, _seed_arg
 
 
 class SeededBatch(NamedTuple):
@@ -34,13 +34,6 @@ def _seed32(seed):
         raise ValueError("a mask seed is 32 bytes")
     buf = (C.c_uint8 * 32)(*seed)
     return C.cast(buf, C.c_void_p), buf
-
-
-def _row0(row0):
-    row0 = int(row0)
-    if not 0 <= row0 < 2**64:
-        raise ValueError("row0 must fit 64 bits")
-    return row0
 
 
 def seeded_encrypt(msgs, key: PartyKeys, params: Params, party, *, words=False, scheme=None, mask_seed=None, deterministic_seed=None, row0=0):

@@ -45,6 +45,26 @@ def gpu_scheme(p: mk.Params, crs, keys, device=0, arith=0):
     return mk.setup(p, keys=keys[0], device=device, arith=arith)[1]
 
 
+def party_set(n, nparty):
+    """n words per party block, nparty blocks: CGGI for one block (a single-key scheme), KMS with k parties otherwise"""
+    return mk.CGGIparam.scaled(n=n, N=256) if nparty == 1 else mk.KMS2party.scaled(n=n, N=256, k=nparty)
+
+
+def secret_keys(p, seed=11):
+    """-> [PartyKeys] holding the secrets only (no bootstrapping / key-switching key: for tests that evaluate nothing)"""
+    crs = mk.CRS(p, seed) if p.multikey else None
+    return [mk.PartyKeys(p, party=i, crs=crs, secrets_only=True, deterministic_seed=seed) for i in range(p.nparty)]
+
+
+def to_device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
+
+
+def device_words(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
 def encrypt_bits(p: mk.Params, keys, bits, seed=100):
     """bit j is encrypted under party (j mod nparty) (lwe_ith_encrypt layout, scheme.jl:379-386)"""
     out = np.empty((len(bits), p.lwe_len), dtype=np.uint32)

@@ -10,30 +10,12 @@ import numpy as np
 import pytest
 
 from helpers import ROOT, gpu_scheme, keygen, mk
+from helpers import device_words as _words, party_set as _set, secret_keys as _secrets, to_device as _dev
 
 pytestmark = pytest.mark.gpu
 MASK_SEED = bytes(range(100, 132))
 SEED = 31
 FILL = 0xA5A5A5A5
-
-
-def _set(n, nparty):
-    """n words per party block, nparty blocks: CGGI for one block (a single-key scheme), KMS with k parties otherwise"""
-    return mk.CGGIparam.scaled(n=n, N=256) if nparty == 1 else mk.KMS2party.scaled(n=n, N=256, k=nparty)
-
-
-def _secrets(p, seed=11):
-    crs = mk.CRS(p, seed) if p.multikey else None
-    return [mk.PartyKeys(p, party=i, crs=crs, secrets_only=True, deterministic_seed=seed) for i in range(p.nparty)]
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 # n: below, at and past one keystream block (1, 3, 15, 16, 17) / four blocks less a word, exactly, plus a word (63, 64, 65) / a row longer

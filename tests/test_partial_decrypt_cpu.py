@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import ref_keys as R
-from helpers import ROOT, mk
+from helpers import ROOT, mk, secret_keys as secrets
 from mktfhe_amd import _lib, decrypt as D, scheme as S
 
 # one reduced set per scheme, plus KMS8party and CCS16party: the sizes of tests/test_gpu_parity.py SMALL
@@ -22,12 +22,6 @@ SETS = [
 ]
 IDS = lambda p: f"{p.name}-n{p.n}"      # noqa: E731
 SIGMA = 2.0 ** 20
-
-
-def secrets(p, seed=11):
-    """-> [PartyKeys] holding the secrets only (no bootstrapping / key-switching key: nothing here evaluates)"""
-    crs = mk.CRS(p, seed) if p.multikey else None
-    return [mk.PartyKeys(p, party=i, crs=crs, secrets_only=True, deterministic_seed=seed) for i in range(p.nparty)]
 
 
 def shares_of(p, keys, ct, sigma, seed=5, row0=0):
@@ -206,6 +200,24 @@ def test_partial_decrypt_refusals():
         mk.partial_decrypt(ct[:, :-1], keys[0], p, 0, SIGMA)
     with pytest.raises(ValueError):
         mk.partial_decrypt(ct, keys[0], p, 0, SIGMA, row0=2**64)
+
+
+def test_lwe_decrypt_is_the_bit_rule_on_lwe_phase():
+    """mkt_client_lwe_decrypt decides on mkt_client_lwe_phase's word -- for a multi-key set the bit is phase < 2^31 -- on 64 uniform rows;
+    through the raw ABI a NULL entry in `keys` is MKT_ERR_ARG from either call, as a NULL `keys` is"""
+    p = mk.KMS2party.scaled(n=16, N=256)
+    keys = secrets(p)
+    ct = np.random.default_rng(9).integers(0, 2**32, (64, p.lwe_len), dtype=np.uint64).astype(np.uint32)
+    phase = mk.lwe_phase(ct, keys, p)
+    bits = mk.lwe_decrypt(ct, keys, p)
+    assert bits.dtype == bool and np.array_equal(bits, phase < 2**31) and 0 < bits.sum() < 64
+    L, pc, word = _lib.lib(), C.byref(p.c()), C.c_uint32(SENT)
+    for arr in ((C.c_void_p * 2)(keys[0].h, None), (C.c_void_p * 2)(None, keys[1].h), None):
+        assert L.mkt_client_lwe_decrypt(pc, arr, 2, S._np_ptr(ct[0])) == -1
+        assert L.mkt_client_lwe_phase(pc, arr, 2, S._np_ptr(ct[0]), C.byref(word)) == -1 and word.value == SENT
+    both = (C.c_void_p * 2)(keys[0].h, keys[1].h)
+    assert L.mkt_client_lwe_decrypt(pc, both, 2, S._np_ptr(ct[0])) == int(bits[0])
+    assert L.mkt_client_lwe_decrypt(pc, both, 1, S._np_ptr(ct[0])) == -1       # a party count that is not the set's
 
 
 @pytest.mark.parametrize("fn,dt", [("mkt_client_merge_phase", np.uint32), ("mkt_client_merge_decrypt", np.uint8)])

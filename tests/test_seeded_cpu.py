@@ -9,20 +9,11 @@ import numpy as np
 import pytest
 
 import ref_seeded as RS
-from helpers import ROOT, mk
+from helpers import ROOT, mk, party_set as _set, secret_keys as secrets
 from mktfhe_amd import _lib, scheme as S
 
 MASK_SEED = bytes(range(100, 132))
 ROW0S = (0, 2**32 - 3)          # the second: the row index carries into the high nonce word inside a batch of 4 or more rows
-
-
-def _set(n, nparty):
-    return mk.CGGIparam.scaled(n=n, N=256) if nparty == 1 else mk.KMS2party.scaled(n=n, N=256, k=nparty)
-
-
-def secrets(p, seed=11):
-    crs = mk.CRS(p, seed) if p.multikey else None
-    return [mk.PartyKeys(p, party=i, crs=crs, secrets_only=True, deterministic_seed=seed) for i in range(p.nparty)]
 
 
 def centered(w):
