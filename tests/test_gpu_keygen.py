@@ -3,7 +3,12 @@ coefficient-form bootstrapping key and the key-switching key -- at every shape w
 (idle lanes), both accumulator instantiations on both ring widths, several ring keys, every UniEnc depth, block schemes with the
 LWE key spanning ring keys, n = 1, every key-switch gadget, a key-switch grid smaller than one block, two parties of one seed.
 Then the exported keys of one set per scheme go through the independent opener and statistics of tests/ref_keys.py, so the
-two-sided judgement of the device keys does not rest on client.cpp."""
+two-sided judgement of the device keys does not rest on client.cpp.
+
+At the sets' own noise (sigma <= 2^17) the comparison cannot see the Gaussian deviate's last bits: rint(sigma g) absorbs them (a build
+with contraction on changes a fifth of the deviates and not one of those words, tests/test_rng_cpu.py).  The wide-noise test makes the
+same comparison at sigma = 2^55, where every noise word carries the deviate's mantissa: it is the test that holds "box_muller gives the
+same bits on host and device" for keygen.hip's noise sites."""
 import numpy as np
 import pytest
 
@@ -49,6 +54,54 @@ def test_device_keys_are_the_host_keys_word_for_word(require_gpu, p):
         assert np.array_equal(brk, host.brk), ("bootstrapping key", _id(p), "party", i, "first differing word", int(np.argmax(brk != host.brk)))
         assert np.array_equal(ksk, host.ksk), ("key-switching key", _id(p), "party", i, "first differing word", int(np.argmax(ksk != host.ksk)))
         assert np.array_equal(sd.get_ksk(i).ravel(), host.ksk), "the resident key-switching key is the exported one"
+        made.append(brk.copy())
+    if len(made) == 2:
+        assert not np.array_equal(made[0], made[1]), "two parties of one seed were given one key"
+    sd.close()
+
+
+WIDE = 2.0 ** 55
+WIDE_SHAPES = [p.scaled(alpha=WIDE, beta=WIDE) for p in (
+    mk.CGGIparam.scaled(n=3, N=256), mk.CGGIparam.scaled(n=2, N=2048),          # RGSW kernel, W = 32: 4- and 16-register accumulator
+    mk.KMS2party.scaled(n=3, N=256), mk.KMS2party.scaled(n=2, N=2048),          # RGSW kernel, W = 64
+    mk.CCS2party.scaled(n=3, N=256), mk.CCS2party.scaled(n=2, N=2048),          # UniEnc kernel, both of its noise sites
+    mk.KMS2partyblock.scaled(n=12, N=256, blk_d=4),                             # the block key-switch path
+    mk.CGGIparam.scaled(n=3, N=32), mk.KMS2party.scaled(n=3, N=32))]            # N = 32: idle lanes in fill_noise, on both ring widths
+
+
+def _same_words(got, want, what, p, party):
+    """got == want word for word, or: the set and the party, the key, the first differing word with both words in hex, and how many differ
+    (about a fifth of the noise-carrying words: contraction; a handful: an edge of the deviate or of the rounding)"""
+    got, want = np.asarray(got).ravel(), np.asarray(want).ravel()
+    assert got.dtype == want.dtype and got.size == want.size, (what, _id(p), "party", party, got.dtype, got.size, want.dtype, want.size)
+    bad = np.nonzero(got != want)[0]
+    if len(bad):
+        i = int(bad[0])
+        pytest.fail(f"{what} of {_id(p)}, party {party}: {len(bad)} of {got.size} words differ, the first at word {i}: "
+                    f"device {int(got[i]):#x}, host {int(want[i]):#x}")
+
+
+@pytest.mark.parametrize("p", WIDE_SHAPES, ids=_id)
+def test_device_keys_are_the_host_keys_at_full_mantissa_noise(require_gpu, p):
+    """the comparison of test_device_keys_are_the_host_keys_word_for_word with alpha = beta = 2^55 (the generators take both deviations
+    as free doubles; such keys are useless as keys and exact as a probe).  A deviate has 53 significant bits, so sigma g has its last
+    bit at 2^3 or below and a one-ulp change of g changes the word -- the 64-bit one and its low 32 bits, which is all a 32-bit ring and
+    the key-switching key keep.  The cast stays defined: 2^55 leaves a factor of 256 under 2^63 and the largest |g| the sampler returns is 8.5717
+    (u1 = 2^-53), so (int64_t) rint(sigma g) is in range on both sides."""
+    seed = 9900 + WIDE_SHAPES.index(p)
+    crs = mk.CRS(p, seed) if p.multikey else None
+    sd = mk.Scheme(p)
+    if p.multikey:
+        sd.load_crs(crs)
+    made = []
+    for i in range(min(p.nparty, 2)):                                   # two parties of one seed
+        host = mk.party_keygen(crs, p, party=i, deterministic_seed=seed)
+        secr = mk.party_keygen(crs, p, party=i, secrets_only=True, deterministic_seed=seed)
+        brk, ksk = sd.keygen_device(i, secr, export=True)
+        assert brk.dtype == p.ring_dtype
+        _same_words(brk, host.brk, "bootstrapping key", p, i)
+        _same_words(ksk, host.ksk, "key-switching key", p, i)
+        _same_words(sd.get_ksk(i), host.ksk, "resident key-switching key", p, i)
         made.append(brk.copy())
     if len(made) == 2:
         assert not np.array_equal(made[0], made[1]), "two parties of one seed were given one key"

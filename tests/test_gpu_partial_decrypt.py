@@ -18,11 +18,23 @@ SEED = 31
 
 # n: below a wave, the 16-byte body absent (1, 3) / one lane short of, exactly and one past one 16-byte pass of 16 lanes (63, 64, 65) /
 # one word past a full wave pass of 256 words (257) / several passes with a ragged end (1500).  Every n is admitted by validate_params.
-@pytest.mark.parametrize("n", [1, 3, 63, 64, 65, 257, 1500])
-def test_device_shares_equal_host_shares(require_gpu, n):
+# Both ends of the admitted range 0 <= sigma <= 2^31, one n of each class, the smallest and the largest B: at 0 the share is the dot product
+# alone; at 2^31 the noise word is the low half of a product of up to 2^34.1, the widest cast the call can be asked for.
+CASES = ([pytest.param(n, SIGMA, (1, 63, 64, 65), id=str(n)) for n in (1, 3, 63, 64, 65, 257, 1500)] +
+         [pytest.param(n, s, (1, 65), id=f"{n}-sigma{name}") for n in (3, 64, 257) for s, name in ((0.0, "0"), (2.0**31, "2^31"))])
+
+
+@pytest.mark.parametrize("n, sigma, batches", CASES)
+def test_device_shares_equal_host_shares(require_gpu, n, sigma, batches):
     """nparty in {1, 2, 3} (rows of n + 1, 2 n + 1, 3 n + 1 words: every 16-byte phase of a block start occurs), the first and the last
     party, B in {1, 63, 64, 65} (one tile short, full, one row over), row0 = 0 and 2^32 - 3 (the row index carries into the high nonce
-    word inside the batch), host arrays and device tensors -- the tensor a slice that starts one row into its allocation"""
+    word inside the batch), host arrays and device tensors -- the tensor a slice that starts one row into its allocation.  sigma = 2^20,
+    and at n = 3, 64, 257 also 0 and 2^31, the ends of the admitted range.  At sigma = 0 the device shares of all parties merge to
+    mk.lwe_phase word for word: the definition, on the device.
+    What the equality can and cannot see: the noise word is 32 bits of rint(sigma g) with sigma <= 2^31, and a one-ulp change of the
+    deviate g never reaches it (0 of 4 000 000 words at any such sigma under a contracted build, tests/test_rng_cpu.py).  The cap is part
+    of the contract, so for this translation unit the bit identity of the Gaussian rests on the shared header -- held at sigma = 2^55 by
+    tests/test_gpu_keygen.py and on the host by tests/test_rng_cpu.py -- and on the shared compile flags, held by tests/test_rng_cpu.py."""
     rng = np.random.default_rng(n)
     for nparty in (1, 2, 3):
         p = _set(n, nparty)
@@ -31,13 +43,16 @@ def test_device_shares_equal_host_shares(require_gpu, n):
         ct = rng.integers(0, 2**32, (66, p.lwe_len), dtype=np.uint64).astype(np.uint32)
         ct_d = _dev(ct)
         for party in sorted({0, nparty - 1}):
-            for B in (1, 63, 64, 65):
+            for B in batches:
                 for row0 in (0, 2**32 - 3):
-                    want = mk.partial_decrypt(ct[1:1 + B], keys[party], p, party, SIGMA, deterministic_seed=SEED, row0=row0)
-                    got = mk.partial_decrypt(ct[1:1 + B], keys[party], p, party, SIGMA, scheme=sch, deterministic_seed=SEED, row0=row0)
+                    want = mk.partial_decrypt(ct[1:1 + B], keys[party], p, party, sigma, deterministic_seed=SEED, row0=row0)
+                    got = mk.partial_decrypt(ct[1:1 + B], keys[party], p, party, sigma, scheme=sch, deterministic_seed=SEED, row0=row0)
                     assert isinstance(got, np.ndarray) and np.array_equal(got, want), (nparty, party, B, row0, "host arrays")
-                    got_d = mk.partial_decrypt(ct_d[1:1 + B], keys[party], p, party, SIGMA, scheme=sch, deterministic_seed=SEED, row0=row0)
+                    got_d = mk.partial_decrypt(ct_d[1:1 + B], keys[party], p, party, sigma, scheme=sch, deterministic_seed=SEED, row0=row0)
                     assert got_d.is_cuda and got_d.shape == (B,) and np.array_equal(_words(got_d), want), (nparty, party, B, row0, "device tensors")
+        if sigma == 0.0:
+            shares = [mk.partial_decrypt(ct_d, keys[i], p, i, 0.0, scheme=sch, deterministic_seed=SEED + i) for i in range(nparty)]
+            assert np.array_equal(mk.merge_phase(ct, shares, p), mk.lwe_phase(ct, keys if p.multikey else keys[0], p)), (nparty, "merge at sigma 0")
         sch.close()
 
 

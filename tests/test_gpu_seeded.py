@@ -51,23 +51,40 @@ def test_device_expand_equals_host_expand(require_gpu, n):
         sch.close()
 
 
-@pytest.mark.parametrize("n", NS)
-def test_device_encrypt_equals_host_encrypt(require_gpu, n):
-    """the same grid of n, nparty, party, B and row0; mu a device tensor (and once per set a host array); noise at the set's alpha"""
+# the noise at the set's alpha (2^17) on every n; at n = 3, 64, 257 also at both ends of the admitted range 0 <= sigma <= 2^31, B the smallest
+# and the largest of the grid
+ENC_CASES = ([pytest.param(n, None, (1, 63, 64, 65), id=str(n)) for n in NS] +
+             [pytest.param(n, s, (1, 65), id=f"{n}-sigma{name}") for n in (3, 64, 257) for s, name in ((0.0, "0"), (2.0**31, "2^31"))])
+
+
+@pytest.mark.parametrize("n, sigma, batches", ENC_CASES)
+def test_device_encrypt_equals_host_encrypt(require_gpu, n, sigma, batches):
+    """the same grid of n, nparty, party, B and row0; mu a device tensor (and once per set a host array); noise at the set's alpha, and at
+    n = 3, 64, 257 also at sigma = 0 and 2^31.  At sigma = 0 a batch encrypted on the device, expanded on the device and opened with
+    mk.lwe_phase gives mu word for word: the definition, on the device.
+    What the equality can and cannot see: the noise word is 32 bits of rint(sigma g) with sigma <= 2^31, and a one-ulp change of the
+    deviate g never reaches it (0 of 4 000 000 words at any such sigma under a contracted build, tests/test_rng_cpu.py).  The cap is part
+    of the contract, so for this translation unit the bit identity of the Gaussian rests on the shared header -- held at sigma = 2^55 by
+    tests/test_gpu_keygen.py and on the host by tests/test_rng_cpu.py -- and on the shared compile flags, held by tests/test_rng_cpu.py."""
     rng = np.random.default_rng(100 + n)
     for nparty in (1, 2, 3):
         p = _set(n, nparty)
+        if sigma is not None:
+            p = p.scaled(alpha=sigma)                        # the deviation both calls are given
         keys = _secrets(p)
         sch = mk.Scheme(p)
         mu = rng.integers(0, 2**32, 65, dtype=np.uint64).astype(np.uint32)
         mu_d = _dev(mu)
         for party in sorted({0, nparty - 1}):
-            for B in (1, 63, 64, 65):
+            for B in batches:
                 for row0 in (0, 2**32 - 3):
                     kw = dict(words=True, mask_seed=MASK_SEED, deterministic_seed=SEED, row0=row0)
                     want = mk.seeded_encrypt(mu[:B], keys[party], p, party, **kw).body
                     got = mk.seeded_encrypt(mu_d[:B], keys[party], p, party, scheme=sch, **kw)
                     assert got.body.is_cuda and got.body.shape == (B,) and np.array_equal(_words(got.body), want), (nparty, party, B, row0)
+                    if sigma == 0.0:
+                        rows = mk.seeded_expand(got, p, scheme=sch)
+                        assert rows.is_cuda and np.array_equal(mk.lwe_phase(_words(rows), keys if p.multikey else keys[0], p), mu[:B]), (nparty, party, B, row0)
             got = mk.seeded_encrypt(mu, keys[party], p, party, scheme=sch, words=True, mask_seed=MASK_SEED, deterministic_seed=SEED)
             assert isinstance(got.body, np.ndarray)
             assert np.array_equal(got.body, mk.seeded_encrypt(mu, keys[party], p, party, words=True, mask_seed=MASK_SEED, deterministic_seed=SEED).body)
