@@ -33,6 +33,14 @@ __device__ __forceinline__ cplx cmul_conj(const cplx x, const cplx w) {
     const double a = x.re * w.re, b = x.im * w.im, c = x.re * w.im, d = x.im * w.re;
     cplx r; r.re = a + b; r.im = d - c; return r;
 }
+// A sum that the reference starts from zero(...) and whose first term is known at compile time is started with that
+// term: s = cmul(z, k) instead of cadd(0, cmul(z, k)).  (+0) + p differs from p only for p = -0, so the two differ at
+// most in the sign of zeros.  IEEE add, subtract, multiply, floor, trunc and ldexp map inputs that differ only in the
+// sign of zeros to outputs that differ only in the sign of zeros (by induction over the CMux: transform, multiply-adds,
+// monomial product, inverse transform, untwist), and native() sends both zeros to the word 0 (x - floor(x * 2^-W) * 2^W
+// is +0 for either, and so is the 2^52 sum).  Everything that leaves a kernel is an integer word or a transform of
+// integer words (the phase-1 RLEV rows are fftto! of the integer accumulator), so no output bit changes.  Only
+// intermediates -- the transform-domain sums tacc / t2 in registers -- may hold -0 where they held +0.
 __device__ __forceinline__ cplx cadd(const cplx x, const cplx y) { cplx r; r.re = x.re + y.re; r.im = x.im + y.im; return r; }
 __device__ __forceinline__ cplx csub(const cplx x, const cplx y) { cplx r; r.re = x.re - y.re; r.im = x.im - y.im; return r; }
 
@@ -495,12 +503,19 @@ template <typename WORD>
 __device__ __forceinline__ double word_to_f64(WORD x) { return (double)(typename WordTraits<WORD>::S)x; }
 
 // arithmetic.jl:1-9 native(x, mask):  x -= floor(x * 2^-W) * 2^W;  x == 2^W ? 0 : trunc_to_unsigned(x)
-// The reduction is the reference's two operations (the scaling by a power of two is exact, the subtraction rounds as
-// it does there) and leaves y in [0, 2^W].  The conversion is done without v_cvt / v_cmp / v_cndmask: for an integer v
-// in [0, 2^32] the low dword of the double v + 2^52 is v mod 2^32 (the sum is exact below 2^53), which maps the one
-// special value 2^W -- the rounded-up sum of a tiny negative x and 2^W -- to 0 exactly like the reference's test.
-// MKT_NATIVE_MAGIC 0 keeps the literal compare-and-convert form (same bits: tests/csrc/native_check.cpp compares the two
-// forms on 46 M inputs of every magnitude class on the host).
+// The reduction rounds once, in the subtraction, as it does in the reference, and leaves y in [0, 2^W].  The conversion
+// is done without v_cmp / v_cndmask: for an integer v in [0, 2^32] the low dword of the double v + 2^52 is v mod 2^32 (the
+// sum is exact below 2^53), which maps the one special value 2^W -- the rounded-up sum of a tiny negative x and 2^W -- to
+// 0 exactly like the reference's test.
+// Steps that are exact are fused into their neighbour (explicit FMA builtins; contraction stays off everywhere):
+//   1. q = floor(x * 2^-W) is an integer and q * 2^W a scaling by a power of two, so the product is exact and
+//      fma(q, -2^W, x) rounds x - q * 2^W once -- the reference's one rounding, one instruction instead of two.
+//   2. 64-bit ring: with x in [0, 2^64] and hi = trunc(x * 2^-32), hi * 2^32 is exact and x - hi * 2^32 is the low bits
+//      of x's significand, a value in [0, 2^32) that needs no rounding at all: fma(hi, -2^32, x) gives the same double.
+//   3. that low part is in [0, 2^32), so one truncating convert (v_cvt_u32_f64 rounds toward zero) replaces trunc and the
+//      2^52 sum.  hi keeps the sum: it is the half that can be 2^32 and must become 0.
+// MKT_NATIVE_MAGIC 0 keeps the literal compare-and-convert form (same bits: tests/csrc/native_check.cpp and
+// tests/csrc/native_fused_check.cpp compare the forms on inputs of every magnitude class on the host).
 #ifndef MKT_NATIVE_MAGIC
 #define MKT_NATIVE_MAGIC 1
 #endif
@@ -511,22 +526,31 @@ __device__ __forceinline__ uint32_t low_dword_of_sum_2p52(double v) {
     const double s = v + 4503599627370496.0;   // 2^52
     return (uint32_t)__double2loint(s);
 }
+// the two 32-bit halves of native<uint64_t>(x)
+__device__ __forceinline__ void native_halves(double x, uint32_t &h, uint32_t &l) {
+    x = __builtin_fma(floor(x * 5.421010862427522e-20), -1.8446744073709552e19, x);
+    const double hi = trunc(x * 2.3283064365386963e-10);    // in [0, 2^32], exact
+    const double lo = __builtin_fma(hi, -4.294967296e9, x);  // exact difference in [0, 2^32)
+    h = low_dword_of_sum_2p52(hi);
+    l = (uint32_t)lo;                                        // fraction dropped
+}
 template <typename WORD> __device__ __forceinline__ WORD native(double x);
 template <> __device__ __forceinline__ uint32_t native<uint32_t>(double x) {
-    x -= floor(x * 2.3283064365386963e-10) * 4.294967296e9;
 #if MKT_NATIVE_MAGIC
+    x = __builtin_fma(floor(x * 2.3283064365386963e-10), -4.294967296e9, x);
     return low_dword_of_sum_2p52(trunc(x));                  // trunc, as the reference (x >= 0 unless x * 2^-W underflowed)
 #else
+    x -= floor(x * 2.3283064365386963e-10) * 4.294967296e9;
     return x == 4.294967296e9 ? 0u : (uint32_t)x;
 #endif
 }
 template <> __device__ __forceinline__ uint64_t native<uint64_t>(double x) {
-    x -= floor(x * 5.421010862427522e-20) * 1.8446744073709552e19;
 #if MKT_NATIVE_MAGIC
-    const double hi = trunc(x * 2.3283064365386963e-10);    // in [0, 2^32], exact
-    const double lo = trunc(x - hi * 4.294967296e9);        // exact difference in [0, 2^32), fraction dropped
-    return ((uint64_t)low_dword_of_sum_2p52(hi) << 32) | (uint64_t)low_dword_of_sum_2p52(lo);
+    uint32_t h, l;
+    native_halves(x, h, l);
+    return ((uint64_t)h << 32) | (uint64_t)l;
 #else
+    x -= floor(x * 5.421010862427522e-20) * 1.8446744073709552e19;
     return x == 1.8446744073709552e19 ? (uint64_t)0 : (uint64_t)x;
 #endif
 }
@@ -537,10 +561,8 @@ template <typename WORD> __device__ __forceinline__ WORD native_add(WORD acc, do
 template <> __device__ __forceinline__ uint32_t native_add<uint32_t>(uint32_t acc, double x) { return acc + native<uint32_t>(x); }
 template <> __device__ __forceinline__ uint64_t native_add<uint64_t>(uint64_t acc, double x) {
 #if MKT_NATIVE_MAGIC && MKT_NATIVE_CARRY
-    x -= floor(x * 5.421010862427522e-20) * 1.8446744073709552e19;
-    const double hi = trunc(x * 2.3283064365386963e-10);
-    const double lo = trunc(x - hi * 4.294967296e9);
-    const uint32_t h = low_dword_of_sum_2p52(hi), l = low_dword_of_sum_2p52(lo);
+    uint32_t h, l;
+    native_halves(x, h, l);
     const uint32_t al = (uint32_t)acc, s = al + l;
     const uint32_t ah = (uint32_t)(acc >> 32) + h + (s < l ? 1u : 0u);
     return ((uint64_t)ah << 32) | s;

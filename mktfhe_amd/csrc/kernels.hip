@@ -435,7 +435,8 @@ void blindrotate_k1_kernel(const RotArgs a) {
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        cplx tacc[LB][2][R];
+        cplx tacc[LB][2][R];                                             // (the zeros are dead only where LB == 1 and the first term below assigns: a key bit
+                                                                         // with ats[q] == 0 skips that assignment)
 #pragma unroll
         for (int q = 0; q < LB; q++)
 #pragma unroll
@@ -470,8 +471,16 @@ void blindrotate_k1_kernel(const RotArgs a) {
 #pragma unroll
                     for (int e = 0; e < R; e++) {                        // :63-68 muladdto!(tacc, digit, row)
                         const cplx kb = table_load(rs_brk, vo_dev[e], so_row), ka = table_load(rs_brk, vo_dev[e], so_row + (unsigned)(M * sizeof(cplx)));
-                        tacc[q][0][e] = cadd(tacc[q][0][e], cmul(z[h2][e], kb));
-                        tacc[q][1][e] = cadd(tacc[q][1][e], cmul(z[h2][e], ka));
+                        // first term of the sum, static once the loop is unrolled: no add to the zero (fft_device.h, cadd).  Not in the block kernels
+                        // at three waves per SIMD: they spill at 168 registers, and the assignment moved 63 more spill instructions into the loop
+                        // of the l = 4 instantiation (the others +-6)
+                        if (LT > 0 && (LB == 1 || RotOcc<LOGM, NB>::MINW < 3) && g0 + h2 == 0) {
+                            tacc[q][0][e] = cmul(z[h2][e], kb);
+                            tacc[q][1][e] = cmul(z[h2][e], ka);
+                        } else {
+                            tacc[q][0][e] = cadd(tacc[q][0][e], cmul(z[h2][e], kb));
+                            tacc[q][1][e] = cadd(tacc[q][1][e], cmul(z[h2][e], ka));
+                        }
                         if (RotOcc<LOGM, NB>::MINW >= 3) __builtin_amdgcn_sched_barrier(0);   // keep the key-row live ranges short at 3 waves/SIMD
                     }
                 }
@@ -2065,11 +2074,10 @@ __global__ __launch_bounds__((2 * LT * Plan<LOGM, LR>::NT)) void blindrotate_wid
             for (int e = 0; e < R; e++) stage[e * NT + t] = ph ? pa[e] : pb[e];
             __syncthreads();
             if (c == ph && j == 0) {
-                czero(ts);
 #pragma unroll
-                for (int g = 0; g < G; g++)
+                for (int g = 0; g < G; g++)                              // the sum starts with its first product, not from a zero (fft_device.h, cadd)
 #pragma unroll
-                    for (int e = 0; e < R; e++) ts[e] = cadd(ts[e], region[(size_t)g * M + e * NT + t]);
+                    for (int e = 0; e < R; e++) ts[e] = g == 0 ? region[e * NT + t] : cadd(ts[e], region[(size_t)g * M + e * NT + t]);
             }
         }
         // :71-73 once per polynomial, by the group of its digit 0; the other groups of that polynomial only keep the
