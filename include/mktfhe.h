@@ -538,6 +538,66 @@ int mkt_seeded_expand_batch(mkt_ctx *ctx, int party, const uint8_t *mask_seed, u
 int mkt_seeded_encrypt_batch(mkt_ctx *ctx, int party, const mkt_client_party *keys, const uint32_t *mu, double sigma_lwe, const uint8_t *mask_seed,
                              const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B, int mem);
 
+/* ---- seeded evaluation keys: almost all of a party's two large keys is public randomness -- every key-switching-key row is n uniform words
+ *      and one body word, every RLWE sample of the bootstrapping key kr uniform polynomials and one body polynomial.  A party therefore ships a
+ *      PUBLIC 256-bit mask seed and the bodies (the COMPACT sections below), and the evaluator regenerates the masks on its GPU, where the
+ *      resident tables live.  This is a key form of its own beside mkt_client_party_keygen, whose calls, streams and words are unchanged; the
+ *      expanded keys are ordinary keys in the layouts at the top of this header.  New symbols only: MKT_ABI_VERSION is unchanged.
+ *      STREAMS.  Keyed by the PUBLIC mask seed, read as 32-bit words with every keystream word used (as stream 10 of the seeded ciphertexts):
+ *      12, key-switching-key mask; 13, bootstrapping-key mask.  Keyed by the party's SECRET seed (the `seed` of the keygen call), 64-bit draws
+ *      as every other secret stream: 14 noise of the RGSW bootstrapping key, 15 noise of the key-switching key, 16 UniEnc (CCS).  Streams 1, 3, 4
+ *      are those of mkt_client_party_keygen: with the same seed the secrets, the public key and the relinearisation key are the same, word for
+ *      word.  Streams 2 and 5 are not read: a party that publishes both key forms from one seed shares no noise between them.
+ *      KEY-SWITCHING KEY.  Row index R = ((c N + j) Drows + d) f + t.  Mask word q < n of row R is 32-bit word (q & 15) of
+ *      chacha20_block(key(mask_seed), q >> 4, {12 | party << 16, lo32(R), hi32(R)}); the surplus of a row's last block is dropped.
+ *      e_R = (uint32_t) Rng(key(seed), party, 15, lo32(R), hi32(R)).noise(sigma_lwe), the first draw of the row's stream.
+ *      body[R] = e_R - sum_q a_R[q] * s[q] + msg(c, j, d, t),  msg = ((d + 1) z_c[j]) << (32 - (t + 1) logD)  (mod 2^32, wrapping uint32_t
+ *      arithmetic, the key word multiplied; z = the uni key for the KMS schemes).  For the block schemes (MKT_LMSS, MKT_KMS_BLOCK) the rows
+ *      with c N + j < n are absent (keygen.jl:46,:147): their body is 0, and expansion leaves the whole row zero without generating a mask.
+ *      BOOTSTRAPPING KEY, RGSW (all schemes but MKT_CCS).  Sample index S = i rows + c l_gsw + j (key bit i, rows = (kr + 1) l_gsw, row
+ *      (c, j) as in the BRK layout above); mask polynomial index P = S kr + cc.  Coefficient q of mask polynomial P comes from
+ *      chacha20_block(key(mask_seed), blk, {13 | party << 16, lo32(P), hi32(P)}): on the 32-bit ring word (q & 15) of block q >> 4, on the
+ *      64-bit ring  w[2 (q & 7)] | w[2 (q & 7) + 1] << 32  of block q >> 3.  Noise: Rng(key(seed), party, 14, lo32(S), hi32(S)), N draws
+ *      noise(sigma_ring) in coefficient order.  THE MESSAGE IS IN THE BODY: for every row a_cc is the public mask unmodified, and
+ *          b = -sum_cc a_cc z_cc + e + s_i g_j m_c,    g_j = 2^(W - (j + 1) logB_gsw),  m_0 = 1 (coefficient 0 only),  m_c = z_{c-1} for c >= 1.
+ *      The reference adds s_i g_j to coefficient 0 of the MASK a_{c-1} (gsw.jl:174-178); under a public mask that word would reveal s_i.
+ *      a -> a + s_i g_j X^0 is a bijection on uniform masks, so the distribution is the reference's, the phase b + sum a z =
+ *      e + s_i g_j z_{c-1} is the same, and the expanded key is an ordinary key.
+ *      BOOTSTRAPPING KEY, UniEnc (MKT_CCS).  d_j = crs_j r + s_i g_j + e depends on the common CRS, not on a fresh mask: the d rows ship in
+ *      full.  f_j = (b, a): a = mask polynomial P = i l_uni + j of stream 13 as above, b = -a z + e + g_j r.  ONE secret stream per key bit,
+ *      Rng(key(seed), party, 16, i), read in this order: N draws next() % 3 - 1 (the ternary r); then for j = 0 .. l_uni - 1: N draws
+ *      noise(sigma_ring) for d_j, N draws noise(sigma_ring) for f_j.b, each in coefficient order.
+ *      COMPACT LAYOUTS.  ksk_seeded: uint32 [kr][N][Drows][f], bodies only (index R).  brk_seeded, RGSW: [n][(kr + 1) l_gsw][N] ring words,
+ *      the b polynomials (index S).  brk_seeded, CCS: [n][2 l_uni][N]: d_0 .. d_{l-1}, then f_0.b .. f_{l-1}.b.  Expansion yields exactly the
+ *      MKT_FMT_INT_COEFF layout of mkt_load_brk and the layout of mkt_load_ksk.
+ *      TRUST.  The mask seed is NOT a secret: it travels with the bodies, and anyone may expand.  The secret seed is, as ever.
+ *      A (MASK SEED, PARTY) PAIR SERVES ONE KEY GENERATION.  TWO GENERATIONS UNDER IT SHARE THEIR MASKS, AND THEIR BODIES DIFFER BY NOISE
+ *      ALONE (under one secret) OR BY <a, s - s'> (under two).  Draw a fresh mask seed (mkt_client_random_seed) per generation.
+ *      REFUSALS (MKT_ERR_ARG): mask_seed NULL; seed given and bytewise equal to mask_seed (publishing the one would publish the secrets);
+ *      party out of range; a compact section without its output or the reverse (expansion).
+ *      NOT SEEDED: the small keys (public key, relinearisation key: O(l) polynomials), which ship as before. ---- */
+/* one party's secrets, small keys and the compact sections; mkt_client_brk / _ksk are empty on it, as after mkt_client_party_secrets */
+int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed, const uint8_t *mask_seed, int party, const void *crs,
+                                   double sigma_lwe, double sigma_ring, mkt_client_party **out);
+const void *mkt_client_brk_seeded(const mkt_client_party *p, size_t *bytes);      /* compact layout above; valid until destroy */
+const uint32_t *mkt_client_ksk_seeded(const mkt_client_party *p, size_t *bytes);
+const uint8_t *mkt_client_mask_seed(const mkt_client_party *p);                   /* 32 bytes; NULL unless the party is a seeded one */
+/* the definition of expansion, host only, needs no key: brk_out in the MKT_FMT_INT_COEFF layout of mkt_load_brk, ksk_out in the layout of
+ * mkt_load_ksk.  Either pair (brk_seeded, brk_out) / (ksk_seeded, ksk_out) may be NULL */
+int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded,
+                                  void *brk_out, uint32_t *ksk_out);
+/* the same words written by the GPU of `ctx` into caller memory; the four arrays live in `mem` (device pointers 16-byte aligned).  Needs no
+ * key loaded and changes no resident table */
+int mkt_seeded_keys_expand(mkt_ctx *ctx, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, void *brk_out,
+                           uint32_t *ksk_out, int mem);
+/* the evaluator's call (host pointers in; either section may be NULL): the resident state of mkt_load_brk + mkt_load_ksk fed with the host
+ * expansion, including the Float64-pipe limbs and "fx_bound" of an MKT_ARITH_EXACT context.  The expanded key never travels to the host: the
+ * key-switching key is generated into its resident table, the bootstrapping key into the coefficient-form staging buffer mkt_keygen_device
+ * uses and pre-transformed from there; peak extra device memory = that buffer plus the compact sections.  MKT_ERR_STATE once the key set is
+ * shared (mkt_ctx_fork); MKT_ERR_UNSUPPORTED where mkt_load_brk is */
+int mkt_load_seeded_keys(mkt_ctx *ctx, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded);
+int mkt_multi_load_seeded_keys(mkt_multi *m, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded);
+
 #ifdef __cplusplus
 }
 #endif

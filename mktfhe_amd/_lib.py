@@ -133,6 +133,14 @@ SYMBOLS = {
     "mkt_client_seeded_expand": (_i, [_pp, _i, _vp, _u64, _vp, _vp, _sz]),
     "mkt_seeded_expand_batch": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _sz, _i]),
     "mkt_seeded_encrypt_batch": (_i, [_vp, _i, _vp, _vp, _dbl, _vp, _vp, _u64, _vp, _sz, _i]),
+    "mkt_client_party_keygen_seeded": (_i, [_pp, _vp, _vp, _i, _vp, _dbl, _dbl, C.POINTER(_vp)]),
+    "mkt_client_brk_seeded": (_vp, [_vp, C.POINTER(_sz)]),
+    "mkt_client_ksk_seeded": (_vp, [_vp, C.POINTER(_sz)]),
+    "mkt_client_mask_seed": (_vp, [_vp]),
+    "mkt_client_seeded_keys_expand": (_i, [_pp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mkt_seeded_keys_expand": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "mkt_load_seeded_keys": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "mkt_multi_load_seeded_keys": (_i, [_vp, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

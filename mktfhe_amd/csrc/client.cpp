@@ -502,3 +502,181 @@ int mkt_client_seeded_expand(const mkt_params *params, int party, const uint8_t 
 }
 
 }  // extern "C"
+
+// ---- seeded evaluation keys (mktfhe.h): a public mask seed and the bodies of the two large keys; these functions are the definition ----
+
+namespace {
+
+// mask polynomial P of the bootstrapping key (stream 13) as ring words
+void brk_mask_poly(const uint32_t mkey[8], uint32_t party, uint64_t P, int N, int W, uint64_t *a) {
+    uint32_t w[16];
+    if (W == 32) for (int q0 = 0; q0 < N; q0 += 16) {
+        mktrng::stream_block(mkey, mktrng::STREAM_BRK_MASK, party, P, (uint32_t)(q0 >> 4), w);
+        for (int i = 0; i < 16; i++) a[q0 + i] = w[i];
+    } else for (int q0 = 0; q0 < N; q0 += 8) {
+        mktrng::stream_block(mkey, mktrng::STREAM_BRK_MASK, party, P, (uint32_t)(q0 >> 3), w);
+        for (int i = 0; i < 8; i++) a[q0 + i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    }
+}
+// the n mask words of key-switching-key row R (stream 12)
+void ksk_mask_row(const uint32_t mkey[8], uint32_t party, uint64_t R, int n, uint32_t *row) {
+    uint32_t w[16];
+    for (int q0 = 0; q0 < n; q0 += 16) {
+        mktrng::stream_block(mkey, mktrng::STREAM_KSK_MASK, party, R, (uint32_t)(q0 >> 4), w);
+        for (int i = 0; i < 16 && q0 + i < n; i++) row[q0 + i] = w[i];
+    }
+}
+// the rows (c, j) a block scheme leaves out: inside the embedded LWE key (keygen.jl:46,:147)
+inline bool ksk_row_absent(const mkt_params &p, long cj) { return is_block(p.scheme) && cj < p.n; }
+
+}  // namespace
+
+extern "C" {
+
+int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed, const uint8_t *mask_seed, int party, const void *crs,
+                                   double sigma_lwe, double sigma_ring, mkt_client_party **out) {
+    if (!mask_seed) return MKT_ERR_ARG;
+    if (seed && std::memcmp(seed, mask_seed, 32) == 0) return MKT_ERR_ARG;      // the mask seed is published: the secrets would be too
+    mkt_client_party *K = nullptr;
+    if (int r = party_keygen_impl(params, seed, party, crs, sigma_lwe, sigma_ring, false, &K)) return r;
+    const mkt_params &p = K->p;
+    const Shape &sh = K->sh;
+    const int N = p.N, n = p.n, W = p.W;
+    const uint64_t wm = wmask(W);
+    const uint32_t *ps = K->key; const uint32_t pa = (uint32_t)party;
+    uint32_t mkey[8];
+    seed_to_key(mask_seed, mkey);
+    K->seeded = true;
+    std::memcpy(K->mask_seed, mask_seed, 32);
+    K->brk_seeded.assign(brk_seeded_polys(p, sh) * N * sh.word, 0);
+    if (p.scheme != MKT_CCS) {
+        // RGSW_z(s_i) with the message in the body: row (c, j) is (b, a_0 ..) with the a_cc the public masks as they are and
+        // b = -sum a_cc z_cc + e + s_i g_j m_c, m_0 = 1, m_c = z_{c-1}: the phase of gsw.jl:174-178, which adds s_i g_j to a_{c-1}[0]
+        const int kr = sh.kr, l = p.l_gsw, rows = (kr + 1) * l;
+        parallel_for(n, [&](int i) {
+            std::vector<uint64_t> a(N), b(N);
+            for (int c = 0; c <= kr; c++) for (int j = 0; j < l; j++) {
+                const uint64_t S = (uint64_t)i * rows + (uint64_t)c * l + j;
+                std::fill(b.begin(), b.end(), 0);
+                for (int cc = 0; cc < kr; cc++) {
+                    brk_mask_poly(mkey, pa, S * kr + cc, N, W, a.data());
+                    mul_small_acc(a.data(), K->zring[cc].data(), b.data(), N, true);
+                }
+                Rng r(ps, pa, mktrng::STREAM_BRK_NOISE, (uint32_t)S, (uint32_t)(S >> 32));
+                const uint64_t g = (uint64_t)K->lwekey[i] << (W - (j + 1) * p.logB_gsw);
+                for (int q = 0; q < N; q++) {
+                    const uint64_t m = c == 0 ? (q == 0 ? 1u : 0u) : (uint64_t)K->zring[c - 1][q];
+                    b[q] = (b[q] + r.noise(sigma_ring) + g * m) & wm;
+                }
+                store_poly(K->brk_seeded, S, b.data(), N, W);
+            }
+        });
+    } else {
+        // UniEnc_z(s_i): d_j = crs_j r + s_i g_j + e ships whole (its "mask" is the common CRS); f_j = RLWE_z(g_j r) ships its body
+        const int l = p.l_uni;
+        parallel_for(n, [&](int i) {
+            Rng r(ps, pa, mktrng::STREAM_UNI_NOISE, (uint32_t)i);
+            std::vector<int8_t> rt(N);
+            for (int q = 0; q < N; q++) rt[q] = (int8_t)((int)(r.next() % 3) - 1);
+            std::vector<uint64_t> a(N), d(N);
+            for (int j = 0; j < l; j++) {
+                const uint64_t g = 1ull << (W - (j + 1) * p.logB_uni);
+                load_poly(crs, j, a.data(), N, W);
+                std::fill(d.begin(), d.end(), 0);
+                mul_small_acc(a.data(), rt.data(), d.data(), N, false);
+                d[0] += (uint64_t)K->lwekey[i] * g;
+                for (int q = 0; q < N; q++) d[q] = (d[q] + r.noise(sigma_ring)) & wm;
+                store_poly(K->brk_seeded, (size_t)i * 2 * l + j, d.data(), N, W);
+                brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data());
+                std::fill(d.begin(), d.end(), 0);
+                mul_small_acc(a.data(), K->zring[0].data(), d.data(), N, true);
+                for (int q = 0; q < N; q++) d[q] = (d[q] + r.noise(sigma_ring) + g * (uint64_t)(int64_t)rt[q]) & wm;
+                store_poly(K->brk_seeded, (size_t)i * 2 * l + l + j, d.data(), N, W);
+            }
+        });
+    }
+    {
+        const int f = p.f, logD = p.logD, dr = sh.ksk_drows, kk = sh.ksk_kr;
+        const int zoff = is_kms(p.scheme) ? 1 : 0;
+        K->ksk_seeded.assign(ksk_rows(p, sh), 0);
+        parallel_for(kk * N, [&](int cj) {
+            if (ksk_row_absent(p, cj)) return;
+            const int c = cj / N, j = cj % N;
+            std::vector<uint32_t> row(n);
+            for (int d = 0; d < dr; d++) for (int t = 0; t < f; t++) {
+                const uint64_t R = ((uint64_t)cj * dr + d) * f + t;
+                const uint32_t msg = (uint32_t)((uint32_t)K->zring[zoff + c][j] * (uint32_t)(d + 1)) << (32 - (t + 1) * logD);
+                ksk_mask_row(mkey, pa, R, n, row.data());
+                uint32_t dot = 0;
+                for (int q = 0; q < n; q++) dot += row[q] * K->lwekey[q];
+                K->ksk_seeded[R] = mktrng::row_noise_word(ps, pa, mktrng::STREAM_KSK_NOISE, R, sigma_lwe) - dot + msg;
+            }
+        });
+    }
+    *out = K;
+    return MKT_OK;
+}
+
+const void *mkt_client_brk_seeded(const mkt_client_party *p, size_t *bytes) { if (bytes) *bytes = p ? p->brk_seeded.size() : 0; return p ? p->brk_seeded.data() : nullptr; }
+const uint32_t *mkt_client_ksk_seeded(const mkt_client_party *p, size_t *bytes) { if (bytes) *bytes = p ? p->ksk_seeded.size() * 4 : 0; return p ? p->ksk_seeded.data() : nullptr; }
+const uint8_t *mkt_client_mask_seed(const mkt_client_party *p) { return p && p->seeded ? p->mask_seed : nullptr; }
+
+// the ordinary keys of a seeded party: the layouts of mkt_load_brk (MKT_FMT_INT_COEFF) and mkt_load_ksk; needs no key
+int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded,
+                                  void *brk_out, uint32_t *ksk_out) {
+    if (!params || !mask_seed) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
+    if (!brk_seeded != !brk_out || !ksk_seeded != !ksk_out) return MKT_ERR_ARG;
+    const int N = p.N, n = p.n, W = p.W;
+    const uint32_t pa = (uint32_t)party;
+    uint32_t mkey[8];
+    seed_to_key(mask_seed, mkey);
+    const size_t pb = (size_t)N * sh.word;
+    if (brk_out && p.scheme != MKT_CCS) {
+        const int kr = sh.kr;
+        const size_t samples = (size_t)n * (kr + 1) * p.l_gsw;
+        parallel_for((int)samples, [&](int S) {
+            std::vector<uint64_t> a(N);
+            uint8_t *o = (uint8_t *)brk_out + (size_t)S * (kr + 1) * pb;
+            std::memcpy(o, (const uint8_t *)brk_seeded + (size_t)S * pb, pb);
+            for (int cc = 0; cc < kr; cc++) {
+                brk_mask_poly(mkey, pa, (uint64_t)S * kr + cc, N, W, a.data());
+                if (W == 64) std::memcpy(o + (size_t)(1 + cc) * pb, a.data(), pb);
+                else { uint32_t *d = (uint32_t *)(o + (size_t)(1 + cc) * pb); for (int q = 0; q < N; q++) d[q] = (uint32_t)a[q]; }
+            }
+        });
+    } else if (brk_out) {
+        const int l = p.l_uni;
+        parallel_for(n, [&](int i) {
+            std::vector<uint64_t> a(N);
+            const uint8_t *src = (const uint8_t *)brk_seeded + (size_t)i * 2 * l * pb;
+            uint8_t *o = (uint8_t *)brk_out + (size_t)i * 3 * l * pb;
+            std::memcpy(o, src, (size_t)l * pb);
+            for (int j = 0; j < l; j++) {
+                std::memcpy(o + (size_t)(l + 2 * j) * pb, src + (size_t)(l + j) * pb, pb);
+                brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data());
+                uint8_t *d8 = o + (size_t)(l + 2 * j + 1) * pb;
+                if (W == 64) std::memcpy(d8, a.data(), pb);
+                else { uint32_t *d = (uint32_t *)d8; for (int q = 0; q < N; q++) d[q] = (uint32_t)a[q]; }
+            }
+        });
+    }
+    if (ksk_out) {
+        const size_t per = (size_t)sh.ksk_drows * p.f, n1 = (size_t)n + 1;
+        parallel_for(sh.ksk_kr * N, [&](int cj) {
+            for (size_t u = 0; u < per; u++) {
+                const uint64_t R = (uint64_t)cj * per + u;
+                uint32_t *row = ksk_out + R * n1;
+                if (ksk_row_absent(p, cj)) { std::memset(row, 0, n1 * 4); continue; }
+                ksk_mask_row(mkey, pa, R, n, row);
+                row[n] = ksk_seeded[R];
+            }
+        });
+    }
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -1129,6 +1129,66 @@ int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, c
     return so.out(body_out);
 }
 
+// Seeded evaluation keys (mktfhe.h): party `party`'s two large keys regenerated on this context's device from the public mask seed and the
+// compact sections (seeded_keys.hip), the words of mkt_client_seeded_keys_expand.  load: into the resident tables -- the bootstrapping key
+// through the coefficient-form staging buffer keygen_device_impl uses and the same to_resident, the key-switching key straight into its
+// table at the padded pitch; else into the caller's brk_out / ksk_out (`mem`), the compact sections living there too.  Nothing is secret.
+static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, bool load,
+                            void *brk_out, uint32_t *ksk_out, int mem) {
+    if (!c || !mask_seed || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!load && (!brk_seeded != !brk_out || !ksk_seeded != !ksk_out)) return fail(c, MKT_ERR_ARG, "mkt_seeded_keys_expand: a compact section and its output come together");
+    const mkt_params &p = c->p;
+    DevGuard dg(c->device);
+    const size_t body_polys = mkt::brk_seeded_polys(p, c->sh), brk_polys_total = (size_t)p.n * c->sh.brk_polys, rows = mkt::ksk_rows(p, c->sh);
+    Staged sb{c}, sk{c}, so{c};
+    DevBuf full, padded;                    // load: the expanded bootstrapping key in coefficient form; expand: the key-switching key at the padded pitch
+    int r;
+    hipError_t e = hipSuccess;
+    if (brk_seeded) {
+        if ((r = sb.in(brk_seeded, body_polys * poly_bytes(c), mem, true))) return r;
+        void *dst;
+        if (load) { HIPCHK(c, hipMalloc(&full.p, brk_polys_total * poly_bytes(c))); dst = full.p; }
+        else { if ((r = so.in(brk_out, brk_polys_total * poly_bytes(c), mem, false))) return r; dst = so.dev; }
+        mktd::SeededBrkArgs a{};
+        mkt::seed_to_key(mask_seed, a.mkey);
+        a.party = party; a.unienc = p.scheme == MKT_CCS; a.kr = c->sh.kr; a.l = a.unienc ? p.l_uni : p.l_gsw;
+        a.log_units = c->logN + (p.W == 64 ? 1 : 0) - 4; a.body = sb.dev; a.out = dst; a.npolys = brk_polys_total;
+        e = mktd::launch_seeded_brk_expand(a, c->stream);
+        if (e == hipSuccess && load) e = to_resident(c, dst, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
+        if (e != hipSuccess) return hipfail(c, e, "seeded bootstrapping key expansion");
+    }
+    if (ksk_seeded) {
+        if ((r = sk.in(ksk_seeded, rows * 4, mem, true))) return r;
+        uint32_t *dst = c->ks->party<uint32_t>(T_KSK, party);
+        if (!load) { HIPCHK(c, hipMalloc(&padded.p, rows * (size_t)c->ks->n1p * 4)); dst = (uint32_t *)padded.p; }
+        mktd::SeededKskArgs a{};
+        mkt::seed_to_key(mask_seed, a.mkey);
+        a.party = party; a.n = p.n; a.n1p = c->ks->n1p; a.rows_per_cj = (uint32_t)(c->sh.ksk_drows * p.f);
+        a.absent_below = mkt::is_block(p.scheme) ? p.n : 0; a.body = (const uint32_t *)sk.dev; a.out = dst; a.rows = rows;
+        e = mktd::launch_seeded_ksk_expand(a, c->stream);
+        const size_t n1 = (size_t)p.n + 1;
+        if (e == hipSuccess && !load) e = hipMemcpy2DAsync(ksk_out, n1 * 4, dst, (size_t)c->ks->n1p * 4, n1 * 4, rows, mem == MKT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream);
+        if (e != hipSuccess) return hipfail(c, e, "seeded key-switching key expansion");
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!load) return brk_out ? so.out(brk_out) : MKT_OK;
+    if (brk_seeded) c->ks->brk_loaded[party] = 1;
+    if (ksk_seeded) c->ks->ksk_loaded[party] = 1;
+    if (brk_seeded && c->ks->d_fx_brk) return fx_after_key_load(c);
+    return MKT_OK;
+}
+
+int mkt_seeded_keys_expand(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, void *brk_out, uint32_t *ksk_out, int mem) {
+    return seeded_keys_impl(c, party, mask_seed, brk_seeded, ksk_seeded, false, brk_out, ksk_out, mem);
+}
+
+int mkt_load_seeded_keys(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded) {
+    if (!c || (!brk_seeded && !ksk_seeded)) return fail(c, MKT_ERR_ARG, "bad argument");
+    MKT_EXACT_GATE(c);
+    if (int w = keys_writable(c)) return w;
+    return seeded_keys_impl(c, party, mask_seed, brk_seeded, ksk_seeded, true, nullptr, nullptr, MKT_MEM_HOST);
+}
+
 // debug / test read-back of a party's key-switching key in the host layout of mkt_load_ksk
 int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
     if (!c || !out_host || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");

@@ -163,6 +163,30 @@ hipError_t launch_seeded_encrypt(SeededArgs a, hipStream_t s);
 // and the encrypt kernel's rows per tile: party_rows.h)
 int seeded_expand_tile_words(int n, int lwe_len);
 
+// Seeded evaluation keys on the device (seeded_keys.hip; mktfhe.h "seeded evaluation keys"), the words of mkt_client_seeded_keys_expand.
+// Key-switching key: out = [rows][n1p] words, the RESIDENT pitch (n1p = 4 ceil((n + 1) / 4), out 16-byte aligned): row R = the n mask words of
+// stream 12 at index R, body[R], zeros; all zeros where R / rows_per_cj < absent_below (block schemes: absent_below = n, else 0)
+struct SeededKskArgs {
+    uint32_t mkey[8];            // ChaCha20 key of the mask streams: the PUBLIC mask seed
+    int party, n, n1p;
+    uint32_t rows_per_cj;        // Drows * f
+    int absent_below;
+    const uint32_t *body;        // [rows]
+    uint32_t *out;
+    uint64_t rows;
+};
+// Bootstrapping key: out = npolys polynomials in the coefficient layout of mkt_load_brk, each 1 << log_units units of 64 bytes (N W / 512);
+// bodies copied from `body` (the compact section), masks from stream 13.  unienc 0: groups of kr + 1 (b, a_0 ..); 1: groups of 3 l (CCS)
+struct SeededBrkArgs {
+    uint32_t mkey[8];
+    int party, unienc, kr, l, log_units;
+    const void *body;            // 16-byte aligned
+    void *out;                   // 16-byte aligned
+    uint64_t npolys;
+};
+hipError_t launch_seeded_ksk_expand(const SeededKskArgs &a, hipStream_t s);
+hipError_t launch_seeded_brk_expand(const SeededBrkArgs &a, hipStream_t s);
+
 hipError_t launch_transform_fwd(int logM, int W, TwPtrs tw, const void *p, cplx *t, size_t B, int dev_order, hipStream_t s);
 hipError_t launch_reorder(int logM, const cplx *in, cplx *out, size_t npolys, int to_device, int order, hipStream_t s);
 hipError_t launch_transform_inv(int logM, int W, TwPtrs tw, const cplx *t, void *p, size_t B, hipStream_t s);

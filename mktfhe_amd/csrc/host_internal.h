@@ -65,6 +65,9 @@ inline bool host_below(const uint32_t *v, size_t n, size_t bound) {
     for (size_t j = 0; j < n; j++) if (v[j] >= bound) return false;
     return true;
 }
+// seeded evaluation keys (mktfhe.h): polynomials of one party's compact bootstrapping-key section, rows (= body words) of its key-switching key
+inline size_t brk_seeded_polys(const mkt_params &p, const Shape &s) { return (size_t)p.n * (p.scheme == MKT_CCS ? 2 * (size_t)p.l_uni : (size_t)(s.kr + 1) * p.l_gsw); }
+inline size_t ksk_rows(const mkt_params &p, const Shape &s) { return (size_t)s.ksk_kr * p.N * s.ksk_drows * p.f; }
 inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
@@ -94,6 +97,11 @@ struct mkt_client_party {
     std::vector<std::vector<int8_t>> zring; // SK: k polys; CCS: 1; KMS: [0] = gsw key z', [1] = uni key z
     std::vector<uint8_t> brk, rlk_d, rlk_f, pub;  // ring words at native width
     std::vector<uint32_t> ksk;
+    // the seeded key form (mkt_client_party_keygen_seeded): the public mask seed and the bodies; brk / ksk above stay empty
+    bool seeded = false;
+    uint8_t mask_seed[32] = {};
+    std::vector<uint8_t> brk_seeded;        // ring words at native width
+    std::vector<uint32_t> ksk_seeded;
 };
 
 namespace mkt {

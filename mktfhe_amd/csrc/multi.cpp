@@ -248,6 +248,7 @@ int mkt_multi_load_ksk(mkt_multi *m, int party, const uint32_t *data) { MKT_MULT
 int mkt_multi_load_rlk(mkt_multi *m, int party, const void *d, const void *f, int fmt) { MKT_MULTI_UNSEALED(m); MKT_MULTI_FWD(m, mkt_load_rlk(m->ctx[0], party, d, f, fmt)); }
 int mkt_multi_load_pubkey(mkt_multi *m, int party, const void *b, int fmt) { MKT_MULTI_UNSEALED(m); MKT_MULTI_FWD(m, mkt_load_pubkey(m->ctx[0], party, b, fmt)); }
 int mkt_multi_load_crs(mkt_multi *m, const void *a, int fmt) { MKT_MULTI_UNSEALED(m); MKT_MULTI_FWD(m, mkt_load_crs(m->ctx[0], a, fmt)); }
+int mkt_multi_load_seeded_keys(mkt_multi *m, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded) { MKT_MULTI_UNSEALED(m); MKT_MULTI_FWD(m, mkt_load_seeded_keys(m->ctx[0], party, mask_seed, brk_seeded, ksk_seeded)); }
 int mkt_multi_keygen_device(mkt_multi *m, int party, const mkt_client_party *keys, const void *crs) { MKT_MULTI_UNSEALED(m); MKT_MULTI_FWD(m, mkt_keygen_device(m->ctx[0], party, keys, crs)); }
 
 // replicate the resident key set of the first device onto every other device (peer copy), fork the logical shards; from here

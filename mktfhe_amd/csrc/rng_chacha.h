@@ -147,11 +147,25 @@ MKT_HD uint32_t row_noise_word(const uint32_t key[8], uint32_t party, uint32_t s
 MKT_HD uint32_t smudge_word(const uint32_t key[8], uint32_t party, uint64_t row, double sigma) {
     return row_noise_word(key, party, STREAM_SMUDGE, row, sigma);
 }
+// keystream block `blk` of the stream (stream, party, idx), whole: the streams that are read as 32-bit words with every keystream word used
+MKT_HD void stream_block(const uint32_t key[8], uint32_t stream, uint32_t party, uint64_t idx, uint32_t blk, uint32_t out[16]) {
+    const uint32_t nonce[3] = {stream | (party << 16), (uint32_t)idx, (uint32_t)(idx >> 32)};
+    chacha20_block(key, blk, nonce, out);
+}
 // mask words 16 blk .. 16 blk + 15 of row `row` of party `party`'s seeded batch: keystream block `blk` of the row's stream, whole
 // (client.cpp and seeded.hip; a row uses the first n words of its blocks and drops the rest of the last one)
 MKT_HD void mask_block(const uint32_t key[8], uint32_t party, uint64_t row, uint32_t blk, uint32_t out[16]) {
-    const uint32_t nonce[3] = {STREAM_ENC_MASK | (party << 16), (uint32_t)row, (uint32_t)(row >> 32)};
-    chacha20_block(key, blk, nonce, out);
+    stream_block(key, STREAM_ENC_MASK, party, row, blk, out);
 }
+// 12 .. 16: seeded evaluation keys (mktfhe.h "seeded evaluation keys"; client.cpp and seeded_keys.hip).  12 and 13 are keyed by the PUBLIC mask
+// seed and read through stream_block like 10: 12 the mask of key-switching-key row R (index R), 13 mask polynomial P of the bootstrapping key
+// (index P; 32-bit ring: coefficient q = word q & 15 of block q >> 4; 64-bit ring: words 2 (q & 7), 2 (q & 7) + 1 of block q >> 3, low first).
+// 14, 15, 16 are keyed by the party's SECRET seed: 14 the noise of RGSW sample S (index S, N draws), 15 the noise word of key-switching-key
+// row R (index R, first draw), 16 the UniEnc stream of key bit i (index i: N ternary draws, then per gadget row N draws for d_j, N for f_j).
+constexpr uint32_t STREAM_KSK_MASK = 12;
+constexpr uint32_t STREAM_BRK_MASK = 13;
+constexpr uint32_t STREAM_BRK_NOISE = 14;
+constexpr uint32_t STREAM_KSK_NOISE = 15;
+constexpr uint32_t STREAM_UNI_NOISE = 16;
 
 }  // namespace mktrng

@@ -6,7 +6,7 @@ a client -- this package's seeded keygen, or the Julia reference through a 30-li
 to an evaluator process.  Secret keys are never written.
 
   offset  size  field
-  0       8     magic  b"MKTKEY\\0\\1"  (last byte = format version 1)
+  0       8     magic  b"MKTKEY\\0\\1"  (last byte = format version: 1, or 2 for a party in the seeded key form)
   8       60    mkt_params: 15 little-endian int32 (scheme, n, N, k, W, l_gsw, logB_gsw, l_lev, logB_lev,
                 l_uni, logB_uni, f, logD, blk_len, blk_d)
   68      4     party index (int32, -1 for a CRS blob)
@@ -16,6 +16,10 @@ to an evaluator process.  Secret keys are never written.
   ...           section payloads, each 16-byte aligned, in table order; sections: "crs" | "brk", "ksk",
                 "rlk_d", "rlk_f", "pubkey" (those that exist for the scheme)
   end     32    SHA-256 of everything before it
+
+Format version 2 (include/mktfhe.h "seeded evaluation keys") replaces "brk" and "ksk" by "mask_seed" (8 x uint32: the PUBLIC 32-byte mask
+seed as little-endian words), "brk_seeded" and "ksk_seeded" (the bodies, compact layouts of the header); the evaluator regenerates the masks
+on its GPU.  Everything else is as in version 1, and version-1 blobs are written and read exactly as before.
 """
 import hashlib
 import struct
@@ -25,11 +29,12 @@ import numpy as np
 from .params import Params
 
 MAGIC = b"MKTKEY\x00\x01"
+MAGIC2 = b"MKTKEY\x00\x02"       # format version 2: the seeded key form
 _PFIELDS = ("scheme", "n", "N", "k", "W", "l_gsw", "logB_gsw", "l_lev", "logB_lev", "l_uni", "logB_uni", "f", "logD", "blk_len", "blk_d")
 
 
-def _pack(params: Params, party, sections):
-    head = bytearray(MAGIC)
+def _pack(params: Params, party, sections, magic=MAGIC):
+    head = bytearray(magic)
     head += struct.pack("<15i", *[getattr(params, f) for f in _PFIELDS])
     head += struct.pack("<ii", party, len(sections))
     table, payload = bytearray(), bytearray()
@@ -48,12 +53,26 @@ def _pack(params: Params, party, sections):
 def dump_party(keys) -> bytes:
     """serialise a PartyKeys' EVALUATION key (never the secret key)"""
     p = keys.params
-    secs = [("brk", keys.brk), ("ksk", keys.ksk)]
+    seeded = getattr(keys, "seeded", False)
+    if seeded:
+        secs = [("mask_seed", np.frombuffer(keys.mask_seed, dtype="<u4").astype(np.uint32)), ("brk_seeded", keys.brk_seeded), ("ksk_seeded", keys.ksk_seeded)]
+    else:
+        secs = [("brk", keys.brk), ("ksk", keys.ksk)]
     for name in ("rlk_d", "rlk_f", "pubkey"):
         v = getattr(keys, name)
         if v is not None:
             secs.append((name, v))
-    return _pack(p, keys.party, secs)
+    return _pack(p, keys.party, secs, MAGIC2 if seeded else MAGIC)
+
+
+def dump_seeded_arrays(params: Params, party, mask_seed, brk_seeded, ksk_seeded, rlk_d=None, rlk_f=None, pubkey=None) -> bytes:
+    """serialise a seeded party's evaluation key from its arrays (format version 2)"""
+    secs = [("mask_seed", np.frombuffer(bytes(mask_seed), dtype="<u4").astype(np.uint32)),
+            ("brk_seeded", np.ascontiguousarray(brk_seeded, dtype=params.ring_dtype).reshape(-1)), ("ksk_seeded", np.ascontiguousarray(ksk_seeded, dtype=np.uint32).reshape(-1))]
+    for name, v in (("rlk_d", rlk_d), ("rlk_f", rlk_f), ("pubkey", pubkey)):
+        if v is not None:
+            secs.append((name, np.ascontiguousarray(v, dtype=params.ring_dtype).reshape(-1)))
+    return _pack(params, party, secs, MAGIC2)
 
 
 def dump_arrays(params: Params, party, brk, ksk, rlk_d=None, rlk_f=None, pubkey=None) -> bytes:
@@ -71,8 +90,8 @@ def dump_crs(params: Params, crs) -> bytes:
 
 def load(blob: bytes):
     """-> (params dict, party, {section: ndarray}); raises ValueError on a corrupt or foreign blob"""
-    if len(blob) < 76 + 32 or blob[:8] != MAGIC:
-        raise ValueError("not a version-1 MKTKEY blob")
+    if len(blob) < 76 + 32 or blob[:8] not in (MAGIC, MAGIC2):
+        raise ValueError("not a version-1 or version-2 MKTKEY blob")
     if hashlib.sha256(blob[:-32]).digest() != blob[-32:]:
         raise ValueError("key blob checksum mismatch")
     pv = struct.unpack_from("<15i", blob, 8)
@@ -85,7 +104,24 @@ def load(blob: bytes):
         dt = {4: np.uint32, 8: np.uint64}[isz]
         out[name.rstrip(b"\0").decode()] = np.frombuffer(blob, dtype=dt, count=nbytes // isz, offset=off)
         off += nbytes
-    return dict(zip(_PFIELDS, pv)), party, out
+    pd = dict(zip(_PFIELDS, pv))
+    if blob[:8] == MAGIC2:
+        _check_seeded(pd, out)
+    return pd, party, out
+
+
+def _check_seeded(pd, secs):
+    """a version-2 blob holds the three seeded sections at exactly the lengths its parameters give"""
+    from .scheme import seeded_section_words
+    if {"brk", "ksk"} & set(secs):
+        raise ValueError("a version-2 key blob holds the seeded sections, not brk / ksk")
+    p = Params("blob", alpha=0.0, beta=0.0, **pd)
+    wb, wk = seeded_section_words(p)
+    for name, dt, want in (("mask_seed", np.uint32, 8), ("brk_seeded", p.ring_dtype, wb), ("ksk_seeded", np.uint32, wk)):
+        if name not in secs:
+            raise ValueError(f"a version-2 key blob needs the section {name}")
+        if secs[name].dtype != dt or secs[name].size != want:
+            raise ValueError(f"key blob section {name}: {secs[name].size} words of {secs[name].dtype}, its parameters need {want} of {np.dtype(dt)}")
 
 
 def load_into(scheme, blob: bytes):
@@ -96,6 +132,9 @@ def load_into(scheme, blob: bytes):
         raise ValueError("key blob was generated for different parameters")
     if party < 0:
         scheme.load_crs(secs["crs"])
+    elif "mask_seed" in secs:      # format version 2 (lengths checked by load): the masks are regenerated on the scheme's GPU
+        scheme.load_party(party, mask_seed=secs["mask_seed"].astype("<u4").tobytes(), brk_seeded=secs["brk_seeded"], ksk_seeded=secs["ksk_seeded"],
+                          rlk_d=secs.get("rlk_d"), rlk_f=secs.get("rlk_f"), pubkey=secs.get("pubkey"))
     else:
         scheme.load_party(party, brk=secs.get("brk"), ksk=secs.get("ksk"), rlk_d=secs.get("rlk_d"), rlk_f=secs.get("rlk_f"), pubkey=secs.get("pubkey"))
     return party

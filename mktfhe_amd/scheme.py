@@ -106,6 +106,14 @@ def _seed_arg(deterministic_seed):
     return C.cast(buf, C.c_void_p), buf
 
 
+def _seed32(seed):
+    """a public 32-byte seed -> (pointer, keepalive)"""
+    if not isinstance(seed, (bytes, bytearray)) or len(seed) != 32:
+        raise ValueError("a mask seed is 32 bytes")
+    buf = (C.c_uint8 * 32)(*seed)
+    return C.cast(buf, C.c_void_p), buf
+
+
 def _row0(row0):
     """the index of a call's first row in a larger batch under one seed, as the library takes it: 64 bits"""
     row0 = int(row0)
@@ -127,19 +135,30 @@ class PartyKeys:
     """One party's secret and evaluation keys (party_keygen, scheme.jl:227,:273,:324; setup for the
     single-key schemes, scheme.jl:151,:190).  Evaluation keys are in integer (coefficient) form."""
 
-    def __init__(self, params: Params, party=0, crs=None, secrets_only=False, deterministic_seed=None):
+    def __init__(self, params: Params, party=0, crs=None, secrets_only=False, deterministic_seed=None, seeded=False, mask_seed=None):
         """Keys are drawn from fresh OS randomness; `deterministic_seed` (an int, or 32 bytes) pins the streams for
         tests and benchmarks ONLY -- such keys are reproducible by anyone.
         secrets_only: leave out the two large keys (bootstrapping key, key-switching key); they are then generated
         on the GPU by Scheme.keygen_device from the same streams (identical words).  That hands this party's secrets
-        to that GPU: a party-local step (own machine), not something an evaluator does for every party."""
-        self.params, self.party, self.secrets_only = params, party, secrets_only
+        to that GPU: a party-local step (own machine), not something an evaluator does for every party.
+        seeded: the seeded key form (mktfhe.h "seeded evaluation keys"): the two large keys as a PUBLIC 32-byte mask seed
+        (mask_seed; None draws a fresh one) and their bodies (brk_seeded, ksk_seeded); brk and ksk are None.  A (mask seed,
+        party) pair serves one key generation."""
+        self.params, self.party, self.secrets_only, self.seeded = params, party, secrets_only and not seeded, bool(seeded)
         h = C.c_void_p()
         self._crs = np.ascontiguousarray(crs, dtype=params.ring_dtype) if crs is not None else None
         crs_p = _np_ptr(self._crs) if crs is not None else None
-        fn = _lib.lib().mkt_client_party_secrets if secrets_only else _lib.lib().mkt_client_party_keygen
         sp, _keep = _seed_arg(deterministic_seed)
-        check(fn(C.byref(params.c()), sp, party, crs_p, params.alpha, params.beta, C.byref(h)))
+        if seeded:
+            if mask_seed is None:
+                buf = (C.c_uint8 * 32)()
+                check(_lib.lib().mkt_client_random_seed(buf))
+                mask_seed = bytes(buf)
+            mp, _mkeep = _seed32(mask_seed)
+            check(_lib.lib().mkt_client_party_keygen_seeded(C.byref(params.c()), sp, mp, party, crs_p, params.alpha, params.beta, C.byref(h)))
+        else:
+            fn = _lib.lib().mkt_client_party_secrets if secrets_only else _lib.lib().mkt_client_party_keygen
+            check(fn(C.byref(params.c()), sp, party, crs_p, params.alpha, params.beta, C.byref(h)))
         self.h = h
 
     def __del__(self):
@@ -183,6 +202,20 @@ class PartyKeys:
         return self._buf(_lib.lib().mkt_client_ksk, np.uint32)
 
     @property
+    def mask_seed(self):
+        """the public 32-byte mask seed of a seeded party, else None"""
+        p = _lib.lib().mkt_client_mask_seed(self.h)
+        return bytes((C.c_uint8 * 32).from_address(p)) if p else None
+
+    @property
+    def brk_seeded(self):
+        return self._buf(_lib.lib().mkt_client_brk_seeded, self.params.ring_dtype)
+
+    @property
+    def ksk_seeded(self):
+        return self._buf(_lib.lib().mkt_client_ksk_seeded, np.uint32)
+
+    @property
     def rlk_d(self):
         return self._buf(_lib.lib().mkt_client_rlk_d, self.params.ring_dtype)
 
@@ -195,10 +228,11 @@ class PartyKeys:
         return self._buf(_lib.lib().mkt_client_pubkey, self.params.ring_dtype)
 
 
-def party_keygen(a, params: Params, party=0, secrets_only=False, deterministic_seed=None):
+def party_keygen(a, params: Params, party=0, secrets_only=False, deterministic_seed=None, seeded=False, mask_seed=None):
     """scheme.jl:227/:273/:324 party_keygen(a, params) -> PartyKeys (lwekey + bootstrapping key); fresh randomness
-    per call unless `deterministic_seed` (tests / benchmarks only) is given"""
-    return PartyKeys(params, party=party, crs=a, secrets_only=secrets_only, deterministic_seed=deterministic_seed)
+    per call unless `deterministic_seed` (tests / benchmarks only) is given.  seeded=True: the seeded key form (a public
+    mask seed and the bodies of the two large keys; PartyKeys)"""
+    return PartyKeys(params, party=party, crs=a, secrets_only=secrets_only, deterministic_seed=deterministic_seed, seeded=seeded, mask_seed=mask_seed)
 
 
 def lwe_encrypt(m, key: PartyKeys, params: Params, deterministic_seed=None):
@@ -321,6 +355,38 @@ class _Batched:
         return self._call("keyswitch_batch", B, _Buf(acc, p.ring_dtype, B * (p.k + 1) * p.N), self._ct(out, B, out=True))[1]
 
 
+def seeded_section_words(params: Params):
+    """(ring words of brk_seeded, words of ksk_seeded) of one party (include/mktfhe.h "seeded evaluation keys", compact layouts)"""
+    p = params
+    D = 1 << p.logD
+    kr = 1 if p.scheme in (KMS, KMS_BLOCK) else p.k
+    brk = p.n * (2 * p.l_uni if p.scheme == CCS else (kr + 1) * p.l_gsw) * p.N
+    return brk, (1 if p.multikey else p.k) * p.N * (D // 2 if p.scheme in (LMSS, KMS_BLOCK) else D - 1) * p.f
+
+
+def _seeded_sections(params, brk_seeded, ksk_seeded):
+    """the compact sections as contiguous arrays of exactly the lengths the library reads -> (brk or None, ksk or None)"""
+    wb, wk = seeded_section_words(params)
+    out = []
+    for name, v, dt, want in (("brk_seeded", brk_seeded, params.ring_dtype, wb), ("ksk_seeded", ksk_seeded, np.uint32, wk)):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=dt)
+            if v.size != want:
+                raise ValueError(f"{name} holds {v.size} words, these parameters need {want}")
+        out.append(v)
+    return out
+
+
+def _load_seeded(sch, party, mask_seed, brk_seeded, ksk_seeded):
+    """mkt_load_seeded_keys / mkt_multi_load_seeded_keys on a Scheme / MultiScheme: sizes checked before the library is called"""
+    b, k = _seeded_sections(sch.params, brk_seeded, ksk_seeded)
+    if b is None and k is None:
+        raise ValueError("a mask seed without a compact section")
+    mp, _keep = _seed32(mask_seed)
+    fn = getattr(_lib.lib(), sch._PREFIX + "load_seeded_keys")
+    sch._ck(fn(sch.h, int(party), mp, None if b is None else _np_ptr(b), None if k is None else _np_ptr(k)))
+
+
 class Scheme(_Batched):
     """The reference's CGGI / LMSS / CCS / KMS / KMS_block scheme object (scheme.jl:107-116, :168-179,
     :209-219, :256-265, :301-312) as a per-device engine context: twiddle tables (fft.jl:18-45),
@@ -372,10 +438,17 @@ class Scheme(_Batched):
         return check(code, self.h)
 
     # -- keys
-    def load_party(self, party, keys: PartyKeys = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF):
+    def load_party(self, party, keys: PartyKeys = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF,
+                   mask_seed=None, brk_seeded=None, ksk_seeded=None):
+        """upload one party's evaluation keys.  A seeded party (PartyKeys(seeded=True)), or mask_seed with brk_seeded / ksk_seeded, goes
+        through mkt_load_seeded_keys: the masks are regenerated on the GPU, the expanded keys never exist on the host"""
         L, p = _lib.lib(), self.params
         if keys is not None:
             brk, ksk, rlk_d, rlk_f, pubkey = keys.brk, keys.ksk, keys.rlk_d, keys.rlk_f, keys.pubkey
+            if getattr(keys, "seeded", False):
+                mask_seed, brk_seeded, ksk_seeded = keys.mask_seed, keys.brk_seeded, keys.ksk_seeded
+        if mask_seed is not None:
+            _load_seeded(self, party, mask_seed, brk_seeded, ksk_seeded)
         kd = np.complex128 if fmt == FMT_F64_FFT else p.ring_dtype
         if brk is not None:
             self._ck(L.mkt_load_brk(self.h, party, _np_ptr(np.ascontiguousarray(brk, dtype=kd)), fmt))
@@ -622,10 +695,16 @@ class MultiScheme(_Batched):
         return s
 
     # -- keys: once, on the first device; replicate() copies them to the others
-    def load_party(self, party, keys: "PartyKeys" = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF):
+    def load_party(self, party, keys: "PartyKeys" = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF,
+                   mask_seed=None, brk_seeded=None, ksk_seeded=None):
+        """as Scheme.load_party, on the first device (a seeded party: mkt_multi_load_seeded_keys)"""
         L, p = _lib.lib(), self.params
         if keys is not None:
             brk, ksk, rlk_d, rlk_f, pubkey = keys.brk, keys.ksk, keys.rlk_d, keys.rlk_f, keys.pubkey
+            if getattr(keys, "seeded", False):
+                mask_seed, brk_seeded, ksk_seeded = keys.mask_seed, keys.brk_seeded, keys.ksk_seeded
+        if mask_seed is not None:
+            _load_seeded(self, party, mask_seed, brk_seeded, ksk_seeded)
         kd = np.complex128 if fmt == FMT_F64_FFT else p.ring_dtype
         if brk is not None:
             self._ck(L.mkt_multi_load_brk(self.h, party, _np_ptr(np.ascontiguousarray(brk, dtype=kd)), fmt))

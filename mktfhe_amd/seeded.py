@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .params import Params
-from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _row0, _seed_arg
+from .scheme import PartyKeys, _Buf, _empty, _is_torch, _np_ptr, _row0, _seed32, _seed_arg
 
 
 class SeededBatch(NamedTuple):
@@ -27,13 +27,6 @@ class SeededBatch(NamedTuple):
     mask_seed: bytes
     row0: int
     body: object
-
-
-def _seed32(seed):
-    if not isinstance(seed, (bytes, bytearray)) or len(seed) != 32:
-        raise ValueError("a mask seed is 32 bytes")
-    buf = (C.c_uint8 * 32)(*seed)
-    return C.cast(buf, C.c_void_p), buf
 
 
 def seeded_encrypt(msgs, key: PartyKeys, params: Params, party, *, words=False, scheme=None, mask_seed=None, deterministic_seed=None, row0=0):
