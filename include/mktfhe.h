@@ -166,7 +166,10 @@ const char *mkt_last_kernel_name(const mkt_ctx *ctx);
 int mkt_get_metric(mkt_ctx *ctx, const char *name, double *out);
 
 /* twiddle tables (fft.jl:31-41): which = 0 Psi, 1 Psiinv, 2 roots, 3 rootsinv; M complex each.
- * mkt_set_twiddles lets a caller install the reference's own ffter tables verbatim. */
+ * mkt_set_twiddles lets a caller install the reference's own ffter tables verbatim.
+ * ORDER: tables first, then keys.  Loaded keys are resident as their transforms under the tables in place when they arrived (or as the
+ * caller's own Trans* values) and their integer form is not kept, so once a bootstrapping key, relinearisation key, public key or the CRS
+ * is loaded (mkt_load_*, mkt_keygen_device, mkt_load_seeded_keys; either format) mkt_set_twiddles returns MKT_ERR_STATE and changes nothing. */
 int mkt_get_twiddles(mkt_ctx *ctx, int which, double *out_host);
 int mkt_set_twiddles(mkt_ctx *ctx, const double *psi, const double *psiinv,
                      const double *roots, const double *rootsinv);

@@ -917,6 +917,11 @@ int mkt_set_twiddles(mkt_ctx *c, const double *psi, const double *psiinv, const 
     if (!c || !psi || !psiinv || !roots || !rootsinv) return fail(c, MKT_ERR_ARG, "null table");
     MKT_F64_ONLY(c);
     if (int w = keys_writable(c)) return w;
+    // tables first, then keys: a loaded bootstrapping key, relinearisation key, public key or CRS is resident as its transform under the tables
+    // it met (or as the caller's Trans* values), and its integer form is not kept -- new tables would leave keys and transforms disagreeing
+    bool keyed = c->ks->crs_loaded;
+    for (int i = 0; i < c->sh.nparty; i++) keyed = keyed || c->ks->brk_loaded[i] || c->ks->rlk_loaded[i] || c->ks->pub_loaded[i];
+    if (keyed) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
     DevGuard dg(c->device);
     const size_t nd = (size_t)2 * c->M;
     // the kernels derive the inverse twiddles from the forward table: Psiinv must be conj(Psi) entry for entry,

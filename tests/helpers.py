@@ -511,3 +511,43 @@ def ks_at_edge_check(p, so, sg, rng, batches, coefs, device=True):
                     assert not len(bad), ("keyswitch_at (edge words), device memory", p.name, p.n, p.f, p.logD, v, B, bad[:4])
                 checks += B
     return checks
+
+
+# ---- one call in host or in device memory, and the same call on a context that has made no other (tests/context_life_cases.py) ----
+_SIGNED = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
+
+
+def to_mem(a, mem):
+    """a host array as the argument of a call in memory kind `mem`: its own contiguous copy (MEM_HOST) or a GPU tensor of the same words
+    (MEM_DEVICE; torch has no unsigned 32- / 64-bit tensors: the signed type of the same size)"""
+    a = np.array(a, order="C", copy=True)
+    if mem == mk.MEM_HOST:
+        return a
+    import torch
+    return torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype))).cuda()
+
+
+def host_words(x):
+    """what a call returned -- an array, a GPU tensor or a tuple of them -- as host arrays; integer words as unsigned"""
+    if isinstance(x, (tuple, list)):
+        return tuple(host_words(v) for v in x)
+    if type(x).__module__.startswith("torch"):
+        x = x.cpu().numpy()
+    x = np.ascontiguousarray(x)
+    return x.view({"i4": np.uint32, "i8": np.uint64}.get(x.dtype.str[1:], x.dtype))
+
+
+def same_words(a, b):
+    """exact equality of two results of host_words, bit for bit (transforms included: no floating-point comparison)"""
+    if isinstance(a, tuple) or isinstance(b, tuple):
+        return isinstance(a, tuple) and isinstance(b, tuple) and len(a) == len(b) and all(same_words(u, v) for u, v in zip(a, b))
+    return a.dtype == b.dtype and bits_equal(a, b)
+
+
+def fresh(make, call):
+    """call(scheme) on a context that make() has just created and keyed, used for this one call and closed -> host_words of the result"""
+    s = make()
+    try:
+        return host_words(call(s))
+    finally:
+        s.close()
