@@ -177,7 +177,10 @@ int mkt_set_twiddles(mkt_ctx *ctx, const double *psi, const double *psiinv,
 /* host-only (no GPU needed): the engine's table generator for ring dimension N, same `which` */
 int mkt_make_twiddles(int N, int which, double *out_host);
 
-/* ---- evaluation keys (host pointers, copied; keygen.jl:3-155) ---- */
+/* ---- evaluation keys (host pointers, copied; keygen.jl:3-155).  Every load works on the context's stream (mkt_set_stream) and returns with
+ *      that stream drained, the host buffer free to reuse.  mkt_load_ksk too: it once wrote the table through the NULL stream, which a
+ *      context pinned to a non-blocking stream does not wait for; now a batch still in flight on that stream reads the old key to its end,
+ *      and every call after the load the new one ---- */
 int mkt_load_brk(mkt_ctx *ctx, int party, const void *data, int fmt);
 int mkt_load_ksk(mkt_ctx *ctx, int party, const uint32_t *data);
 int mkt_load_rlk(mkt_ctx *ctx, int party, const void *d, const void *f, int fmt); /* KMS: keygen.jl:103 */

@@ -92,10 +92,10 @@ struct KeySet {
     mkt::Twiddles tw;
     cplx *d_tw = nullptr;        // psi | psiinv | roots | rootsinv, M each
     cplx *d_monomial = nullptr;  // [2N][M]
-    cplx *d_brk = nullptr;  std::vector<char> brk_loaded;
-    uint32_t *d_ksk = nullptr; int n1p = 0; std::vector<char> ksk_loaded;
+    cplx *d_brk = nullptr;
+    uint32_t *d_ksk = nullptr; mkt::KskLayout ksk;   // host_internal.h: rows, the callers' pitch, the resident pitch
     cplx *d_rlk_d = nullptr, *d_rlk_f = nullptr, *d_pub = nullptr, *d_crs = nullptr;
-    std::vector<char> rlk_loaded, pub_loaded; bool crs_loaded = false;
+    mkt::LoadedKeys loaded;      // which pieces of which party are resident (host_internal.h)
     // rotation slots (KMS phase 1: party-major rows)
     int rtot = 1;
     int *d_slot_party = nullptr, *d_slot_row = nullptr;
@@ -181,7 +181,8 @@ void clear_spans(mkt_ctx *c) {
 
 size_t poly_bytes(const mkt_ctx *c) { return (size_t)c->p.N * c->sh.word; }
 
-int fx_after_key_load(mkt_ctx *c);
+hipError_t fx_after_key_load(mkt_ctx *c);
+hipError_t install_brk(mkt_ctx *c, int party, const void *src);
 bool fx_usable(const mkt_ctx *c);
 mktd::FxRotArgs fx_rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre);
 // `npolys` coefficient-form polynomials on the device (src) into the resident form of this context's tables at dst.  small: coefficients far below 2^32 in magnitude
@@ -193,29 +194,21 @@ hipError_t to_resident(mkt_ctx *c, const void *src, size_t npolys, cplx *dst, bo
     if (e == hipSuccess && fx_dst) e = mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), src, fx_dst, npolys, c->ks->d_fx_stat, c->stream);
     return e;
 }
-// transform `npolys` coefficient-form polynomials (host) into TransPolys at `dst` (device)
-int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt, bool small = false, cplx *fx_dst = nullptr) {
+struct DevBuf { void *p = nullptr; ~DevBuf() { (void)hipFree(p); } };   // a call's own device buffer that holds no secret
+// transform `npolys` coefficient-form polynomials (host) into TransPolys at `dst` (device); returns with the stream drained.  brk_party >= 0: they
+// are that party's bootstrapping key, which in coefficient form goes through install_brk
+int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt, bool small = false, int brk_party = -1) {
     if (c->exact && fmt != MKT_FMT_INT_COEFF) return fail(c, MKT_ERR_UNSUPPORTED, "an MKT_ARITH_EXACT context takes keys in integer form (MKT_FMT_INT_COEFF)");
-    if (fmt == MKT_FMT_F64_FFT) {   // the reference's Trans* values: copy, then natural -> device point order
-        cplx *tmpc = nullptr;
-        const size_t nb = npolys * (size_t)c->M * sizeof(cplx);
-        HIPCHK(c, hipMalloc((void **)&tmpc, nb));
-        hipError_t e = hipMemcpyAsync(tmpc, host, nb, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = mktd::launch_reorder(c->logM, tmpc, dst, npolys, 1, c->dev_order, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(tmpc);
-        if (e != hipSuccess) return hipfail(c, e, "key upload");
-        return MKT_OK;
-    }
-    if (fmt != MKT_FMT_INT_COEFF) return fail(c, MKT_ERR_ARG, "unknown key format");
-    void *tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, npolys * poly_bytes(c)));
-    hipError_t e = hipMemcpyAsync(tmp, host, npolys * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = to_resident(c, tmp, npolys, dst, small, fx_dst);
+    if (fmt != MKT_FMT_F64_FFT && fmt != MKT_FMT_INT_COEFF) return fail(c, MKT_ERR_ARG, "unknown key format");
+    const bool fft = fmt == MKT_FMT_F64_FFT;   // the reference's Trans* values: copy, then natural -> device point order
+    const size_t nb = npolys * (fft ? (size_t)c->M * sizeof(cplx) : poly_bytes(c));
+    DevBuf tmp;
+    HIPCHK(c, hipMalloc(&tmp.p, nb));
+    hipError_t e = hipMemcpyAsync(tmp.p, host, nb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = fft ? mktd::launch_reorder(c->logM, static_cast<cplx *>(tmp.p), dst, npolys, 1, c->dev_order, c->stream)
+                                 : brk_party >= 0 ? install_brk(c, brk_party, tmp.p) : to_resident(c, tmp.p, npolys, dst, small, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return hipfail(c, e, "key pre-transform");
-    if (fx_dst) return fx_after_key_load(c);
+    if (e != hipSuccess) return hipfail(c, e, fft ? "key upload" : "key pre-transform");
     return MKT_OK;
 }
 
@@ -300,13 +293,16 @@ int ensure_workspace(mkt_ctx *c, size_t gates) {
 constexpr size_t CHUNK_GATES = 8192;   // bounds the workspace (KMS N=2048, k=2: ~1.9 GiB)
 
 int check_ready(mkt_ctx *c, bool need_brk, bool need_ksk) {
-    for (int i = 0; i < c->sh.nparty; i++) {
-        if (need_brk && !c->ks->brk_loaded[i]) return fail(c, MKT_ERR_STATE, "bootstrapping key not loaded");
-        if (need_ksk && !c->ks->ksk_loaded[i]) return fail(c, MKT_ERR_STATE, "key-switching key not loaded");
-        if (need_brk && c->p.scheme == MKT_CCS && !c->ks->pub_loaded[i]) return fail(c, MKT_ERR_STATE, "public key not loaded");
-        if (need_brk && mkt::is_kms(c->p.scheme) && (!c->ks->rlk_loaded[i] || !c->ks->pub_loaded[i])) return fail(c, MKT_ERR_STATE, "rlk / public key not loaded");
-    }
-    if (need_brk && mkt::is_mk(c->p.scheme) && !c->ks->crs_loaded) return fail(c, MKT_ERR_STATE, "crs not loaded");
+    using L = mkt::LoadedKeys;
+    const int s = c->p.scheme;
+    // what every party must have resident, in the order it is refused: the side of the call that asks, the schemes it holds for, the pieces
+    const struct { bool asked, applies; unsigned pieces; int code; const char *msg; } per_party[] = {
+        {need_brk, true,           L::bit(mkt::K_BRK),                      MKT_ERR_STATE, "bootstrapping key not loaded"},
+        {need_ksk, true,           L::bit(mkt::K_KSK),                      MKT_ERR_STATE, "key-switching key not loaded"},
+        {need_brk, s == MKT_CCS,   L::bit(mkt::K_PUB),                      MKT_ERR_STATE, "public key not loaded"},
+        {need_brk, mkt::is_kms(s), L::bit(mkt::K_RLK) | L::bit(mkt::K_PUB), MKT_ERR_STATE, "rlk / public key not loaded"}};
+    for (int i = 0; i < c->sh.nparty; i++) for (const auto &r : per_party) if (r.asked && r.applies && !c->ks->loaded.has_all(r.pieces, i)) return fail(c, r.code, r.msg);
+    if (need_brk && mkt::is_mk(s) && !c->ks->loaded.has(mkt::K_CRS, -1)) return fail(c, MKT_ERR_STATE, "crs not loaded");
     return MKT_OK;
 }
 
@@ -442,7 +438,7 @@ int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, const uin
     const mkt_params &p = c->p;
     mktd::KsArgs a{};
     a.src = src; a.coef = coef; a.nacc = nacc;
-    a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->stride(T_KSK); a.n1p = c->ks->n1p;
+    a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->stride(T_KSK); a.n1p = c->ks->ksk.n1p;
     a.N = p.N; a.n = p.n; a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.kacc = c->sh.kacc;
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
     size_t dw = 0, pw = 0;
@@ -558,7 +554,6 @@ template <class Args> hipError_t wipe_secrets(hipError_t e, DeviceSecret &secret
     explicit_bzero(&a, sizeof a);
     return e != hipSuccess ? e : es;   // the call's status so far, else that of the drain
 }
-struct DevBuf { void *p = nullptr; ~DevBuf() { (void)hipFree(p); } };   // a call's own device buffer that holds no secret
 bool mem_ok(int mem) { return mem == MKT_MEM_DEVICE || mem == MKT_MEM_HOST; }
 
 // ---- MKT_ARITH_EXACT: tables of the two-prime negacyclic NTT (ntt_exact.hip), computed on the host, uploaded once ----
@@ -657,12 +652,12 @@ double fx_polymul_bound(const mkt_ctx *c, double amax, double kmax) {
     const double gt = (3.0 + 5.5 * (c->logM - 2) + 1.5 * 2) * u, gm = 5.0 * u;
     return (gt + (gt + u) + gm) * N * amax * 32768.0 + gt * std::sqrt(N) * amax * kmax * (1.0 + 1e-6);
 }
-int fx_after_key_load(mkt_ctx *c) {   // the key's largest transform magnitude, for fx_bound
+hipError_t fx_after_key_load(mkt_ctx *c) {   // the key's largest transform magnitude, for fx_bound
     unsigned long long bits = 0;
-    HIPCHK(c, hipMemcpy(&bits, c->ks->d_fx_stat, 8, hipMemcpyDeviceToHost));
+    const hipError_t e = hipMemcpy(&bits, c->ks->d_fx_stat, 8, hipMemcpyDeviceToHost);
     double v; std::memcpy(&v, &bits, 8);
-    c->ks->fx_kmax = std::sqrt(v);
-    return MKT_OK;
+    if (e == hipSuccess) c->ks->fx_kmax = std::sqrt(v);
+    return e;
 }
 mktd::FxRotArgs fx_rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre) {
     const mkt_params &p = c->p;
@@ -674,14 +669,14 @@ mktd::FxRotArgs fx_rot_args(mkt_ctx *c, const uint32_t *lwe, int stride, int pre
     return q;
 }
 
-// The one description of the resident key set of `c` (KeySet::tab, n1p); c->ks->rtot and the switches are set before.
+// The one description of the resident key set of `c` (KeySet::tab, ksk); c->ks->rtot and the switches are set before.
 void describe_key_set(mkt_ctx *c) {
     KeySet &ks = *c->ks;
     const mkt_params &p = c->p;
     const size_t M = (size_t)c->M, N = (size_t)p.N;
     const size_t tp = M * c->split;   // complex values of one resident key polynomial (EXACT on the 64-bit ring: two residue polynomials per logical one)
     const bool mk = mkt::is_mk(p.scheme), kms = mkt::is_kms(p.scheme);
-    ks.n1p = (p.n + 1 + 3) / 4 * 4;   // device rows padded to 16 B
+    ks.ksk = mkt::ksk_layout(p, c->sh);
     // second copy of the bootstrapping key as limb transforms + the engine's own tables, where a party's copy fits one buffer descriptor (2 GiB)
     const size_t fx_per = (size_t)p.n * 2 * p.l_gsw * 2 * (p.W / 16) * M;
     const bool fx = fx_shape(c) && c->tune.exact_impl != 0 && fx_per * sizeof(cplx) <= 0x7fffffffull;
@@ -690,7 +685,7 @@ void describe_key_set(mkt_ctx *c) {
     row(T_TW,         ks.d_tw,         4 * M,                                                         false,     true,    true);    // a caller may have replaced them on the source (mkt_set_twiddles)
     row(T_MONOMIAL,   ks.d_monomial,   2 * N * M,                                                     false,     true,    true);    // depends on the twiddles; small coefficients, never split
     row(T_BRK,        ks.d_brk,        (size_t)p.n * c->sh.brk_polys * tp,                            true,      true,    true);
-    row(T_KSK,        ks.d_ksk,        (size_t)c->sh.ksk_kr * N * c->sh.ksk_drows * p.f * ks.n1p,     true,      true,    true);
+    row(T_KSK,        ks.d_ksk,        ks.ksk.resident_words(),                                        true,      true,    true);
     row(T_PUB,        ks.d_pub,        (size_t)p.l_uni * tp,                                          true,      mk,      true);
     row(T_CRS,        ks.d_crs,        (size_t)p.l_uni * tp,                                          false,     mk,      true);
     row(T_RLK_D,      ks.d_rlk_d,      (size_t)p.l_uni * tp,                                          true,      kms,     true);
@@ -702,6 +697,31 @@ void describe_key_set(mkt_ctx *c) {
     row(T_FX_STAT,    ks.d_fx_stat,    1,                                                             false,     fx,      true);
     row(T_NTT,        ks.d_ntt,        (N + 4) * 2,                                                   false,     c->exact, false);   // (N + 4) points of 4 words (upload_ntt_tables)
 }
+
+// ---- the one install path of a party's keys ----  The start of every call that writes keys: the argument check (ptrs_ok: the call's own pointers; party NO_PARTY: the CRS, or a party
+// checked further on; scheme_ok: the schemes that have the piece), the arithmetic gate, the key set still this context's alone
+constexpr int NO_PARTY = -1; enum class Gate { EXACT, F64_OR_EXACT_KMS };   // MKT_EXACT_GATE, MKT_F64_OR_EXACT_KMS
+int key_write_guard(mkt_ctx *c, bool ptrs_ok, int party, Gate gate, bool (*scheme_ok)(int) = nullptr) {
+    if (!c || !ptrs_ok || (party != NO_PARTY && (party < 0 || party >= c->sh.nparty)) || (scheme_ok && !scheme_ok(c->p.scheme))) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (gate == Gate::EXACT) MKT_EXACT_GATE(c); else MKT_F64_OR_EXACT_KMS(c);
+    return keys_writable(c);
+}
+// A party's bootstrapping key, in coefficient form on the device at `src`, into the resident tables: the transforms (and the limb
+// transforms where the key set keeps them), the stream drained, the limb maximum read back; marked only once all of it has succeeded
+hipError_t install_brk(mkt_ctx *c, int party, const void *src) {
+    KeySet &ks = *c->ks;
+    hipError_t e = to_resident(c, src, mkt::brk_polys_total(c->p, c->sh), ks.party<cplx>(T_BRK, party), false, ks.d_fx_brk ? ks.party<cplx>(T_FX_BRK, party) : nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && ks.d_fx_brk) e = fx_after_key_load(c);
+    if (e == hipSuccess) ks.loaded.mark(mkt::K_BRK, party);
+    return e;
+}
+// The key-switching key between its two layouts (mkt::KskLayout), on the context's stream: a party's table zeroed (the padding and the rows a
+// generator leaves absent), rows at the callers' pitch into it, and rows at the resident pitch (`padded`) out to a caller
+hipError_t ksk_zero(mkt_ctx *c, int party) { return hipMemsetAsync(c->ks->party<uint32_t>(T_KSK, party), 0, c->ks->stride(T_KSK) * sizeof(uint32_t), c->stream); }
+hipError_t ksk_repitch(mkt_ctx *c, uint32_t *dst, int dpitch, const uint32_t *src, int spitch, hipMemcpyKind kind) { return hipMemcpy2DAsync(dst, (size_t)dpitch * 4, src, (size_t)spitch * 4, (size_t)c->ks->ksk.n1 * 4, c->ks->ksk.rows, kind, c->stream); }
+hipError_t ksk_to_resident(mkt_ctx *c, int party, const uint32_t *rows, hipMemcpyKind kind) { return ksk_repitch(c, c->ks->party<uint32_t>(T_KSK, party), c->ks->ksk.n1p, rows, c->ks->ksk.n1, kind); }
+hipError_t ksk_to_rows(mkt_ctx *c, const uint32_t *padded, uint32_t *rows, hipMemcpyKind kind) { return ksk_repitch(c, rows, c->ks->ksk.n1, padded, c->ks->ksk.n1p, kind); }
 
 }  // namespace
 
@@ -743,7 +763,7 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     if (!dg.ok) { c->err = "hipSetDevice failed"; return bail(MKT_ERR_HIP); }
     const mkt_params &p = c->p;
     const int np = c->sh.nparty, M = c->M;
-    c->ks->brk_loaded.assign(np, 0); c->ks->ksk_loaded.assign(np, 0); c->ks->rlk_loaded.assign(np, 0); c->ks->pub_loaded.assign(np, 0);
+    c->ks->loaded.reset(np);
     mkt::make_twiddles(p.N, c->ks->tw);
     // rotation slots: KMS phase 1 runs 1 row for party 0 and l_lev rows for the others (bootstrapping.jl:400)
     std::vector<int> sp, sr;
@@ -840,7 +860,7 @@ int mkt_internal_clone_keys(mkt_ctx *src, mkt_ctx *dst, int no_peer) {
         if (a.tab[t].cloned && a.tab[t].present && b.tab[t].present)
             HIPCHK(dst, (hipError_t)mkt_internal_copy_across(*b.tab[t].slot, dd, *a.tab[t].slot, sd, a.tab[t].bytes(src->sh.nparty), no_peer));
     if (a.d_fx_brk && b.d_fx_brk) b.fx_kmax = a.fx_kmax;
-    b.brk_loaded = a.brk_loaded; b.ksk_loaded = a.ksk_loaded; b.rlk_loaded = a.rlk_loaded; b.pub_loaded = a.pub_loaded; b.crs_loaded = a.crs_loaded;
+    b.loaded = a.loaded;
     dst->tune = src->tune;
     // hipMemcpyPeer may return before the copy has landed, and the shards evaluate on non-blocking streams that the NULL stream does
     // not order: both devices are drained before the replica may be used (one-time cost, off the evaluation path)
@@ -919,9 +939,7 @@ int mkt_set_twiddles(mkt_ctx *c, const double *psi, const double *psiinv, const 
     if (int w = keys_writable(c)) return w;
     // tables first, then keys: a loaded bootstrapping key, relinearisation key, public key or CRS is resident as its transform under the tables
     // it met (or as the caller's Trans* values), and its integer form is not kept -- new tables would leave keys and transforms disagreeing
-    bool keyed = c->ks->crs_loaded;
-    for (int i = 0; i < c->sh.nparty; i++) keyed = keyed || c->ks->brk_loaded[i] || c->ks->rlk_loaded[i] || c->ks->pub_loaded[i];
-    if (keyed) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
+    if (c->ks->loaded.any_transformed()) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
     DevGuard dg(c->device);
     const size_t nd = (size_t)2 * c->M;
     // the kernels derive the inverse twiddles from the forward table: Psiinv must be conj(Psi) entry for entry,
@@ -953,79 +971,67 @@ int mkt_get_monomial(mkt_ctx *c, int e, double *out_host) {
 }
 
 int mkt_load_brk(mkt_ctx *c, int party, const void *data, int fmt) {
-    if (!c || !data || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_EXACT_GATE(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, data != nullptr, party, Gate::EXACT)) return r;
     DevGuard dg(c->device);
-    int r = upload_polys(c, data, (size_t)c->p.n * c->sh.brk_polys, c->ks->party<cplx>(T_BRK, party), fmt, false,
-                         c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
-    if (!r) c->ks->brk_loaded[party] = 1;
+    int r = upload_polys(c, data, mkt::brk_polys_total(c->p, c->sh), c->ks->party<cplx>(T_BRK, party), fmt, false, party);
+    if (!r && fmt != MKT_FMT_INT_COEFF) c->ks->loaded.mark(mkt::K_BRK, party);   // the caller's transforms, reordered only; install_brk marks a key it installed
     return r;
 }
 
+// on the context's stream like every other key load (mktfhe.h), and drained before the call returns: `data` is the caller's
 int mkt_load_ksk(mkt_ctx *c, int party, const uint32_t *data) {
-    if (!c || !data || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_EXACT_GATE(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, data != nullptr, party, Gate::EXACT)) return r;
     DevGuard dg(c->device);
-    const size_t rows = (size_t)c->sh.ksk_kr * c->p.N * c->sh.ksk_drows * c->p.f, n1 = (size_t)c->p.n + 1;
-    HIPCHK(c, hipMemset(c->ks->party<uint32_t>(T_KSK, party), 0, c->ks->stride(T_KSK) * sizeof(uint32_t)));
-    HIPCHK(c, hipMemcpy2D(c->ks->party<uint32_t>(T_KSK, party), (size_t)c->ks->n1p * 4, data, n1 * 4, n1 * 4, rows, hipMemcpyHostToDevice));
-    c->ks->ksk_loaded[party] = 1;
+    HIPCHK(c, ksk_zero(c, party));
+    HIPCHK(c, ksk_to_resident(c, party, data, hipMemcpyHostToDevice));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ks->loaded.mark(mkt::K_KSK, party);
     return MKT_OK;
 }
 
 int mkt_load_rlk(mkt_ctx *c, int party, const void *d, const void *f, int fmt) {
-    if (!c || !d || !f || party < 0 || party >= c->sh.nparty || !mkt::is_kms(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_F64_OR_EXACT_KMS(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, d && f, party, Gate::F64_OR_EXACT_KMS, mkt::is_kms)) return r;
     DevGuard dg(c->device);
     const size_t l = (size_t)c->p.l_uni;
     int r = upload_polys(c, d, l, c->ks->party<cplx>(T_RLK_D, party), fmt);
     if (!r) r = upload_polys(c, f, 2 * l, c->ks->party<cplx>(T_RLK_F, party), fmt);
-    if (!r) c->ks->rlk_loaded[party] = 1;
+    if (!r) c->ks->loaded.mark(mkt::K_RLK, party);
     return r;
 }
 
 int mkt_load_pubkey(mkt_ctx *c, int party, const void *b, int fmt) {
-    if (!c || !b || party < 0 || party >= c->sh.nparty || !mkt::is_mk(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_F64_OR_EXACT_KMS(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, b != nullptr, party, Gate::F64_OR_EXACT_KMS, mkt::is_mk)) return r;
     DevGuard dg(c->device);
     int r = upload_polys(c, b, (size_t)c->p.l_uni, c->ks->party<cplx>(T_PUB, party), fmt);
-    if (!r) c->ks->pub_loaded[party] = 1;
+    if (!r) c->ks->loaded.mark(mkt::K_PUB, party);
     return r;
 }
 
 int mkt_load_crs(mkt_ctx *c, const void *a, int fmt) {
-    if (!c || !a || !mkt::is_mk(c->p.scheme)) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_F64_OR_EXACT_KMS(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, a != nullptr, NO_PARTY, Gate::F64_OR_EXACT_KMS, mkt::is_mk)) return r;
     DevGuard dg(c->device);
     int r = upload_polys(c, a, (size_t)c->p.l_uni, c->ks->d_crs, fmt);
-    if (!r) c->ks->crs_loaded = true;
+    if (!r) c->ks->loaded.mark(mkt::K_CRS, NO_PARTY);
     return r;
 }
 
 // Bootstrapping key and key-switching key of party `party` generated on the device from the party's secrets
 // (keygen.hip: the seeded streams of mkt_client_party_keygen, identical words), pre-transformed in place of an upload.
 static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, const void *crs, void *brk_out, uint32_t *ksk_out) {
-    if (!c || !K || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_EXACT_GATE(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, K != nullptr, party, Gate::EXACT)) return r;
     const mkt_params &p = c->p;
     if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: the party's keys were made for other parameters / another party index");
     const bool unienc = p.scheme == MKT_CCS;
     if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: CCS needs the integer CRS");
     DevGuard dg(c->device);
     const int N = p.N, nz = (int)K->zring.size();
-    const size_t brk_polys_total = (size_t)p.n * c->sh.brk_polys;
+    const size_t brk_bytes = mkt::brk_polys_total(p, c->sh) * poly_bytes(c);
     DevBuf out, crs_int;                      // freed behind the secrets' drain of the stream
     DeviceSecret lwe{c}, z{c};
     hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
     if (e == hipSuccess) e = z.alloc((size_t)nz * N);
     for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync((int8_t *)z.dev + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&out.p, brk_polys_total * poly_bytes(c));
+    if (e == hipSuccess) e = hipMalloc(&out.p, brk_bytes);
     if (e == hipSuccess && unienc) e = hipMalloc(&crs_int.p, (size_t)p.l_uni * poly_bytes(c));
     if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return hipfail(c, e, "device keygen setup");
@@ -1036,16 +1042,14 @@ static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, 
     if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; a.zoff = 0; }
     else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; a.zoff = 0; }
     e = mktd::launch_keygen_brk(a, unienc ? 1 : 0, c->stream);
-    if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, out.p, brk_polys_total * poly_bytes(c), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = to_resident(c, out.p, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
-    uint32_t *ksk = c->ks->party<uint32_t>(T_KSK, party);
-    if (e == hipSuccess) e = hipMemsetAsync(ksk, 0, c->ks->stride(T_KSK) * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, out.p, brk_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = install_brk(c, party, out.p);
+    if (e == hipSuccess) e = ksk_zero(c, party);
     a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
-    if (e == hipSuccess) e = mktd::launch_keygen_ksk(a, ksk, c->ks->n1p, c->sh.ksk_kr, c->sh.ksk_drows, mkt::is_block(p.scheme) ? 1 : 0, c->stream);
+    if (e == hipSuccess) e = mktd::launch_keygen_ksk(a, c->ks->party<uint32_t>(T_KSK, party), c->ks->ksk.n1p, c->sh.ksk_kr, c->sh.ksk_drows, mkt::is_block(p.scheme) ? 1 : 0, c->stream);
     e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);
     if (e != hipSuccess) return hipfail(c, e, "device keygen");
-    c->ks->brk_loaded[party] = 1; c->ks->ksk_loaded[party] = 1;
-    if (c->ks->d_fx_brk) { int r = fx_after_key_load(c); if (r) return r; }
+    c->ks->loaded.mark(mkt::K_KSK, party);
     if (ksk_out) return mkt_get_ksk(c, party, ksk_out);
     return MKT_OK;
 }
@@ -1136,7 +1140,7 @@ int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, c
 
 // Seeded evaluation keys (mktfhe.h): party `party`'s two large keys regenerated on this context's device from the public mask seed and the
 // compact sections (seeded_keys.hip), the words of mkt_client_seeded_keys_expand.  load: into the resident tables -- the bootstrapping key
-// through the coefficient-form staging buffer keygen_device_impl uses and the same to_resident, the key-switching key straight into its
+// expanded into a coefficient-form buffer and installed like every other (install_brk), the key-switching key straight into its
 // table at the padded pitch; else into the caller's brk_out / ksk_out (`mem`), the compact sections living there too.  Nothing is secret.
 static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, bool load,
                             void *brk_out, uint32_t *ksk_out, int mem) {
@@ -1144,7 +1148,7 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
     if (!load && (!brk_seeded != !brk_out || !ksk_seeded != !ksk_out)) return fail(c, MKT_ERR_ARG, "mkt_seeded_keys_expand: a compact section and its output come together");
     const mkt_params &p = c->p;
     DevGuard dg(c->device);
-    const size_t body_polys = mkt::brk_seeded_polys(p, c->sh), brk_polys_total = (size_t)p.n * c->sh.brk_polys, rows = mkt::ksk_rows(p, c->sh);
+    const size_t body_polys = mkt::brk_seeded_polys(p, c->sh), brk_polys_total = mkt::brk_polys_total(p, c->sh), rows = c->ks->ksk.rows;
     Staged sb{c}, sk{c}, so{c};
     DevBuf full, padded;                    // load: the expanded bootstrapping key in coefficient form; expand: the key-switching key at the padded pitch
     int r;
@@ -1159,27 +1163,24 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
         a.party = party; a.unienc = p.scheme == MKT_CCS; a.kr = c->sh.kr; a.l = a.unienc ? p.l_uni : p.l_gsw;
         a.log_units = c->logN + (p.W == 64 ? 1 : 0) - 4; a.body = sb.dev; a.out = dst; a.npolys = brk_polys_total;
         e = mktd::launch_seeded_brk_expand(a, c->stream);
-        if (e == hipSuccess && load) e = to_resident(c, dst, brk_polys_total, c->ks->party<cplx>(T_BRK, party), false, c->ks->d_fx_brk ? c->ks->party<cplx>(T_FX_BRK, party) : nullptr);
+        if (e == hipSuccess && load) e = install_brk(c, party, dst);
         if (e != hipSuccess) return hipfail(c, e, "seeded bootstrapping key expansion");
     }
     if (ksk_seeded) {
         if ((r = sk.in(ksk_seeded, rows * 4, mem, true))) return r;
         uint32_t *dst = c->ks->party<uint32_t>(T_KSK, party);
-        if (!load) { HIPCHK(c, hipMalloc(&padded.p, rows * (size_t)c->ks->n1p * 4)); dst = (uint32_t *)padded.p; }
+        if (!load) { HIPCHK(c, hipMalloc(&padded.p, c->ks->ksk.resident_words() * 4)); dst = (uint32_t *)padded.p; }
         mktd::SeededKskArgs a{};
         mkt::seed_to_key(mask_seed, a.mkey);
-        a.party = party; a.n = p.n; a.n1p = c->ks->n1p; a.rows_per_cj = (uint32_t)(c->sh.ksk_drows * p.f);
+        a.party = party; a.n = p.n; a.n1p = c->ks->ksk.n1p; a.rows_per_cj = (uint32_t)(c->sh.ksk_drows * p.f);
         a.absent_below = mkt::is_block(p.scheme) ? p.n : 0; a.body = (const uint32_t *)sk.dev; a.out = dst; a.rows = rows;
         e = mktd::launch_seeded_ksk_expand(a, c->stream);
-        const size_t n1 = (size_t)p.n + 1;
-        if (e == hipSuccess && !load) e = hipMemcpy2DAsync(ksk_out, n1 * 4, dst, (size_t)c->ks->n1p * 4, n1 * 4, rows, mem == MKT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess && !load) e = ksk_to_rows(c, dst, ksk_out, mem == MKT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
         if (e != hipSuccess) return hipfail(c, e, "seeded key-switching key expansion");
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!load) return brk_out ? so.out(brk_out) : MKT_OK;
-    if (brk_seeded) c->ks->brk_loaded[party] = 1;
-    if (ksk_seeded) c->ks->ksk_loaded[party] = 1;
-    if (brk_seeded && c->ks->d_fx_brk) return fx_after_key_load(c);
+    if (ksk_seeded) c->ks->loaded.mark(mkt::K_KSK, party);
     return MKT_OK;
 }
 
@@ -1188,9 +1189,7 @@ int mkt_seeded_keys_expand(mkt_ctx *c, int party, const uint8_t *mask_seed, cons
 }
 
 int mkt_load_seeded_keys(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded) {
-    if (!c || (!brk_seeded && !ksk_seeded)) return fail(c, MKT_ERR_ARG, "bad argument");
-    MKT_EXACT_GATE(c);
-    if (int w = keys_writable(c)) return w;
+    if (int r = key_write_guard(c, brk_seeded || ksk_seeded, NO_PARTY, Gate::EXACT)) return r;   // (the party and the seed: seeded_keys_impl)
     return seeded_keys_impl(c, party, mask_seed, brk_seeded, ksk_seeded, true, nullptr, nullptr, MKT_MEM_HOST);
 }
 
@@ -1199,9 +1198,8 @@ int mkt_get_ksk(mkt_ctx *c, int party, uint32_t *out_host) {
     if (!c || !out_host || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
     MKT_EXACT_GATE(c);
     DevGuard dg(c->device);
-    const size_t rows = (size_t)c->sh.ksk_kr * c->p.N * c->sh.ksk_drows * c->p.f, n1 = (size_t)c->p.n + 1;
+    HIPCHK(c, ksk_to_rows(c, c->ks->party<uint32_t>(T_KSK, party), out_host, hipMemcpyDeviceToHost));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(out_host, n1 * 4, c->ks->party<uint32_t>(T_KSK, party), (size_t)c->ks->n1p * 4, n1 * 4, rows, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 

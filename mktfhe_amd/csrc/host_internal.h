@@ -68,6 +68,32 @@ inline bool host_below(const uint32_t *v, size_t n, size_t bound) {
 // seeded evaluation keys (mktfhe.h): polynomials of one party's compact bootstrapping-key section, rows (= body words) of its key-switching key
 inline size_t brk_seeded_polys(const mkt_params &p, const Shape &s) { return (size_t)p.n * (p.scheme == MKT_CCS ? 2 * (size_t)p.l_uni : (size_t)(s.kr + 1) * p.l_gsw); }
 inline size_t ksk_rows(const mkt_params &p, const Shape &s) { return (size_t)s.ksk_kr * p.N * s.ksk_drows * p.f; }
+// a party's bootstrapping key: polynomials in coefficient form (mkt_load_brk, MKT_FMT_INT_COEFF)
+inline size_t brk_polys_total(const mkt_params &p, const Shape &s) { return (size_t)p.n * s.brk_polys; }
+// The key-switching key of one party in its two layouts: ksk_rows rows of n1 = n + 1 words as a caller holds them (mkt_load_ksk, mkt_get_ksk),
+// the same rows at the pitch n1p -- padded to 16 bytes, the padding zero -- in the resident table
+struct KskLayout {
+    size_t rows = 0; int n1 = 0, n1p = 0;
+    size_t resident_words() const { return rows * (size_t)n1p; }
+};
+inline KskLayout ksk_layout(const mkt_params &p, const Shape &s) { return KskLayout{ksk_rows(p, s), p.n + 1, (p.n + 1 + 3) / 4 * 4}; }
+
+// Which key pieces of which party are resident (KeySet::loaded): the one record that key loads write and check_ready, mkt_set_twiddles and
+// the key replication read.  The CRS belongs to no party (party < 0): it is marked for all of them.
+enum KeyPiece { K_BRK, K_KSK, K_RLK, K_PUB, K_CRS };
+struct LoadedKeys {
+    std::vector<uint8_t> of;   // [party]: bit k = piece k of the party is resident
+    static constexpr unsigned bit(KeyPiece k) { return 1u << k; }
+    void reset(int nparty) { of.assign((size_t)nparty, 0); }
+    void mark(KeyPiece k, int party) { for (size_t i = 0; i < of.size(); i++) if (party < 0 || (size_t)party == i) of[i] |= (uint8_t)bit(k); }
+    bool has_all(unsigned pieces, int party) const { return (of[(size_t)party] & pieces) == pieces; }
+    bool has(KeyPiece k, int party) const { return has_all(bit(k), party < 0 ? 0 : party); }
+    // pieces that are resident as transforms under the tables they met (the key-switching key is integer data): mkt_set_twiddles
+    bool any_transformed() const {
+        for (uint8_t m : of) if (m & (bit(K_BRK) | bit(K_RLK) | bit(K_PUB) | bit(K_CRS))) return true;
+        return false;
+    }
+};
 inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;

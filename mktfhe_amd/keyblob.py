@@ -112,12 +112,10 @@ def load(blob: bytes):
 
 def _check_seeded(pd, secs):
     """a version-2 blob holds the three seeded sections at exactly the lengths its parameters give"""
-    from .scheme import seeded_section_words
     if {"brk", "ksk"} & set(secs):
         raise ValueError("a version-2 key blob holds the seeded sections, not brk / ksk")
     p = Params("blob", alpha=0.0, beta=0.0, **pd)
-    wb, wk = seeded_section_words(p)
-    for name, dt, want in (("mask_seed", np.uint32, 8), ("brk_seeded", p.ring_dtype, wb), ("ksk_seeded", np.uint32, wk)):
+    for name, dt, want in (("mask_seed", np.uint32, 8), ("brk_seeded", p.ring_dtype, p.brk_seeded_words), ("ksk_seeded", np.uint32, p.ksk_rows)):
         if name not in secs:
             raise ValueError(f"a version-2 key blob needs the section {name}")
         if secs[name].dtype != dt or secs[name].size != want:

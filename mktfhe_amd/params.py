@@ -47,6 +47,28 @@ class Params:
         import numpy as np
         return np.uint64 if self.W == 64 else np.uint32
 
+    # -- sizes of one party's two large keys (include/mktfhe.h layouts), stated here once: everything that allocates, checks or ships them reads these
+    @property
+    def _kr(self):
+        """RLWE length of the RGSW rotation: 1 for the KMS schemes, else k"""
+        return 1 if self.scheme in (KMS, KMS_BLOCK) else self.k
+
+    @property
+    def brk_words(self):
+        """ring words of the bootstrapping key"""
+        return self.n * (3 * self.l_uni if self.scheme == CCS else (self._kr + 1) * self.l_gsw * (self._kr + 1)) * self.N
+
+    @property
+    def brk_seeded_words(self):
+        """ring words of the compact bootstrapping-key section (seeded key form): the bodies, and for CCS the d rows whole"""
+        return self.n * (2 * self.l_uni if self.scheme == CCS else (self._kr + 1) * self.l_gsw) * self.N
+
+    @property
+    def ksk_rows(self):
+        """rows of the key-switching key, n + 1 words each; the compact section holds one body word per row"""
+        D = 1 << self.logD
+        return (1 if self.multikey else self.k) * self.N * (D // 2 if self.scheme in (LMSS, KMS_BLOCK) else D - 1) * self.f
+
     def c(self):
         return MktParams(self.scheme, self.n, self.N, self.k, self.W, self.l_gsw, self.logB_gsw, self.l_lev,
                          self.logB_lev, self.l_uni, self.logB_uni, self.f, self.logD, self.blk_len, self.blk_d)

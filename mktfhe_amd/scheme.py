@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MktError, check
-from .params import CGGI, LMSS, CCS, KMS, KMS_BLOCK, Params
+from .params import CCS, Params
 
 MEM_DEVICE, MEM_HOST = 0, 1
 FMT_INT_COEFF, FMT_F64_FFT = 0, 1
@@ -303,6 +303,32 @@ class _Batched:
         self._ck(getattr(_lib.lib(), fn)(self.h, *cargs, B, mem))
         return kept
 
+    # -- keys (MultiScheme: once, on the first device; replicate() copies them to the others)
+    def load_party(self, party, keys: "PartyKeys" = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF,
+                   mask_seed=None, brk_seeded=None, ksk_seeded=None):
+        """upload one party's evaluation keys.  A seeded party (PartyKeys(seeded=True)), or mask_seed with brk_seeded / ksk_seeded, goes
+        through mkt_load_seeded_keys: the masks are regenerated on the GPU, the expanded keys never exist on the host"""
+        fn = lambda name: getattr(_lib.lib(), self._PREFIX + name)      # noqa: E731
+        if keys is not None:
+            brk, ksk, rlk_d, rlk_f, pubkey = keys.brk, keys.ksk, keys.rlk_d, keys.rlk_f, keys.pubkey
+            if getattr(keys, "seeded", False):
+                mask_seed, brk_seeded, ksk_seeded = keys.mask_seed, keys.brk_seeded, keys.ksk_seeded
+        if mask_seed is not None:
+            _load_seeded(self, party, mask_seed, brk_seeded, ksk_seeded)
+        kd = np.complex128 if fmt == FMT_F64_FFT else self.params.ring_dtype
+        if brk is not None:
+            self._ck(fn("load_brk")(self.h, party, _np_ptr(np.ascontiguousarray(brk, dtype=kd)), fmt))
+        if ksk is not None:
+            self._ck(fn("load_ksk")(self.h, party, _np_ptr(np.ascontiguousarray(ksk, dtype=np.uint32))))
+        if rlk_d is not None:
+            self._ck(fn("load_rlk")(self.h, party, _np_ptr(np.ascontiguousarray(rlk_d, dtype=kd)), _np_ptr(np.ascontiguousarray(rlk_f, dtype=kd)), fmt))
+        if pubkey is not None:
+            self._ck(fn("load_pubkey")(self.h, party, _np_ptr(np.ascontiguousarray(pubkey, dtype=kd)), fmt))
+
+    def load_crs(self, a, fmt=FMT_INT_COEFF):
+        kd = np.complex128 if fmt == FMT_F64_FFT else self.params.ring_dtype
+        self._ck(getattr(_lib.lib(), self._PREFIX + "load_crs")(self.h, _np_ptr(np.ascontiguousarray(a, dtype=kd)), fmt))
+
     def gate(self, op, x, y, out=None):
         B, out = _one_shape(x, y, out=out)
         return self._call("gate_batch", B, op, self._ct(x, B), self._ct(y, B), self._ct(out, B, out=True))[-1]
@@ -357,11 +383,7 @@ class _Batched:
 
 def seeded_section_words(params: Params):
     """(ring words of brk_seeded, words of ksk_seeded) of one party (include/mktfhe.h "seeded evaluation keys", compact layouts)"""
-    p = params
-    D = 1 << p.logD
-    kr = 1 if p.scheme in (KMS, KMS_BLOCK) else p.k
-    brk = p.n * (2 * p.l_uni if p.scheme == CCS else (kr + 1) * p.l_gsw) * p.N
-    return brk, (1 if p.multikey else p.k) * p.N * (D // 2 if p.scheme in (LMSS, KMS_BLOCK) else D - 1) * p.f
+    return params.brk_seeded_words, params.ksk_rows
 
 
 def _seeded_sections(params, brk_seeded, ksk_seeded):
@@ -437,29 +459,7 @@ class Scheme(_Batched):
     def _ck(self, code):
         return check(code, self.h)
 
-    # -- keys
-    def load_party(self, party, keys: PartyKeys = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF,
-                   mask_seed=None, brk_seeded=None, ksk_seeded=None):
-        """upload one party's evaluation keys.  A seeded party (PartyKeys(seeded=True)), or mask_seed with brk_seeded / ksk_seeded, goes
-        through mkt_load_seeded_keys: the masks are regenerated on the GPU, the expanded keys never exist on the host"""
-        L, p = _lib.lib(), self.params
-        if keys is not None:
-            brk, ksk, rlk_d, rlk_f, pubkey = keys.brk, keys.ksk, keys.rlk_d, keys.rlk_f, keys.pubkey
-            if getattr(keys, "seeded", False):
-                mask_seed, brk_seeded, ksk_seeded = keys.mask_seed, keys.brk_seeded, keys.ksk_seeded
-        if mask_seed is not None:
-            _load_seeded(self, party, mask_seed, brk_seeded, ksk_seeded)
-        kd = np.complex128 if fmt == FMT_F64_FFT else p.ring_dtype
-        if brk is not None:
-            self._ck(L.mkt_load_brk(self.h, party, _np_ptr(np.ascontiguousarray(brk, dtype=kd)), fmt))
-        if ksk is not None:
-            self._ck(L.mkt_load_ksk(self.h, party, _np_ptr(np.ascontiguousarray(ksk, dtype=np.uint32))))
-        if rlk_d is not None:
-            self._ck(L.mkt_load_rlk(self.h, party, _np_ptr(np.ascontiguousarray(rlk_d, dtype=kd)),
-                                    _np_ptr(np.ascontiguousarray(rlk_f, dtype=kd)), fmt))
-        if pubkey is not None:
-            self._ck(L.mkt_load_pubkey(self.h, party, _np_ptr(np.ascontiguousarray(pubkey, dtype=kd)), fmt))
-
+    # -- keys (load_party, load_crs: _Batched)
     def keygen_device(self, party, keys: PartyKeys, export=False):
         """keygen.jl:13-23 etc. on the GPU: bootstrapping + key-switching key of `party` from its secrets (the small
         keys -- public key, relinearisation key -- are uploaded from `keys`).  This hands the party's SECRETS to this
@@ -469,8 +469,7 @@ class Scheme(_Batched):
         crs_p = _np_ptr(keys._crs) if (self.params.scheme == CCS and keys._crs is not None) else None
         out = None
         if export:
-            p = self.params
-            brk = np.empty(self.brk_words(), dtype=p.ring_dtype)
+            brk = np.empty(self.brk_words(), dtype=self.params.ring_dtype)
             ksk = np.empty(self.get_ksk_shape(), dtype=np.uint32)
             self._ck(L.mkt_keygen_device_export(self.h, party, keys.h, crs_p, _np_ptr(brk), _np_ptr(ksk)))
             out = (brk, ksk.ravel())
@@ -481,26 +480,15 @@ class Scheme(_Batched):
 
     def brk_words(self):
         """ring words of one party's bootstrapping key (include/mktfhe.h layouts)"""
-        p = self.params
-        if p.scheme == CCS:
-            return p.n * 3 * p.l_uni * p.N
-        kr = 1 if p.scheme in (KMS, KMS_BLOCK) else p.k
-        return p.n * (kr + 1) * p.l_gsw * (kr + 1) * p.N
+        return self.params.brk_words
 
     def get_ksk_shape(self):
-        p = self.params
-        D = 1 << p.logD
-        rows = (1 if p.multikey else p.k) * p.N * (D // 2 if p.scheme in (LMSS, KMS_BLOCK) else D - 1) * p.f
-        return (rows, p.n + 1)
+        return (self.params.ksk_rows, self.params.n + 1)
 
     def get_ksk(self, party):
         out = np.empty(self.get_ksk_shape(), dtype=np.uint32)
         self._ck(_lib.lib().mkt_get_ksk(self.h, party, _np_ptr(out)))
         return out
-
-    def load_crs(self, a, fmt=FMT_INT_COEFF):
-        kd = np.complex128 if fmt == FMT_F64_FFT else self.params.ring_dtype
-        self._ck(_lib.lib().mkt_load_crs(self.h, _np_ptr(np.ascontiguousarray(a, dtype=kd)), fmt))
 
     def set_stream(self, stream_handle):
         """pin the HIP stream (hipStream_t handle) every later call is enqueued on; None = back to the default:
@@ -694,36 +682,11 @@ class MultiScheme(_Batched):
         s._owned = False
         return s
 
-    # -- keys: once, on the first device; replicate() copies them to the others
-    def load_party(self, party, keys: "PartyKeys" = None, *, brk=None, ksk=None, rlk_d=None, rlk_f=None, pubkey=None, fmt=FMT_INT_COEFF,
-                   mask_seed=None, brk_seeded=None, ksk_seeded=None):
-        """as Scheme.load_party, on the first device (a seeded party: mkt_multi_load_seeded_keys)"""
-        L, p = _lib.lib(), self.params
-        if keys is not None:
-            brk, ksk, rlk_d, rlk_f, pubkey = keys.brk, keys.ksk, keys.rlk_d, keys.rlk_f, keys.pubkey
-            if getattr(keys, "seeded", False):
-                mask_seed, brk_seeded, ksk_seeded = keys.mask_seed, keys.brk_seeded, keys.ksk_seeded
-        if mask_seed is not None:
-            _load_seeded(self, party, mask_seed, brk_seeded, ksk_seeded)
-        kd = np.complex128 if fmt == FMT_F64_FFT else p.ring_dtype
-        if brk is not None:
-            self._ck(L.mkt_multi_load_brk(self.h, party, _np_ptr(np.ascontiguousarray(brk, dtype=kd)), fmt))
-        if ksk is not None:
-            self._ck(L.mkt_multi_load_ksk(self.h, party, _np_ptr(np.ascontiguousarray(ksk, dtype=np.uint32))))
-        if rlk_d is not None:
-            self._ck(L.mkt_multi_load_rlk(self.h, party, _np_ptr(np.ascontiguousarray(rlk_d, dtype=kd)),
-                                          _np_ptr(np.ascontiguousarray(rlk_f, dtype=kd)), fmt))
-        if pubkey is not None:
-            self._ck(L.mkt_multi_load_pubkey(self.h, party, _np_ptr(np.ascontiguousarray(pubkey, dtype=kd)), fmt))
-
+    # -- keys: once, on the first device; replicate() copies them to the others (load_party, load_crs: _Batched)
     def keygen_device(self, party, keys: "PartyKeys"):
         crs_p = _np_ptr(keys._crs) if (self.params.scheme == CCS and keys._crs is not None) else None
         self._ck(_lib.lib().mkt_multi_keygen_device(self.h, party, keys.h, crs_p))
         self.load_party(party, rlk_d=keys.rlk_d, rlk_f=keys.rlk_f, pubkey=keys.pubkey)
-
-    def load_crs(self, a, fmt=FMT_INT_COEFF):
-        kd = np.complex128 if fmt == FMT_F64_FFT else self.params.ring_dtype
-        self._ck(_lib.lib().mkt_multi_load_crs(self.h, _np_ptr(np.ascontiguousarray(a, dtype=kd)), fmt))
 
     def replicate(self):
         self._ck(_lib.lib().mkt_multi_replicate(self.h))
@@ -731,6 +694,11 @@ class MultiScheme(_Batched):
 
     def set_option(self, name, value):
         self._ck(_lib.lib().mkt_multi_set_option(self.h, name.encode(), int(value)))
+
+
+def _install(sch, party, keys):
+    """one party's keys into a Scheme or MultiScheme; keys made with secrets_only=True get their large keys generated on the device"""
+    (sch.keygen_device if keys.secrets_only else sch.load_party)(party, keys)
 
 
 def setup_multi(params: Params, devices, keys=None, a=None, arith=ARITH_F64REF, private_keys=False, stage_always=False, no_peer=False):
@@ -743,7 +711,7 @@ def setup_multi(params: Params, devices, keys=None, a=None, arith=ARITH_F64REF, 
     else:
         klist = [keys if isinstance(keys, PartyKeys) else keys[0]]
     for i, kk in enumerate(klist):
-        (sch.keygen_device if kk.secrets_only else sch.load_party)(i, kk)
+        _install(sch, i, kk)
     sch.replicate()
     return sch
 
@@ -753,17 +721,15 @@ def setup(params: Params, keys=None, a=None, device=0, deterministic_seed=None, 
     scheme.jl:244 / :292 / :343 setup(a, btk, params) -> scheme for the multi-key ones
     (keys = list of PartyKeys, a = CRS).  The evaluation keys are uploaded and pre-transformed
     on `device`."""
-    def install(sch, i, kk):      # keys made with secrets_only=True get their large keys generated on the device
-        (sch.keygen_device if kk.secrets_only else sch.load_party)(i, kk)
     if not params.multikey:
         ks = keys if keys is not None else PartyKeys(params, party=0, deterministic_seed=deterministic_seed)
         sch = Scheme(params, device=device, arith=arith)
-        install(sch, 0, ks)
+        _install(sch, 0, ks)
         return ks, sch
     sch = Scheme(params, device=device, arith=arith)
     sch.load_crs(a)
     for i, kk in enumerate(keys):
-        install(sch, i, kk)
+        _install(sch, i, kk)
     return sch
 
 

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .params import CCS, KMS, KMS_BLOCK, LMSS, Params
+from .params import Params
 from .scheme import MEM_DEVICE, PartyKeys, _arg, _Buf, _empty, _np_ptr, _seed32, _seeded_sections, seeded_section_words
 
 
@@ -27,12 +27,7 @@ def party_keygen_seeded(a, params: Params, party=0, mask_seed=None, deterministi
 
 def full_key_words(params: Params):
     """(ring words of the bootstrapping key, (rows, n + 1) of the key-switching key) of one party: the layouts of load_party"""
-    p = params
-    D = 1 << p.logD
-    kr = 1 if p.scheme in (KMS, KMS_BLOCK) else p.k
-    brk = p.n * (3 * p.l_uni if p.scheme == CCS else (kr + 1) * p.l_gsw * (kr + 1)) * p.N
-    rows = (1 if p.multikey else p.k) * p.N * (D // 2 if p.scheme in (LMSS, KMS_BLOCK) else D - 1) * p.f
-    return brk, (rows, p.n + 1)
+    return params.brk_words, (params.ksk_rows, params.n + 1)
 
 
 def seeded_keys_expand(params: Params, party, mask_seed, brk_seeded=None, ksk_seeded=None, scheme=None):

@@ -412,13 +412,39 @@ def made(name, keyed):
     return make
 
 
+def ksk_reload_behind_a_batch(s, name, want):
+    """the context pinned to a fresh non-blocking stream: a device-memory gate_ops batch, the last party's key-switching key loaded again
+    (load_party(ksk=...), the words it already holds) with no synchronisation in between, the batch again; both results are `want`, the
+    fresh context's.  A GUARD, NOT A RACE DETECTOR: it passes whether or not the reload is ordered behind the first batch, as long as the
+    copy happens to land outside the key switch.  That mkt_load_ksk IS ordered -- it zeroes and fills the table on the context's stream and
+    drains it, where it once used the NULL stream, which a non-blocking stream does not wait for -- is an argument made by reading
+    context.cpp.  The operands are held here until the stream is drained: the batch reads them after the calls have returned"""
+    import torch
+    i, B = inputs(name), 33
+    party = i.p.nparty - 1
+    ksk = s.get_ksk(party)
+    ops, x, y = to_mem(i.ops[:B], D), to_mem(i.x[:B], D), to_mem(i.y[:B], D)
+    stream = torch.cuda.Stream()                # torch creates its streams non-blocking
+    torch.cuda.synchronize()                    # the operands are there before the pinned stream reads them
+    s.set_stream(stream.cuda_stream)
+    first = s.gate_ops(ops, x, y)
+    s.load_party(party, ksk=ksk)
+    second = s.gate_ops(ops, x, y)
+    s.synchronize()
+    s.set_stream(None)
+    assert same_words(host_words(first), want), (name, "the batch before the key-switching key was loaded again")
+    assert same_words(host_words(second), want), (name, "the batch after the key-switching key was loaded again")
+    assert np.array_equal(s.get_ksk(party), ksk)
+
+
 @pytest.mark.parametrize("name", ["cggi", "kms", "ccs", "x-kms"])
 def test_key_set_life_cycle(require_gpu, name):
     """READINESS: the pieces one at a time in the order ksk, crs, pubkey, rlk, brk, the last party first -- and, so that every line of
     check_ready is the first to refuse at some point, also in the reverse order, the first party first: every refusal is MKT_ERR_STATE
     with check_ready's message, keyswitch is served as soon as every key-switching key is there, blindrotate_ as soon as everything but
     them is.  RELOAD: keys of another seed over the resident ones, party by party, then mixed loading routes (load_party, keygen_device,
-    load_seeded): the words of a fresh context that only ever saw those keys.  IMMUTABILITY: after fork() every loading call and
+    load_seeded): the words of a fresh context that only ever saw those keys.  Then a key-switching key loaded again between two batches on a
+    pinned non-blocking stream (ksk_reload_behind_a_batch: a guard, not a race detector).  IMMUTABILITY: after fork() every loading call and
     mkt_set_twiddles return MKT_ERR_STATE on parent and fork, and both still serve gates"""
     p, arith = K.set_of(name)
     gate = STEP["gate"]
@@ -447,6 +473,7 @@ def test_key_set_life_cycle(require_gpu, name):
             assert s.get_metric("fx_kmax") >= kmax > 0, (how, s.get_metric("fx_kmax"), kmax)
             assert s.last_kernel_name() in ("fx_blindrotate_kernel", "exact_kms_phase1_p2pf_kernel"), s.last_kernel_name()
     seed, keyed, how = rounds[-1][1], rounds[-1][2], rounds[-1][0]
+    ksk_reload_behind_a_batch(s, name, fresh_step(name, STEP["gate_ops"], 33, D, seed, made(name, keyed), how))
 
     # immutability
     f = s.fork()

@@ -4,13 +4,14 @@ sides, copies elsewhere, so equality is exact -- at the shapes where the kernels
 the words of a scheme that received the host-expanded keys through load_party, on both arithmetic modes; a version-2 blob serves a shipped
 set end to end; forks refuse the load; the multi-device evaluator and the C example run."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import GATE_FUNCS, ROOT, encrypt_bits, gpu_scheme, mk
+from helpers import GATE_FUNCS, ROOT, encrypt_bits, gpu_scheme, mk, oracle_scheme
 from test_seeded_keys_cpu import MS, SHAPES, seeded_party
 
 pytestmark = pytest.mark.gpu
@@ -141,6 +142,89 @@ def test_a_seeded_scheme_computes_the_words_of_the_expanded_keys(require_gpu, p,
     mk.load_seeded(one, 0, mask_seed=MS, ksk_seeded=keys[0].ksk_seeded)
     assert np.array_equal(one.get_ksk(0), expanded[0][1])
     one.close(); want_s.close(); got_s.close()
+
+
+class _Expanded:
+    """a seeded party's secrets and small keys, with the two large keys as expanded on the host"""
+
+    def __init__(self, party, brk, ksk):
+        self._s, self.brk, self.ksk = party, brk, ksk
+
+    def __getattr__(self, name):
+        return getattr(self._s, name)
+
+
+def _neg(c):
+    return (0 - c.astype(np.int64)).astype(np.uint32)
+
+
+def _reference_row(p, arith, crs, keys, op, x, y):
+    """one gate_ops row under `keys`: the CPU oracle (Float64 reference) or its exact-arithmetic restatement (tests/ref_exact.py)"""
+    import ref_exact as RX
+    so = oracle_scheme(p, crs, keys)
+    x, y = _neg(x) if op & mk.OP_NOT_X else x, _neg(y) if op & mk.OP_NOT_Y else y
+    if arith == mk.ARITH_F64REF:
+        return so.gate(op & 7, x, y)
+    if p.scheme == mk.KMS:
+        return RX.kms_gate(p, so, keys, crs, op & 7, x, y)
+    return RX.gate(p, so, keys[0].brk, op & 7, x, y)
+
+
+@functools.lru_cache(maxsize=None)
+def _unseeded_set(p, seed):
+    """([party_keygen's PartyKeys], [the same parties' secrets and small keys only]) of every party, under the CRS of _seeded_set"""
+    crs = mk.CRS(p, seed) if p.multikey else None
+    return [mk.party_keygen(crs, p, party=i, deterministic_seed=seed) for i in range(p.nparty)], \
+        [mk.party_keygen(crs, p, party=i, secrets_only=True, deterministic_seed=seed) for i in range(p.nparty)]
+
+
+# one party set per scheme family at the shapes tests/test_gpu_keygen.py judges exported keys at, in the Float64 reference; CGGI and KMS also
+# in MKT_ARITH_EXACT, where the key set keeps the limb transforms of the bootstrapping key and (KMS, 64-bit ring) the split residue tables
+ROUTE_SETS = [(mk.CGGIparam.scaled(n=16), mk.ARITH_F64REF), (mk.Blockparam.scaled(n=18, blk_d=6), mk.ARITH_F64REF), (mk.CCS2party.scaled(n=20), mk.ARITH_F64REF),
+              (mk.KMS2party.scaled(n=16), mk.ARITH_F64REF), (mk.CGGIparam.scaled(n=16), mk.ARITH_EXACT), (mk.KMS2party.scaled(n=16), mk.ARITH_EXACT)]
+
+
+@pytest.mark.parametrize("p, arith", ROUTE_SETS, ids=lambda v: v.name if hasattr(v, "name") else ("exact" if v else "f64"))
+def test_three_routes_leave_one_resident_state(require_gpu, p, arith):
+    """The three ways a party's large keys become resident -- host upload (load_party), device generation (keygen_device), seeded load
+    (mkt_load_seeded_keys) -- end in one install path; contexts keyed by different routes with the same keys hold the same state: get_ksk of
+    every party word for word, "fx_kmax" bit for bit (> 0 on the MKT_ARITH_EXACT sets, which keep the limb transforms), and the words of one
+    gate_ops batch of 8 rows (row j under party j mod nparty, so the last party and, as every gate reads every polynomial of every party's
+    key, the last polynomial of a party's stride are met).
+    One key set cannot go through all three: the device generator makes the words of party_keygen, a seeded party's large keys come from
+    other streams (test_secrets_and_small_keys_are_those_of_the_unseeded_keygen).  So, secrets and small keys from one seed throughout:
+    device generation against an upload of party_keygen's keys, which are also the resident key-switching key (the rule of
+    tests/test_gpu_keygen.py: the device's words are the host's); the seeded load against an upload of the host-expanded keys, and rows 0 and
+    7 of that pair against the CPU oracle (the EXACT sets: row 7 against tests/ref_exact.py)"""
+    seed = 77
+    crs, seeded, expanded = _seeded_set(p, seed)
+    host, secrets = _unseeded_set(p, seed)
+    rng = np.random.default_rng(3)
+    c = encrypt_bits(p, host, rng.integers(0, 2, 16).astype(bool), seed=900)
+    ops = (rng.integers(0, 6, 8) | rng.choice([0, mk.OP_NOT_X, mk.OP_NOT_Y, mk.OP_NOT_X | mk.OP_NOT_Y], 8)).astype(np.uint8)
+
+    def state(s):
+        out = [s.get_ksk(i) for i in range(p.nparty)], s.get_metric("fx_kmax"), s.gate_ops(ops, c[:8], c[8:])
+        s.close()
+        return out
+
+    def same(a, b, what):
+        for i in range(p.nparty):
+            assert np.array_equal(a[0][i], b[0][i]), (what, "key-switching key of party", i)
+        assert a[1] == b[1] and (a[1] > 0.0) == (arith == mk.ARITH_EXACT), (what, "fx_kmax", a[1], b[1])
+        assert np.array_equal(a[2], b[2]), (what, "gate_ops rows that differ", np.nonzero((a[2] != b[2]).any(axis=1))[0])
+
+    uploaded = state(gpu_scheme(p, crs, host, arith=arith))
+    same(state(gpu_scheme(p, crs, secrets, arith=arith)), uploaded, "device generation against upload")
+    for i in range(p.nparty):
+        assert np.array_equal(uploaded[0][i].ravel(), host[i].ksk), i
+    uploaded = state(_plain_scheme(p, crs, seeded, expanded, arith))
+    same(state(gpu_scheme(p, crs, seeded, arith=arith)), uploaded, "seeded load against upload")
+    keys = [_Expanded(k, *e) for k, e in zip(seeded, expanded)]
+    for i in range(p.nparty):
+        assert np.array_equal(uploaded[0][i], expanded[i][1]), i
+    for j in ((0, 7) if arith == mk.ARITH_F64REF else (7,)):
+        assert np.array_equal(uploaded[2][j], _reference_row(p, arith, crs, keys, int(ops[j]), c[j], c[8 + j])), ("reference, row", j)
 
 
 def test_a_shipped_set_from_a_version_2_blob(require_gpu):

@@ -103,6 +103,32 @@ def test_every_mask_word_is_the_keystream_word_the_header_names(case):
     assert np.array_equal(mk.seeded_keys_expand(p, party, MS, ksk_seeded=k.ksk_seeded)[1], ksk)
 
 
+def _shipped_sets():
+    return [v for v in vars(mk.params).values() if isinstance(v, mk.Params)]
+
+
+# every shipped parameter set as it ships, and the scaled shapes of the GPU route test (tests/test_gpu_seeded_keys.py ROUTE_SETS)
+SIZE_SETS = _shipped_sets() + [mk.CGGIparam.scaled(n=16), mk.Blockparam.scaled(n=18, blk_d=6), mk.CCS2party.scaled(n=20), mk.KMS2party.scaled(n=16)]
+
+
+@pytest.mark.parametrize("p", SIZE_SETS, ids=lambda p: f"{p.name}-n{p.n}")
+def test_the_stated_sizes_are_those_of_the_host_keys(p):
+    """Params.brk_words / ksk_rows / brk_seeded_words -- the one Python statement of a party's key sizes, which Scheme.brk_words,
+    Scheme.get_ksk_shape, seeded_section_words, seeded_keys.full_key_words and the key blob read -- against the arrays the host keygen
+    returns for the last party: brk, ksk, brk_seeded, ksk_seeded.  The arrays are the reference, not a formula"""
+    party = p.nparty - 1
+    crs = mk.CRS(p, 3) if p.multikey else None
+    full = mk.party_keygen(crs, p, party=party, deterministic_seed=3)
+    seeded = mk.party_keygen_seeded(crs, p, party=party, mask_seed=MS, deterministic_seed=3)
+    assert (p.brk_words, p.ksk_rows * (p.n + 1)) == (full.brk.size, full.ksk.size)
+    assert (p.brk_seeded_words, p.ksk_rows) == (seeded.brk_seeded.size, seeded.ksk_seeded.size)
+    assert mk.seeded_section_words(p) == (seeded.brk_seeded.size, seeded.ksk_seeded.size)
+    assert mk.seeded_keys.full_key_words(p) == (full.brk.size, (full.ksk.size // (p.n + 1), p.n + 1))
+    s = object.__new__(mk.Scheme)               # no context behind it: the two size methods read the parameters only
+    s.params, s.h = p, None
+    assert s.brk_words() == full.brk.size and int(np.prod(s.get_ksk_shape())) == full.ksk.size and s.get_ksk_shape()[1] == p.n + 1
+
+
 @pytest.mark.parametrize("case", HOST_SHAPES, ids=ids)
 def test_expanded_keys_open_under_the_secrets(case):
     """ref_keys.open_rgsw / open_ccs_brk / open_ksk open the expanded keys unchanged: the phase of a seeded row is the reference's"""
