@@ -603,6 +603,27 @@ int mkt_seeded_keys_expand(mkt_ctx *ctx, int party, const uint8_t *mask_seed, co
  * shared (mkt_ctx_fork); MKT_ERR_UNSUPPORTED where mkt_load_brk is */
 int mkt_load_seeded_keys(mkt_ctx *ctx, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded);
 int mkt_multi_load_seeded_keys(mkt_multi *m, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded);
+/* the compact sections GENERATED ON THE PARTY'S OWN GPU: brk_seeded_out / ksk_seeded_out (HOST pointers, the compact layouts above; both given or
+ * both NULL) receive the sections mkt_client_party_keygen_seeded(params, seed, mask_seed, party, crs, sigmas of `keys`) writes for the seed `keys`
+ * was made from, word for word: noise from the secret streams 14, 15, 16, masks from the public streams 12, 13 keyed by `mask_seed`.  The
+ * large keys are never expanded, on the host or on the device.  `keys` is any party object of these parameters and this party index
+ * (mkt_client_party_keygen, _secrets or _keygen_seeded): only its secrets, its stream key and its sigmas are read.  `crs` = the integer CRS
+ * for MKT_CCS, NULL otherwise.
+ * install = 0: changes no resident table, needs no key loaded, runs on the context's stream; a context from mkt_ctx_create alone serves it.
+ * install = 1: the sections, still on the device, are also expanded and installed: the resident state of mkt_load_seeded_keys fed with them,
+ * including the Float64-pipe limbs and "fx_bound" of an MKT_ARITH_EXACT context; refused as mkt_keygen_device is (MKT_ERR_STATE once the key
+ * set is shared, MKT_ERR_UNSUPPORTED where mkt_load_brk is).
+ * REFUSALS (MKT_ERR_ARG, no output word written, no resident table touched): mask_seed NULL; mask_seed, read as eight little-endian words,
+ * equal to the party's stream key (publishing it would publish the secrets); party out of range; `keys` made for other parameters or another
+ * party; MKT_CCS without crs; exactly one output NULL; both outputs NULL with install = 0.
+ * TRUST: this call hands party `party`'s SECRET keys to the GPU of this context.  It is a party-local operation: a party runs it on its own
+ * machine / GPU and ships the compact sections with the mask seed (key blob, format version 2) to the evaluator.  An evaluator context that
+ * runs it for every party holds all k secrets -- acceptable only in tests and benchmarks.  The secret buffers (LWE key, ring keys) are zeroed
+ * on the device before they are freed and the host-side copies of the party's stream key are wiped; the copy of that key carried in the
+ * kernel-argument segment of the launches lives in runtime-owned memory the library cannot erase (it is overwritten by later launches).  The
+ * compact sections and the mask seed are public.  A (mask seed, party) pair serves one key generation, as above */
+int mkt_keygen_device_seeded(mkt_ctx *ctx, int party, const mkt_client_party *keys, const void *crs, const uint8_t *mask_seed, void *brk_seeded_out,
+                             uint32_t *ksk_seeded_out, int install);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ from .lut import keyswitch_at, lut_bootstrap_at, lut_gather_at, lut_threshold_co
 from .lut import lut_pack, lut_many_bootstrap, lut_many_gather, lut_many_testvector, lut_extract  # noqa: F401
 from .decrypt import partial_decrypt, merge_phase, merge_decrypt  # noqa: F401
 from .seeded import SeededBatch, seeded_encrypt, seeded_expand  # noqa: F401
-from .seeded_keys import party_keygen_seeded, seeded_keys_expand, load_seeded, seeded_section_words  # noqa: F401
+from .seeded_keys import party_keygen_seeded, seeded_keys_expand, load_seeded, seeded_section_words, keygen_device_seeded  # noqa: F401
 from ._lib import MktError, LIB_PATH, build_id  # noqa: F401
 from . import keyblob  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402

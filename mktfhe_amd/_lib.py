@@ -141,6 +141,7 @@ SYMBOLS = {
     "mkt_seeded_keys_expand": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "mkt_load_seeded_keys": (_i, [_vp, _i, _vp, _vp, _vp]),
     "mkt_multi_load_seeded_keys": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "mkt_keygen_device_seeded": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

@@ -1142,6 +1142,8 @@ int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, c
 // compact sections (seeded_keys.hip), the words of mkt_client_seeded_keys_expand.  load: into the resident tables -- the bootstrapping key
 // expanded into a coefficient-form buffer and installed like every other (install_brk), the key-switching key straight into its
 // table at the padded pitch; else into the caller's brk_out / ksk_out (`mem`), the compact sections living there too.  Nothing is secret.
+// `mem` says where the compact sections live in either case: MKT_MEM_DEVICE sections are read where they are, not staged -- the bodies
+// mkt_keygen_device_seeded has just generated on this device are installed from there.
 static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, bool load,
                             void *brk_out, uint32_t *ksk_out, int mem) {
     if (!c || !mask_seed || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
@@ -1191,6 +1193,55 @@ int mkt_seeded_keys_expand(mkt_ctx *c, int party, const uint8_t *mask_seed, cons
 int mkt_load_seeded_keys(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded) {
     if (int r = key_write_guard(c, brk_seeded || ksk_seeded, NO_PARTY, Gate::EXACT)) return r;   // (the party and the seed: seeded_keys_impl)
     return seeded_keys_impl(c, party, mask_seed, brk_seeded, ksk_seeded, true, nullptr, nullptr, MKT_MEM_HOST);
+}
+
+// The seeded key form generated on the party's own GPU (keygen_seeded.hip): the compact sections of mkt_client_party_keygen_seeded for the seed
+// `K` was made from, word for word, the large keys never expanded.  install: the sections, still on the device, also go through the
+// expansion and install of mkt_load_seeded_keys.  Party-local like mkt_keygen_device: the secrets are wiped before they are freed.
+int mkt_keygen_device_seeded(mkt_ctx *c, int party, const mkt_client_party *K, const void *crs, const uint8_t *mask_seed, void *brk_seeded_out,
+                             uint32_t *ksk_seeded_out, int install) {
+    if (!c || !K || !mask_seed || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!brk_seeded_out != !ksk_seeded_out) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the two compact outputs come together");
+    if (!brk_seeded_out && !install) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: neither an output nor an install was asked for");
+    const mkt_params &p = c->p;
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the party's keys were made for other parameters / another party index");
+    const bool unienc = p.scheme == MKT_CCS;
+    if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: CCS needs the integer CRS");
+    // (the stream key is the seed's 32 bytes as eight little-endian words, seed_to_key: compared where it lies, no copy of it made)
+    if (std::memcmp(mask_seed, K->key, sizeof K->key) == 0) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the mask seed is the party's secret seed (it is published: the secrets would be too)");
+    if (install) if (int r = key_write_guard(c, true, party, Gate::EXACT)) return r;
+    DevGuard dg(c->device);
+    const int N = p.N, nz = (int)K->zring.size();
+    const size_t brk_bytes = mkt::brk_seeded_polys(p, c->sh) * poly_bytes(c), rows = c->ks->ksk.rows;
+    DevBuf bodies, words, crs_int;            // freed behind the secrets' drain of the stream
+    DeviceSecret lwe{c}, z{c};
+    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
+    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
+    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync((int8_t *)z.dev + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMalloc(&bodies.p, brk_bytes);
+    if (e == hipSuccess) e = hipMalloc(&words.p, rows * 4);
+    if (e == hipSuccess && unienc) e = hipMalloc(&crs_int.p, (size_t)p.l_uni * poly_bytes(c));
+    if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hipfail(c, e, "device seeded keygen setup");
+    mktd::KeygenSeededArgs a{};
+    mkt::seed_to_key(mask_seed, a.mkey);
+    std::memcpy(a.key, K->key, sizeof a.key); a.party = K->party; a.N = N; a.n = p.n; a.W = p.W;
+    a.sigma_ring = K->sigma_ring; a.sigma_lwe = K->sigma_lwe;
+    a.lwekey = (const uint32_t *)lwe.dev; a.zring = (const int8_t *)z.dev; a.crs = crs_int.p;
+    a.brk_body = bodies.p; a.ksk_body = (uint32_t *)words.p; a.ksk_rows = rows;
+    if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; }
+    else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; }
+    a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.absent_below = mkt::is_block(p.scheme) ? p.n : 0;
+    a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
+    if (nz < (unienc ? 1 : a.kr) || nz < a.zoff + c->sh.ksk_kr) e = hipErrorInvalidValue;       // every ring key the kernels index is there
+    if (e == hipSuccess) e = mktd::launch_keygen_seeded_brk(a, unienc ? 1 : 0, c->stream);
+    if (e == hipSuccess) e = mktd::launch_keygen_seeded_ksk(a, c->stream);
+    if (e == hipSuccess && brk_seeded_out) e = hipMemcpyAsync(brk_seeded_out, bodies.p, brk_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && ksk_seeded_out) e = hipMemcpyAsync(ksk_seeded_out, words.p, rows * 4, hipMemcpyDeviceToHost, c->stream);
+    e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);       // (drains the stream: the outputs have landed)
+    if (e != hipSuccess) return hipfail(c, e, "device seeded keygen");
+    if (!install) return MKT_OK;
+    return seeded_keys_impl(c, party, mask_seed, bodies.p, (const uint32_t *)words.p, true, nullptr, nullptr, MKT_MEM_DEVICE);
 }
 
 // debug / test read-back of a party's key-switching key in the host layout of mkt_load_ksk

@@ -127,6 +127,29 @@ struct KeygenArgs {
 hipError_t launch_keygen_brk(const KeygenArgs &a, int unienc, hipStream_t s);
 hipError_t launch_keygen_ksk(const KeygenArgs &a, uint32_t *ksk, int n1p, int kk, int dr, int is_block, hipStream_t s);
 
+// The seeded key form generated on the device (keygen_seeded.hip; mktfhe.h "seeded evaluation keys"): the BODIES of one party's two large
+// keys, the words of mkt_client_party_keygen_seeded.  Masks come from the public streams 12 and 13 and are never stored
+struct KeygenSeededArgs {
+    uint32_t key[8];             // the party's 256-bit ChaCha20 stream key: the secret streams 14, 15, 16
+    uint32_t mkey[8];            // key of the mask streams 12, 13: the PUBLIC mask seed
+    int party;
+    int N, n, W;
+    int kr, l, logB;             // RGSW: RLWE length, gadget ; UniEnc: l_uni, logB_uni
+    int zoff;                    // ring-key polynomial the key switch starts from (the uni key of the KMS schemes: 1)
+    int f, logD, drows;          // key-switching gadget
+    int absent_below;            // key-switching rows (c, j) with c N + j below it are absent (block schemes: n, else 0)
+    int width;                   // key-switching kernel: lanes that share a row's keystream blocks (set by the launcher, as SeededArgs::width)
+    double sigma_ring, sigma_lwe;
+    const uint32_t *lwekey;      // [n]
+    const int8_t *zring;         // [nz][N]
+    const void *crs;             // [l][N] ring words (UniEnc only)
+    void *brk_body;              // compact bootstrapping-key section, native word width
+    uint32_t *ksk_body;          // [ksk_rows]
+    uint64_t ksk_rows;
+};
+hipError_t launch_keygen_seeded_brk(const KeygenSeededArgs &a, int unienc, hipStream_t s);
+hipError_t launch_keygen_seeded_ksk(KeygenSeededArgs a, hipStream_t s);
+
 // A party's decryption shares on the device (partial_decrypt.hip; mktfhe.h "distributed decryption"):
 // out[j] = <lwe[j] block `party`, lwekey> + smudge_word(key, party, row0 + j, sigma), j < B
 struct PartialDecryptArgs {

@@ -5,6 +5,8 @@ party ships a PUBLIC mask seed and the bodies, and the evaluator's GPU regenerat
     blob = keyblob.dump_party(keys)                                 format version 2: mask_seed, brk_seeded, ksk_seeded (+ small keys)
     load_seeded(evaluator, i, keys)  /  keyblob.load_into(...)      the evaluator: masks expanded on its GPU, never on a host
     brk, ksk = seeded_keys_expand(params, i, keys.mask_seed, keys.brk_seeded, keys.ksk_seeded)      anyone: the ordinary keys; needs no key
+    keys = keygen_device_seeded(own_scheme, i, party_keygen(crs, params, party=i, secrets_only=True))      party i, the compact sections made on
+                                                                                                            its OWN GPU: the same words
 
 A (mask seed, party) pair serves ONE key generation: two generations under it share their masks.  party_keygen_seeded draws a fresh mask
 seed unless one is given.  The mask seed is not a secret.  This module holds no arithmetic: all of it is the C ABI's.
@@ -15,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .params import Params
+from .params import CCS, Params
 from .scheme import MEM_DEVICE, PartyKeys, _arg, _Buf, _empty, _np_ptr, _seed32, _seeded_sections, seeded_section_words
 
 
@@ -84,3 +86,38 @@ def load_seeded(scheme, party, keys: PartyKeys = None, *, mask_seed=None, brk_se
             raise ValueError("load_seeded takes a seeded party (party_keygen_seeded)")
         return scheme.load_party(party, keys)
     return scheme.load_party(party, mask_seed=mask_seed, brk_seeded=brk_seeded, ksk_seeded=ksk_seeded)
+
+
+class SeededDeviceKeys:
+    """a party in the seeded key form whose compact sections were generated on its own GPU (keygen_device_seeded): mask_seed, brk_seeded,
+    ksk_seeded as party_keygen_seeded gives them, brk = ksk = None; params, party, the small keys and the secret accessors are those of the
+    party object the sections were made from"""
+    seeded, secrets_only, brk, ksk = True, False, None, None
+
+    def __init__(self, keys, mask_seed, brk_seeded, ksk_seeded):
+        self._keys, self.mask_seed, self.brk_seeded, self.ksk_seeded = keys, mask_seed, brk_seeded, ksk_seeded
+
+    def __getattr__(self, name):        # params, party, rlk_d, rlk_f, pubkey, lwekey, ringkey, h, _crs
+        return getattr(self._keys, name)
+
+
+def keygen_device_seeded(scheme, party, keys: PartyKeys, mask_seed=None, install=False):
+    """the seeded key form generated on the party's OWN GPU (mkt_keygen_device_seeded) -> a seeded party view (SeededDeviceKeys): the compact
+    sections are those party_keygen_seeded makes on the host for the seed `keys` was made from, word for word, and the large keys are never
+    expanded.  `keys`: any PartyKeys of these parameters and this party (secrets_only=True is enough).  mask_seed None draws a fresh public
+    seed.  This hands the party's SECRETS to scheme's GPU: the party's own step.  install=True: the sections also become the resident keys of
+    `party` on `scheme`, as load_seeded of the result would make them, and the small keys of `keys` are uploaded as Scheme.keygen_device does"""
+    if mask_seed is None:
+        buf = (C.c_uint8 * 32)()
+        check(_lib.lib().mkt_client_random_seed(buf))
+        mask_seed = bytes(buf)
+    mp, _keep = _seed32(mask_seed)
+    params = scheme.params
+    sb, sk = seeded_section_words(params)
+    brk = np.empty(sb, dtype=params.ring_dtype)
+    ksk = np.empty(sk, dtype=np.uint32)
+    crs_p = _np_ptr(keys._crs) if (params.scheme == CCS and keys._crs is not None) else None
+    scheme._ck(_lib.lib().mkt_keygen_device_seeded(scheme.h, int(party), keys.h, crs_p, mp, _np_ptr(brk), _np_ptr(ksk), 1 if install else 0))
+    if install:
+        scheme.load_party(party, rlk_d=keys.rlk_d, rlk_f=keys.rlk_f, pubkey=keys.pubkey)
+    return SeededDeviceKeys(keys, bytes(mask_seed), brk, ksk)
