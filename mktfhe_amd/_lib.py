@@ -144,6 +144,17 @@ SYMBOLS = {
     "mkt_keygen_device_seeded": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
+# every symbol include/mktfhe_pack.h declares (packed outputs), bound beside SYMBOLS: SYMBOLS stays the table of mktfhe.h alone
+PACK_SYMBOLS = {
+    "mkt_client_packing_keygen": (_i, [_pp, _vp, _i, _i, _i, _vp, _vp]),
+    "mkt_client_rlwe_phase": (_i, [_pp, C.POINTER(_vp), _i, _vp, _vp]),
+    "mkt_client_rlwe_partial_decrypt": (_i, [_pp, _vp, _i, _vp, _dbl, _vp, _u64, _vp, _sz]),
+    "mkt_client_rlwe_merge_phase": (_i, [_pp, _vp, _vp, _i, _sz, _vp]),
+    "mkt_client_rlwe_merge_decrypt": (_i, [_pp, _vp, _vp, _i, _sz, _vp]),
+    "mkt_load_packing_key": (_i, [_vp, _i, _vp, _i, _i]),
+    "mkt_pack_batch": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i]),
+}
+
 _lib = None
 
 
@@ -165,7 +176,7 @@ def lib():
         except Exception:  # noqa: BLE001
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in {**SYMBOLS, **PACK_SYMBOLS}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -680,3 +680,114 @@ int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uin
 }
 
 }  // extern "C"
+
+// ---- packed outputs (mktfhe_pack.h): the packing key, and the ring forms of the phase, the decryption share and the merge ----
+
+namespace {
+
+void store_poly_raw(void *dst, size_t poly_index, const uint64_t *v, int N, int W) {
+    if (W == 64) std::memcpy((uint8_t *)dst + poly_index * N * 8, v, (size_t)N * 8);
+    else { uint32_t *d = (uint32_t *)dst + poly_index * N; for (int i = 0; i < N; i++) d[i] = (uint32_t)v[i]; }
+}
+// the ring keys a packed ciphertext is under (the ones the key-switching key switches from): first ring-key polynomial of a party, how many
+inline int pack_zoff(const mkt_params &p) { return is_kms(p.scheme) ? 1 : 0; }
+// acc += sum_c a_{slot(party, c)} (*) z_{party, c} for one party's components of one packed ciphertext [1 + k][N]
+void ring_share_acc(const mkt_params &p, const Shape &sh, const mkt_client_party *K, int party, const void *rlwe, uint64_t *acc, uint64_t *a) {
+    for (int c = 0; c < sh.ksk_kr; c++) {
+        load_poly(rlwe, (size_t)1 + (is_mk(p.scheme) ? party : c), a, p.N, p.W);
+        mul_small_acc(a, K->zring[(size_t)pack_zoff(p) + c].data(), acc, p.N, false);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// row (q, t) = RLWE_z(s[q] g_t): rlev_encrypt (lev.jl:88-94) of the constant s[q]; one stream per row
+int mkt_client_packing_keygen(const mkt_params *params, const mkt_client_party *K, int party, int l_pk, int logB_pk, const uint8_t *seed, void *pk_out) {
+    if (!params || !K || !pk_out || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    const int N = p.N, W = p.W, kr = sh.ksk_kr, polys = kr + 1;
+    const uint64_t wm = wmask(W);
+    uint32_t key[8];
+    if (seed_to_key(seed, key)) return MKT_ERR_STATE;
+    parallel_for(p.n, [&](int q) {
+        std::vector<uint64_t> buf((size_t)polys * N);
+        for (int t = 0; t < l_pk; t++) {
+            Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_KEY, (uint32_t)q, (uint32_t)t);
+            rlwe_sample(r, K->zring, pack_zoff(p), kr, K->sigma_ring, N, W, buf.data());
+            buf[0] = (buf[0] + ((uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk))) & wm;
+            for (int c = 0; c < polys; c++) store_poly_raw(pk_out, ((size_t)q * l_pk + t) * polys + c, buf.data() + (size_t)c * N, N, W);
+        }
+    });
+    explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// TEST HARNESS: the top 32 bits of b + sum a z, every product exact
+int mkt_client_rlwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const void *rlwe, uint32_t *phase_out) {
+    if (!params || !keys || !rlwe || !phase_out) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (nparties != sh.nparty) return MKT_ERR_ARG;
+    for (int i = 0; i < nparties; i++) if (!keys[i] || !party_keys_match(keys[i], p, i)) return MKT_ERR_ARG;
+    std::vector<uint64_t> acc(p.N), a(p.N);
+    load_poly(rlwe, 0, acc.data(), p.N, p.W);
+    for (int i = 0; i < nparties; i++) ring_share_acc(p, sh, keys[i], i, rlwe, acc.data(), a.data());
+    for (int j = 0; j < p.N; j++) phase_out[j] = (uint32_t)((acc[j] & wmask(p.W)) >> (p.W - 32));
+    return MKT_OK;
+}
+
+// share[g] = sum_c a_{slot(party,c)}[g] (*) z_c + e[g], e[g] the N smudging words of pack row0 + g (stream 18), lifted to the ring's width
+int mkt_client_rlwe_partial_decrypt(const mkt_params *params, const mkt_client_party *K, int party, const void *rlwe, double sigma_smudge,
+                                    const uint8_t *seed, uint64_t row0, void *share_out, size_t G) {
+    if (!params || !K || !smudge_sigma_ok(sigma_smudge)) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    if (!G) return MKT_OK;
+    if (!rlwe || !share_out) return MKT_ERR_ARG;
+    uint32_t key[8];
+    if (seed_to_key(seed, key)) return MKT_ERR_STATE;
+    const size_t ctb = (size_t)(1 + sh.kacc) * p.N * sh.word;
+    std::vector<uint64_t> acc(p.N), a(p.N);
+    for (size_t g = 0; g < G; g++) {
+        std::fill(acc.begin(), acc.end(), 0);
+        ring_share_acc(p, sh, K, party, (const uint8_t *)rlwe + g * ctb, acc.data(), a.data());
+        Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_SMUDGE, (uint32_t)(row0 + g), (uint32_t)((row0 + g) >> 32));
+        for (int j = 0; j < p.N; j++) acc[j] = (acc[j] + (r.noise(sigma_smudge) << (p.W - 32))) & wmask(p.W);
+        store_poly_raw(share_out, g, acc.data(), p.N, p.W);
+    }
+    explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// top 32 bits of b[j] + sum_i share_i[j], j < count; shares [nparty][N]
+static int rlwe_merge(const mkt_params *params, const void *rlwe, const void *shares, int nparties, size_t count, uint32_t *phase_out, uint8_t *bits_out) {
+    if (!params || !rlwe || !shares || (!phase_out && !bits_out)) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    if (nparties != shape_of(p).nparty || count > (size_t)p.N) return MKT_ERR_ARG;
+    std::vector<uint64_t> acc(p.N), s(p.N);
+    load_poly(rlwe, 0, acc.data(), p.N, p.W);
+    for (int i = 0; i < nparties; i++) { load_poly(shares, (size_t)i, s.data(), p.N, p.W); for (int j = 0; j < p.N; j++) acc[j] += s[j]; }
+    for (size_t j = 0; j < count; j++) {
+        const uint32_t ph = (uint32_t)((acc[j] & wmask(p.W)) >> (p.W - 32));
+        if (phase_out) phase_out[j] = ph;
+        if (bits_out) bits_out[j] = (uint8_t)bit_of_phase(p, ph);
+    }
+    return MKT_OK;
+}
+int mkt_client_rlwe_merge_phase(const mkt_params *params, const void *rlwe, const void *shares, int nparties, size_t count, uint32_t *phase_out) {
+    return phase_out ? rlwe_merge(params, rlwe, shares, nparties, count, phase_out, nullptr) : (int)MKT_ERR_ARG;
+}
+int mkt_client_rlwe_merge_decrypt(const mkt_params *params, const void *rlwe, const void *shares, int nparties, size_t count, uint8_t *bits_out) {
+    return bits_out ? rlwe_merge(params, rlwe, shares, nparties, count, nullptr, bits_out) : (int)MKT_ERR_ARG;
+}
+
+}  // extern "C"

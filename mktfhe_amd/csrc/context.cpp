@@ -105,12 +105,18 @@ struct KeySet {
     cplx *d_fx_brk = nullptr;    // [party][n][2l][2][W/16][M], scaled by 1 / M
     unsigned long long *d_fx_stat = nullptr;   // largest |key transform value|^2 over the loaded keys (bit pattern)
     double fx_kmax = 0.0;        // sqrt of [0], read back after every key load
+    // packed outputs (mktfhe_pack.h): every party's packing key, outside the table description below (no multi-device replica).  F64REF:
+    // [party][n][l][1 + kr][M] transforms in the slot-major point order; EXACT: [party][1 + kr][n l][N] ring words, polynomial-major -- the
+    // rows one exact-product launch reads in a run.  The first load fixes the gadget
+    void *d_pack = nullptr; int pack_l = 0, pack_logB = 0; size_t pack_party_bytes = 0;
+    std::vector<uint8_t> pack_loaded;   // [party]
     ResidentTable tab[T_COUNT];  // describe_key_set
     size_t stride(KeyTable t) const { return tab[t].elems; }   // elements from one party's rows to the next
     template <class T> T *party(KeyTable t, int party) const { return static_cast<T *>(*tab[t].slot) + (size_t)party * tab[t].elems; }   // base of one party's rows
     ~KeySet() {
         DevGuard g(device);
         for (const ResidentTable &t : tab) if (t.slot && *t.slot) (void)hipFree(*t.slot);
+        if (d_pack) (void)hipFree(d_pack);
     }
 };
 
@@ -133,6 +139,8 @@ struct mkt_ctx {
     cplx *ws_lev = nullptr, *ws_scratch = nullptr;
     void *ws_fxacc = nullptr;    // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
     uint32_t *ws_ksd = nullptr; size_t ws_ksd_words = 0;   // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
+    // mkt_pack_batch: its own workspace for ws_pack_n packs at a time -- the lifted columns; F64REF the product kernel's slabs; EXACT the digits and products of one chunk of columns
+    size_t ws_pack_n = 0; void *ws_pack_cols = nullptr, *ws_pack_slabs = nullptr, *ws_pack_dig = nullptr, *ws_pack_prod = nullptr;
     uint32_t *ws_at = nullptr; size_t ws_at_rows = 0;      // lookup-table bootstrap with more than one output per input: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call)
     // timing
     bool timing = false;
@@ -801,7 +809,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_fxacc, c->d_pm_stat};
+    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_fxacc, c->d_pm_stat, c->ws_pack_cols, c->ws_pack_slabs, c->ws_pack_dig, c->ws_pack_prod};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
@@ -939,7 +947,7 @@ int mkt_set_twiddles(mkt_ctx *c, const double *psi, const double *psiinv, const 
     if (int w = keys_writable(c)) return w;
     // tables first, then keys: a loaded bootstrapping key, relinearisation key, public key or CRS is resident as its transform under the tables
     // it met (or as the caller's Trans* values), and its integer form is not kept -- new tables would leave keys and transforms disagreeing
-    if (c->ks->loaded.any_transformed()) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
+    if (c->ks->loaded.any_transformed() || c->ks->d_pack) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
     DevGuard dg(c->device);
     const size_t nd = (size_t)2 * c->M;
     // the kernels derive the inverse twiddles from the forward table: Psiinv must be conj(Psi) entry for entry,
@@ -1804,6 +1812,128 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
     { Timer tm(c, 3); HIPCHK(c, mktd::launch_exact_polymul(c->logN, c->p.W, c->ks->d_ntt, sa.dev, sb.dev, so.dev, B, c->stream)); }
     c->last_rot_kernel = "exact_polymul_kernel";
     return so.out(out);
+}
+
+// ---- packed outputs (mktfhe_pack.h): N LWE rows into one RLWE ciphertext by the packing key switch (pack.hip) ----
+constexpr size_t PACK_CHUNK = 16;      // packs per launch sequence: bounds the workspace (KMS2party: 16 packs = 0.3 GiB of columns, 0.15 GiB of slabs)
+constexpr int PACK_EXACT_COLS = 64;    // MKT_ARITH_EXACT: columns per decompose / exact-product launch
+
+int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int logB_pk) {
+    if (!c || !pk || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
+    const mkt_params &p = c->p;
+    const int np = c->sh.ksk_kr + 1;
+    if (!mktd::pack_supported(np)) return fail(c, MKT_ERR_UNSUPPORTED, "mkt_load_packing_key: RLWE lengths beyond 3 are not served");
+    // EXACT: every product of a digit polynomial (N digits of magnitude <= 2^(logB_pk - 1)) with a centered 32-bit piece of a key polynomial must stay below P / 2
+    if (c->exact && (double)p.N * std::ldexp(1.0, logB_pk - 1) * 2147483648.0 >= 0.5 * (double)NTT_P[0] * (double)NTT_P[1])
+        return fail(c, MKT_ERR_UNSUPPORTED, "mkt_load_packing_key: the rows of this gadget could reach P / 2 of the two-prime modulus");
+    if (int w = keys_writable(c)) return w;
+    KeySet &ks = *c->ks;
+    if (ks.d_pack && (ks.pack_l != l_pk || ks.pack_logB != logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: all parties of a context use one packing gadget");
+    DevGuard dg(c->device);
+    const size_t rows = (size_t)p.n * l_pk, polys = rows * np, pb = poly_bytes(c);
+    const size_t per = polys * (c->exact ? pb : (size_t)c->M * sizeof(cplx));
+    if (!ks.d_pack) {
+        HIPCHK(c, hipMalloc(&ks.d_pack, per * c->sh.nparty));
+        ks.pack_l = l_pk; ks.pack_logB = logB_pk; ks.pack_party_bytes = per; ks.pack_loaded.assign((size_t)c->sh.nparty, 0);
+    }
+    char *dst = static_cast<char *>(ks.d_pack) + (size_t)party * per;
+    if (!c->exact) {          // pre-transformed like the bootstrapping key, in the slot-major point order whatever the context's own
+        DevBuf tmp;
+        HIPCHK(c, hipMalloc(&tmp.p, polys * pb));
+        HIPCHK(c, hipMemcpyAsync(tmp.p, pk, polys * pb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, mktd::launch_transform_fwd(c->logM, p.W, c->twp(), tmp.p, reinterpret_cast<cplx *>(dst), polys, 1, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {                  // coefficient form, [row][polynomial] -> [polynomial][row]
+        std::vector<unsigned char> host(polys * pb);
+        for (size_t r = 0; r < rows; r++) for (int q = 0; q < np; q++)
+            std::memcpy(host.data() + ((size_t)q * rows + r) * pb, static_cast<const unsigned char *>(pk) + (r * np + q) * pb, pb);
+        HIPCHK(c, hipMemcpyAsync(dst, host.data(), polys * pb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    ks.pack_loaded[(size_t)party] = 1;
+    return MKT_OK;
+}
+
+// the readiness check of a pack: every party's packing key, and nothing else
+static int pack_ready(mkt_ctx *c) {
+    const KeySet &ks = *c->ks;
+    for (int i = 0; i < c->sh.nparty; i++)
+        if (!ks.d_pack || !ks.pack_loaded[(size_t)i]) return fail(c, MKT_ERR_STATE, "packing key not loaded");
+    return MKT_OK;
+}
+
+static int ensure_pack_workspace(mkt_ctx *c, size_t packs, int nchunk) {
+    if (packs <= c->ws_pack_n) return MKT_OK;
+    void **ws[] = {&c->ws_pack_cols, &c->ws_pack_slabs, &c->ws_pack_dig, &c->ws_pack_prod};
+    for (void **w : ws) { if (*w) (void)hipFree(*w); *w = nullptr; }
+    c->ws_pack_n = 0;
+    const size_t pb = poly_bytes(c), np = (size_t)c->sh.ksk_kr + 1;
+    HIPCHK(c, hipMalloc(&c->ws_pack_cols, packs * (size_t)c->sh.lwe_len * pb));
+    if (!c->exact) HIPCHK(c, hipMalloc(&c->ws_pack_slabs, packs * (size_t)c->sh.nparty * nchunk * np * pb));
+    else {
+        HIPCHK(c, hipMalloc(&c->ws_pack_dig, (size_t)PACK_EXACT_COLS * c->ks->pack_l * pb));
+        HIPCHK(c, hipMalloc(&c->ws_pack_prod, (size_t)PACK_EXACT_COLS * c->ks->pack_l * pb));
+    }
+    c->ws_pack_n = packs;
+    return MKT_OK;
+}
+
+int mkt_pack_batch(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, const uint32_t *idx, size_t B, void *rlwe_out, int mem) {
+    if (!c || !pool || !rlwe_out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (B && !pool_rows) return fail(c, MKT_ERR_ARG, "mkt_pack_batch: rows of an empty pool");
+    if (!idx && B > pool_rows) return fail(c, MKT_ERR_ARG, "mkt_pack_batch: idx NULL names rows 0 .. B-1: B must not exceed pool_rows");
+    if (mem == MKT_MEM_HOST && idx) {
+        const uint32_t *iv[] = {idx};
+        if (!in_pool_host(iv, 1, B, pool_rows)) return fail(c, MKT_ERR_ARG, "mkt_pack_batch: row index outside the pool");
+    }
+    const mkt_params &p = c->p;
+    const size_t N = (size_t)p.N, len = (size_t)c->sh.lwe_len, pb = poly_bytes(c), ctb = (size_t)(1 + c->sh.kacc) * pb;
+    const size_t npacks = (B + N - 1) / N;
+    if (mkt::ranges_overlap(pool, pool_rows * len * 4, rlwe_out, npacks * ctb)) return fail(c, MKT_ERR_ARG, "mkt_pack_batch: rlwe_out overlaps the pool");
+    int r;
+    if ((r = pack_ready(c))) return r;
+    if (!B) return MKT_OK;
+    DevGuard dg(c->device);
+    const KeySet &ks = *c->ks;
+    Staged sp{c}, si{c}, so{c};
+    if ((r = sp.in(pool, pool_rows * len * 4, mem, true)) || (r = so.in(rlwe_out, npacks * ctb, mem, false))) return r;
+    if (idx && (r = si.in(idx, B * 4, mem, true))) return r;
+    mktd::PackArgs a{};
+    a.tw = c->twp(); a.pool = (const uint32_t *)sp.dev; a.pool_rows = pool_rows; a.idx = idx ? (const uint32_t *)si.dev : nullptr; a.B = B;
+    a.logN = c->logN; a.n = p.n; a.nparty = c->sh.nparty; a.lwe_len = (int)len; a.kacc = c->sh.kacc; a.mk = mkt::is_mk(p.scheme) ? 1 : 0;
+    a.np = c->sh.ksk_kr + 1; a.l = ks.pack_l; a.logB = ks.pack_logB; a.nchunk = (p.n + mktd::PACK_QCHUNK - 1) / mktd::PACK_QCHUNK;
+    a.key = static_cast<const cplx *>(ks.d_pack); a.key_party_stride = ks.pack_party_bytes / sizeof(cplx);
+    for (size_t g0 = 0; g0 < npacks; g0 += PACK_CHUNK) {
+        const size_t nb = std::min(PACK_CHUNK, npacks - g0);
+        if ((r = ensure_pack_workspace(c, nb, a.nchunk))) return r;
+        a.pack0 = g0; a.cols = c->ws_pack_cols; a.slabs = c->ws_pack_slabs; a.out = static_cast<char *>(so.dev) + g0 * ctb;
+        HIPCHK(c, mktd::launch_pack_columns(p.W, a, nb, c->stream));
+        if (!c->exact) {
+            HIPCHK(c, mktd::launch_pack_product(c->logM, p.W, a, nb, c->stream));
+            HIPCHK(c, mktd::launch_pack_reduce(p.W, a, nb, c->stream));
+            continue;
+        }
+        // EXACT: per pack, the body column and zeros, then per party and chunk of columns the digits, the exact products with each key polynomial, their integer sum
+        const size_t rows_all = (size_t)p.n * a.l;
+        for (size_t g = 0; g < nb; g++) {
+            char *o = static_cast<char *>(a.out) + g * ctb;
+            const char *cols = static_cast<const char *>(a.cols) + g * len * pb;
+            HIPCHK(c, hipMemcpyAsync(o, cols + (len - 1) * pb, pb, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemsetAsync(o + pb, 0, ctb - pb, c->stream));
+            for (int i = 0; i < a.nparty; i++) for (int q0 = 0; q0 < p.n; q0 += PACK_EXACT_COLS) {
+                const size_t cnt = (size_t)std::min(PACK_EXACT_COLS, p.n - q0), prods = cnt * a.l;
+                HIPCHK(c, mktd::launch_decompose(p.W, cols + ((size_t)i * p.n + q0) * pb, c->ws_pack_dig, p.N, a.l, a.logB, cnt, c->stream));
+                for (int q = 0; q < a.np; q++) {
+                    const char *key = static_cast<const char *>(ks.d_pack) + (size_t)i * ks.pack_party_bytes + ((size_t)q * rows_all + (size_t)q0 * a.l) * pb;
+                    HIPCHK(c, mktd::launch_exact_polymul(c->logN, p.W, ks.d_ntt, c->ws_pack_dig, key, c->ws_pack_prod, prods, c->stream));
+                    const int slot = q == 0 ? 0 : (a.mk ? 1 + i : q);
+                    HIPCHK(c, mktd::launch_pack_accumulate(p.W, o + (size_t)slot * pb, c->ws_pack_prod, prods, p.N, c->stream));
+                }
+            }
+        }
+    }
+    return so.out(rlwe_out);
 }
 
 int mkt_enable_timing(mkt_ctx *c, int on) {

@@ -210,6 +210,31 @@ struct SeededBrkArgs {
 hipError_t launch_seeded_ksk_expand(const SeededKskArgs &a, hipStream_t s);
 hipError_t launch_seeded_brk_expand(const SeededBrkArgs &a, hipStream_t s);
 
+// Packed outputs (pack.hip; mktfhe_pack.h): one launch sequence packs `npacks` ciphertexts, pack0 .. pack0 + npacks - 1 of the call
+constexpr int PACK_QCHUNK = 4;   // mask words per workgroup of the product kernel: k n / 4 workgroups per pack (280 at the headline shape)
+struct PackArgs {
+    TwPtrs tw;
+    const uint32_t *pool;     // [pool_rows][lwe_len]
+    size_t pool_rows;
+    const uint32_t *idx;      // [B] rows of the pool (clamped), or null: row r of the call = row r of the pool
+    size_t B, pack0;          // picked rows of the whole call; first pack of this launch sequence
+    int logN, n, nparty, lwe_len, kacc;
+    int mk;                   // 1: party i's polynomial 1 -> slot i; 0: party 0's polynomial 1 + c -> slot c
+    int np;                   // polynomials of a key row, 1 + kr
+    int l, logB;              // packing gadget
+    int nchunk;               // ceil(n / PACK_QCHUNK)
+    const cplx *key;          // party 0 base; [n][l][np][M], slot-major point order (dev_pos order 1)
+    size_t key_party_stride;  // in cplx
+    void *cols;               // [npacks][lwe_len][N] ring words: the lifted columns
+    void *slabs;              // [npacks][nparty][nchunk][np][N] ring words
+    void *out;                // [npacks][1 + kacc][N] ring words
+};
+bool pack_supported(int np);
+hipError_t launch_pack_columns(int W, const PackArgs &a, size_t npacks, hipStream_t s);
+hipError_t launch_pack_product(int logM, int W, const PackArgs &a, size_t npacks, hipStream_t s);
+hipError_t launch_pack_reduce(int W, const PackArgs &a, size_t npacks, hipStream_t s);
+hipError_t launch_pack_accumulate(int W, void *dst, const void *prod, size_t rows, int N, hipStream_t s);
+
 hipError_t launch_transform_fwd(int logM, int W, TwPtrs tw, const void *p, cplx *t, size_t B, int dev_order, hipStream_t s);
 hipError_t launch_reorder(int logM, const cplx *in, cplx *out, size_t npolys, int to_device, int order, hipStream_t s);
 hipError_t launch_transform_inv(int logM, int W, TwPtrs tw, const cplx *t, void *p, size_t B, hipStream_t s);

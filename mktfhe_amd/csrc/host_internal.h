@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mktfhe.h"
+#include "../../include/mktfhe_pack.h"
 
 namespace mkt {
 
@@ -94,6 +95,9 @@ struct LoadedKeys {
         return false;
     }
 };
+// packed outputs (mktfhe_pack.h): the gadget a packing key admits; the polynomials of one party's key [n][l_pk][1 + kr][N], kr = ksk_kr
+inline bool pack_gadget_ok(int l, int logB) { return logB >= 1 && logB <= 16 && l >= 1 && l * logB <= 32; }
+inline size_t pack_key_polys(const mkt_params &p, const Shape &s, int l) { return (size_t)p.n * l * (s.ksk_kr + 1); }
 inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;

@@ -167,5 +167,10 @@ constexpr uint32_t STREAM_BRK_MASK = 13;
 constexpr uint32_t STREAM_BRK_NOISE = 14;
 constexpr uint32_t STREAM_KSK_NOISE = 15;
 constexpr uint32_t STREAM_UNI_NOISE = 16;
+// 17, 18: packed outputs (mktfhe_pack.h; client.cpp).  Both SECRET.  17 the packing key: one stream per key row (index words q, t), read as an
+// RLWE sample is -- kr mask polynomials, then N noise draws.  18 the smudging noise of a ring share: one stream per PACK, the 64-bit pack index
+// in the two index words, N noise draws in coefficient order.
+constexpr uint32_t STREAM_PACK_KEY = 17;
+constexpr uint32_t STREAM_PACK_SMUDGE = 18;
 
 }  // namespace mktrng

@@ -1,0 +1,63 @@
+// Stand-alone host check of the packed-output functions of mktfhe_amd/csrc/client.cpp (no GPU, no Python): generates packing keys at reduced
+// shapes (KMS on the 64-bit ring with two parties; CCS; CGGI with RLWE length 2), builds a packed ciphertext of known phase by hand from the
+// key rows (coefficient 0 of row (q, t) carries s[q] g_t), opens it with the all-keys harness, by ring shares with and without smudging noise
+// and by the merge, and runs the refusals.  Meant to be built with the host sanitizers, from the repository root:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -Iinclude \
+//       tools/pack_hostcheck.cpp mktfhe_amd/csrc/client.cpp mktfhe_amd/csrc/twiddle.cpp -lpthread -o pack_hostcheck && ./pack_hostcheck
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "mktfhe_pack.h"
+
+static int run(mkt_params p, int l, int logB, double beta) {
+    const int nparty = (p.scheme >= MKT_CCS) ? p.k : 1, kr = nparty > 1 ? 1 : p.k, word = p.W / 8, N = p.N;
+    uint8_t seed[32];
+    mkt_client_test_seed(3, seed);
+    std::vector<uint8_t> crs((size_t)(p.l_uni ? p.l_uni : 1) * N * word);
+    if (nparty > 1 && mkt_client_crs(&p, seed, crs.data())) return 1;
+    std::vector<mkt_client_party *> K((size_t)nparty, nullptr);
+    std::vector<std::vector<uint8_t>> pk((size_t)nparty);
+    for (int i = 0; i < nparty; i++) {
+        if (mkt_client_party_secrets(&p, seed, i, nparty > 1 ? crs.data() : nullptr, 131072.0, beta, &K[i])) return 2;
+        pk[i].assign((size_t)p.n * l * (kr + 1) * N * word, 0);
+        if (mkt_client_packing_keygen(&p, K[i], i, l, logB, i ? nullptr : seed, pk[i].data())) return 3;
+        if (mkt_client_packing_keygen(&p, K[i], (i + 1) % (nparty > 1 ? nparty : 2), l, logB, seed, pk[i].data()) != MKT_ERR_ARG) return 4;
+    }
+    if (mkt_client_packing_keygen(&p, K[0], 0, 3, 11, seed, pk[0].data()) != MKT_ERR_ARG) return 5;
+    // a ciphertext made of key row (q = 0, t = 0) of party 0: polynomial 0 = its b, the party's slot(s) = its a_c, every other slot zero
+    std::vector<uint8_t> ct((size_t)(1 + p.k) * N * word, 0);
+    std::memcpy(ct.data(), pk[0].data(), (size_t)N * word);
+    for (int c = 0; c < kr; c++) std::memcpy(ct.data() + (size_t)(1 + c) * N * word, pk[0].data() + (size_t)(1 + c) * N * word, (size_t)N * word);
+    std::vector<uint32_t> ph((size_t)N), merged((size_t)N);
+    if (mkt_client_rlwe_phase(&p, K.data(), nparty, ct.data(), ph.data())) return 6;
+    const uint32_t want0 = mkt_client_lwekey(K[0])[0] << (32 - logB);        // s[0] g_0 on the 32-bit torus, plus noise
+    if ((uint32_t)(ph[0] - want0 + (1u << 20)) > (2u << 20)) return 7;
+    for (int j = 1; j < N; j++) if ((uint32_t)(ph[(size_t)j] + (1u << 20)) > (2u << 20)) return 8;
+    std::vector<uint8_t> shares((size_t)nparty * N * word), noisy((size_t)N * word);
+    for (int i = 0; i < nparty; i++)
+        if (mkt_client_rlwe_partial_decrypt(&p, K[i], i, ct.data(), 0.0, nullptr, 0, shares.data() + (size_t)i * N * word, 1)) return 9;
+    if (mkt_client_rlwe_merge_phase(&p, ct.data(), shares.data(), nparty, (size_t)N, merged.data())) return 10;
+    if (std::memcmp(merged.data(), ph.data(), (size_t)N * 4)) return 11;                           // sigma_smudge = 0: word for word
+    if (mkt_client_rlwe_partial_decrypt(&p, K[0], 0, ct.data(), 2147483648.0, seed, ~0ull, noisy.data(), 1)) return 12;
+    if (!std::memcmp(noisy.data(), shares.data(), (size_t)N * word)) return 13;
+    std::vector<uint8_t> bits((size_t)N);
+    if (mkt_client_rlwe_merge_decrypt(&p, ct.data(), shares.data(), nparty, (size_t)N, bits.data())) return 14;
+    if (mkt_client_rlwe_merge_decrypt(&p, ct.data(), shares.data(), nparty, (size_t)N + 1, bits.data()) != MKT_ERR_ARG) return 15;
+    if (mkt_client_rlwe_merge_phase(&p, ct.data(), shares.data(), nparty + 1, 1, merged.data()) != MKT_ERR_ARG) return 16;
+    if (mkt_client_rlwe_partial_decrypt(&p, K[0], 0, ct.data(), -1.0, seed, 0, noisy.data(), 1) != MKT_ERR_ARG) return 17;
+    if (mkt_client_rlwe_partial_decrypt(&p, K[0], 0, nullptr, 0.0, seed, 0, nullptr, 0)) return 18;
+    for (auto *k : K) mkt_client_party_destroy(k);
+    std::printf("scheme %d n %d N %d W %d gadget (%d, %d): %zu key bytes per party\n", p.scheme, p.n, N, p.W, l, logB, pk[0].size());
+    return 0;
+}
+
+int main() {
+    const mkt_params kms = { MKT_KMS, 5, 32, 2, 64, 3, 12, 2, 7, 3, 10, 8, 2, 0, 0 };
+    const mkt_params ccs = { MKT_CCS, 4, 64, 3, 32, 0, 0, 0, 0, 3, 8, 8, 2, 0, 0 };
+    const mkt_params cggi = { MKT_CGGI, 3, 32, 2, 32, 3, 9, 0, 0, 0, 0, 8, 2, 0, 0 };
+    int r;
+    if ((r = run(kms, 4, 4, 85.4084)) || (r = run(ccs, 3, 5, 16.0)) || (r = run(cggi, 8, 4, 128.0)) || (r = run(kms, 1, 16, 85.4084))) { std::printf("FAILED at step %d\n", r); return 1; }
+    std::printf("ok\n");
+    return 0;
+}

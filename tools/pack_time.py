@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Cost of packing results (mkt_pack_batch) beside the cost of producing them, on the GPU, and the live pack noise.
+
+For each parameter set, on one context with evaluation keys generated on the device and host-generated packing keys (gadget --gadget):
+B = N and 8 N rows; alternating, after a warm-up of each, `reps` times:
+  gate   mkt_gate_batch NAND of B row pairs                      the bootstraps that produce B results
+  pack   mkt_pack_batch of those B rows                          ceil(B / N) packed ciphertexts
+every call on device tensors between two device events; the medians are reported.  Beside them the transform counts the two are made of:
+a pack runs nparty n (l_pk + 1 + kr) transforms, a bootstrap nparty n (kr + 1) (l_gsw + 1) (the blind rotation's CMux count; the KMS
+schemes' second phase and every key switch are left out, so the estimate flatters the pack).
+--noise: the three cases of tests/test_gpu_pack.py (measured / predicted deviation, derived bands), written beside the timings.
+Writes pack_<build id>.json (and pack_noise_<build id>.json) into --out-dir.  A measurement path: it fails without a GPU."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import mktfhe_amd as mk  # noqa: E402
+
+
+def setup(p, seed):
+    """secrets on the CPU, evaluation keys generated on the device"""
+    if p.multikey:
+        crs = mk.CRS(p, seed)
+        keys = [mk.party_keygen(crs, p, party=i, secrets_only=True, deterministic_seed=seed + i) for i in range(p.k)]
+        return keys, mk.setup(p, keys=keys, a=crs)
+    k, sch = mk.setup(p, keys=mk.PartyKeys(p, party=0, secrets_only=True, deterministic_seed=seed))
+    return [k], sch
+
+
+def event_ms(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def measure(p, l, logB, reps, torch):
+    keys, sch = setup(p, 11)
+    for i in range(p.nparty):
+        mk.load_packing_key(sch, i, mk.packing_keygen(keys[i], p, l, logB, deterministic_seed=70 + i), l, logB)
+    kr = 1 if p.multikey else p.k
+    rot_kr = 1 if p.scheme in (mk.KMS, mk.KMS_BLOCK) else p.k
+    l_rot = p.l_uni if p.scheme == mk.CCS else p.l_gsw
+    t_pack, t_boot = p.nparty * p.n * (l + 1 + kr), p.nparty * p.n * (rot_kr + 1) * (l_rot + 1)
+    rng = np.random.default_rng(5)
+    out = {"set": p.name, "n": p.n, "N": p.N, "nparty": p.nparty, "W": p.W, "gadget": [l, logB], "reps": reps,
+           "transforms_per_pack": t_pack, "transforms_per_bootstrap": t_boot, "batches": []}
+    for B in (p.N, 8 * p.N):
+        x = torch.from_numpy(rng.integers(0, 2**32, (B, p.lwe_len), dtype=np.uint64).astype(np.uint32).view(np.int32)).cuda()
+        y = torch.from_numpy(rng.integers(0, 2**32, (B, p.lwe_len), dtype=np.uint64).astype(np.uint32).view(np.int32)).cuda()
+        res = torch.empty_like(x)
+        packed = mk.pack(sch, x)
+        calls = {"gate": lambda: sch.gate(0, x, y, out=res), "pack": lambda: mk.pack(sch, res, out=packed)}
+        for fn in calls.values():
+            fn()                                        # warm-up: code objects, workspaces
+        torch.cuda.synchronize()
+        ms = {k: [] for k in calls}
+        for _ in range(reps):
+            for k, fn in calls.items():                 # alternating
+                ms[k].append(event_ms(torch, fn))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        packs = -(-B // p.N)
+        out["batches"].append({
+            "B": B, "packs": packs, "ms_median": {k: round(v, 4) for k, v in med.items()}, "ms_min": {k: round(min(v), 4) for k, v in ms.items()},
+            "ms_max": {k: round(max(v), 4) for k, v in ms.items()}, "pack_over_gate": round(med["pack"] / med["gate"], 5),
+            "transform_estimate_pack_over_gate": round(packs * t_pack / (B * t_boot), 5),
+            "lwe_bytes": B * p.lwe_len * 4, "packed_bytes": packs * (p.k + 1) * p.N * p.W // 8})
+    sch.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", default="KMS2party_N1024_l2,KMS2party")
+    ap.add_argument("--gadget", default="4,4")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    a = ap.parse_args()
+    import torch
+    assert torch.cuda.is_available(), "a GPU is required: nothing here is measured on a CPU"
+    l, logB = (int(v) for v in a.gadget.split(","))
+    head = {"build_id": mk.build_id(), "device": torch.cuda.get_device_name(0)}
+    res = dict(head, tool="pack_time", results=[measure(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
+    files = {f"pack_{mk.build_id()}.json": res}
+    if a.noise:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import test_gpu_pack as T
+        files[f"pack_noise_{mk.build_id()}.json"] = dict(head, tool="pack_time --noise", cases=[T.measure_noise(c) for c in sorted(T.NOISE_CASES)])
+    os.makedirs(a.out_dir, exist_ok=True)
+    for name, rec in files.items():
+        line = json.dumps(rec)
+        print(line)
+        with open(os.path.join(a.out_dir, name), "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
