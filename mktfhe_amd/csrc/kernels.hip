@@ -3,6 +3,8 @@
 // contraction off (one rounding per reference operation); see fft_device.h for the mapping.
 #include "kernel_common.h"
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 // The file is compiled once per translation unit MKT_TU (Makefile) so the template instantiations build in parallel:
@@ -1211,26 +1213,40 @@ __device__ __forceinline__ uint32_t ks_word(const WORD *poly, int j, int N, int 
     else return extract_word_at<WORD>(poly, j, N, v);
 }
 
-// out = 0 except: b = acc.b[0] >> (W-32) (:86 / :569) and, for the block schemes, the extracted words that are
-// copied instead of switched (:180-191, :676-679).  The key-switch kernel then accumulates with atomics.
+// words of an output row: one mask block per party (or one in all) and the body
+__host__ __device__ inline int ks_lwe_len(const KsArgs &a) { return (a.mk ? a.kacc : 1) * a.n + 1; }
+
+// Word q of output row g as the key switch leaves it alone: b = acc.b[0] >> (W-32) (:86 / :569) and, for the block schemes, the
+// extracted words that are copied instead of switched (:180-191, :676-679; LMSS counts them across the components, KMS_block per
+// party); 0 everywhere else.
+template <typename WORD, bool AT>
+__device__ __forceinline__ uint32_t ks_kept_word(const KsArgs &a, size_t g, int q) {
+    const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + ks_row<AT>(a, g) * (size_t)(1 + a.kacc) * a.N;
+    const int cf = ks_coef<AT>(a, g);
+    if (q == ks_lwe_len(a) - 1) return (uint32_t)(accg[cf] >> (WordTraits<WORD>::W - 32));
+    if (!a.balanced) return 0;
+    const int per = a.lmss ? a.N : a.n, c = q / per, j = q % per;
+    return ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf);
+}
+// The other side of the same rule: the first coefficient of component c that IS switched -- the gather kernels run over [it, N) and
+// ks_kept_word copies what lies before it.
+template <bool BAL>
+__device__ __forceinline__ int ks_first_switched(const KsArgs &a, int c) {
+    if constexpr (!BAL) return 0;
+    else {
+        if (!a.lmss) return a.n;
+        const long cur = (long)c * a.N;
+        return cur >= a.n ? 0 : (cur + a.N <= a.n ? a.N : (int)(a.n - cur));
+    }
+}
+
+// out = the kept words.  The per-digit key-switch kernel then accumulates with atomics.
 template <typename WORD, bool AT>
 __global__ void ks_init_kernel(const KsArgs a, size_t B) {
-    constexpr int sh = WordTraits<WORD>::W - 32;
-    const int nblocks_out = a.mk ? a.kacc : 1;
-    const int lwe_len = nblocks_out * a.n + 1;
+    const int lwe_len = ks_lwe_len(a);
     const size_t total = B * (size_t)lwe_len;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t g = i / lwe_len; const int q = (int)(i % lwe_len);
-        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + ks_row<AT>(a, g) * (size_t)(1 + a.kacc) * a.N;
-        const int cf = ks_coef<AT>(a, g);
-        uint32_t v = 0;
-        if (q == lwe_len - 1) v = (uint32_t)(accg[cf] >> sh);
-        else if (a.balanced) {
-            if (a.lmss) { const int c = q / a.N, j = q % a.N; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
-            else { const int c = q / a.n, j = q % a.n; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
-        }
-        a.out[i] = v;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        a.out[i] = ks_kept_word<WORD, AT>(a, i / lwe_len, (int)(i % lwe_len));
 }
 
 // Multi-gate key switch.  One wave handles G ciphertexts, one slab of the extracted coefficients j and one
@@ -1242,6 +1258,47 @@ __global__ void ks_init_kernel(const KsArgs a, size_t B) {
 // addition is order independent, so the result is deterministic.
 constexpr int KS_LANES = 64, KS_CHUNK_WORDS = 4 * KS_LANES, KS_STAGES = 2;
 constexpr int KS_BATCH = 8;
+
+__device__ __forceinline__ uint4 ks_add(uint4 x, uint4 y) { return make_uint4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w); }
+__device__ __forceinline__ uint4 ks_neg(uint4 r) { return make_uint4(0u - r.x, 0u - r.y, 0u - r.z, 0u - r.w); }
+
+// The tile of a gather wave, the same in both gather kernels: ciphertexts [g_base, g_base + G) x coefficient slab `slab` x the four LWE-row
+// words from q0 on (active: inside the padded row), over components [c_begin, c_end) -- the party's own (grid.y) or all of them.
+template <int G, int WAVES>
+struct KsTile {
+    int lane, wv, gblocks, gg, slab, q0, c_begin, c_end, blk, g_base;   // blk: the mask block of the output row that the tile adds to
+    bool active;
+    size_t comp_words;
+    __device__ __forceinline__ KsTile(const KsArgs &a, int ngroups) {
+        lane = threadIdx.x & (KS_LANES - 1);
+        wv = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / KS_LANES)) : 0;   // wave-uniform, and known to be
+        gblocks = (ngroups + WAVES - 1) / WAVES;
+        gg = (int)(blockIdx.x % (unsigned)gblocks) * WAVES + wv; slab = (int)(blockIdx.x / (unsigned)gblocks);
+        q0 = (int)blockIdx.z * KS_CHUNK_WORDS + 4 * lane;
+        active = q0 < a.n1p;
+        c_begin = a.mk ? (int)blockIdx.y : 0; c_end = a.mk ? c_begin + 1 : a.kacc; blk = a.mk ? c_begin : 0;
+        comp_words = (size_t)a.N * a.drows * a.f * a.n1p;
+        g_base = gg * G;
+    }
+    // the key rows of component c
+    __device__ __forceinline__ const uint32_t *ksk(const KsArgs &a, int c) const { return a.mk ? a.ksk + (size_t)c * a.ksk_party_stride : a.ksk + (size_t)c * comp_words; }
+};
+
+// One staged table row per ciphertext, added into its four sums: row row0 + row(g) of the [row][lane] table, row(g) the caller's index
+// for ciphertext g (the two kernels index differently).  BATCH table reads are issued back to back before their sums: one LDS latency
+// per batch instead of one per ciphertext.  The index is formed here, as one integer expression: handed a pointer to the stage's
+// rows the per-digit kernel spills at G = 32, handed the caller's finished read the pair kernel runs 8 % slower (measured, docs/history.md)
+template <int G, int BATCH, typename ROW>
+__device__ __forceinline__ void ks_accumulate(uint4 (&sum)[G], const uint4 *tabp, int row0, int lane, ROW row) {
+#pragma unroll
+    for (int g0 = 0; g0 < G; g0 += BATCH) {
+        uint4 v[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; u++) v[u] = tabp[(row0 + row(g0 + u)) * KS_LANES + lane];
+#pragma unroll
+        for (int u = 0; u < BATCH; u++) sum[g0 + u] = ks_add(sum[g0 + u], v[u]);
+    }
+}
 
 // WAVES > 1: the waves of a workgroup (each with its own G ciphertexts) share one staged table -- every row is fetched
 // from L2 / Infinity Cache once per WAVES*G ciphertexts; one barrier per stage.  The two stage buffers alternate on a
@@ -1255,21 +1312,14 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
     uint4 *tabp = reinterpret_cast<uint4 *>(mkt_smem);
     const int trows = 1 + a.drows * (BAL ? 2 : 1);
 #define tab(s, r, l) tabp[((s) * trows + (r)) * KS_LANES + (l)]
-    const int lane = threadIdx.x & (KS_LANES - 1);
-    const int wv = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / KS_LANES)) : 0;   // wave-uniform, and known to be
-    const int gblocks = (ngroups + WAVES - 1) / WAVES;
-    const int gg = (int)(blockIdx.x % (unsigned)gblocks) * WAVES + wv, slab = (int)(blockIdx.x / (unsigned)gblocks);
+    const KsTile<G, WAVES> tile(a, ngroups);
+    const int lane = tile.lane, wv = tile.wv, q0 = tile.q0, g_base = tile.g_base;
+    const bool active = tile.active;
     const int N = a.N, n = a.n, n1p = a.n1p, f = a.f, logD = a.logD;
-    const int q0 = (int)blockIdx.z * KS_CHUNK_WORDS + 4 * lane;
-    const bool active = q0 < n1p;
-    const int nblocks_out = a.mk ? a.kacc : 1;
-    const int lwe_len = nblocks_out * n + 1;
-    const int c_begin = a.mk ? (int)blockIdx.y : 0, c_end = a.mk ? c_begin + 1 : a.kacc;
+    const int lwe_len = ks_lwe_len(a);
     const uint32_t Dm = (1u << logD) - 1;
     const int half = 1 << (logD - 1);
     const Gadget<uint32_t> gb(f, logD);
-    const size_t comp_words = (size_t)N * a.drows * f * n1p;
-    const int g_base = gg * G;
     const int drows = a.drows;
     uint4 sum[G];
 #pragma unroll
@@ -1280,15 +1330,11 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
     }
 
     int it = 0;   // stage counter over the WHOLE (c, j, td) loop: consecutive stagings always alternate buffers, also for odd f
-    for (int c = c_begin; c < c_end; c++) {
-        const uint32_t *ksk = a.mk ? a.ksk + (size_t)c * a.ksk_party_stride : a.ksk + (size_t)c * comp_words;
-        int jstart = 0;
-        if (BAL) {
-            if (a.lmss) { const long cur = (long)c * N; jstart = cur >= n ? 0 : (cur + N <= n ? N : (int)(n - cur)); }
-            else jstart = n;
-        }
-        int j0 = slab * jslab, j1 = j0 + jslab;
-        if (j0 < jstart) j0 = jstart;
+    for (int c = tile.c_begin; c < tile.c_end; c++) {
+        const uint32_t *ksk = tile.ksk(a, c);
+        // the slabs cut [0, N); a slab keeps what it holds of the switched coefficients
+        int j0 = tile.slab * jslab, j1 = j0 + jslab;
+        if (const int jstart = ks_first_switched<BAL>(a, c); j0 < jstart) j0 = jstart;
         if (j1 > N) j1 = N;
         for (int j = j0; j < j1; j++) {
             uint32_t tt[G];   // wave-uniform: the prepared digit word of every ciphertext of the group
@@ -1308,31 +1354,19 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
                     uint4 r = make_uint4(0, 0, 0, 0);
                     if (active) r = *reinterpret_cast<const uint4 *>(rowj + ((size_t)(d - 1) * f + td) * n1p);
                     tab(st, d, lane) = r;
-                    if (BAL) tab(st, drows + d, lane) = make_uint4(0u - r.x, 0u - r.y, 0u - r.z, 0u - r.w);
+                    if (BAL) tab(st, drows + d, lane) = ks_neg(r);
                 }
                 if (WAVES > 1) __syncthreads();
-                // KS_BATCH table reads are issued back to back before their sums: one LDS latency per batch instead of
-                // one per ciphertext
-#pragma unroll
-                for (int g0 = 0; g0 < G; g0 += KS_BATCH) {
-                    uint4 v[KS_BATCH];
-#pragma unroll
-                    for (int u = 0; u < KS_BATCH; u++) {
-                        int idx = (int)((tt[g0 + u] >> shift) & Dm);
-                        if (BAL) { idx -= half; if (idx < 0) idx = drows - idx; }   // -1 -> drows+1, -2 -> drows+2
-                        v[u] = tab(st, idx, lane);
-                    }
-#pragma unroll
-                    for (int u = 0; u < KS_BATCH; u++) {
-                        sum[g0 + u].x += v[u].x; sum[g0 + u].y += v[u].y; sum[g0 + u].z += v[u].z; sum[g0 + u].w += v[u].w;
-                    }
-                }
+                ks_accumulate<G, KS_BATCH>(sum, tabp, st * trows, lane, [&](int g) {
+                    int idx = (int)((tt[g] >> shift) & Dm);
+                    if (BAL) { idx -= half; if (idx < 0) idx = drows - idx; }   // -1 -> drows+1, -2 -> drows+2
+                    return idx;
+                });
             }
         }
     }
 #undef tab
     if (!active) return;
-    const int blk = a.mk ? c_begin : 0;
 #pragma unroll
     for (int g = 0; g < G; g++) {
         if (g_base + g >= B) break;
@@ -1341,7 +1375,7 @@ __global__ __launch_bounds__(KS_LANES * WAVES, G == 32 ? 3 : 1) void keyswitch_m
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int q = q0 + u;
-            if (q < n) { if (v[u]) atomicAdd(&outg[(size_t)blk * n + q], v[u]); }
+            if (q < n) { if (v[u]) atomicAdd(&outg[(size_t)tile.blk * n + q], v[u]); }
             else if (q == n) { if (v[u]) atomicAdd(&outg[lwe_len - 1], v[u]); }
         }
     }
@@ -1380,40 +1414,28 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(const KsArgs a, int B, i
 #define MKT_KSP_OCC 3
 #endif
 constexpr int KSP_BATCH = MKT_KSP_BATCH;
-template <typename WORD, int G, int WAVES, bool BAL>
+template <int G, int WAVES, bool BAL>
 __global__ __launch_bounds__(KS_LANES * WAVES, MKT_KSP_OCC) void keyswitch_pair_kernel(const KsArgs a, int B, int ngroups) {
     uint4 *tabp = reinterpret_cast<uint4 *>(mkt_smem);   // [stage][16][lane]
 #define tab(s, r, l) tabp[((s) * 16 + (r)) * KS_LANES + (l)]
-    const int lane = threadIdx.x & (KS_LANES - 1);
-    const int wv = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / KS_LANES)) : 0;
-    const int gblocks = (ngroups + WAVES - 1) / WAVES;
-    const int gg = (int)(blockIdx.x % (unsigned)gblocks) * WAVES + wv, slab = (int)(blockIdx.x / (unsigned)gblocks);
-    const int N = a.N, n = a.n, n1p = a.n1p, f = a.f;
-    const int q0 = (int)blockIdx.z * KS_CHUNK_WORDS + 4 * lane;
-    const bool active = q0 < n1p;
-    const int c_begin = a.mk ? (int)blockIdx.y : 0, c_end = a.mk ? c_begin + 1 : a.kacc;
+    const KsTile<G, WAVES> tile(a, ngroups);
+    const int lane = tile.lane, wv = tile.wv, gg = tile.gg, q0 = tile.q0, g_base = tile.g_base;
+    const bool active = tile.active;
+    const int N = a.N, n1p = a.n1p, f = a.f;
     const int drows = a.drows;
-    const size_t comp_words = (size_t)N * drows * f * n1p;
-    const int g_base = gg * G;
     uint4 sum[G];
 #pragma unroll
     for (int g = 0; g < G; g++) sum[g] = make_uint4(0, 0, 0, 0);
     const uint4 zero = make_uint4(0, 0, 0, 0);
-    auto neg = [](uint4 r) { return make_uint4(0u - r.x, 0u - r.y, 0u - r.z, 0u - r.w); };
-    auto add = [](uint4 x, uint4 y) { return make_uint4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w); };
 
     int it = 0;
-    for (int c = c_begin; c < c_end; c++) {
-        const uint32_t *ksk = a.mk ? a.ksk + (size_t)c * a.ksk_party_stride : a.ksk + (size_t)c * comp_words;
-        int jstart = 0;
-        if (BAL) {
-            if (a.lmss) { const long cur = (long)c * N; jstart = cur >= n ? 0 : (cur + N <= n ? N : (int)(n - cur)); }
-            else jstart = n;
-        }
+    for (int c = tile.c_begin; c < tile.c_end; c++) {
+        const uint32_t *ksk = tile.ksk(a, c);
+        const int jstart = ks_first_switched<BAL>(a, c);
         // the slabs share the coefficients that ARE switched, [jstart, N): equal work per slab also for the block schemes, whose
         // first n coefficients are copied (Blockparam: 337 of 1024 left)
-        const int nslabs = (int)(gridDim.x / (unsigned)gblocks), js = (N - jstart + nslabs - 1) / nslabs;
-        const int j0 = jstart + slab * js;
+        const int nslabs = (int)(gridDim.x / (unsigned)tile.gblocks), js = (N - jstart + nslabs - 1) / nslabs;
+        const int j0 = jstart + tile.slab * js;
         int j1 = j0 + js;
         if (j1 > N) j1 = N;
         // the prepared digit words of this wave's 32 ciphertexts: 128 contiguous bytes per coefficient (ks_digits_kernel), read on
@@ -1434,27 +1456,18 @@ __global__ __launch_bounds__(KS_LANES * WAVES, MKT_KSP_OCC) void keyswitch_pair_
                 for (int r = 0; r < (BAL ? 2 : 3); r++) r2[r] = ld(r, td + 1);
                 for (int d1 = wv; d1 < 4; d1 += WAVES) {    // the waves share the sixteen sums
                     uint4 e1;
-                    if (BAL) e1 = d1 == 2 ? zero : (d1 == 3 ? ld(0, td) : neg(ld(1 - d1, td)));
+                    if (BAL) e1 = d1 == 2 ? zero : (d1 == 3 ? ld(0, td) : ks_neg(ld(1 - d1, td)));
                     else e1 = d1 ? ld(d1 - 1, td) : zero;
                     if constexpr (BAL) {
-                        tab(st, d1 * 4 + 0, lane) = add(e1, neg(r2[1])); tab(st, d1 * 4 + 1, lane) = add(e1, neg(r2[0]));
-                        tab(st, d1 * 4 + 2, lane) = e1; tab(st, d1 * 4 + 3, lane) = add(e1, r2[0]);
+                        tab(st, d1 * 4 + 0, lane) = ks_add(e1, ks_neg(r2[1])); tab(st, d1 * 4 + 1, lane) = ks_add(e1, ks_neg(r2[0]));
+                        tab(st, d1 * 4 + 2, lane) = e1; tab(st, d1 * 4 + 3, lane) = ks_add(e1, r2[0]);
                     } else {
-                        tab(st, d1 * 4 + 0, lane) = e1; tab(st, d1 * 4 + 1, lane) = add(e1, r2[0]);
-                        tab(st, d1 * 4 + 2, lane) = add(e1, r2[1]); tab(st, d1 * 4 + 3, lane) = add(e1, r2[2]);
+                        tab(st, d1 * 4 + 0, lane) = e1; tab(st, d1 * 4 + 1, lane) = ks_add(e1, r2[0]);
+                        tab(st, d1 * 4 + 2, lane) = ks_add(e1, r2[1]); tab(st, d1 * 4 + 3, lane) = ks_add(e1, r2[2]);
                     }
                 }
                 if (WAVES > 1) __syncthreads();
-#pragma unroll
-                for (int g0 = 0; g0 < G; g0 += KSP_BATCH) {
-                    uint4 v[KSP_BATCH];
-#pragma unroll
-                    for (int u = 0; u < KSP_BATCH; u++) v[u] = tab(st, (int)((tt[g0 + u] >> shift) & 15u), lane);
-#pragma unroll
-                    for (int u = 0; u < KSP_BATCH; u++) {
-                        sum[g0 + u].x += v[u].x; sum[g0 + u].y += v[u].y; sum[g0 + u].z += v[u].z; sum[g0 + u].w += v[u].w;
-                    }
-                }
+                ks_accumulate<G, KSP_BATCH>(sum, tabp, st * 16, lane, [&](int g) { return (int)((tt[g] >> shift) & 15u); });
             }
         }
     }
@@ -1462,37 +1475,26 @@ __global__ __launch_bounds__(KS_LANES * WAVES, MKT_KSP_OCC) void keyswitch_pair_
     if (!active) return;
     // this wave's share of the sum over (component, coefficient, digit): one 16-byte store per ciphertext into the partial-sum rows
     // [slab][party][ciphertext][n1p]; ks_reduce_kernel adds the slabs (atomics on the output words cost 0.2 ms of a 0.6 ms kernel)
-    const int blk = a.mk ? c_begin : 0;
 #pragma unroll
     for (int g = 0; g < G; g++) {
         if (g_base + g >= B) break;
-        *reinterpret_cast<uint4 *>(a.partial + (((size_t)slab * gridDim.y + blk) * B + (g_base + g)) * n1p + q0) = sum[g];
+        *reinterpret_cast<uint4 *>(a.partial + (((size_t)tile.slab * gridDim.y + tile.blk) * B + (g_base + g)) * n1p + q0) = sum[g];
     }
 }
 
-// out = what the key switch leaves alone (b, and for the block schemes the extracted words that are copied, :180-191 / :676-679:
-// ks_init_kernel's words) + the partial sums of every slab (and, for b, of every party).
+// out = the kept words (ks_init_kernel's) + the partial sums of every slab (and, for b, of every party).
 template <typename WORD, bool AT>
 __global__ void ks_reduce_kernel(const KsArgs a, size_t B, int slabs, int parties) {
-    constexpr int sh = WordTraits<WORD>::W - 32;
-    const int nblocks_out = a.mk ? a.kacc : 1;
-    const int lwe_len = nblocks_out * a.n + 1;
+    const int lwe_len = ks_lwe_len(a);
     const size_t total = B * (size_t)lwe_len;
     const size_t row = (size_t)a.n1p, slab_stride = (size_t)parties * B * row;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t g = i / lwe_len; const int q = (int)(i % lwe_len);
-        const WORD *accg = reinterpret_cast<const WORD *>(a.acc) + ks_row<AT>(a, g) * (size_t)(1 + a.kacc) * a.N;
-        const int cf = ks_coef<AT>(a, g);
-        uint32_t v = 0;
+        uint32_t v = ks_kept_word<WORD, AT>(a, g, q);
         if (q == lwe_len - 1) {
-            v = (uint32_t)(accg[cf] >> sh);
             for (int sl = 0; sl < slabs; sl++)
                 for (int pt = 0; pt < parties; pt++) v += a.partial[sl * slab_stride + ((size_t)pt * B + g) * row + a.n];
         } else {
-            if (a.balanced) {
-                if (a.lmss) { const int c = q / a.N, j = q % a.N; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
-                else { const int c = q / a.n, j = q % a.n; v = ks_word<WORD, AT>(accg + (size_t)(1 + c) * a.N, j, a.N, cf); }
-            }
             const int pt = a.mk ? q / a.n : 0, w = a.mk ? q % a.n : q;
             const uint32_t *src = a.partial + ((size_t)pt * B + g) * row + w;
             for (int sl = 0; sl < slabs; sl++) v += src[sl * slab_stride];
@@ -1936,45 +1938,38 @@ void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *pa
 template <bool AT>
 static hipError_t launch_keyswitch_as(int W, const KsArgs &a, size_t B, hipStream_t s) {
     const KsPlan q = ks_plan(a, B, a.digits && a.partial);
-    const int G = q.G, waves = q.waves, ngroups = q.ngroups, parties = q.parties, gblocks = q.gblocks, slabs = q.slabs, jslab = q.jslab;
-    const bool pair = q.pair;
-    const dim3 grid((unsigned)(gblocks * slabs), (unsigned)parties, (unsigned)((a.n1p + KS_CHUNK_WORDS - 1) / KS_CHUNK_WORDS));
-    const size_t ks_lds = pair ? (size_t)KS_STAGES * 16 * KS_LANES * sizeof(uint4) : (size_t)KS_STAGES * (1 + a.drows * (a.balanced ? 2 : 1)) * KS_LANES * sizeof(uint4);
+    const int ngroups = q.ngroups;
+    const dim3 grid((unsigned)(q.gblocks * q.slabs), (unsigned)q.parties, (unsigned)((a.n1p + KS_CHUNK_WORDS - 1) / KS_CHUNK_WORDS));
+    const size_t ks_lds = q.pair ? (size_t)KS_STAGES * 16 * KS_LANES * sizeof(uint4) : (size_t)KS_STAGES * (1 + a.drows * (a.balanced ? 2 : 1)) * KS_LANES * sizeof(uint4);
     if (ks_lds > 64 * 1024) return hipErrorInvalidValue;   // logD <= 5
-    const size_t total = B * (size_t)(parties * a.n + 1);
-    if (pair) {      // digit words -> partial sums per slab -> output
-#define MKT_KSP_LAUNCH_B(WT, BV) do { if (waves == 4) hipLaunchKernelGGL((keyswitch_pair_kernel<WT, 32, 4, BV>), grid, dim3(KS_LANES * 4), ks_lds, s, a, (int)B, ngroups); \
-        else if (waves == 2) hipLaunchKernelGGL((keyswitch_pair_kernel<WT, 32, 2, BV>), grid, dim3(KS_LANES * 2), ks_lds, s, a, (int)B, ngroups); \
-        else hipLaunchKernelGGL((keyswitch_pair_kernel<WT, 32, 1, BV>), grid, dim3(KS_LANES), ks_lds, s, a, (int)B, ngroups); } while (0)
+    const dim3 words(blocks_for(B * (size_t)ks_lwe_len(a), 256));   // ks_init_kernel / ks_reduce_kernel: the output words
+    // W -> WORD, a.balanced -> BAL, the plan's wave count -> WAVES: every launch below is written once and asks for what it takes
+    using C1 = std::integral_constant<int, 1>; using C2 = std::integral_constant<int, 2>; using C4 = std::integral_constant<int, 4>;
+    auto with_word = [&](auto f) { if (W == 64) f(uint64_t{}); else f(uint32_t{}); };
+    auto with_bal = [&](auto f) { if (a.balanced) f(std::true_type{}); else f(std::false_type{}); };
+    auto with_waves = [&](auto f) { if (q.waves == 4) f(C4{}); else if (q.waves == 2) f(C2{}); else f(C1{}); };
+    if (q.pair) {      // digit words -> partial sums per slab -> output
         const dim3 dgrid((unsigned)((a.N + 7) / 8), (unsigned)ngroups, (unsigned)a.kacc);
-#define MKT_KSD_LAUNCH(WT) do { if (a.balanced) hipLaunchKernelGGL((ks_digits_kernel<WT, true, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); \
-        else hipLaunchKernelGGL((ks_digits_kernel<WT, false, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); } while (0)
-        if (W == 64) {
-            MKT_KSD_LAUNCH(uint64_t);
-            if (a.balanced) MKT_KSP_LAUNCH_B(uint64_t, true); else MKT_KSP_LAUNCH_B(uint64_t, false);
-            hipLaunchKernelGGL((ks_reduce_kernel<uint64_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
-        } else {
-            MKT_KSD_LAUNCH(uint32_t);
-            if (a.balanced) MKT_KSP_LAUNCH_B(uint32_t, true); else MKT_KSP_LAUNCH_B(uint32_t, false);
-            hipLaunchKernelGGL((ks_reduce_kernel<uint32_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B, slabs, parties);
-        }
-#undef MKT_KSD_LAUNCH
-#undef MKT_KSP_LAUNCH_B
+        with_word([&](auto w) { with_bal([&](auto bal) {
+            hipLaunchKernelGGL((ks_digits_kernel<decltype(w), decltype(bal)::value, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups);
+        }); });
+        with_bal([&](auto bal) { with_waves([&](auto wv) {
+            hipLaunchKernelGGL((keyswitch_pair_kernel<32, decltype(wv)::value, decltype(bal)::value>), grid, dim3(KS_LANES * decltype(wv)::value), ks_lds, s, a, (int)B, ngroups);
+        }); });
+        with_word([&](auto w) { hipLaunchKernelGGL((ks_reduce_kernel<decltype(w), AT>), words, dim3(256), 0, s, a, B, q.slabs, q.parties); });
         return hipGetLastError();
     }
-#define MKT_KS_LAUNCH_B(WT, GV, BV) do { if (GV == 32 && waves == 4) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 4, BV, AT>), grid, dim3(KS_LANES * 4), ks_lds, s, a, (int)B, ngroups, jslab); \
-        else if (GV == 32 && waves == 2) hipLaunchKernelGGL((keyswitch_mg_kernel<WT, 32, 2, BV, AT>), grid, dim3(KS_LANES * 2), ks_lds, s, a, (int)B, ngroups, jslab); \
-        else hipLaunchKernelGGL((keyswitch_mg_kernel<WT, GV, 1, BV, AT>), grid, dim3(KS_LANES), ks_lds, s, a, (int)B, ngroups, jslab); } while (0)
-#define MKT_KS_LAUNCH(WT, GV) do { if (a.balanced) MKT_KS_LAUNCH_B(WT, GV, true); else MKT_KS_LAUNCH_B(WT, GV, false); } while (0)
-    if (W == 64) {
-        hipLaunchKernelGGL((ks_init_kernel<uint64_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
-        if (G == 8) MKT_KS_LAUNCH(uint64_t, 8); else if (G == 32) MKT_KS_LAUNCH(uint64_t, 32); else MKT_KS_LAUNCH(uint64_t, 16);
-    } else {
-        hipLaunchKernelGGL((ks_init_kernel<uint32_t, AT>), dim3(blocks_for(total, 256)), dim3(256), 0, s, a, B);
-        if (G == 8) MKT_KS_LAUNCH(uint32_t, 8); else if (G == 32) MKT_KS_LAUNCH(uint32_t, 32); else MKT_KS_LAUNCH(uint32_t, 16);
-    }
-#undef MKT_KS_LAUNCH_B
-#undef MKT_KS_LAUNCH
+    with_word([&](auto w) {
+        hipLaunchKernelGGL((ks_init_kernel<decltype(w), AT>), words, dim3(256), 0, s, a, B);
+        with_bal([&](auto bal) {
+            auto mg = [&](auto g, auto wv) {   // the 8- and 16-wide tiles are one wave
+                hipLaunchKernelGGL((keyswitch_mg_kernel<decltype(w), decltype(g)::value, decltype(wv)::value, decltype(bal)::value, AT>), grid, dim3(KS_LANES * decltype(wv)::value), ks_lds, s, a, (int)B, ngroups, q.jslab);
+            };
+            if (q.G == 32) with_waves([&](auto wv) { mg(std::integral_constant<int, 32>{}, wv); });
+            else if (q.G == 8) mg(std::integral_constant<int, 8>{}, C1{});
+            else mg(std::integral_constant<int, 16>{}, C1{});
+        });
+    });
     return hipGetLastError();
 }
 

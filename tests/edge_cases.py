@@ -14,7 +14,8 @@ _KXB = mk.KMS2partyblock.scaled(n=6, N=256, blk_d=2)
 
 
 def sid(p):
-    return f"{p.name}-n{p.n}-N{p.N}-k{p.k}-b{p.blk_len}"
+    """a set of KS_SETS that differs from an earlier one in the key-switch gadget alone names its gadget too"""
+    return f"{p.name}-n{p.n}-N{p.N}-k{p.k}-b{p.blk_len}" + (f"-f{p.f}x{p.logD}" if p in _KS_GADGET_TWINS else "")
 
 
 # (parameter set, options, kernel the case means to reach, batch size): blind rotation, Float64 mode.  B = 5 is ragged for every
@@ -73,13 +74,17 @@ EXACT_CASES = [
 EXACT_PAIR_SETS = [mk.CGGIparam.scaled(n=6, N=1024), mk.CGGIparam.scaled(n=4, N=4096), mk.KMS2party_N1024_l2.scaled(n=4), mk.KMS2party.scaled(n=2, N=4096)]
 
 # key switch: the four full-length sets (digit-pair kernel: D = 4, f even), other gadgets (per-digit kernel; f = 5: stage-buffer
-# parity), LMSS with n > N (whole components copied)
+# parity), LMSS with n > N (whole components copied), and the LMSS copy rule's remaining branches: a component wholly beyond n (every
+# coefficient switched) on the per-digit and on the digit-pair kernel, components wholly copied (and one cut at 44) on the per-digit kernel
 KS_SETS = [
     mk.CGGIparam, mk.Blockparam_k2, mk.KMS2partyblock, mk.CCS2party,
     mk.CGGIparam.scaled(n=20, N=256, f=5, logD=3), mk.Blockparam.scaled(n=30, N=256, blk_d=10, f=4, logD=3),
     mk.KMS2party.scaled(n=12, N=256, f=5, logD=3), mk.KMS2partyblock.scaled(n=24, N=256, blk_d=8, f=4, logD=3),
     mk.Blockparam.scaled(n=300, N=128, blk_d=100, k=3), mk.Blockparam.scaled(n=150, N=128, blk_d=50, k=2, blk_len=3),
+    mk.Blockparam.scaled(n=96, N=128, blk_d=32, k=2, f=4, logD=3), mk.Blockparam.scaled(n=300, N=128, blk_d=100, k=3, f=4, logD=3),
+    mk.Blockparam.scaled(n=96, N=128, blk_d=32, k=2),
 ]
+_KS_GADGET_TWINS = [p for i, p in enumerate(KS_SETS) if any(q != p and q.scaled(f=p.f, logD=p.logD) == p for q in KS_SETS[:i])]
 KS_BATCHES = (1, 33, 70)
 # the sets of the launcher-switch child (tests/test_gpu_switches.py _child_ks), reduced n
 KS_CHILD_FULL = (mk.CGGIparam, (33,))          # and the full key length (the child's own first context), one ragged batch
