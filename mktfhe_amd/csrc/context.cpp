@@ -13,10 +13,12 @@
 #include <vector>
 
 #include "device_api.h"
+#include "device_mem.h"
 #include "fft_device.h"
 #include "host_internal.h"
 
 using mktd::cplx;
+using mkt::DevBuf;
 
 namespace {
 thread_local std::string g_create_error;
@@ -108,16 +110,33 @@ struct KeySet {
     // packed outputs (mktfhe_pack.h): every party's packing key, outside the table description below (no multi-device replica).  F64REF:
     // [party][n][l][1 + kr][M] transforms in the slot-major point order; EXACT: [party][1 + kr][n l][N] ring words, polynomial-major -- the
     // rows one exact-product launch reads in a run.  The first load fixes the gadget
-    void *d_pack = nullptr; int pack_l = 0, pack_logB = 0; size_t pack_party_bytes = 0;
+    DevBuf d_pack; int pack_l = 0, pack_logB = 0; size_t pack_party_bytes = 0;
     std::vector<uint8_t> pack_loaded;   // [party]
     ResidentTable tab[T_COUNT];  // describe_key_set
     size_t stride(KeyTable t) const { return tab[t].elems; }   // elements from one party's rows to the next
     template <class T> T *party(KeyTable t, int party) const { return static_cast<T *>(*tab[t].slot) + (size_t)party * tab[t].elems; }   // base of one party's rows
-    ~KeySet() {
-        DevGuard g(device);
-        for (const ResidentTable &t : tab) if (t.slot && *t.slot) (void)hipFree(*t.slot);
-        if (d_pack) (void)hipFree(d_pack);
-    }
+    ~KeySet() { for (const ResidentTable &t : tab) if (t.slot && *t.slot) (void)hipFree(*t.slot); }
+};
+// a key set lets go of its tables and owners under its own device, whoever drops the last reference
+static std::shared_ptr<KeySet> new_key_set() { return std::shared_ptr<KeySet>(new KeySet, [](KeySet *k) { DevGuard g(k->device); delete k; }); }
+
+// The device memory a context keeps between calls, every buffer with its owner (device_mem.h), grouped as it grows.  mkt_ctx_destroy drops it whole
+struct MKT_HIDDEN Workspace {
+    // the rotation group, for `gates` gates, sized per gate by the route (ensure_workspace): the linear combinations, the accumulators, what the route's kernels are handed
+    size_t gates = 0;
+    DevBuf lin, acc, lev, scratch;
+    DevBuf fxacc;                // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
+    DevBuf ksd;                  // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
+    // lookup-table bootstrap with more than one output per input: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call): the src half, then the coef half
+    DevBuf at;
+    uint32_t *at_src() const { return at.as<uint32_t>(); }
+    uint32_t *at_coef() const { return at.as<uint32_t>() + at.cap / 8; }   // at the row count the table was allocated for
+    // mkt_pack_batch: its own group for `packs` packs at a time -- the lifted columns; F64REF the product kernel's slabs; EXACT the digits and products of one chunk of columns
+    size_t packs = 0;
+    DevBuf pack_cols, pack_slabs, pack_dig, pack_prod;
+    // mkt_exact_polymul_batch: [0] max|a_i| over the batch, [1] largest |limb transform of b|^2, [2] largest |q - round(q)| of the Float64 kernel (bit patterns)
+    DevBuf pm_stat;
+    unsigned long long *pm() const { return pm_stat.as<unsigned long long>(); }
 };
 
 struct mkt_ctx {
@@ -132,23 +151,13 @@ struct mkt_ctx {
     std::shared_ptr<KeySet> ks;  // shared with the contexts forked from this one
     bool exact = false;          // MKT_ARITH_EXACT (integer NTT, two 30-bit primes)
     int split = 1;               // EXACT on the 64-bit ring: every resident 64-bit table is kept as (low, high) residue polynomials -> 2 per logical polynomial
-    // workspace
-    size_t ws_gates = 0;
-    uint32_t *ws_lin = nullptr;
-    void *ws_acc = nullptr;
-    cplx *ws_lev = nullptr, *ws_scratch = nullptr;
-    void *ws_fxacc = nullptr;    // fx_exact.hip, KMS: the phase-1 rows as ring words [gates][rtot][2][N] before they become split residue tables
-    uint32_t *ws_ksd = nullptr; size_t ws_ksd_words = 0;   // key switch: prepared digit words + partial sums per slab (grows with the largest batch seen)
-    // mkt_pack_batch: its own workspace for ws_pack_n packs at a time -- the lifted columns; F64REF the product kernel's slabs; EXACT the digits and products of one chunk of columns
-    size_t ws_pack_n = 0; void *ws_pack_cols = nullptr, *ws_pack_slabs = nullptr, *ws_pack_dig = nullptr, *ws_pack_prod = nullptr;
-    uint32_t *ws_at = nullptr; size_t ws_at_rows = 0;      // lookup-table bootstrap with more than one output per input: (src | coef) rows of a chunk's key switch, 8 bytes per output row (first such call)
+    Workspace ws;
     // timing
     bool timing = false;
     std::vector<TimedSpan> spans;
     Tune tune{};
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
     // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
-    unsigned long long *d_pm_stat = nullptr;   // [0] max|a_i| over the batch, [1] largest |limb transform of b|^2, [2] largest |q - round(q)| of the Float64 kernel (bit patterns)
     double pm_amax = 0.0;               // max|a_i| of the last call
     double pm_bound = -1.0;             // fx_polymul_bound of the last call (-1: not evaluated -- exact_impl != 1 or no Float64 tables)
     double fx_last_resid = 0.0;         // largest |q - round(q)| of the last call that ran the Float64 kernel (diagnostic, not a certificate)
@@ -202,7 +211,6 @@ hipError_t to_resident(mkt_ctx *c, const void *src, size_t npolys, cplx *dst, bo
     if (e == hipSuccess && fx_dst) e = mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), src, fx_dst, npolys, c->ks->d_fx_stat, c->stream);
     return e;
 }
-struct DevBuf { void *p = nullptr; ~DevBuf() { (void)hipFree(p); } };   // a call's own device buffer that holds no secret
 // transform `npolys` coefficient-form polynomials (host) into TransPolys at `dst` (device); returns with the stream drained.  brk_party >= 0: they
 // are that party's bootstrapping key, which in coefficient form goes through install_brk
 int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt, bool small = false, int brk_party = -1) {
@@ -211,7 +219,7 @@ int upload_polys(mkt_ctx *c, const void *host, size_t npolys, cplx *dst, int fmt
     const bool fft = fmt == MKT_FMT_F64_FFT;   // the reference's Trans* values: copy, then natural -> device point order
     const size_t nb = npolys * (fft ? (size_t)c->M * sizeof(cplx) : poly_bytes(c));
     DevBuf tmp;
-    HIPCHK(c, hipMalloc(&tmp.p, nb));
+    HIPCHK(c, tmp.alloc(nb));
     hipError_t e = hipMemcpyAsync(tmp.p, host, nb, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = fft ? mktd::launch_reorder(c->logM, static_cast<cplx *>(tmp.p), dst, npolys, 1, c->dev_order, c->stream)
                                  : brk_party >= 0 ? install_brk(c, brk_party, tmp.p) : to_resident(c, tmp.p, npolys, dst, small, nullptr);
@@ -271,10 +279,8 @@ Route rot_route(const mkt_ctx *c) {
 }
 
 int ensure_workspace(mkt_ctx *c, size_t gates) {
-    if (gates <= c->ws_gates) return MKT_OK;
-    void **ws[] = {(void **)&c->ws_lin, &c->ws_acc, (void **)&c->ws_lev, (void **)&c->ws_scratch, &c->ws_fxacc};
-    for (void **w : ws) { if (*w) (void)hipFree(*w); *w = nullptr; }
-    c->ws_gates = 0;
+    Workspace &w = c->ws;
+    if (gates <= w.gates) return MKT_OK;   // (reserve_group asks the same: the route is not looked up for a call that fits)
     const size_t tpoly = (size_t)c->M * sizeof(cplx);   // one transformed polynomial
     size_t lev = 0, scratch = 0, fxacc = 0;              // bytes per gate of what the route's kernels are handed
     switch (rot_route(c)) {
@@ -292,9 +298,9 @@ int ensure_workspace(mkt_ctx *c, size_t gates) {
         break;
     default: break;                                 // the register kernels keep their sums to themselves
     }
-    const size_t need[] = {(size_t)c->sh.lwe_len * 4, (size_t)(1 + c->sh.kacc) * poly_bytes(c), lev, scratch, fxacc};
-    for (int i = 0; i < 5; i++) if (need[i]) HIPCHK(c, hipMalloc(ws[i], gates * need[i]));
-    c->ws_gates = gates;
+    DevBuf *const group[] = {&w.lin, &w.acc, &w.lev, &w.scratch, &w.fxacc};
+    const size_t need[] = {gates * c->sh.lwe_len * 4, gates * (1 + c->sh.kacc) * poly_bytes(c), gates * lev, gates * scratch, gates * fxacc};
+    HIPCHK(c, mkt::reserve_group(w.gates, gates, group, need));
     return MKT_OK;
 }
 
@@ -342,19 +348,20 @@ mktd::ExactKmsArgs exact_kms_args(mkt_ctx *c, const uint32_t *lwe, int stride, i
     q.wide = c->tune.exact_wide;
     return q;
 }
-// EXACT KMS phase 1 of `gates` gates on the Float64 pipe (a per-call choice: fx_usable; ensure_workspace holds ws_fxacc whenever the key set has the limb transforms): rows as ring words in ws_fxacc, then as split residue tables at levkey for the integer phase 2
+// EXACT KMS phase 1 of `gates` gates on the Float64 pipe (a per-call choice: fx_usable; ensure_workspace holds ws.fxacc whenever the key set has the limb transforms): rows as ring words in ws.fxacc, then as split residue tables at levkey for the integer phase 2
 int fx_phase1(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, size_t gates, uint64_t *levkey) {
     mktd::FxRotArgs f = fx_rot_args(c, lwe, stride, pre);
-    f.init_mode = 1; f.acc_io = c->ws_fxacc; f.ngates = gates;
+    f.init_mode = 1; f.acc_io = c->ws.fxacc.p; f.ngates = gates;
     const size_t nrot = gates * (size_t)c->ks->rtot;
     HIPCHK(c, mktd::launch_fx_blindrotate(c->logM, c->p.W, f, nrot, c->stream));
-    HIPCHK(c, mktd::launch_ntt_fwd_split(c->logN, c->ks->d_ntt, c->ws_fxacc, levkey, nrot * 2, c->stream));
+    HIPCHK(c, mktd::launch_ntt_fwd_split(c->logN, c->ks->d_ntt, c->ws.fxacc.p, levkey, nrot * 2, c->stream));
     return MKT_OK;
 }
 
-// blind rotation of `B` accumulators resident at `acc` ([B][1+k][N]); atilde source described by (lwe, stride, pre)
-int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const uint32_t *lin_for_tv, void *acc, cplx *lev, cplx *scratch, size_t B) {
+// blind rotation of `B` accumulators resident at `acc` ([B][1+k][N]); atilde source described by (lwe, stride, pre); the route's kernels are handed ws.lev and ws.scratch
+int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const uint32_t *lin_for_tv, void *acc, size_t B) {
     const mkt_params &p = c->p;
+    cplx *const lev = c->ws.lev.as<cplx>(), *const scratch = c->ws.scratch.as<cplx>();
     const Route route = rot_route(c);
     if (route == Route::F64_KMS) {   // phase 1 (the rows of every party, as transforms), then phase 2
         {
@@ -451,33 +458,28 @@ int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, const uin
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
     size_t dw = 0, pw = 0;
     mktd::ks_scratch_words(a, B, &dw, &pw);
-    if (dw + pw > c->ws_ksd_words) {
-        if (c->ws_ksd) (void)hipFree(c->ws_ksd);
-        c->ws_ksd = nullptr; c->ws_ksd_words = 0;
-        HIPCHK(c, hipMalloc((void **)&c->ws_ksd, (dw + pw) * 4));
-        c->ws_ksd_words = dw + pw;
-    }
-    if (dw) { a.digits = c->ws_ksd; a.partial = c->ws_ksd + dw; }
+    HIPCHK(c, c->ws.ksd.reserve((dw + pw) * 4));
+    if (dw) { a.digits = c->ws.ksd.as<uint32_t>(); a.partial = a.digits + dw; }
     Timer tm(c, 2);
     HIPCHK(c, mktd::launch_keyswitch(p.W, a, B, c->stream));
     return MKT_OK;
 }
 
-// bootstrapping.jl:8-24 (mod-switch, test vector, blindrotate!) for a device-resident chunk of linear combinations: ws_acc <- accumulators
+// bootstrapping.jl:8-24 (mod-switch, test vector, blindrotate!) for a device-resident chunk of linear combinations: ws.acc <- accumulators
 int rotate_chunk(mkt_ctx *c, const uint32_t *lin, size_t B) {
     const mkt_params &p = c->p;
     if (!mkt::is_kms(p.scheme)) {
-        HIPCHK(c, mktd::launch_testvector(p.W, lin, c->sh.lwe_len, c->logN, c->sh.kacc, c->ws_acc, B, c->stream));
-        return do_blindrotate(c, lin, c->sh.lwe_len, 0, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B);
+        HIPCHK(c, mktd::launch_testvector(p.W, lin, c->sh.lwe_len, c->logN, c->sh.kacc, c->ws.acc.p, B, c->stream));
+        return do_blindrotate(c, lin, c->sh.lwe_len, 0, nullptr, c->ws.acc.p, B);
     }
-    return do_blindrotate(c, lin, c->sh.lwe_len, 0, lin, c->ws_acc, c->ws_lev, c->ws_scratch, B);
+    return do_blindrotate(c, lin, c->sh.lwe_len, 0, lin, c->ws.acc.p, B);
 }
 
 // bootstrapping!(lin) -> out for a device-resident chunk
 int bootstrap_chunk(mkt_ctx *c, const uint32_t *lin, uint32_t *out, size_t B) {
     int r;
     if ((r = rotate_chunk(c, lin, B))) return r;
-    return do_keyswitch(c, c->ws_acc, out, B);
+    return do_keyswitch(c, c->ws.acc.p, out, B);
 }
 
 // A caller's lookup tables on the device: luts [nluts][N] ring words, sel [B] rows or nullptr (row 0)
@@ -486,72 +488,70 @@ struct LutArgs { const void *luts; size_t nluts; const uint32_t *sel; };
 // ---- lookup-table bootstrap (mktfhe.h "programmable bootstrap", "many-table bootstrap", "key switch at a coefficient") ----
 // One chunk of any of them: the tables, the mod-switch exponent nu (0: the caller's words as they are; 1 .. 3: the grid 2^nu times coarser),
 // `per` outputs per input, and where the key switch reads.  at: output row j * per + i is accumulator j at coef[i] (coef [per] on the device;
-// nullptr = the list 0 .. per - 1, the many-table form), through the context's (row, coefficient) table ws_at.  Not at (per == 1): the plain
+// nullptr = the list 0 .. per - 1, the many-table form), through the context's (row, coefficient) table ws.at.  Not at (per == 1): the plain
 // key switch, coefficient 0 of every accumulator
 struct LutChunk { LutArgs t; int nu; size_t per; bool at; const uint32_t *coef; };
 
-// ws_at <- where every output row of a chunk's key switch reads.  Written once per call, for its largest chunk (a shorter last chunk reads
+// ws.at <- where every output row of a chunk's key switch reads.  Written once per call, for its largest chunk (a shorter last chunk reads
 // a prefix), 8 bytes per output row
 int at_table(mkt_ctx *c, const LutChunk &k, size_t rows) {
-    if (rows > c->ws_at_rows) {
-        if (c->ws_at) (void)hipFree(c->ws_at);
-        c->ws_at = nullptr; c->ws_at_rows = 0;
-        HIPCHK(c, hipMalloc((void **)&c->ws_at, rows * 8));
-        c->ws_at_rows = rows;
-    }
-    HIPCHK(c, mktd::launch_ks_at_table(k.coef, k.per, c->ws_at, c->ws_at + c->ws_at_rows, rows, c->stream));
+    HIPCHK(c, c->ws.at.reserve(rows * 8));
+    HIPCHK(c, mktd::launch_ks_at_table(k.coef, k.per, c->ws.at_src(), c->ws.at_coef(), rows, c->stream));
     return MKT_OK;
 }
 
 // a device-resident chunk of B inputs: lin [B][len] -> out [B * per][len] (out may be lin when per == 1: the masks and b are read before the
-// key switch writes).  ws_acc <- (X^btilde T, 0 ...) for the caller's table, then blindrotate! with the accumulator it is handed (the multi-key
+// key switch writes).  ws.acc <- (X^btilde T, 0 ...) for the caller's table, then blindrotate! with the accumulator it is handed (the multi-key
 // phase 2 with lin_for_tv == nullptr, as mkt_blindrotate_batch runs it): on the caller's masks for nu = 0, else on the coarse-switched mask
-// words, which go to ws_lin (rows of lwe_len words; lin may BE ws_lin, the gather form).  The key switch reads the B rotated accumulators
-// where they lie in ws_acc
+// words, which go to ws.lin (rows of lwe_len words; lin may BE ws.lin, the gather form).  The key switch reads the B rotated accumulators
+// where they lie in ws.acc
 int lut_chunk(mkt_ctx *c, const LutChunk &k, const uint32_t *lin, uint32_t *out, size_t B) {
     const int len = c->sh.lwe_len;
+    uint32_t *const ws_lin = c->ws.lin.as<uint32_t>();
+    void *const acc = c->ws.acc.p;
     int r;
-    if (!k.nu) HIPCHK(c, mktd::launch_lut_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, c->ws_acc, B, c->stream));
-    else HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, k.nu, c->ws_lin, len, c->ws_acc, B, c->stream));
-    if ((r = do_blindrotate(c, k.nu ? c->ws_lin : lin, len, k.nu ? 1 : 0, nullptr, c->ws_acc, c->ws_lev, c->ws_scratch, B))) return r;
-    if (!k.at) return do_keyswitch(c, c->ws_acc, out, B);
-    return do_keyswitch(c, c->ws_acc, out, B * k.per, c->ws_at, c->ws_at + c->ws_at_rows, B);
+    if (!k.nu) HIPCHK(c, mktd::launch_lut_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, acc, B, c->stream));
+    else HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, k.t.luts, k.t.nluts, k.t.sel, lin, len, c->logN, c->sh.kacc, k.nu, ws_lin, len, acc, B, c->stream));
+    if ((r = do_blindrotate(c, k.nu ? ws_lin : lin, len, k.nu ? 1 : 0, nullptr, acc, B))) return r;
+    if (!k.at) return do_keyswitch(c, acc, out, B);
+    return do_keyswitch(c, acc, out, B * k.per, c->ws.at_src(), c->ws.at_coef(), B);
 }
 
 // staging helper for MKT_MEM_HOST callers
 struct Staged {
-    mkt_ctx *c; void *dev = nullptr; void *host_out = nullptr; size_t bytes = 0; bool owned = false;
+    mkt_ctx *c; void *dev = nullptr; size_t bytes = 0; DevBuf own;   // dev: the caller's device array, or own.p -- a host array's copy for this call
+    template <class T> T *as() const { return static_cast<T *>(dev); }
     int in(const void *ptr, size_t nbytes, int mem, bool copy_in) {
         bytes = nbytes;
         if (mem == MKT_MEM_DEVICE) { dev = const_cast<void *>(ptr); return MKT_OK; }
-        hipError_t e = hipMalloc(&dev, nbytes ? nbytes : 1);
+        hipError_t e = own.alloc(nbytes);
         if (e != hipSuccess) return hipfail(c, e, "hipMalloc(staging)");
-        owned = true;
+        dev = own.p;
         if (copy_in && nbytes) { e = hipMemcpyAsync(dev, ptr, nbytes, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) return hipfail(c, e, "H2D"); }
         return MKT_OK;
     }
     int out(void *ptr) {
-        if (!owned || !bytes) return MKT_OK;
+        if (!own.p || !bytes) return MKT_OK;
         hipError_t e = hipMemcpyAsync(ptr, dev, bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hipfail(c, e, "D2H");
         return MKT_OK;
     }
-    ~Staged() { if (owned && dev) { (void)hipStreamSynchronize(c->stream); (void)hipFree(dev); } }
+    ~Staged() { if (own.p) (void)hipStreamSynchronize(c->stream); }   // drained, then `own` frees
 };
 
 // A secret on the device for the length of one scope (the TRUST note in mktfhe.h): uploaded on the context's stream; zeroed on that stream and
 // the stream drained before the buffer is freed, by whatever path the scope is left.  Declared AFTER a call's Staged objects: its wipe is drained before they free
 struct DeviceSecret {
-    mkt_ctx *c; void *dev = nullptr; size_t bytes = 0;
-    DeviceSecret(const DeviceSecret &) = delete;
-    hipError_t alloc(size_t nbytes) { bytes = nbytes; const hipError_t e = hipMalloc(&dev, nbytes ? nbytes : 1); if (e != hipSuccess) dev = nullptr; return e; }
-    hipError_t in(const void *host, size_t nbytes) { const hipError_t e = alloc(nbytes); return e != hipSuccess ? e : hipMemcpyAsync(dev, host, nbytes, hipMemcpyHostToDevice, c->stream); }
+    mkt_ctx *c; DevBuf buf; size_t bytes = 0;
+    template <class T> T *as() const { return buf.as<T>(); }
+    hipError_t alloc(size_t nbytes) { bytes = nbytes; return buf.alloc(nbytes); }
+    hipError_t in(const void *host, size_t nbytes) { const hipError_t e = alloc(nbytes); return e != hipSuccess ? e : hipMemcpyAsync(buf.p, host, nbytes, hipMemcpyHostToDevice, c->stream); }
     hipError_t wipe_now() {   // behind everything enqueued so far; the result of draining the stream
-        if (!dev) return hipSuccess;
-        (void)hipMemsetAsync(dev, 0, bytes, c->stream);
+        if (!buf.p) return hipSuccess;
+        (void)hipMemsetAsync(buf.p, 0, bytes, c->stream);
         const hipError_t e = hipStreamSynchronize(c->stream);
-        (void)hipFree(dev); dev = nullptr;
+        buf.release();
         return e;
     }
     ~DeviceSecret() { (void)wipe_now(); }
@@ -561,6 +561,34 @@ template <class Args> hipError_t wipe_secrets(hipError_t e, DeviceSecret &secret
     const hipError_t es = secret.wipe_now();
     explicit_bzero(&a, sizeof a);
     return e != hipSuccess ? e : es;   // the call's status so far, else that of the drain
+}
+// The start of both device keygens (keygen.hip, keygen_seeded.hip), on the context's stream: the party's LWE key and ring keys uploaded as secrets, the call's
+// output buffers allocated (outs: owner, bytes), the integer CRS uploaded for CCS; and the fields KeygenArgs and KeygenSeededArgs share
+struct KeygenOut { DevBuf *buf; size_t bytes; };
+template <class Args> hipError_t keygen_setup(mkt_ctx *c, const mkt_client_party *K, const void *crs, DeviceSecret &lwe, DeviceSecret &z, std::initializer_list<KeygenOut> outs, DevBuf &crs_int, Args &a) {
+    const mkt_params &p = c->p;
+    const bool unienc = p.scheme == MKT_CCS;
+    const int N = p.N, nz = (int)K->zring.size();
+    const size_t crs_bytes = (size_t)p.l_uni * poly_bytes(c);
+    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
+    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
+    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    for (const KeygenOut &o : outs) if (e == hipSuccess) e = o.buf->alloc(o.bytes);
+    if (e == hipSuccess && unienc) e = crs_int.alloc(crs_bytes);
+    if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, crs_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return e;   // (the stream key is copied only into a struct that the call goes on to wipe: wipe_secrets)
+    std::memcpy(a.key, K->key, sizeof a.key); a.party = K->party; a.N = N; a.n = p.n; a.W = p.W; a.f = p.f; a.logD = p.logD;
+    a.sigma_ring = K->sigma_ring; a.sigma_lwe = K->sigma_lwe;
+    a.lwekey = lwe.as<const uint32_t>(); a.zring = z.as<const int8_t>(); a.crs = crs_int.p;
+    if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; }
+    else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; }
+    return e;
+}
+// every ring key the keygen kernels index is there: kr of them from 0 for the bootstrapping key (one under CCS), ksk_kr of them from the key switch's
+// first (the uni key of the KMS schemes: 1) -- the same in keygen.hip and keygen_seeded.hip
+bool ring_keys_cover(const mkt_ctx *c, const mkt_client_party *K) {
+    const int nz = (int)K->zring.size();
+    return nz >= (c->p.scheme == MKT_CCS ? 1 : c->sh.kr) && nz >= (mkt::is_kms(c->p.scheme) ? 1 : 0) + c->sh.ksk_kr;
 }
 bool mem_ok(int mem) { return mem == MKT_MEM_DEVICE || mem == MKT_MEM_HOST; }
 
@@ -757,7 +785,7 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
         return fail(nullptr, MKT_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", the engine is built for gfx950 only");
 
     auto *c = new mkt_ctx();
-    c->ks = std::make_shared<KeySet>();
+    c->ks = new_key_set();
     c->ks->device = device;
     c->p = *params; c->sh = mkt::shape_of(*params); c->device = device;
     c->logN = logN; c->logM = logN - 1; c->M = params->N / 2;
@@ -809,8 +837,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);   // before the workspace goes: work queued on the fork's own stream may still use it
     clear_spans(c);
-    void *ptrs[] = {c->ws_lin, c->ws_acc, c->ws_lev, c->ws_scratch, c->ws_ksd, c->ws_at, c->ws_fxacc, c->d_pm_stat, c->ws_pack_cols, c->ws_pack_slabs, c->ws_pack_dig, c->ws_pack_prod};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    c->ws = Workspace();           // every owner lets go here: before the fork's stream and the key set
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                      // drops this context's reference to the key set; the last one frees it
     return MKT_OK;
@@ -900,7 +927,7 @@ int mkt_set_option(mkt_ctx *c, const char *name, int value) {
             for (int v : w.allowed) list += (list.empty() ? "" : ", ") + std::to_string(v);
             return fail(c, MKT_ERR_ARG, "mkt_set_option: " + k + " = " + std::to_string(value) + " is not one of " + list);
         }
-        if (w.resets_workspace && c->tune.*w.member != value) c->ws_gates = 0;
+        if (w.resets_workspace && c->tune.*w.member != value) c->ws.gates = 0;   // the next call allocates the rotation group anew (mkt::reserve_group), for the new route alone
         c->tune.*w.member = value;
         return MKT_OK;
     }
@@ -947,7 +974,7 @@ int mkt_set_twiddles(mkt_ctx *c, const double *psi, const double *psiinv, const 
     if (int w = keys_writable(c)) return w;
     // tables first, then keys: a loaded bootstrapping key, relinearisation key, public key or CRS is resident as its transform under the tables
     // it met (or as the caller's Trans* values), and its integer form is not kept -- new tables would leave keys and transforms disagreeing
-    if (c->ks->loaded.any_transformed() || c->ks->d_pack) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
+    if (c->ks->loaded.any_transformed() || c->ks->d_pack.p) return fail(c, MKT_ERR_STATE, "mkt_set_twiddles: install the tables before the keys (the loaded keys stay as they were transformed under the tables in place)");
     DevGuard dg(c->device);
     const size_t nd = (size_t)2 * c->M;
     // the kernels derive the inverse twiddles from the forward table: Psiinv must be conj(Psi) entry for entry,
@@ -1032,24 +1059,15 @@ static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, 
     const bool unienc = p.scheme == MKT_CCS;
     if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: CCS needs the integer CRS");
     DevGuard dg(c->device);
-    const int N = p.N, nz = (int)K->zring.size();
     const size_t brk_bytes = mkt::brk_polys_total(p, c->sh) * poly_bytes(c);
     DevBuf out, crs_int;                      // freed behind the secrets' drain of the stream
     DeviceSecret lwe{c}, z{c};
-    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
-    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
-    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync((int8_t *)z.dev + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&out.p, brk_bytes);
-    if (e == hipSuccess && unienc) e = hipMalloc(&crs_int.p, (size_t)p.l_uni * poly_bytes(c));
-    if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hipfail(c, e, "device keygen setup");
     mktd::KeygenArgs a{};
-    std::memcpy(a.key, K->key, sizeof a.key); a.party = K->party; a.N = N; a.n = p.n; a.W = p.W; a.f = p.f; a.logD = p.logD;
-    a.sigma_ring = K->sigma_ring; a.sigma_lwe = K->sigma_lwe;
-    a.lwekey = (const uint32_t *)lwe.dev; a.zring = (const int8_t *)z.dev; a.crs = crs_int.p; a.out = out.p;
-    if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; a.zoff = 0; }
-    else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; a.zoff = 0; }
-    e = mktd::launch_keygen_brk(a, unienc ? 1 : 0, c->stream);
+    hipError_t e = keygen_setup(c, K, crs, lwe, z, {{&out, brk_bytes}}, crs_int, a);
+    if (e != hipSuccess) return hipfail(c, e, "device keygen setup");
+    a.out = out.p; a.zoff = 0;
+    if (!ring_keys_cover(c, K)) e = hipErrorInvalidValue;
+    if (e == hipSuccess) e = mktd::launch_keygen_brk(a, unienc ? 1 : 0, c->stream);
     if (e == hipSuccess && brk_out) e = hipMemcpyAsync(brk_out, out.p, brk_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = install_brk(c, party, out.p);
     if (e == hipSuccess) e = ksk_zero(c, party);
@@ -1093,7 +1111,7 @@ int mkt_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, 
     if (mkt::seed_to_key(seed, a.key)) return fail(c, MKT_ERR_STATE, "mkt_partial_decrypt_batch: no entropy from the OS");
     hipError_t e = key.in(K->lwekey.data(), (size_t)p.n * 4);
     a.party = party; a.n = p.n; a.lwe_stride = c->sh.lwe_len; a.sigma = sigma_smudge; a.row0 = row0;
-    a.lwe = (const uint32_t *)sx.dev; a.lwekey = (const uint32_t *)key.dev; a.out = (uint32_t *)so.dev; a.B = B;
+    a.lwe = sx.as<const uint32_t>(); a.lwekey = key.as<const uint32_t>(); a.out = so.as<uint32_t>(); a.B = B;
     if (e == hipSuccess) e = mktd::launch_partial_decrypt(a, c->stream);
     e = wipe_secrets(e, key, a);
     if (e != hipSuccess) return hipfail(c, e, "device partial decryption");
@@ -1113,7 +1131,7 @@ int mkt_seeded_expand_batch(mkt_ctx *c, int party, const uint8_t *mask_seed, uin
     mktd::SeededArgs a{};
     mkt::seed_to_key(mask_seed, a.mkey);
     a.party = party; a.n = c->p.n; a.lwe_len = c->sh.lwe_len; a.row0 = row0;
-    a.in = (const uint32_t *)sb.dev; a.out = (uint32_t *)so.dev; a.B = B;
+    a.in = sb.as<const uint32_t>(); a.out = so.as<uint32_t>(); a.B = B;
     HIPCHK(c, mktd::launch_seeded_expand(a, c->stream));
     return so.out(out);
 }
@@ -1139,7 +1157,7 @@ int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, c
     if (mkt::seed_to_key(noise_seed, a.nkey)) return fail(c, MKT_ERR_STATE, "mkt_seeded_encrypt_batch: no entropy from the OS");
     hipError_t e = key.in(K->lwekey.data(), (size_t)p.n * 4);
     a.party = party; a.n = p.n; a.lwe_len = c->sh.lwe_len; a.sigma = sigma_lwe; a.row0 = row0;
-    a.in = (const uint32_t *)sx.dev; a.lwekey = (const uint32_t *)key.dev; a.out = (uint32_t *)so.dev; a.B = B;
+    a.in = sx.as<const uint32_t>(); a.lwekey = key.as<const uint32_t>(); a.out = so.as<uint32_t>(); a.B = B;
     if (e == hipSuccess) e = mktd::launch_seeded_encrypt(a, c->stream);
     e = wipe_secrets(e, key, a);
     if (e != hipSuccess) return hipfail(c, e, "device seeded encryption");
@@ -1166,7 +1184,7 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
     if (brk_seeded) {
         if ((r = sb.in(brk_seeded, body_polys * poly_bytes(c), mem, true))) return r;
         void *dst;
-        if (load) { HIPCHK(c, hipMalloc(&full.p, brk_polys_total * poly_bytes(c))); dst = full.p; }
+        if (load) { HIPCHK(c, full.alloc(brk_polys_total * poly_bytes(c))); dst = full.p; }
         else { if ((r = so.in(brk_out, brk_polys_total * poly_bytes(c), mem, false))) return r; dst = so.dev; }
         mktd::SeededBrkArgs a{};
         mkt::seed_to_key(mask_seed, a.mkey);
@@ -1179,11 +1197,11 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
     if (ksk_seeded) {
         if ((r = sk.in(ksk_seeded, rows * 4, mem, true))) return r;
         uint32_t *dst = c->ks->party<uint32_t>(T_KSK, party);
-        if (!load) { HIPCHK(c, hipMalloc(&padded.p, c->ks->ksk.resident_words() * 4)); dst = (uint32_t *)padded.p; }
+        if (!load) { HIPCHK(c, padded.alloc(c->ks->ksk.resident_words() * 4)); dst = padded.as<uint32_t>(); }
         mktd::SeededKskArgs a{};
         mkt::seed_to_key(mask_seed, a.mkey);
         a.party = party; a.n = p.n; a.n1p = c->ks->ksk.n1p; a.rows_per_cj = (uint32_t)(c->sh.ksk_drows * p.f);
-        a.absent_below = mkt::is_block(p.scheme) ? p.n : 0; a.body = (const uint32_t *)sk.dev; a.out = dst; a.rows = rows;
+        a.absent_below = mkt::is_block(p.scheme) ? p.n : 0; a.body = sk.as<const uint32_t>(); a.out = dst; a.rows = rows;
         e = mktd::launch_seeded_ksk_expand(a, c->stream);
         if (e == hipSuccess && !load) e = ksk_to_rows(c, dst, ksk_out, mem == MKT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
         if (e != hipSuccess) return hipfail(c, e, "seeded key-switching key expansion");
@@ -1219,29 +1237,17 @@ int mkt_keygen_device_seeded(mkt_ctx *c, int party, const mkt_client_party *K, c
     if (std::memcmp(mask_seed, K->key, sizeof K->key) == 0) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the mask seed is the party's secret seed (it is published: the secrets would be too)");
     if (install) if (int r = key_write_guard(c, true, party, Gate::EXACT)) return r;
     DevGuard dg(c->device);
-    const int N = p.N, nz = (int)K->zring.size();
     const size_t brk_bytes = mkt::brk_seeded_polys(p, c->sh) * poly_bytes(c), rows = c->ks->ksk.rows;
     DevBuf bodies, words, crs_int;            // freed behind the secrets' drain of the stream
     DeviceSecret lwe{c}, z{c};
-    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
-    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
-    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync((int8_t *)z.dev + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&bodies.p, brk_bytes);
-    if (e == hipSuccess) e = hipMalloc(&words.p, rows * 4);
-    if (e == hipSuccess && unienc) e = hipMalloc(&crs_int.p, (size_t)p.l_uni * poly_bytes(c));
-    if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, (size_t)p.l_uni * poly_bytes(c), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hipfail(c, e, "device seeded keygen setup");
     mktd::KeygenSeededArgs a{};
+    hipError_t e = keygen_setup(c, K, crs, lwe, z, {{&bodies, brk_bytes}, {&words, rows * 4}}, crs_int, a);
+    if (e != hipSuccess) return hipfail(c, e, "device seeded keygen setup");
     mkt::seed_to_key(mask_seed, a.mkey);
-    std::memcpy(a.key, K->key, sizeof a.key); a.party = K->party; a.N = N; a.n = p.n; a.W = p.W;
-    a.sigma_ring = K->sigma_ring; a.sigma_lwe = K->sigma_lwe;
-    a.lwekey = (const uint32_t *)lwe.dev; a.zring = (const int8_t *)z.dev; a.crs = crs_int.p;
-    a.brk_body = bodies.p; a.ksk_body = (uint32_t *)words.p; a.ksk_rows = rows;
-    if (unienc) { a.kr = 1; a.l = p.l_uni; a.logB = p.logB_uni; }
-    else { a.kr = c->sh.kr; a.l = p.l_gsw; a.logB = p.logB_gsw; }
-    a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.absent_below = mkt::is_block(p.scheme) ? p.n : 0;
+    a.brk_body = bodies.p; a.ksk_body = words.as<uint32_t>(); a.ksk_rows = rows;
+    a.drows = c->sh.ksk_drows; a.absent_below = mkt::is_block(p.scheme) ? p.n : 0;
     a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
-    if (nz < (unienc ? 1 : a.kr) || nz < a.zoff + c->sh.ksk_kr) e = hipErrorInvalidValue;       // every ring key the kernels index is there
+    if (!ring_keys_cover(c, K)) e = hipErrorInvalidValue;
     if (e == hipSuccess) e = mktd::launch_keygen_seeded_brk(a, unienc ? 1 : 0, c->stream);
     if (e == hipSuccess) e = mktd::launch_keygen_seeded_ksk(a, c->stream);
     if (e == hipSuccess && brk_seeded_out) e = hipMemcpyAsync(brk_seeded_out, bodies.p, brk_bytes, hipMemcpyDeviceToHost, c->stream);
@@ -1249,7 +1255,7 @@ int mkt_keygen_device_seeded(mkt_ctx *c, int party, const mkt_client_party *K, c
     e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);       // (drains the stream: the outputs have landed)
     if (e != hipSuccess) return hipfail(c, e, "device seeded keygen");
     if (!install) return MKT_OK;
-    return seeded_keys_impl(c, party, mask_seed, bodies.p, (const uint32_t *)words.p, true, nullptr, nullptr, MKT_MEM_DEVICE);
+    return seeded_keys_impl(c, party, mask_seed, bodies.p, words.as<const uint32_t>(), true, nullptr, nullptr, MKT_MEM_DEVICE);
 }
 
 // debug / test read-back of a party's key-switching key in the host layout of mkt_load_ksk
@@ -1283,16 +1289,17 @@ static int gate_impl(mkt_ctx *c, int arity, int op, const uint8_t *ops, const ui
     for (size_t off = 0; off < B; off += CHUNK_GATES) {
         const size_t nb = std::min(CHUNK_GATES, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
-        const uint8_t *o = ops ? (const uint8_t *)sops.dev + off : nullptr;
+        uint32_t *const ws_lin = c->ws.lin.as<uint32_t>();
+        const uint8_t *o = ops ? sops.as<const uint8_t>() + off : nullptr;
         const uint32_t *d[3] = {}, *di[3] = {};
         for (int i = 0; i < arity; i++) {
-            d[i] = pool ? (const uint32_t *)sv[0].dev : (const uint32_t *)sv[i].dev + off * len;
-            di[i] = pool ? (const uint32_t *)si[i].dev + off : nullptr;
+            d[i] = pool ? sv[0].as<const uint32_t>() : sv[i].as<const uint32_t>() + off * len;
+            di[i] = pool ? si[i].as<const uint32_t>() + off : nullptr;
         }
         const size_t prows = pool ? rows : 0;
-        HIPCHK(c, arity == 2 ? mktd::launch_gate_linear(op, o, d[0], d[1], di[0], di[1], prows, c->ws_lin, (int)len, nb, c->stream)
-                             : mktd::launch_gate3_linear(o, d[0], d[1], d[2], di[0], di[1], di[2], prows, c->ws_lin, (int)len, nb, c->stream));
-        if ((r = bootstrap_chunk(c, c->ws_lin, (uint32_t *)so.dev + off * len, nb))) return r;
+        HIPCHK(c, arity == 2 ? mktd::launch_gate_linear(op, o, d[0], d[1], di[0], di[1], prows, ws_lin, (int)len, nb, c->stream)
+                             : mktd::launch_gate3_linear(o, d[0], d[1], d[2], di[0], di[1], di[2], prows, ws_lin, (int)len, nb, c->stream));
+        if ((r = bootstrap_chunk(c, ws_lin, so.as<uint32_t>() + off * len, nb))) return r;
     }
     return so.out(out);
 }
@@ -1383,17 +1390,18 @@ static int mux_impl(mkt_ctx *c, const uint32_t *const *v, size_t rows, const uin
     for (size_t off = 0; off < B; off += HALF) {
         const size_t nb = std::min(HALF, B - off);
         if ((r = ensure_workspace(c, 2 * nb))) return r;
+        uint32_t *const ws_lin = c->ws.lin.as<uint32_t>();
         if (pool) {
-            HIPCHK(c, mktd::launch_mux_linear((const uint32_t *)sv[0].dev, rows, (const uint32_t *)si[0].dev + off, (const uint32_t *)si[1].dev + off, (const uint32_t *)si[2].dev + off,
-                                              not_ab ? (const uint8_t *)sf.dev + off : nullptr, c->ws_lin, (int)len, nb, c->stream));
+            HIPCHK(c, mktd::launch_mux_linear(sv[0].as<const uint32_t>(), rows, si[0].as<const uint32_t>() + off, si[1].as<const uint32_t>() + off, si[2].as<const uint32_t>() + off,
+                                              not_ab ? sf.as<const uint8_t>() + off : nullptr, ws_lin, (int)len, nb, c->stream));
         } else {
-            const uint32_t *ps = (const uint32_t *)sv[0].dev + off * len;
-            HIPCHK(c, mktd::launch_gate_linear(MKT_AND, nullptr, ps, (const uint32_t *)sv[1].dev + off * len, nullptr, nullptr, 0, c->ws_lin, (int)len, nb, c->stream));
-            HIPCHK(c, mktd::launch_gate_linear(MKT_AND | MKT_OP_NOT_X, nullptr, ps, (const uint32_t *)sv[2].dev + off * len, nullptr, nullptr, 0, c->ws_lin + nb * len, (int)len, nb, c->stream));
+            const uint32_t *ps = sv[0].as<const uint32_t>() + off * len;
+            HIPCHK(c, mktd::launch_gate_linear(MKT_AND, nullptr, ps, sv[1].as<const uint32_t>() + off * len, nullptr, nullptr, 0, ws_lin, (int)len, nb, c->stream));
+            HIPCHK(c, mktd::launch_gate_linear(MKT_AND | MKT_OP_NOT_X, nullptr, ps, sv[2].as<const uint32_t>() + off * len, nullptr, nullptr, 0, ws_lin + nb * len, (int)len, nb, c->stream));
         }
-        if ((r = rotate_chunk(c, c->ws_lin, 2 * nb))) return r;
-        HIPCHK(c, mktd::launch_mux_combine(c->p.W, c->ws_acc, nb, words, c->stream));
-        if ((r = do_keyswitch(c, c->ws_acc, (uint32_t *)so.dev + off * len, nb))) return r;
+        if ((r = rotate_chunk(c, ws_lin, 2 * nb))) return r;
+        HIPCHK(c, mktd::launch_mux_combine(c->p.W, c->ws.acc.p, nb, words, c->stream));
+        if ((r = do_keyswitch(c, c->ws.acc.p, so.as<uint32_t>() + off * len, nb))) return r;
     }
     return so.out(out);
 }
@@ -1425,7 +1433,7 @@ int mkt_not_batch(mkt_ctx *c, uint32_t *x, size_t B, int mem) {
     int r;
     const size_t words = B * (size_t)c->sh.lwe_len;
     if ((r = sx.in(x, words * 4, mem, true))) return r;
-    HIPCHK(c, mktd::launch_negate((uint32_t *)sx.dev, words, c->stream));
+    HIPCHK(c, mktd::launch_negate(sx.as<uint32_t>(), words, c->stream));
     return sx.out(x);
 }
 
@@ -1442,7 +1450,7 @@ int mkt_bootstrap_batch(mkt_ctx *c, uint32_t *lwe, size_t B, int mem) {
     for (size_t off = 0; off < B; off += CHUNK_GATES) {
         const size_t nb = std::min(CHUNK_GATES, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
-        uint32_t *chunk = (uint32_t *)sx.dev + off * len;
+        uint32_t *chunk = sx.as<uint32_t>() + off * len;
         // the rotation reads the masks, phase 2 / the test vector read b, all before key switching overwrites them
         if ((r = bootstrap_chunk(c, chunk, chunk, nb))) return r;
     }
@@ -1462,7 +1470,7 @@ struct StagedLuts {
         if ((r = luts.in(l, nluts * poly_bytes(c), mem, true))) return r;
         return s ? sel.in(s, B * 4, mem, true) : MKT_OK;
     }
-    LutArgs chunk(size_t nluts, size_t off) const { return LutArgs{luts.dev, nluts, sel.dev ? (const uint32_t *)sel.dev + off : nullptr}; }
+    LutArgs chunk(size_t nluts, size_t off) const { return LutArgs{luts.dev, nluts, sel.dev ? sel.as<const uint32_t>() + off : nullptr}; }
 };
 
 // unit level: acc[j] = (X^btilde(lwe[j]) * luts[sel[j]], 0 ...), what the programmable bootstrap hands to blindrotate!; no keys needed
@@ -1475,7 +1483,7 @@ int mkt_lut_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, const u
     int r;
     if ((r = t.in(c, "mkt_lut_testvector_batch", luts, nluts, sel, B, mem)) || (r = sx.in(lwe, B * len * 4, mem, true)) || (r = sc.in(acc, B * accb, mem, false))) return r;
     const LutArgs a = t.chunk(nluts, 0);
-    HIPCHK(c, mktd::launch_lut_testvector(c->p.W, a.luts, a.nluts, a.sel, (const uint32_t *)sx.dev, (int)len, c->logN, c->sh.kacc, sc.dev, B, c->stream));
+    HIPCHK(c, mktd::launch_lut_testvector(c->p.W, a.luts, a.nluts, a.sel, sx.as<const uint32_t>(), (int)len, c->logN, c->sh.kacc, sc.dev, B, c->stream));
     return sc.out(acc);
 }
 
@@ -1506,21 +1514,21 @@ static int lut_impl(mkt_ctx *c, const char *who, LutChunk k, const uint32_t *lwe
     Staged sv{c}, so{c}, si{c}, sw{c}, sk{c}, sf{c};
     if (k.coef && !B) return MKT_OK;
     if (k.coef && (r = sf.in(k.coef, k.per * 4, mem, true))) return r;
-    k.coef = (const uint32_t *)sf.dev;
+    k.coef = sf.as<const uint32_t>();
     if (k.at && (r = at_table(c, k, std::min(step, B) * k.per))) return r;
     if ((r = t.in(c, who, k.t.luts, nluts, k.t.sel, B, mem)) || (r = sv.in(g ? g->pool : lwe, rows * len * 4, mem, true)) || (r = so.in(out, B * k.per * len * 4, mem, false))) return r;
     if (g && ((r = si.in(g->idx, B * 16, mem, true)) || (r = sw.in(g->wt, B * 4, mem, true)) || (r = sk.in(g->cst, B * 4, mem, true)))) return r;
     for (size_t off = 0; off < B; off += step) {
         const size_t nb = std::min(step, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
-        const uint32_t *lin = (const uint32_t *)sv.dev + off * len;
+        const uint32_t *lin = sv.as<const uint32_t>() + off * len;
         if (g) {
-            HIPCHK(c, mktd::launch_lut_linear((const uint32_t *)sv.dev, rows, (const uint32_t *)si.dev + off * 4, (const int8_t *)sw.dev + off * 4, (const uint32_t *)sk.dev + off,
-                                              c->ws_lin, (int)len, nb, c->stream));
-            lin = c->ws_lin;
+            HIPCHK(c, mktd::launch_lut_linear(sv.as<const uint32_t>(), rows, si.as<const uint32_t>() + off * 4, sw.as<const int8_t>() + off * 4, sk.as<const uint32_t>() + off,
+                                              c->ws.lin.as<uint32_t>(), (int)len, nb, c->stream));
+            lin = c->ws.lin.as<uint32_t>();
         }
         k.t = t.chunk(nluts, off);
-        if ((r = lut_chunk(c, k, lin, (uint32_t *)so.dev + off * k.per * len, nb))) return r;
+        if ((r = lut_chunk(c, k, lin, so.as<uint32_t>() + off * k.per * len, nb))) return r;
     }
     return so.out(out);
 }
@@ -1562,7 +1570,7 @@ int mkt_lut_many_testvector_batch(mkt_ctx *c, const void *luts, size_t nluts, co
     if ((r = t.in(c, "mkt_lut_many_testvector_batch", luts, nluts, sel, B, mem)) || (r = sx.in(lwe, B * len * 4, mem, true)) || (r = sa.in(atilde, B * (len - 1) * 4, mem, false)) ||
         (r = sc.in(acc, B * accb, mem, false))) return r;
     const LutArgs a = t.chunk(nluts, 0);
-    HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, a.luts, a.nluts, a.sel, (const uint32_t *)sx.dev, (int)len, c->logN, c->sh.kacc, nu, (uint32_t *)sa.dev, (int)len - 1, sc.dev, B, c->stream));
+    HIPCHK(c, mktd::launch_lut_many_testvector(c->p.W, a.luts, a.nluts, a.sel, sx.as<const uint32_t>(), (int)len, c->logN, c->sh.kacc, nu, sa.as<uint32_t>(), (int)len - 1, sc.dev, B, c->stream));
     if ((r = sa.out(atilde))) return r;
     return sc.out(acc);
 }
@@ -1641,7 +1649,7 @@ int mkt_modswitch_batch(mkt_ctx *c, const uint32_t *lwe, uint32_t *atilde, uint3
     Staged sl{c}, sa{c}, sb{c};
     int r;
     if ((r = sl.in(lwe, B * len * 4, mem, true)) || (r = sa.in(atilde, B * (len - 1) * 4, mem, false)) || (r = sb.in(btilde, B * 4, mem, false))) return r;
-    HIPCHK(c, mktd::launch_modswitch((const uint32_t *)sl.dev, (uint32_t *)sa.dev, (uint32_t *)sb.dev, (int)len, c->logN, B, c->stream));
+    HIPCHK(c, mktd::launch_modswitch(sl.as<const uint32_t>(), sa.as<uint32_t>(), sb.as<uint32_t>(), (int)len, c->logN, B, c->stream));
     if ((r = sa.out(atilde))) return r;
     return sb.out(btilde);
 }
@@ -1659,7 +1667,7 @@ int mkt_blindrotate_batch(mkt_ctx *c, const uint32_t *atilde, void *acc, size_t 
     for (size_t off = 0; off < B; off += CHUNK_GATES) {
         const size_t nb = std::min(CHUNK_GATES, B - off);
         if ((r = ensure_workspace(c, nb))) return r;
-        if ((r = do_blindrotate(c, (const uint32_t *)sa.dev + off * alen, (int)alen, 1, nullptr, (char *)sc.dev + off * accb, c->ws_lev, c->ws_scratch, nb))) return r;
+        if ((r = do_blindrotate(c, sa.as<const uint32_t>() + off * alen, (int)alen, 1, nullptr, sc.as<char>() + off * accb, nb))) return r;
     }
     return sc.out(acc);
 }
@@ -1679,18 +1687,18 @@ int mkt_kms_phase1_batch(mkt_ctx *c, const uint32_t *atilde, double *levkey, siz
             for (size_t off = 0; off < B; off += CHUNK_GATES) {
                 const size_t nb = B - off < CHUNK_GATES ? B - off : CHUNK_GATES;
                 Timer tm(c, 1);
-                if ((r = fx_phase1(c, (const uint32_t *)sa.dev + off * alen, (int)alen, 1, nb, (uint64_t *)sl.dev + off * (lb / 8)))) return r;
+                if ((r = fx_phase1(c, sa.as<const uint32_t>() + off * alen, (int)alen, 1, nb, sl.as<uint64_t>() + off * (lb / 8)))) return r;
             }
         } else {
-            mktd::ExactKmsArgs q = exact_kms_args(c, (const uint32_t *)sa.dev, (int)alen, 1);
-            q.levkey = (uint64_t *)sl.dev; q.phase1_only = 1;
+            mktd::ExactKmsArgs q = exact_kms_args(c, sa.as<const uint32_t>(), (int)alen, 1);
+            q.levkey = sl.as<uint64_t>(); q.phase1_only = 1;
             Timer tm(c, 1);
             HIPCHK(c, mktd::launch_exact_kms(c->logN, c->ks->d_ntt, q, B, c->stream));
         }
         return sl.out(levkey);
     }
-    mktd::RotArgs a = rot_args(c, (const uint32_t *)sa.dev, (int)alen, 1);
-    a.init_mode = 1; a.out_mode = 1; a.tout = (cplx *)sl.dev; a.tout_natural = 1; a.ngates = B;
+    mktd::RotArgs a = rot_args(c, sa.as<const uint32_t>(), (int)alen, 1);
+    a.init_mode = 1; a.out_mode = 1; a.tout = sl.as<cplx>(); a.tout_natural = 1; a.ngates = B;
     { Timer tm(c, 1); HIPCHK(c, mktd::launch_blindrotate_k1(c->logM, c->p.W, a, B * (size_t)c->ks->rtot, c->stream)); }
     return sl.out(levkey);
 }
@@ -1704,7 +1712,7 @@ int mkt_keyswitch_batch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, in
     const size_t accb = (size_t)(1 + c->sh.kacc) * poly_bytes(c), len = (size_t)c->sh.lwe_len;
     Staged sc{c}, so{c};
     if ((r = sc.in(acc, B * accb, mem, true)) || (r = so.in(out, B * len * 4, mem, false))) return r;
-    if ((r = do_keyswitch(c, sc.dev, (uint32_t *)so.dev, B))) return r;
+    if ((r = do_keyswitch(c, sc.dev, so.as<uint32_t>(), B))) return r;
     return so.out(out);
 }
 
@@ -1730,8 +1738,8 @@ int mkt_keyswitch_at_batch(mkt_ctx *c, const void *acc, size_t nacc, const uint3
     if (coef && (r = sf.in(coef, B * 4, mem, true))) return r;
     for (size_t off = 0; off < B; off += CHUNK_GATES) {
         const size_t nb = std::min(CHUNK_GATES, B - off);
-        const void *a0 = src ? sc.dev : (const void *)((const char *)sc.dev + off * accb);
-        if ((r = do_keyswitch(c, a0, (uint32_t *)so.dev + off * len, nb, src ? (const uint32_t *)ss.dev + off : nullptr, coef ? (const uint32_t *)sf.dev + off : nullptr, src ? nacc : nb))) return r;
+        const void *a0 = src ? sc.dev : sc.as<const char>() + off * accb;
+        if ((r = do_keyswitch(c, a0, so.as<uint32_t>() + off * len, nb, src ? ss.as<const uint32_t>() + off : nullptr, coef ? sf.as<const uint32_t>() + off : nullptr, src ? nacc : nb))) return r;
     }
     return so.out(out);
 }
@@ -1742,8 +1750,8 @@ int mkt_transform_fwd_batch(mkt_ctx *c, const void *p, double *t, size_t B, int 
     Staged sp{c}, st{c};
     int r;
     if ((r = sp.in(p, B * poly_bytes(c), mem, true)) || (r = st.in(t, B * (size_t)c->M * sizeof(cplx), mem, false))) return r;
-    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_fwd(c->logN, c->p.W, c->ks->d_ntt, sp.dev, (uint64_t *)st.dev, B, 0, c->stream)); }
-    else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_fwd(c->logM, c->p.W, c->twp(), sp.dev, (cplx *)st.dev, B, 0, c->stream)); }
+    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_fwd(c->logN, c->p.W, c->ks->d_ntt, sp.dev, st.as<uint64_t>(), B, 0, c->stream)); }
+    else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_fwd(c->logM, c->p.W, c->twp(), sp.dev, st.as<cplx>(), B, 0, c->stream)); }
     return st.out(t);
 }
 
@@ -1753,8 +1761,8 @@ int mkt_transform_inv_batch(mkt_ctx *c, const double *t, void *p, size_t B, int 
     Staged st{c}, sp{c};
     int r;
     if ((r = st.in(t, B * (size_t)c->M * sizeof(cplx), mem, true)) || (r = sp.in(p, B * poly_bytes(c), mem, false))) return r;
-    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_inv(c->logN, c->p.W, c->ks->d_ntt, (const uint64_t *)st.dev, sp.dev, B, c->stream)); }
-    else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_inv(c->logM, c->p.W, c->twp(), (const cplx *)st.dev, sp.dev, B, c->stream)); }
+    if (c->exact) { Timer tm(c, 3); HIPCHK(c, mktd::launch_ntt_inv(c->logN, c->p.W, c->ks->d_ntt, st.as<const uint64_t>(), sp.dev, B, c->stream)); }
+    else { Timer tm(c, 3); HIPCHK(c, mktd::launch_transform_inv(c->logM, c->p.W, c->twp(), st.as<const cplx>(), sp.dev, B, c->stream)); }
     return sp.out(p);
 }
 
@@ -1784,13 +1792,13 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
     Staged sa{c}, sb{c}, so{c};
     int r;
     if ((r = sa.in(a, B * poly_bytes(c), mem, true)) || (r = sb.in(b, B * poly_bytes(c), mem, true)) || (r = so.in(out, B * poly_bytes(c), mem, false))) return r;
-    if (!c->d_pm_stat) HIPCHK(c, hipMalloc((void **)&c->d_pm_stat, 3 * sizeof(unsigned long long)));
+    HIPCHK(c, c->ws.pm_stat.reserve(3 * sizeof(unsigned long long)));   // at the first call
     const bool fx = c->ks->d_fx_tab && c->tune.exact_impl == 1;
     unsigned long long st[2] = {0, 0};
-    HIPCHK(c, hipMemsetAsync(c->d_pm_stat, 0, 3 * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, mktd::launch_exact_amax(c->p.W, sa.dev, B * (size_t)c->p.N, c->d_pm_stat, c->stream));
-    if (fx) HIPCHK(c, mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), sb.dev, nullptr, B, c->d_pm_stat + 1, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st, c->d_pm_stat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ws.pm(), 0, 3 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, mktd::launch_exact_amax(c->p.W, sa.dev, B * (size_t)c->p.N, c->ws.pm(), c->stream));
+    if (fx) HIPCHK(c, mktd::launch_fx_key_fwd(c->logM, c->p.W, c->fx_om(), c->fx_tw(), sb.dev, nullptr, B, c->ws.pm() + 1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st, c->ws.pm(), sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->pm_amax = (double)st[0];
     if (st[0] > POLYMUL_NA_MAX / (uint64_t)c->p.N)
@@ -1800,9 +1808,9 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
         double k2; std::memcpy(&k2, &st[1], 8);
         c->pm_bound = fx_polymul_bound(c, (double)st[0], std::sqrt(k2));
         if (c->pm_bound < 0.45 || c->tune.fx_polymul_force) {   // the Float64-pipe product (fx_exact.hip)
-            { Timer tm(c, 3); HIPCHK(c, mktd::launch_fx_polymul(c->logM, c->p.W, c->fx_om(), c->fx_tw(), c->fx_nat(), sa.dev, sb.dev, so.dev, B, c->d_pm_stat + 2, c->stream)); }
+            { Timer tm(c, 3); HIPCHK(c, mktd::launch_fx_polymul(c->logM, c->p.W, c->fx_om(), c->fx_tw(), c->fx_nat(), sa.dev, sb.dev, so.dev, B, c->ws.pm() + 2, c->stream)); }
             unsigned long long bits = 0;
-            HIPCHK(c, hipMemcpyAsync(&bits, c->d_pm_stat + 2, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&bits, c->ws.pm() + 2, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::memcpy(&c->fx_last_resid, &bits, 8);
             c->last_rot_kernel = "fx_polymul_kernel";
@@ -1829,18 +1837,18 @@ int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int lo
         return fail(c, MKT_ERR_UNSUPPORTED, "mkt_load_packing_key: the rows of this gadget could reach P / 2 of the two-prime modulus");
     if (int w = keys_writable(c)) return w;
     KeySet &ks = *c->ks;
-    if (ks.d_pack && (ks.pack_l != l_pk || ks.pack_logB != logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: all parties of a context use one packing gadget");
+    if (ks.d_pack.p && (ks.pack_l != l_pk || ks.pack_logB != logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: all parties of a context use one packing gadget");
     DevGuard dg(c->device);
     const size_t rows = (size_t)p.n * l_pk, polys = rows * np, pb = poly_bytes(c);
     const size_t per = polys * (c->exact ? pb : (size_t)c->M * sizeof(cplx));
-    if (!ks.d_pack) {
-        HIPCHK(c, hipMalloc(&ks.d_pack, per * c->sh.nparty));
+    if (!ks.d_pack.p) {
+        HIPCHK(c, ks.d_pack.alloc(per * c->sh.nparty));
         ks.pack_l = l_pk; ks.pack_logB = logB_pk; ks.pack_party_bytes = per; ks.pack_loaded.assign((size_t)c->sh.nparty, 0);
     }
-    char *dst = static_cast<char *>(ks.d_pack) + (size_t)party * per;
+    char *dst = ks.d_pack.as<char>() + (size_t)party * per;
     if (!c->exact) {          // pre-transformed like the bootstrapping key, in the slot-major point order whatever the context's own
         DevBuf tmp;
-        HIPCHK(c, hipMalloc(&tmp.p, polys * pb));
+        HIPCHK(c, tmp.alloc(polys * pb));
         HIPCHK(c, hipMemcpyAsync(tmp.p, pk, polys * pb, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, mktd::launch_transform_fwd(c->logM, p.W, c->twp(), tmp.p, reinterpret_cast<cplx *>(dst), polys, 1, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1859,23 +1867,17 @@ int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int lo
 static int pack_ready(mkt_ctx *c) {
     const KeySet &ks = *c->ks;
     for (int i = 0; i < c->sh.nparty; i++)
-        if (!ks.d_pack || !ks.pack_loaded[(size_t)i]) return fail(c, MKT_ERR_STATE, "packing key not loaded");
+        if (!ks.d_pack.p || !ks.pack_loaded[(size_t)i]) return fail(c, MKT_ERR_STATE, "packing key not loaded");
     return MKT_OK;
 }
 
 static int ensure_pack_workspace(mkt_ctx *c, size_t packs, int nchunk) {
-    if (packs <= c->ws_pack_n) return MKT_OK;
-    void **ws[] = {&c->ws_pack_cols, &c->ws_pack_slabs, &c->ws_pack_dig, &c->ws_pack_prod};
-    for (void **w : ws) { if (*w) (void)hipFree(*w); *w = nullptr; }
-    c->ws_pack_n = 0;
+    Workspace &w = c->ws;
     const size_t pb = poly_bytes(c), np = (size_t)c->sh.ksk_kr + 1;
-    HIPCHK(c, hipMalloc(&c->ws_pack_cols, packs * (size_t)c->sh.lwe_len * pb));
-    if (!c->exact) HIPCHK(c, hipMalloc(&c->ws_pack_slabs, packs * (size_t)c->sh.nparty * nchunk * np * pb));
-    else {
-        HIPCHK(c, hipMalloc(&c->ws_pack_dig, (size_t)PACK_EXACT_COLS * c->ks->pack_l * pb));
-        HIPCHK(c, hipMalloc(&c->ws_pack_prod, (size_t)PACK_EXACT_COLS * c->ks->pack_l * pb));
-    }
-    c->ws_pack_n = packs;
+    const size_t slabs = c->exact ? 0 : packs * (size_t)c->sh.nparty * nchunk * np * pb, chunk = c->exact ? (size_t)PACK_EXACT_COLS * c->ks->pack_l * pb : 0;
+    DevBuf *const group[] = {&w.pack_cols, &w.pack_slabs, &w.pack_dig, &w.pack_prod};
+    const size_t need[] = {packs * (size_t)c->sh.lwe_len * pb, slabs, chunk, chunk};
+    HIPCHK(c, mkt::reserve_group(w.packs, packs, group, need));
     return MKT_OK;
 }
 
@@ -1900,14 +1902,14 @@ int mkt_pack_batch(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, const uin
     if ((r = sp.in(pool, pool_rows * len * 4, mem, true)) || (r = so.in(rlwe_out, npacks * ctb, mem, false))) return r;
     if (idx && (r = si.in(idx, B * 4, mem, true))) return r;
     mktd::PackArgs a{};
-    a.tw = c->twp(); a.pool = (const uint32_t *)sp.dev; a.pool_rows = pool_rows; a.idx = idx ? (const uint32_t *)si.dev : nullptr; a.B = B;
+    a.tw = c->twp(); a.pool = sp.as<const uint32_t>(); a.pool_rows = pool_rows; a.idx = idx ? si.as<const uint32_t>() : nullptr; a.B = B;
     a.logN = c->logN; a.n = p.n; a.nparty = c->sh.nparty; a.lwe_len = (int)len; a.kacc = c->sh.kacc; a.mk = mkt::is_mk(p.scheme) ? 1 : 0;
     a.np = c->sh.ksk_kr + 1; a.l = ks.pack_l; a.logB = ks.pack_logB; a.nchunk = (p.n + mktd::PACK_QCHUNK - 1) / mktd::PACK_QCHUNK;
-    a.key = static_cast<const cplx *>(ks.d_pack); a.key_party_stride = ks.pack_party_bytes / sizeof(cplx);
+    a.key = ks.d_pack.as<const cplx>(); a.key_party_stride = ks.pack_party_bytes / sizeof(cplx);
     for (size_t g0 = 0; g0 < npacks; g0 += PACK_CHUNK) {
         const size_t nb = std::min(PACK_CHUNK, npacks - g0);
         if ((r = ensure_pack_workspace(c, nb, a.nchunk))) return r;
-        a.pack0 = g0; a.cols = c->ws_pack_cols; a.slabs = c->ws_pack_slabs; a.out = static_cast<char *>(so.dev) + g0 * ctb;
+        a.pack0 = g0; a.cols = c->ws.pack_cols.p; a.slabs = c->ws.pack_slabs.p; a.out = so.as<char>() + g0 * ctb;
         HIPCHK(c, mktd::launch_pack_columns(p.W, a, nb, c->stream));
         if (!c->exact) {
             HIPCHK(c, mktd::launch_pack_product(c->logM, p.W, a, nb, c->stream));
@@ -1923,12 +1925,12 @@ int mkt_pack_batch(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, const uin
             HIPCHK(c, hipMemsetAsync(o + pb, 0, ctb - pb, c->stream));
             for (int i = 0; i < a.nparty; i++) for (int q0 = 0; q0 < p.n; q0 += PACK_EXACT_COLS) {
                 const size_t cnt = (size_t)std::min(PACK_EXACT_COLS, p.n - q0), prods = cnt * a.l;
-                HIPCHK(c, mktd::launch_decompose(p.W, cols + ((size_t)i * p.n + q0) * pb, c->ws_pack_dig, p.N, a.l, a.logB, cnt, c->stream));
+                HIPCHK(c, mktd::launch_decompose(p.W, cols + ((size_t)i * p.n + q0) * pb, c->ws.pack_dig.p, p.N, a.l, a.logB, cnt, c->stream));
                 for (int q = 0; q < a.np; q++) {
-                    const char *key = static_cast<const char *>(ks.d_pack) + (size_t)i * ks.pack_party_bytes + ((size_t)q * rows_all + (size_t)q0 * a.l) * pb;
-                    HIPCHK(c, mktd::launch_exact_polymul(c->logN, p.W, ks.d_ntt, c->ws_pack_dig, key, c->ws_pack_prod, prods, c->stream));
+                    const char *key = ks.d_pack.as<const char>() + (size_t)i * ks.pack_party_bytes + ((size_t)q * rows_all + (size_t)q0 * a.l) * pb;
+                    HIPCHK(c, mktd::launch_exact_polymul(c->logN, p.W, ks.d_ntt, c->ws.pack_dig.p, key, c->ws.pack_prod.p, prods, c->stream));
                     const int slot = q == 0 ? 0 : (a.mk ? 1 + i : q);
-                    HIPCHK(c, mktd::launch_pack_accumulate(p.W, o + (size_t)slot * pb, c->ws_pack_prod, prods, p.N, c->stream));
+                    HIPCHK(c, mktd::launch_pack_accumulate(p.W, o + (size_t)slot * pb, c->ws.pack_prod.p, prods, p.N, c->stream));
                 }
             }
         }

@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "device_mem.h"
 #include "host_internal.h"
 
 struct mkt_multi {
@@ -36,8 +37,8 @@ struct mkt_multi {
     bool sealed = false;               // keys replicated, logical shards forked
     std::string err;
     // staging buffers of the shards whose device is not the one a device-resident argument lives on: [shard][argument slot],
-    // grown on demand and kept (a hipMalloc / hipFree pair per call costs more than the peer copy of a ciphertext slice)
-    struct Stage { void *p = nullptr; size_t cap = 0; };
+    // grown on demand (DevBuf::reserve) and kept: an allocation and a release per call cost more than the peer copy of a ciphertext slice
+    using Stage = mkt::DevBuf;
     std::vector<std::vector<Stage>> stage;
 };
 
@@ -87,12 +88,7 @@ struct ShardArg {
         const int owner = device_of_ptr(base);
         if (owner < 0 || (owner == shard_dev && !always)) { use = rows; return 0; }
         remote = rows; remote_dev = owner; copy_back = out;
-        if (pool.cap < bytes) {
-            if (pool.p) (void)hipFree(pool.p);
-            pool.p = nullptr; pool.cap = 0;
-            if (hipMalloc(&pool.p, bytes) != hipSuccess) return -1;
-            pool.cap = bytes;
-        }
+        if (pool.reserve(bytes) != hipSuccess) return -1;
         stage = pool.p;
         if (in && across(stage, dev, remote, remote_dev, bytes, no_peer) != 0) return -1;   // the shard's own stream is non-blocking: the copy must have landed before its kernels start
         use = stage;
@@ -207,7 +203,7 @@ int mkt_multi_create(const mkt_params *params, int arith_mode, const int *device
     m->devices.assign(devices, devices + nshards);
     m->ctx.assign((size_t)nshards, nullptr);
     m->root_of.assign((size_t)nshards, -1);
-    m->stage.assign((size_t)nshards, {});
+    m->stage.resize((size_t)nshards);
     for (int s = 0; s < nshards; s++) {
         // MKT_MULTI_PRIVATE_KEYS: shards that share a device still get their own replicated key copy (the replication path on a one-GPU box)
         if (!(flags & MKT_MULTI_PRIVATE_KEYS)) for (int r = 0; r < s; r++) if (m->devices[r] == m->devices[s]) { m->root_of[s] = m->root_of[r]; break; }
@@ -223,7 +219,7 @@ int mkt_multi_create(const mkt_params *params, int arith_mode, const int *device
 int mkt_multi_destroy(mkt_multi *m) {
     if (!m) return MKT_OK;
     for (size_t s = 0; s < m->stage.size(); s++)
-        for (auto &st : m->stage[s]) if (st.p) { int prev = -1; (void)hipGetDevice(&prev); (void)hipSetDevice(m->devices[s]); (void)hipFree(st.p); if (prev >= 0) (void)hipSetDevice(prev); }
+        for (auto &st : m->stage[s]) if (st.p) { int prev = -1; (void)hipGetDevice(&prev); (void)hipSetDevice(m->devices[s]); st.release(); if (prev >= 0) (void)hipSetDevice(prev); }
     for (size_t s = m->ctx.size(); s-- > 0;) if (m->ctx[s]) (void)mkt_ctx_destroy(m->ctx[s]);   // forks first, roots last (either order is safe: the key set is reference counted)
     delete m;
     return MKT_OK;
