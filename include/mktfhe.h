@@ -162,7 +162,10 @@ const char *mkt_last_kernel_name(const mkt_ctx *ctx);
  * "fx_kmax" (largest transform-domain magnitude of the loaded key limbs); of the last mkt_exact_polymul_batch of this context:
  * "polymul_amax" (max|a_i| over its batch), "fx_polymul_bound" (the proven bound of its Float64 product, evaluated under exact_impl = 1
  * before the kernel runs: below 0.45 the Float64 pipe served it; -1 = not evaluated), "fx_last_resid" (largest distance |q - round(q)|
- * met by the Float64 kernel: a DIAGNOSTIC beside the proven bound, not a certificate; 0 when the integer NTT served) */
+ * met by the Float64 kernel: a DIAGNOSTIC beside the proven bound, not a certificate; 0 when the integer NTT served).
+ * Of the blind-rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" -- the gadget length and the log2 of the
+ * gadget base that the instantiation which ran holds as COMPILE-TIME constants, each 0 where it takes the value at run time (and after
+ * mkt_exact_polymul_batch).  They say which specialisation of a kernel name a call reached (the tests assert it); no result depends on them */
 int mkt_get_metric(mkt_ctx *ctx, const char *name, double *out);
 
 /* twiddle tables (fft.jl:31-41): which = 0 Psi, 1 Psiinv, 2 roots, 3 rootsinv; M complex each.

@@ -64,6 +64,7 @@ Tune tune_from_env() { Tune t; for (const Switch &w : SWITCHES) t.*w.member = w.
 }  // namespace
 
 thread_local const char *mktd::last_rot_kernel = "";
+thread_local int mktd::last_rot_static_l = 0, mktd::last_rot_static_logB = 0;
 
 // launcher-level switches (grid shapes of the transform and key-switch kernels): process-wide, read from the environment
 // on first use only (device_api.h)
@@ -157,6 +158,7 @@ struct mkt_ctx {
     std::vector<TimedSpan> spans;
     Tune tune{};
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
+    int rot_static_l = 0, rot_static_logB = 0;   // ... and its compile-time gadget, 0 = taken at run time (mkt_get_metric "rot_static_l" / "rot_static_logB")
     // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
     double pm_amax = 0.0;               // max|a_i| of the last call
     double pm_bound = -1.0;             // fx_polymul_bound of the last call (-1: not evaluated -- exact_impl != 1 or no Float64 tables)
@@ -186,7 +188,7 @@ struct Timer {
         else a = b = nullptr;
     }
     ~Timer() {
-        if (cls == 1) c->last_rot_kernel = mktd::last_rot_kernel;   // the blind-rotation launcher noted which kernel it picked
+        if (cls == 1) { c->last_rot_kernel = mktd::last_rot_kernel; c->rot_static_l = mktd::last_rot_static_l; c->rot_static_logB = mktd::last_rot_static_logB; }   // the blind-rotation launcher noted which kernel it picked
         if (a && b) { (void)hipEventRecord(b, c->stream); c->spans.push_back(TimedSpan{cls, a, b}); }
     }
 };
@@ -418,8 +420,9 @@ int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const u
             if (int r = fx_phase1(c, lwe, stride, pre, B, q.levkey)) return r;
             q.phase2_only = 1;
         }
+        const int fx_l = mktd::last_rot_static_l;   // (phase 1 ran on the Float64 pipe: the call is named after it, with its gadget)
         HIPCHK(c, mktd::launch_exact_kms(c->logN, c->ks->d_ntt, q, B, c->stream));
-        if (q.phase2_only) mktd::last_rot_kernel = "fx_blindrotate_kernel";
+        if (q.phase2_only) mktd::note_rot_kernel("fx_blindrotate_kernel", fx_l, 0);
         return MKT_OK;
     }
     case Route::EXACT_KANY:   // CGGI / LMSS, any RLWE length: sums in memory
@@ -938,7 +941,8 @@ const char *mkt_last_kernel_name(const mkt_ctx *c) { return c ? c->last_rot_kern
 
 // diagnostics of the Float64-pipe EXACT implementation (fx_exact.hip): "fx_available" (1 if the loaded keys are certified and exact_impl admits it),
 // "fx_bound" (proven bound on |computed - exact| of a rounded sum for the loaded keys), "fx_kmax" (largest |key transform value|); of the last
-// mkt_exact_polymul_batch on this context: "fx_last_resid" (diagnostic), "polymul_amax" (max|a_i|), "fx_polymul_bound" (fx_polymul_bound, -1 if not evaluated)
+// mkt_exact_polymul_batch on this context: "fx_last_resid" (diagnostic), "polymul_amax" (max|a_i|), "fx_polymul_bound" (fx_polymul_bound, -1 if not evaluated);
+// of the rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" (its compile-time gadget, 0 = taken at run time)
 int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     if (!c || !name || !out) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
@@ -948,6 +952,8 @@ int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     else if (k == "fx_last_resid") *out = c->fx_last_resid;
     else if (k == "polymul_amax") *out = c->pm_amax;
     else if (k == "fx_polymul_bound") *out = c->pm_bound;
+    else if (k == "rot_static_l") *out = c->rot_static_l;
+    else if (k == "rot_static_logB") *out = c->rot_static_logB;
     else return fail(c, MKT_ERR_ARG, "mkt_get_metric: unknown metric '" + k + "'");
     return MKT_OK;
 }
@@ -1788,7 +1794,7 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
     if (!c || !a || !b || !out || !mem_ok(mem)) return fail(c, MKT_ERR_ARG, "bad argument");
     if (!c->exact) return fail(c, MKT_ERR_UNSUPPORTED, "mkt_exact_polymul_batch needs an MKT_ARITH_EXACT context");
     DevGuard dg(c->device);
-    c->last_rot_kernel = ""; c->pm_amax = 0.0; c->pm_bound = -1.0; c->fx_last_resid = 0.0;
+    c->last_rot_kernel = ""; c->rot_static_l = c->rot_static_logB = 0; c->pm_amax = 0.0; c->pm_bound = -1.0; c->fx_last_resid = 0.0;
     Staged sa{c}, sb{c}, so{c};
     int r;
     if ((r = sa.in(a, B * poly_bytes(c), mem, true)) || (r = sb.in(b, B * poly_bytes(c), mem, true)) || (r = so.in(out, B * poly_bytes(c), mem, false))) return r;

@@ -17,6 +17,13 @@ const LaunchTuning &launch_tuning();
 // base name of the blind-rotation kernel the calling thread launched last (set by every rotation launcher; read by
 // mkt_last_kernel_name so that bench.py's roofline names the kernel that actually ran)
 extern thread_local const char *last_rot_kernel;
+// the compile-time gadget of that launch, (length, log2 of the base): 0 where the instantiation takes the value at run time
+// (mkt_get_metric "rot_static_l" / "rot_static_logB": which specialisation a test reached; no result depends on them)
+extern thread_local int last_rot_static_l, last_rot_static_logB;
+// the one way a launcher notes its kernel: a launcher that names no compile-time gadget clears the pair of the launch before
+inline void note_rot_kernel(const char *name, int static_l = 0, int static_logB = 0) {
+    last_rot_kernel = name; last_rot_static_l = static_l; last_rot_static_logB = static_logB;
+}
 
 // Blind rotation with an RLWE accumulator of length 1 (b, a): CGGI/LMSS with k = 1 and every row of
 // KMS / KMS_block phase 1.  One workgroup per rotation.

@@ -492,6 +492,7 @@ hipError_t fx_rot_launch(const FxRotArgs &a, size_t nrot, hipStream_t s) {
     static_assert(P::LDS_BYTES >= (size_t)4 * P::M * sizeof(WORD), "the staging buffers hold the turned sums of both polynomials");
     hipError_t e = set_lds(fx_blindrotate_kernel<LM, WORD, LT>, LB);
     if (e != hipSuccess) return e;
+    note_rot_kernel("fx_blindrotate_kernel", LT, 0);
     hipLaunchKernelGGL((fx_blindrotate_kernel<LM, WORD, LT>), dim3((unsigned)nrot), dim3(P::NT), LB, s, a);
     return hipGetLastError();
 }
@@ -541,7 +542,6 @@ hipError_t launch_fx_polymul(int logM, int W, const cplx *om, const cplx *twist,
 hipError_t launch_fx_blindrotate(int logM, int W, const FxRotArgs &a, size_t nrot, hipStream_t s) {
     if (!nrot) return hipSuccess;
     if (!fx_supported(logM, W, a.l)) return hipErrorInvalidValue;
-    last_rot_kernel = "fx_blindrotate_kernel";
     // One launch per chip-fill on the 64-bit ring up to N = 1024.  Every rotation of a party walks the same key rows, step by step, and the workgroups of ONE fill run in
     // lock-step, so a fill reads each row from the fabric once per L2 and then hits; in a single launch of several fills the later workgroups start whenever a slot frees,
     // the resident ones spread over all key bits and the 4 x larger key of this arithmetic no longer fits the L2s (headline: hit rate 0.66 -> 0.96, 34.3 -> 31.6 ms).  At

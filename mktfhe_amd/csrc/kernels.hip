@@ -839,7 +839,7 @@ __global__ __launch_bounds__((Plan<LOGM, LOGR>::NT)) void blindrotate_kany_kerne
 hipError_t launch_blindrotate_kany(int logM, int W, int kr, const RotArgs &a, cplx *scratch, size_t nrot, hipStream_t s) {
     if (!nrot) return hipSuccess;
     if (kr < 1 || !scratch) return hipErrorInvalidValue;
-    last_rot_kernel = "blindrotate_kany_kernel";
+    note_rot_kernel("blindrotate_kany_kernel");
     MKT_DISPATCH_LOGM(logM, {
         using P = Plan<LM, LOGR>;
         constexpr size_t LB = P::LDS_BYTES + (size_t)P::M * sizeof(cplx);
@@ -1638,7 +1638,7 @@ static hipError_t launch_rot_lt(const RotArgs &a, size_t nrot, hipStream_t s) {
     const size_t lds_bytes = P::LDS_BYTES + (size_t)P::M * sizeof(cplx);
     hipError_t e = set_lds(blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>, lds_bytes);
     if (e != hipSuccess) return e;
-    last_rot_kernel = "blindrotate_k1_kernel";
+    note_rot_kernel("blindrotate_k1_kernel", LT, BT);
     if (a.split == 0 || a.split >= nrot) {
         hipLaunchKernelGGL((blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>), dim3((unsigned)nrot), dim3(P::NT), lds_bytes, s, a);
         return hipGetLastError();
@@ -1811,7 +1811,7 @@ static hipError_t launch_kr_one(const RotArgs &a, size_t nrot, hipStream_t s) {
     constexpr size_t LB = P::LDS_BYTES + (size_t)P::M * sizeof(cplx);
     hipError_t e = set_lds(blindrotate_kr_kernel<LM, WORD, KR, BLK, BL>, LB);
     if (e != hipSuccess) return e;
-    last_rot_kernel = "blindrotate_kr_kernel";
+    note_rot_kernel("blindrotate_kr_kernel");
     hipLaunchKernelGGL((blindrotate_kr_kernel<LM, WORD, KR, BLK, BL>), dim3((unsigned)nrot), dim3(P::NT), LB, s, a);
     return hipGetLastError();
 }
@@ -1867,7 +1867,7 @@ static hipError_t launch_ccs_one(const CcsArgs &a, size_t B, hipStream_t s) {
     using P = Plan<LM, LOGR, 1>;
     constexpr size_t LB = P::LDS_BYTES + (size_t)P::M * sizeof(cplx);
     hipError_t e = set_lds(ccs_blindrotate_kernel<LM, WORD, LT, BT>, LB); if (e != hipSuccess) return e;
-    last_rot_kernel = "ccs_blindrotate_kernel";
+    note_rot_kernel("ccs_blindrotate_kernel", LT, BT);
     hipLaunchKernelGGL((ccs_blindrotate_kernel<LM, WORD, LT, BT>), dim3((unsigned)B), dim3(P::NT), LB, s, a);
     return hipGetLastError();
 }
@@ -2136,7 +2136,7 @@ static hipError_t launch_wide_one(const RotArgs &a, size_t nrot, hipStream_t s) 
     const size_t lds_bytes = (size_t)(1 + 2 * LT) * P::M * sizeof(cplx);
     hipError_t e = set_lds(blindrotate_wide_kernel<LM, WORD, LR, LT>, lds_bytes);
     if (e != hipSuccess) return e;
-    last_rot_kernel = "blindrotate_wide_kernel";
+    note_rot_kernel("blindrotate_wide_kernel", LT, 0);
     hipLaunchKernelGGL((blindrotate_wide_kernel<LM, WORD, LR, LT>), dim3((unsigned)nrot), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }

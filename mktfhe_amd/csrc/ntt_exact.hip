@@ -1568,7 +1568,7 @@ hipError_t launch_exact_blindrotate(int logN, const uint64_t *tab, const uint64_
                                     int pre_switched, int n, int l, int logB, int blk_len, uint32_t *acc, size_t B, hipStream_t s) {
     if (!B) return hipSuccess;
     if (blk_len != 1 && blk_len != 3) return hipErrorInvalidValue;
-    last_rot_kernel = "exact_blindrotate_kernel";
+    note_rot_kernel("exact_blindrotate_kernel");
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
     MKT_NTT_DISPATCH(logN, {
         const size_t lds = lds_bytes<LN>(1);
@@ -1587,7 +1587,7 @@ hipError_t launch_exact_blindrotate_kr(int logN, const uint64_t *tab, const uint
                                        int pre_switched, int n, int kr, int l, int logB, int blk_len, uint32_t *acc, size_t B, hipStream_t s) {
     if (!B) return hipSuccess;
     if (kr < 1 || kr > 3 || blk_len < 1 || n % blk_len) return hipErrorInvalidValue;
-    last_rot_kernel = "exact_blindrotate_kr_kernel";
+    note_rot_kernel("exact_blindrotate_kr_kernel");
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
 #define MKT_EXACT_KR_LAUNCH(KRV) do { hipError_t e = ntt_set_lds(exact_blindrotate_kr_kernel<LN, KRV>, lds); if (e != hipSuccess) return e; \
         hipLaunchKernelGGL((exact_blindrotate_kr_kernel<LN, KRV>), dim3((unsigned)B), dim3(1 << (LN - NLR)), lds, s, tb, brk, mono, lwe, lwe_stride, pre_switched, n, l, logB, blk_len, acc); } while (0)
@@ -1603,7 +1603,7 @@ hipError_t launch_exact_blindrotate_kany(int logN, const uint64_t *tab, const ui
                                          int pre_switched, int n, int kr, int l, int logB, int blk_len, uint32_t *acc, uint64_t *scratch, size_t B, hipStream_t s) {
     if (!B) return hipSuccess;
     if (kr < 1 || blk_len < 1 || n % blk_len || !scratch) return hipErrorInvalidValue;
-    last_rot_kernel = "exact_blindrotate_kany_kernel";
+    note_rot_kernel("exact_blindrotate_kany_kernel");
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
     MKT_NTT_DISPATCH(logN, {
         const size_t lds = lds_bytes<LN>(1);
@@ -1631,14 +1631,14 @@ hipError_t launch_ntt_fwd_split(int logN, const uint64_t *tab, const void *p, ui
 #if MKT_NTT_IN(2)
 hipError_t launch_exact_kms_phase1(int logN, const uint64_t *tab, const ExactKmsArgs &a, size_t B, hipStream_t s) {      // internal: phase 1 of launch_exact_kms (unit 2)
     if (!B || a.phase2_only) return hipSuccess;
-    last_rot_kernel = "exact_kms_phase1_kernel";
+    note_rot_kernel("exact_kms_phase1_kernel");
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
     MKT_NTT_DISPATCH(logN, {
         const size_t lds = lds_bytes<LN>(1, 2);                                      // two staging buffers: the halves of a lifted sum are inverse-transformed side by side
         hipError_t e = hipSuccess;
         if (a.phase2_only) {                                                       // phase 1 ran on the Float64 pipe (fx_exact.hip) and levkey holds its rows
         } else if (a.blk_len > 1 && a.wide != 0) {                                // exact_wide = 0: the per-key-bit kernel below (tests force both)
-            last_rot_kernel = "exact_kms_block_phase1_kernel";
+            note_rot_kernel("exact_kms_block_phase1_kernel");
             e = ntt_set_lds(exact_kms_block_phase1_kernel<LN>, lds); if (e != hipSuccess) return e;
             hipLaunchKernelGGL((exact_kms_block_phase1_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride, a.mono,
                                a.lwe, a.lwe_stride, a.pre_switched, a.n, a.l_gsw, a.logB_gsw, a.blk_len, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
@@ -1649,7 +1649,7 @@ hipError_t launch_exact_kms_phase1(int logN, const uint64_t *tab, const ExactKms
         } else {
             if (a.wide != 0 && a.l_gsw == 2) {                                     // the paired-transform kernel (default); exact_wide = 0: the one-at-a-time kernel below (tests force both)
                 const size_t lds2 = lds_bytes<LN>(1, 2);
-                last_rot_kernel = "exact_kms_phase1_p2pf_kernel";
+                note_rot_kernel("exact_kms_phase1_p2pf_kernel");
                 e = ntt_set_lds(exact_kms_phase1_p2pf_kernel<LN>, lds2); if (e != hipSuccess) return e;
                 hipLaunchKernelGGL((exact_kms_phase1_p2pf_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds2, s, tb, a.brk, a.brk_party_stride,
                                    a.lwe, a.lwe_stride, a.pre_switched, a.n, a.logB_gsw, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
@@ -1684,7 +1684,7 @@ hipError_t launch_exact_kms(int logN, const uint64_t *tab, const ExactKmsArgs &a
 
 hipError_t launch_exact_ccs(int logN, const uint64_t *tab, const ExactCcsHostArgs &h, size_t B, hipStream_t s) {
     if (!B) return hipSuccess;
-    last_rot_kernel = "exact_ccs_kernel";
+    note_rot_kernel("exact_ccs_kernel");
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
     ExactCcsArgs a;
     a.lwe = h.lwe; a.lwe_stride = h.lwe_stride; a.pre_switched = h.pre_switched; a.n = h.n; a.k = h.k; a.l = h.l; a.logB = h.logB;

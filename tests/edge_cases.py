@@ -18,36 +18,81 @@ def sid(p):
     return f"{p.name}-n{p.n}-N{p.N}-k{p.k}-b{p.blk_len}" + (f"-f{p.f}x{p.logD}" if p in _KS_GADGET_TWINS else "")
 
 
-# (parameter set, options, kernel the case means to reach, batch size): blind rotation, Float64 mode.  B = 5 is ragged for every
-# grouping; 9 is one past a grouping of 8 (rot_map), 3 / 5 one past 2 / 4 rotations per workgroup (rot_block.hip)
+# (parameter set, options, kernel the case means to reach, batch size, the (gadget length, log2 base) that the instantiation it means to
+# reach holds as compile-time constants -- mkt_get_metric "rot_static_l" / "rot_static_logB", 0 = a run-time value): blind rotation,
+# Float64 mode.  B = 5 is ragged for every grouping; 9 is one past a grouping of 8 (rot_map), 3 / 5 one past 2 / 4 rotations per
+# workgroup (rot_block.hip)
 ROT_CASES = [
-    (_CG, {"rot_wide": 1, "rot_variant": 21}, "blindrotate_k1_kernel", 5),
-    (_CG, {"rot_wide": 1, "rot_variant": 22}, "blindrotate_k1_kernel", 9),
-    (_CG, {"rot_wide": 1, "rot_map": 0}, "blindrotate_k1_kernel", 9),
-    (_CG, {"rot_wide": 1, "rot_map": 1, "rot_stagger": 64}, "blindrotate_k1_kernel", 5),
-    (mk.CGGIparam.scaled(n=12, N=512), {"rot_wide": 2}, "blindrotate_wide_kernel", 5),
-    (mk.CGGI_N1024_l2.scaled(n=8), {"rot_wide": 1, "rot_variant": 22}, "blindrotate_k1_kernel", 3),
-    (mk.CGGIparam.scaled(n=4, N=4096), {"rot_wide": 1}, "blindrotate_k1_kernel", 3),
-    (mk.CGGIparam.scaled(n=8, N=64), {"rot_wide": 1}, "blindrotate_k1_kernel", 5),
-    (mk.CGGIparam.scaled(n=12, N=256, k=2), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5),
-    (mk.CGGIparam.scaled(n=12, N=256, k=2), {"rot_blkg": 4}, "blindrotate_blk_kernel", 5),
-    (mk.CGGIparam.scaled(n=8, N=512, k=3, l_gsw=2, logB_gsw=10), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5),
-    (mk.CGGIparam.scaled(n=8, N=256, k=4), {}, "blindrotate_kany_kernel", 5),
-    (mk.CGGIparam.scaled(n=6, N=128, k=6, l_gsw=2, logB_gsw=10), {}, "blindrotate_kany_kernel", 5),
-    (_BL2, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5), (_BL2, {"rot_blkg": 2}, "blindrotate_blk_kernel", 3), (_BL2, {"rot_blkg": 4}, "blindrotate_blk_kernel", 5),
-    (_BL3, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5), (_BL3, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5), (_BL3, {"rot_blkg": 4}, "blindrotate_blk_kernel", 9),
-    (_BL4, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5), (_BL4, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5), (_BL4, {"rot_blkg": 4}, "blindrotate_blk_kernel", 5),
-    (mk.Blockparam_k2.scaled(n=12, N=256, blk_d=4), {"rot_blkg": 4}, "blindrotate_blk_kernel", 5),
-    (mk.Blockparam_k2.scaled(n=12, N=256, blk_d=4), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5),
-    (_CC2, {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5), (_CC2, {"ccs_pipe": 1}, "ccs_pipe_kernel", 5),
-    (mk.CCS8party.scaled(n=2, N=512, k=3), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5), (mk.CCS8party.scaled(n=2, N=512, k=3), {"ccs_pipe": 1}, "ccs_pipe_kernel", 5),
-    (mk.CCS16party.scaled(n=2, N=128, k=5), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5), (mk.CCS16party.scaled(n=2, N=128, k=5), {"ccs_pipe": 1}, "ccs_pipe_kernel", 5),
-    (mk.CCS2party.scaled(n=2, N=4096), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 3),
-    (_K2, {"rot_wide": 1, "rot_variant": 21}, "blindrotate_k1_kernel", 5),
-    (mk.KMS2party_N1024_l2.scaled(n=6), {"rot_wide": 2}, "blindrotate_wide_kernel", 5),
-    (mk.KMS4party.scaled(n=6, N=256), {"rot_wide": 1, "rot_map": 1}, "blindrotate_k1_kernel", 5),
-    (mk.KMS2party.scaled(n=2, N=4096), {"rot_wide": 1}, "blindrotate_k1_kernel", 3),
-    (_KB, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5), (_KB, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5),
+    (_CG, {"rot_wide": 1, "rot_variant": 21}, "blindrotate_k1_kernel", 5, (0, 0)),
+    (_CG, {"rot_wide": 1, "rot_variant": 22}, "blindrotate_k1_kernel", 9, (0, 0)),
+    (_CG, {"rot_wide": 1, "rot_map": 0}, "blindrotate_k1_kernel", 9, (0, 0)),
+    (_CG, {"rot_wide": 1, "rot_map": 1, "rot_stagger": 64}, "blindrotate_k1_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=12, N=512), {"rot_wide": 2}, "blindrotate_wide_kernel", 5, (3, 0)),
+    (mk.CGGI_N1024_l2.scaled(n=8), {"rot_wide": 1, "rot_variant": 22}, "blindrotate_k1_kernel", 3, (2, 0)),
+    (mk.CGGIparam.scaled(n=4, N=4096), {"rot_wide": 1}, "blindrotate_k1_kernel", 3, (0, 0)),
+    (mk.CGGIparam.scaled(n=8, N=64), {"rot_wide": 1}, "blindrotate_k1_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=12, N=256, k=2), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=12, N=256, k=2), {"rot_blkg": 4}, "blindrotate_blk_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=8, N=512, k=3, l_gsw=2, logB_gsw=10), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=8, N=256, k=4), {}, "blindrotate_kany_kernel", 5, (0, 0)),
+    (mk.CGGIparam.scaled(n=6, N=128, k=6, l_gsw=2, logB_gsw=10), {}, "blindrotate_kany_kernel", 5, (0, 0)),
+    (_BL2, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5, (0, 0)), (_BL2, {"rot_blkg": 2}, "blindrotate_blk_kernel", 3, (0, 0)), (_BL2, {"rot_blkg": 4}, "blindrotate_blk_kernel", 5, (0, 0)),
+    (_BL3, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5, (0, 0)), (_BL3, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5, (0, 0)), (_BL3, {"rot_blkg": 4}, "blindrotate_blk_kernel", 9, (0, 0)),
+    (_BL4, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5, (0, 0)), (_BL4, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5, (0, 0)), (_BL4, {"rot_blkg": 4}, "blindrotate_blk_kernel", 5, (0, 0)),
+    (mk.Blockparam_k2.scaled(n=12, N=256, blk_d=4), {"rot_blkg": 4}, "blindrotate_blk_kernel", 5, (0, 0)),
+    (mk.Blockparam_k2.scaled(n=12, N=256, blk_d=4), {"rot_blkg": 1}, "blindrotate_kr_kernel", 5, (0, 0)),
+    (_CC2, {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5, (0, 0)), (_CC2, {"ccs_pipe": 1}, "ccs_pipe_kernel", 5, (0, 0)),
+    (mk.CCS8party.scaled(n=2, N=512, k=3), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5, (0, 0)), (mk.CCS8party.scaled(n=2, N=512, k=3), {"ccs_pipe": 1}, "ccs_pipe_kernel", 5, (0, 0)),
+    (mk.CCS16party.scaled(n=2, N=128, k=5), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 5, (0, 0)), (mk.CCS16party.scaled(n=2, N=128, k=5), {"ccs_pipe": 1}, "ccs_pipe_kernel", 5, (0, 0)),
+    (mk.CCS2party.scaled(n=2, N=4096), {"ccs_pipe": 0}, "ccs_blindrotate_kernel", 3, (0, 0)),
+    (_K2, {"rot_wide": 1, "rot_variant": 21}, "blindrotate_k1_kernel", 5, (0, 0)),
+    (mk.KMS2party_N1024_l2.scaled(n=6), {"rot_wide": 2}, "blindrotate_wide_kernel", 5, (2, 0)),
+    (mk.KMS4party.scaled(n=6, N=256), {"rot_wide": 1, "rot_map": 1}, "blindrotate_k1_kernel", 5, (0, 0)),
+    (mk.KMS2party.scaled(n=2, N=4096), {"rot_wide": 1}, "blindrotate_k1_kernel", 3, (0, 0)),
+    (_KB, {"rot_blkg": 1}, "blindrotate_k1_kernel", 5, (0, 0)), (_KB, {"rot_blkg": 2}, "blindrotate_blk_kernel", 5, (0, 0)),
+]
+
+# The instantiations that the shipped sets and the benchmark run: gadget length and base are template constants, picked by the launchers
+# (launch_rot_one, launch_blk_g / launch_blk_np, launch_ccs_blindrotate / launch_ccs_pipe, launch_wide_lm) at the shipped N, word, block
+# length and gadget only.  Each set keeps those of its shipped set and reduces n, blk_d and the party count, which the dispatch does not
+# read; one line per instantiation, and the pair it must reach.  With batches this small the default route at M <= 512 is the latency
+# kernel: rot_wide 1 where blindrotate_k1_kernel is meant.  tests/test_edges_cpu.py holds this list against the launchers' source
+_X2 = mk.KMS2party_N1024_l2.scaled(n=6)
+_X2B15 = mk.KMS2party_N1024_l2.scaled(name="KMS2party_N1024_l2_logB15", n=6, logB_gsw=15)
+_CG1 = mk.CGGIparam.scaled(n=8)
+_BL1 = mk.Blockparam.scaled(n=12, blk_d=4)
+_BLK2 = mk.Blockparam_k2.scaled(n=12, blk_d=4)
+_KMS = [mk.KMS2party.scaled(n=6), mk.KMS4party.scaled(n=4, k=2), mk.KMS8party.scaled(n=4, k=2), mk.KMS32party.scaled(n=4, k=2)]
+_KMSB = [q.scaled(n=6, blk_d=2, k=2) for q in (mk.KMS2partyblock, mk.KMS4partyblock, mk.KMS8partyblock, mk.KMS32partyblock)]
+_CCS1 = [mk.CCS2party.scaled(n=4), mk.CCS4party.scaled(n=2, k=2), mk.CCS8party.scaled(n=2, k=2)]
+_CCS2 = [mk.CCS2party.scaled(n=4, N=2048), mk.CCS4party.scaled(n=2, k=2, N=2048), mk.CCS8party_N2048.scaled(n=2, k=2)]
+_K1, _BLK, _CCS, _PIPE, _WIDE = "blindrotate_k1_kernel", "blindrotate_blk_kernel", "ccs_blindrotate_kernel", "ccs_pipe_kernel", "blindrotate_wide_kernel"
+ROT_CASES += [
+    # blindrotate_k1_kernel, M = 512: the 64-bit ring's (2, 16) -- the dropped part is exactly the low half -- and l = 2 with a run-time base
+    (_X2, {"rot_wide": 1}, _K1, 5, (2, 16)), (_X2, {"rot_wide": 1, "rot_variant": 21}, _K1, 3, (2, 16)),
+    (_X2B15, {"rot_wide": 1}, _K1, 5, (2, 0)),
+    # ... the 32-bit ring's (3, 9), block length 1 and 3
+    (_CG1, {"rot_wide": 1}, _K1, 5, (3, 9)), (_CG1, {"rot_wide": 1, "rot_variant": 21}, _K1, 3, (3, 9)),
+    (_BL1, {"rot_blkg": 1}, _K1, 5, (3, 9)),
+    # ... M = 1024, 64-bit ring: the four KMS gadgets, block length 1 and 3
+    (_KMS[0], {"rot_wide": 1}, _K1, 5, (3, 12)), (_KMS[0], {"rot_wide": 1, "rot_variant": 21}, _K1, 3, (3, 12)),
+    (_KMS[1], {"rot_wide": 1}, _K1, 5, (5, 8)), (_KMS[2], {"rot_wide": 1}, _K1, 5, (4, 9)), (_KMS[3], {"rot_wide": 1}, _K1, 5, (6, 7)),
+    (_KMSB[0], {"rot_blkg": 1}, _K1, 5, (3, 12)), (_KMSB[1], {"rot_blkg": 1}, _K1, 5, (5, 8)), (_KMSB[2], {"rot_blkg": 1}, _K1, 5, (4, 9)),
+    (_KMSB[3], {"rot_blkg": 1}, _K1, 5, (6, 7)),
+    # blindrotate_blk_kernel: two and four rotations per workgroup (one past each), and the three-polynomial form of Blockparam_k2
+    (_BL1, {"rot_blkg": 2}, _BLK, 3, (3, 9)), (_BL1, {"rot_blkg": 4}, _BLK, 5, (3, 9)),
+    (_KMSB[0], {"rot_blkg": 2}, _BLK, 3, (3, 12)),
+    (_BLK2, {"rot_blkg": 4}, _BLK, 5, (3, 7)),
+    # the CCS kernels, one and two thread groups per ciphertext, M = 512 and 1024
+    (_CCS1[0], {"ccs_pipe": 0}, _CCS, 5, (3, 8)), (_CCS1[0], {"ccs_pipe": 1}, _PIPE, 5, (3, 8)),
+    (_CCS1[1], {"ccs_pipe": 0}, _CCS, 5, (4, 8)), (_CCS1[1], {"ccs_pipe": 1}, _PIPE, 5, (4, 8)),
+    (_CCS1[2], {"ccs_pipe": 0}, _CCS, 5, (5, 6)), (_CCS1[2], {"ccs_pipe": 1}, _PIPE, 5, (5, 6)),
+    (_CCS2[0], {"ccs_pipe": 0}, _CCS, 3, (3, 8)), (_CCS2[0], {"ccs_pipe": 1}, _PIPE, 3, (3, 8)),
+    (_CCS2[1], {"ccs_pipe": 0}, _CCS, 3, (4, 8)), (_CCS2[1], {"ccs_pipe": 1}, _PIPE, 3, (4, 8)),
+    (_CCS2[2], {"ccs_pipe": 0}, _CCS, 3, (5, 6)), (_CCS2[2], {"ccs_pipe": 1}, _PIPE, 3, (5, 6)),
+    # blindrotate_wide_kernel at M = 1024: eight points per thread, l = 3 and 4, both rings (its gadget length is always a constant)
+    (_KMS[0], {"rot_wide": 2}, _WIDE, 5, (3, 0)), (_KMS[2], {"rot_wide": 2}, _WIDE, 5, (4, 0)),
+    (mk.CGGIparam.scaled(n=6, N=2048), {"rot_wide": 2}, _WIDE, 5, (3, 0)),
 ]
 
 # EXACT mode (N <= 256: compared with tests/ref_exact.py; above: the two implementations with each other).  exact_impl 1 with a
@@ -120,6 +165,9 @@ BOOT_CASES = [
     (_CC2, {"ccs_pipe": 0}, "ccs_blindrotate_kernel"), (_CC2, {"ccs_pipe": 1}, "ccs_pipe_kernel"),
     (_K2, {"rot_wide": 1}, "blindrotate_k1_kernel"), (mk.KMS2party_N1024_l2.scaled(n=6), {"rot_wide": 2}, "blindrotate_wide_kernel"),
     (_KB, {"rot_blkg": 1}, "blindrotate_k1_kernel"), (_KB, {"rot_blkg": 2}, "blindrotate_blk_kernel"),
+    # (appended: LUT_BOOT_CASES below indexes this list by position) three of the compile-time-gadget instantiations of ROT_CASES:
+    # the (2, 16) one-rotation kernel, Blockparam's four rotations per workgroup, CCS2party on two thread groups
+    (_X2, {"rot_wide": 1}, _K1), (_BL1, {"rot_blkg": 4}, _BLK), (_CCS1[0], {"ccs_pipe": 1}, _PIPE),
 ]
 # the gate entry points (six gates, gate_ops, gate3, MUX) on crafted rows: the same kernels
 GATE_CASES = BOOT_CASES

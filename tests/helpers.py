@@ -288,11 +288,13 @@ def edge_positions(N):
 def acc_edge(p, gadgets, rng, B):
     """accumulators [B][1 + k][N] (uint64 holding W-bit words) with EVERY polynomial populated: edge_words, and on top the
     gadget_words of every gadget in `gadgets` at the first edge_positions, the list rotated from polynomial to polynomial (what that
-    reaches -- every class in both halves, a boundary word at each of 0, M - 1, M, N - 1 -- is asserted in tests/test_edges_cpu.py)"""
+    reaches -- every class in both halves, a boundary word at each of 0, M - 1, M, N - 1 -- is asserted in tests/test_edges_cpu.py).
+    A lone gadget that drops no bit (W = l logB: CCS4party) has three words only, which the rotation below does not move: they are laid
+    down four times over, so that each still meets both halves and the four corner positions hold one"""
     N, W = p.N, p.W
     S = [v for (l, logB) in gadgets for v in gadget_words(l, logB, W).values()]
     pos = edge_positions(N)
-    m = min(len(S), len(pos), N // 2)
+    m = min(len(S) * (4 if len(S) < 4 else 1), len(pos), N // 2)
     acc = np.empty((B, 1 + p.k, N), dtype=np.uint64)
     for b in range(B):
         for q in range(1 + p.k):

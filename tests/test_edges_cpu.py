@@ -2,6 +2,9 @@
 builders of helpers.py produce for every parameter set of tests/edge_cases.py (a count per class > 0: the condition that keeps
 the GPU tests from silently testing nothing), the oracle's own composition identity holds on the crafted rows, and each class
 separates the oracle from the plausible wrong variant written next to it."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -258,6 +261,145 @@ def test_lut_edge_tables_hold_every_class_after_every_rotation(p, o):
             if W == 64 and W - l * logB > 32:
                 low = tv[0] & np.uint64(0xFFFFFFFF)
                 assert (low == 0xFFFFFFFF).any() and (low == 0x80000000).any()
+
+
+# ---------------------------------------------------------------- 1b. the compile-time-gadget instantiations and their cases
+_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mktfhe_amd", "csrc")
+# launcher of a specialised instantiation -> (source file, kernel name of its cases, positions of LB, LT, BT, NP among its template arguments;
+# None: the launcher has no such argument).  launch_rot_lt<LM, WORD, LB, LR, NB, LT, BT = 0>, launch_blk_lt<LM, WORD, LB, G, LT, BT, NP = 2>,
+# launch_ccs_one / launch_ccs_pipe_one<LM, WORD, LT, BT>
+_LAUNCHERS = {
+    "launch_rot_lt": ("kernels.hip", "blindrotate_k1_kernel", 2, 5, 6, None),
+    "launch_blk_lt": ("rot_block.hip", "blindrotate_blk_kernel", 2, 4, 5, 6),
+    "launch_ccs_one": ("kernels.hip", "ccs_blindrotate_kernel", None, 2, 3, None),
+    "launch_ccs_pipe_one": ("ccs_pipe.hip", "ccs_pipe_kernel", None, 2, 3, None),
+}
+_WORDS = {"uint32_t": 4, "uint64_t": 8}
+
+
+def _conditions(lines, i, col):
+    """the text of every `if` / `if constexpr` condition that the call at lines[i][:col] sits under: the headers of the braces open at
+    that point, and what stands before the call on its own line.  The branch after `{ return hipErrorInvalidValue; } else {` holds the
+    NEGATION of its header (a chain of ||): there each `x != v` reads `x == v`, and what is no equality is dropped"""
+    stack = []
+    for ln in lines[:i]:
+        code = ln.split("//")[0]
+        for m in re.finditer(r"[{}]", code):
+            if m.group() == "}":
+                if stack:
+                    stack.pop()
+                if re.match(r"\s*else\s*\{", code[m.end():]) and re.search(r"\{\s*return hipErrorInvalidValue;\s*$", code[:m.start()]):
+                    head = code[:code.index("{")]
+                    stack.append(" && ".join(a.replace("!=", "==") for a in head.split("||") if "!=" in a))
+                    break
+            else:
+                stack.append(code[:m.start()] if re.search(r"\bif\b", code[:m.start()]) else "")
+    return " && ".join(stack + [lines[i][:col]])
+
+
+def _one_of(cond, pattern, every):
+    """the values that `pattern == v` admits in a conjunction of conditions (a parenthesised `x == 1 || x == 3` admits both); none named: every"""
+    found = [int(v) for v in re.findall(pattern + r" == (\d+)", cond)]
+    return sorted(set(found)) if found else list(every)
+
+
+def source_specialisations():
+    """every (launcher, LM, word bytes, LB, NP, l, logB) whose gadget length is a non-zero literal in a launcher call of the sources (logB 0:
+    the base stays a run-time value); a template argument or a condition that the call leaves open expands over every value the dispatch has"""
+    out = []
+    for name, (fname, _, i_lb, i_lt, i_bt, i_np) in _LAUNCHERS.items():
+        lines = open(os.path.join(_CSRC, fname)).read().split("\n")
+        for i, ln in enumerate(lines):
+            for m in re.finditer(name + r"<([^<>()]*)>\(a, ", ln.split("//")[0]):
+                args = [a.strip() for a in m.group(1).split(",")]
+                lt, bt = args[i_lt], args[i_bt] if i_bt < len(args) else "0"
+                if not (lt.isdigit() and int(lt) > 0):
+                    continue
+                assert bt.isdigit(), (fname, i + 1, "a literal gadget length with a base that is no literal")
+                cond = _conditions(lines, i, m.start())
+                assert re.search(r"a\.l == " + lt + r"\b", cond) and (bt == "0" or re.search(r"a\.logB == " + bt + r"\b", cond)), (fname, i + 1, cond)
+                words = [_WORDS[args[1]]] if args[1] in _WORDS else _one_of(cond, r"sizeof\(WORD\)", (4, 8))
+                lbs = [None] if i_lb is None else [int(args[i_lb])] if args[i_lb].isdigit() else _one_of(cond, "LB", (1, 2, 3, 4))
+                np_ = None if i_np is None else int(args[i_np]) if i_np < len(args) else 2
+                for lm in _one_of(cond, "LM", ()):
+                    out += [(name, lm, w, lb, np_, int(lt), int(bt)) for w in words for lb in lbs]
+                assert _one_of(cond, "LM", ()), (fname, i + 1, "a specialisation at every ring size: name the sizes here")
+    return out
+
+
+def _case_shape(p, kernel):
+    """what the dispatch reads of a set: (log2 M, word bytes, block length as the rotation kernels see it, accumulator polynomials of a
+    rotation, the gadget of the kernel's digit loop)"""
+    block = p.scheme in (mk.LMSS, mk.KMS_BLOCK)
+    gadget = (p.l_uni, p.logB_uni) if p.scheme == mk.CCS else (p.l_gsw, p.logB_gsw)
+    kr = 1 if p.scheme in (mk.KMS, mk.KMS_BLOCK) else p.k
+    return p.N.bit_length() - 2, p.W // 8, p.blk_len if block else 1, kr + 1, gadget
+
+
+def test_every_specialisation_in_the_source_has_a_rotation_case():
+    """a launcher call with a literal gadget is an instantiation of its own, which only its own shipped shape reaches: each has a line in
+    ROT_CASES whose set has that ring size, word, block length and gadget and which expects that pair"""
+    specs = source_specialisations()
+    assert {s[0] for s in specs} == set(_LAUNCHERS), "the reader found no specialisation of a launcher: has the source changed its form?"
+    assert len(set(specs)) == len(specs)
+    missing = []
+    for (name, lm, w, lb, np_, l, logB) in specs:
+        kernel = _LAUNCHERS[name][1]
+        hit = False
+        for (p, opts, k, B, static) in EC.ROT_CASES:
+            LM, word, LB, NP, gadget = _case_shape(p, k)
+            hit |= (k == kernel and static == (l, logB) and LM == lm and word == w and lb in (None, LB) and np_ in (None, NP)
+                    and gadget[0] == l and (logB == 0 or gadget[1] == logB))
+        if not hit:
+            missing.append((name, lm, w, lb, np_, l, logB))
+    assert not missing, missing
+    print(f"{len(specs)} specialisations, each with a case")
+
+
+def _dispatch_static(p, opts, kernel):
+    """the launchers' conditions restated (launch_rot_one, launch_blk_g / launch_blk_np, launch_ccs_blindrotate / launch_ccs_pipe,
+    launch_wide_lm): the (gadget length, log2 base) that the instantiation serving this set holds as constants"""
+    LM, word, LB, NP, (l, logB) = _case_shape(p, kernel)
+    if kernel == "blindrotate_wide_kernel":
+        return (l, 0)                                                          # the gadget length is always a template argument, the base never
+    if kernel in ("ccs_blindrotate_kernel", "ccs_pipe_kernel"):
+        return (l, logB) if word == 4 and LM in (9, 10) and (l, logB) in ((3, 8), (4, 8), (5, 6)) else (0, 0)
+    if kernel == "blindrotate_k1_kernel":
+        if LB == 1 and LM == 9 and l == 2:
+            return (2, 16) if logB == 16 and word == 8 else (2, 0)
+        if LB in (1, 3) and LM == 9 and word == 4 and (l, logB) == (3, 9):
+            return (3, 9)
+        if LB in (1, 3) and LM == 10 and word == 8 and (l, logB) in ((3, 12), (5, 8), (4, 9), (6, 7)):
+            return (l, logB)
+        return (0, 0)
+    if kernel == "blindrotate_blk_kernel":
+        if NP == 2:
+            if LB == 3 and ((LM == 9 and word == 4 and (l, logB) == (3, 9)) or (LM == 10 and word == 8 and (l, logB) == (3, 12))):
+                return (l, logB)
+            return (0, 0)
+        return (3, 7) if NP == 3 and LB == 3 and LM == 9 and word == 4 and (l, logB) == (3, 7) else (0, 0)
+    assert kernel in ("blindrotate_kr_kernel", "blindrotate_kany_kernel"), kernel
+    return (0, 0)
+
+
+@pytest.mark.parametrize("i", range(len(EC.ROT_CASES)), ids=lambda i: "-".join([EC.sid(EC.ROT_CASES[i][0]), EC.ROT_CASES[i][2]]))
+def test_every_rotation_case_expects_the_pair_of_its_instantiation(i):
+    p, opts, kernel, B, static = EC.ROT_CASES[i]
+    assert static == _dispatch_static(p, opts, kernel), (EC.sid(p), opts, kernel)
+
+
+def test_the_specialised_sets_keep_their_shipped_shape():
+    """each rotation set at a compile-time base keeps N (CCS: or 2048), W, block length and gadgets of the shipped set it reduces; the whole-bootstrap
+    list ends with one such line per kernel family, behind every line that LUT_BOOT_CASES picks by position"""
+    shipped = {q.name: q for q in vars(mk).values() if isinstance(q, mk.Params)}
+    for (p, opts, kernel, B, static) in EC.ROT_CASES:
+        if static[1] and p.name in shipped:
+            q = shipped[p.name]
+            assert (p.W, p.blk_len, p.l_gsw, p.logB_gsw, p.l_uni, p.logB_uni) == (q.W, q.blk_len, q.l_gsw, q.logB_gsw, q.l_uni, q.logB_uni), EC.sid(p)
+            assert p.N == q.N or (p.scheme == mk.CCS and p.N == 2048), EC.sid(p)
+    rot = {(EC.sid(p), tuple(sorted(o.items())), k): s for (p, o, k, B, s) in EC.ROT_CASES}
+    tail = [rot[(EC.sid(p), tuple(sorted(o.items())), k)] for (p, o, k) in EC.BOOT_CASES[14:]]
+    assert tail == [(2, 16), (3, 9), (3, 8)] and EC.GATE_CASES is EC.BOOT_CASES
 
 
 # ---------------------------------------------------------------- 2. the oracle's composition identity on the crafted rows

@@ -16,7 +16,10 @@ compare EVERY ciphertext with the oracle / tests/ref_exact.py.  Every rotation c
 | key-switch digits at a coefficient | the `AT = true` instantiations of keyswitch_mg_kernel, ks_digits_kernel (+ keyswitch_pair_kernel), ks_init_kernel / ks_reduce_kernel; extract_word_at; ks_at_table_kernel (the coefficient list, NULL = 0 .. o-1) | the classes of the line above in X^v times the same accumulators, v in {0, 1, n-1, n, n+1, N/2, N-1}, rows and coefficients mixed in one call; W = 64, the borrow: a word wrapped by X^v was negated at 64 bits and is truncated and negated again at 32, so the extracted word is trunc(a) + (low half != 0) -- low halves 0 and 1, and a tie / carry (and the word one below) over a non-zero low half on both sides of j = v |
 | lookup-table route (context.cpp lut_chunk) | lut_testvector_kernel: `divbits(w, 32-logN-1+nu) << nu` on b and (nu > 0) on the mask words, which the rotation reads pre-switched; the caller's table rotated into acc.b | the mod-switch classes of the first line on the plain (nu = 0) and the coarse grid (targets 0, nout, N-nout, N, N+nout, 2N-nout, 2N); tables whose words sit on the first CMux's gadget boundaries (and their negatives: the table step negates) at 0, M-1, M, N-1 and pairs (i, i + M) |
 
-A kernel that gets its own copy of one of these steps gets a line in tests/edge_cases.py.
+A kernel that gets its own copy of one of these steps gets a line in tests/edge_cases.py, and an instantiation that gets its own
+compile-time gadget gets a line: every rotation case also asserts the (gadget length, base) that the instantiation it reached holds as
+template constants (mkt_get_metric "rot_static_l" / "rot_static_logB"), and tests/test_edges_cpu.py reads the launchers' source so that
+a specialisation without a line fails without a GPU.
 
 `tb >= N` in place of `tb > N` is not a bug these tests could see: at tb == N both forms write +1/8 to all N coefficients
 (tests/test_edges_cpu.py asserts it); the test-vector cases separate `i <= tb`, a sign not flipped, and a half turn taken one early / late.
@@ -83,12 +86,18 @@ def _rot_inputs(p, B, seed):
 
 
 # ---------------------------------------------------------------- 1. blind rotation from arbitrary accumulators
-@pytest.mark.parametrize("p,opts,kernel,B", EC.ROT_CASES, ids=_cid)
-def test_blindrotate_from_edge_accumulators(require_gpu, p, opts, kernel, B):
+def _static_gadget(s):
+    """the compile-time (gadget length, log2 base) of the instantiation that the last rotation launched, 0 = a run-time value"""
+    return int(s.get_metric("rot_static_l")), int(s.get_metric("rot_static_logB"))
+
+
+@pytest.mark.parametrize("p,opts,kernel,B,static", EC.ROT_CASES, ids=["-".join(_cid(v) for v in c[:4]) for c in EC.ROT_CASES])
+def test_blindrotate_from_edge_accumulators(require_gpu, p, opts, kernel, B, static):
     crs, keys, so, sg = _engines(p, 21, opts)
     for at, acc in _rot_inputs(p, B, 22):
         got = sg.blindrotate_(at, acc.astype(p.ring_dtype).copy()).astype(np.uint64).reshape(acc.shape)
         assert sg.last_kernel_name() == kernel, sg.last_kernel_name()
+        assert _static_gadget(sg) == static, _static_gadget(sg)
         for j in range(len(at)):
             assert np.array_equal(got[j], so.blindrotate(at[j], acc[j])), (j, at[j].nonzero()[0], at[j][at[j] != 0][:1])
     sg.close()

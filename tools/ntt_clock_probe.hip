@@ -13,6 +13,7 @@
 namespace mktd {
 const LaunchTuning &launch_tuning() { static LaunchTuning t{}; return t; }
 thread_local const char *last_rot_kernel = "";
+thread_local int last_rot_static_l = 0, last_rot_static_logB = 0;
 namespace {
 template <int LOGN, bool COMPUTE>
 __global__ __launch_bounds__((Ppw<LOGN>::v << (LOGN - NLR))) void ntt_fwd_stamped(const uint4 *__restrict__ tab, const uint64_t *__restrict__ p, uint64_t *__restrict__ out, size_t B, uint64_t *stamps) {
