@@ -134,7 +134,11 @@ int mkt_ctx_destroy(mkt_ctx *ctx);
 int mkt_ctx_fork(mkt_ctx *ctx, mkt_ctx **out);
 const char *mkt_last_error(const mkt_ctx *ctx); /* ctx may be NULL: last creation error */
 /* HIP stream (hipStream_t) all subsequent batch calls are enqueued on; NULL = default stream.  The per-batch workspace
- * belongs to the context: calls on one context must not overlap (one context per host thread / stream: mkt_ctx_fork).
+ * belongs to the context, so CALLS ON ONE CONTEXT RUN IN THE ORDER THEY WERE MADE, WHATEVER STREAM EACH WAS ENQUEUED ON: when
+ * mkt_set_stream moves the context to another stream, that stream first waits (one event, no host synchronisation) for everything
+ * the context enqueued on the stream it leaves.  The stream it leaves must therefore still exist at that moment.  Naming the stream
+ * the context is on already does nothing.  Only the context's own calls are ordered this way: one context still serves one host
+ * thread at a time (a context per concurrent caller: mkt_ctx_fork).
  * STREAM ORDER.  A context made by mkt_ctx_create starts on the NULL stream.  A context made by mkt_ctx_fork starts on its
  * OWN stream, created hipStreamNonBlocking: its calls are NOT ordered against work on the NULL stream or on any other
  * stream.  A caller that hands MKT_MEM_DEVICE buffers to a fork must order producer and consumer itself: point the fork at

@@ -148,6 +148,7 @@ struct mkt_ctx {
     int dev_order = MKT_DEVORDER;   // device point order of this context's resident tables (fft_device.h dev_pos)
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;   // a fork's own non-blocking stream (destroyed with the context); `stream` may be re-pointed by mkt_set_stream
+    hipEvent_t moved = nullptr;         // mkt_set_stream: recorded on the stream the context leaves, waited for by the one it moves to (no timing; destroyed with the context)
     std::string err;
     std::shared_ptr<KeySet> ks;  // shared with the contexts forked from this one
     bool exact = false;          // MKT_ARITH_EXACT (integer NTT, two 30-bit primes)
@@ -842,6 +843,7 @@ int mkt_ctx_destroy(mkt_ctx *c) {
     clear_spans(c);
     c->ws = Workspace();           // every owner lets go here: before the fork's stream and the key set
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    if (c->moved) (void)hipEventDestroy(c->moved);
     delete c;                      // drops this context's reference to the key set; the last one frees it
     return MKT_OK;
 }
@@ -914,7 +916,19 @@ int mkt_internal_device_of(const mkt_ctx *c) { return c ? c->device : -1; }
 size_t mkt_internal_lwe_len(const mkt_ctx *c) { return c ? (size_t)c->sh.lwe_len : 0; }
 size_t mkt_internal_acc_bytes(const mkt_ctx *c) { return c ? (size_t)(1 + c->sh.kacc) * poly_bytes(c) : 0; }
 
-int mkt_set_stream(mkt_ctx *c, void *hip_stream) { if (!c) return MKT_ERR_ARG; c->stream = (hipStream_t)hip_stream; return MKT_OK; }
+// Calls on one context run in the order they were made, whatever stream each was enqueued on: the workspace is the context's, so the stream it moves to
+// waits for everything enqueued on the stream it leaves (one event, recorded there).  Naming the stream it is on already costs nothing
+int mkt_set_stream(mkt_ctx *c, void *hip_stream) {
+    if (!c) return MKT_ERR_ARG;
+    const hipStream_t next = (hipStream_t)hip_stream;
+    if (next == c->stream) return MKT_OK;
+    DevGuard dg(c->device);
+    if (!c->moved) HIPCHK(c, hipEventCreateWithFlags(&c->moved, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->moved, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(next, c->moved, 0));
+    c->stream = next;
+    return MKT_OK;
+}
 
 int mkt_get_stream(mkt_ctx *c, void **hip_stream) { if (!c || !hip_stream) return MKT_ERR_ARG; *hip_stream = (void *)c->stream; return MKT_OK; }
 

@@ -426,7 +426,9 @@ class Scheme(_Batched):
     def _follow_torch(self, tensors):
         """GPU tensors must live on this scheme's device; unless the caller pinned a stream with set_stream, the engine enqueues on
         torch's CURRENT stream of that device, so its kernels are ordered with the producer and the consumer of the tensors like any
-        torch op"""
+        torch op.  Calls on one Scheme run in the order they were made, whatever stream each was enqueued on: when the current stream
+        has changed since the last call, mkt_set_stream makes the new one wait for what this Scheme enqueued on the old one (the
+        workspace is the Scheme's); while it stays the same the call below does nothing"""
         for t in tensors:
             if t.device.index != self.device:
                 raise ValueError(f"tensor lives on cuda:{t.device.index}, this scheme on device {self.device}")

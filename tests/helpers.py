@@ -519,14 +519,24 @@ def ks_at_edge_check(p, so, sg, rng, batches, coefs, device=True):
 _SIGNED = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
 
 
+def _signed(a):
+    return a.view(_SIGNED.get(a.dtype, a.dtype))
+
+
+def device_tensor(a):
+    """the GPU tensor to_mem makes of a contiguous host array: copied on torch's current stream, the host waiting for it.  The one place
+    it is made, so that the stream-order tests can put LateProducer.tensor here (pytest's monkeypatch) and leave every step function alone"""
+    import torch
+    return torch.from_numpy(_signed(a)).cuda()
+
+
 def to_mem(a, mem):
     """a host array as the argument of a call in memory kind `mem`: its own contiguous copy (MEM_HOST) or a GPU tensor of the same words
     (MEM_DEVICE; torch has no unsigned 32- / 64-bit tensors: the signed type of the same size)"""
     a = np.array(a, order="C", copy=True)
     if mem == mk.MEM_HOST:
         return a
-    import torch
-    return torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype))).cuda()
+    return device_tensor(a)
 
 
 def host_words(x):
@@ -553,3 +563,49 @@ def fresh(make, call):
         return host_words(call(s))
     finally:
         s.close()
+
+
+# ---- a producer that is late on purpose (tests/test_gpu_stream_order.py; the case lists are tests/stream_cases.py) ----
+def sleep_cycles_per_ms():
+    """how many cycles of torch.cuda._sleep last one millisecond on this GPU: _sleep(10**7) between two timing events, after a short one
+    that takes the first launch's set-up out of the measurement"""
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(10**5)
+    torch.cuda.synchronize()
+    a.record()
+    torch.cuda._sleep(10**7)
+    b.record()
+    b.synchronize()
+    return 10**7 / a.elapsed_time(b)
+
+
+class LateProducer:
+    """Device tensors whose real words arrive late.  delay() enqueues a spin of `cycles` on `stream`; tensor(a) -- what device_tensor is
+    replaced with -- returns a tensor that holds POISON (all-zero words: valid indices, selectors, gate codes and ciphertext words for
+    every entry point, so a mis-ordered call computes wrong words and never faults), written and waited for on a side stream at once, and
+    enqueues on `stream`, behind the delay, the asynchronous copy of the real words from pinned host memory.  A call that is ordered behind
+    `stream` reads the real words; any step of it that is not reads zeros, every time.  The poison is written, not assumed: the caching
+    allocator may hand out the block that held the real words a moment before.  Everything made here is kept until the caller has drained
+    the device and drops the producer"""
+
+    def __init__(self, stream, cycles, side=None):
+        import torch
+        self.stream, self.cycles, self.side, self.kept = stream, int(cycles), side or torch.cuda.Stream(), []
+
+    def delay(self):
+        import torch
+        with torch.cuda.stream(self.stream):
+            torch.cuda._sleep(self.cycles)
+
+    def tensor(self, a):
+        import torch
+        assert a.size and a.view(np.uint8).any(), "the real words are the poison words: this tensor could not show a mis-ordered read"
+        host = torch.from_numpy(_signed(a)).pin_memory()
+        with torch.cuda.stream(self.side):
+            t = torch.zeros(host.shape, dtype=host.dtype, device="cuda")
+        self.side.synchronize()
+        with torch.cuda.stream(self.stream):
+            t.copy_(host, non_blocking=True)
+        self.kept.append((host, t))
+        return t
