@@ -93,7 +93,10 @@ enum {
                              On such a KMS context mkt_kms_phase1_batch returns the rows as split residue tables
                              [B][rows][2 polynomials][low, high half][N] uint64 (Montgomery form)   */
 };
-/* where batch pointers live */
+/* where batch pointers live.  ALIGNMENT: a buffer, in either memory, needs the alignment of its element type and no more -- 1 byte for gate codes,
+ * 4 for 32-bit words, 8 for 64-bit words, 16 for the complex Float64 values of a transform -- whatever its row length: the kernels that move 16
+ * bytes at a time find the 16-byte boundaries of a row themselves.  The one exception is stated at mkt_seeded_keys_expand, which refuses
+ * (MKT_ERR_ARG) what it cannot take.  tests/test_gpu_footprint.py runs every batch call on buffers so aligned and no better. */
 enum { MKT_MEM_DEVICE = 0, MKT_MEM_HOST = 1 };
 /* key data formats */
 enum {
@@ -169,7 +172,13 @@ const char *mkt_last_kernel_name(const mkt_ctx *ctx);
  * met by the Float64 kernel: a DIAGNOSTIC beside the proven bound, not a certificate; 0 when the integer NTT served).
  * Of the blind-rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" -- the gadget length and the log2 of the
  * gadget base that the instantiation which ran holds as COMPILE-TIME constants, each 0 where it takes the value at run time (and after
- * mkt_exact_polymul_batch).  They say which specialisation of a kernel name a call reached (the tests assert it); no result depends on them */
+ * mkt_exact_polymul_batch).  They say which specialisation of a kernel name a call reached (the tests assert it); no result depends on them.
+ * MEMORY GUARDS (diagnostic): with MKT_MEM_GUARD=<KiB> in the environment at mkt_ctx_create / mkt_multi_create (0 or unset: off; no batch call reads
+ * it), every device buffer the library allocates from then on -- key tables, workspace, staged copies -- lies between two filled guards of that length.
+ * "mem_guard_check" drains the context's device, compares the guards of every live buffer of that device and gives the number of guards found written
+ * since the process started (buffers are also compared when they are freed; mkt_last_error then describes the latest finding: which guard, the
+ * buffer's size, the first changed byte); "mem_guard_buffers" is how many buffers that sweep looked at, "mem_guard_released" how many were compared
+ * at their release so far.  It sees stores only, and only those that leave a buffer by less than a guard */
 int mkt_get_metric(mkt_ctx *ctx, const char *name, double *out);
 
 /* twiddle tables (fft.jl:31-41): which = 0 Psi, 1 Psiinv, 2 roots, 3 rootsinv; M complex each.
@@ -599,7 +608,8 @@ const uint8_t *mkt_client_mask_seed(const mkt_client_party *p);                 
  * mkt_load_ksk.  Either pair (brk_seeded, brk_out) / (ksk_seeded, ksk_out) may be NULL */
 int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded,
                                   void *brk_out, uint32_t *ksk_out);
-/* the same words written by the GPU of `ctx` into caller memory; the four arrays live in `mem` (device pointers 16-byte aligned).  Needs no
+/* the same words written by the GPU of `ctx` into caller memory; the four arrays live in `mem`.  With MKT_MEM_DEVICE, brk_seeded and brk_out must
+ * be 16-byte aligned (the kernel moves them 16 bytes at a time): another pointer is MKT_ERR_ARG, before anything is launched or written.  Needs no
  * key loaded and changes no resident table */
 int mkt_seeded_keys_expand(mkt_ctx *ctx, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded, void *brk_out,
                            uint32_t *ksk_out, int mem);

@@ -114,9 +114,9 @@ struct KeySet {
     DevBuf d_pack; int pack_l = 0, pack_logB = 0; size_t pack_party_bytes = 0;
     std::vector<uint8_t> pack_loaded;   // [party]
     ResidentTable tab[T_COUNT];  // describe_key_set
+    DevBuf own[T_COUNT];         // the owner of each table's memory (device_mem.h: guarded in guard mode like every other buffer); *tab[t].slot is own[t].p under the table's type
     size_t stride(KeyTable t) const { return tab[t].elems; }   // elements from one party's rows to the next
     template <class T> T *party(KeyTable t, int party) const { return static_cast<T *>(*tab[t].slot) + (size_t)party * tab[t].elems; }   // base of one party's rows
-    ~KeySet() { for (const ResidentTable &t : tab) if (t.slot && *t.slot) (void)hipFree(*t.slot); }
 };
 // a key set lets go of its tables and owners under its own device, whoever drops the last reference
 static std::shared_ptr<KeySet> new_key_set() { return std::shared_ptr<KeySet>(new KeySet, [](KeySet *k) { DevGuard g(k->device); delete k; }); }
@@ -525,9 +525,13 @@ int lut_chunk(mkt_ctx *c, const LutChunk &k, const uint32_t *lin, uint32_t *out,
 struct Staged {
     mkt_ctx *c; void *dev = nullptr; size_t bytes = 0; DevBuf own;   // dev: the caller's device array, or own.p -- a host array's copy for this call
     template <class T> T *as() const { return static_cast<T *>(dev); }
-    int in(const void *ptr, size_t nbytes, int mem, bool copy_in) {
+    // align: what the kernels that are handed `dev` need beyond the alignment of the element type (mktfhe.h "ALIGNMENT"); a staged copy has hipMalloc's
+    int in(const void *ptr, size_t nbytes, int mem, bool copy_in, size_t align = 1) {
         bytes = nbytes;
-        if (mem == MKT_MEM_DEVICE) { dev = const_cast<void *>(ptr); return MKT_OK; }
+        if (mem == MKT_MEM_DEVICE) {
+            if (reinterpret_cast<uintptr_t>(ptr) % align) return fail(c, MKT_ERR_ARG, "a device buffer of this call must be aligned to " + std::to_string(align) + " bytes");
+            dev = const_cast<void *>(ptr); return MKT_OK;
+        }
         hipError_t e = own.alloc(nbytes);
         if (e != hipSuccess) return hipfail(c, e, "hipMalloc(staging)");
         dev = own.p;
@@ -788,6 +792,11 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
         return fail(nullptr, MKT_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", the engine is built for gfx950 only");
 
+    // MKT_MEM_GUARD (KiB; device_mem.h), read where the switches are seeded: the guard length of every buffer the process allocates from here on, 0 or unset = none
+    // (mkt_multi_create comes through here for every root shard)
+    const int guard_kib = env_int("MKT_MEM_GUARD", 0);
+    if (guard_kib < 0 || guard_kib > (1 << 20) || !mkt::memguard::set_guard_length((size_t)guard_kib * 1024)) return fail(nullptr, MKT_ERR_ARG, "MKT_MEM_GUARD: a guard length in KiB, 0 .. 2^20");
+
     auto *c = new mkt_ctx();
     c->ks = new_key_set();
     c->ks->device = device;
@@ -816,7 +825,7 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     // count, 32-bit row offsets); a larger key would read zeros silently, so it is refused here (largest shipped set: 0.25 GB)
     if (c->ks->stride(T_BRK) * sizeof(cplx) > 0x7fffffffull) { c->err = "per-party bootstrapping key exceeds the 2 GiB window of the rotation kernels' buffer descriptors"; return bail(MKT_ERR_UNSUPPORTED); }
 #define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { c->err = std::string(#call) + ": " + hipGetErrorString(_e); return bail(_e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP); } } while (0)
-    for (const ResidentTable &t : c->ks->tab) if (t.present) CK(hipMalloc(t.slot, t.bytes(np)));
+    for (int t = 0; t < T_COUNT; t++) if (c->ks->tab[t].present) { CK(c->ks->own[t].alloc(c->ks->tab[t].bytes(np))); *c->ks->tab[t].slot = c->ks->own[t].p; }
     CK(hipMemcpy(c->ks->d_slot_party, sp.data(), sp.size() * sizeof(int), hipMemcpyHostToDevice));
     CK(hipMemcpy(c->ks->d_slot_row, sr.data(), sr.size() * sizeof(int), hipMemcpyHostToDevice));
     if (c->ks->d_fx_tab) {
@@ -956,7 +965,10 @@ const char *mkt_last_kernel_name(const mkt_ctx *c) { return c ? c->last_rot_kern
 // diagnostics of the Float64-pipe EXACT implementation (fx_exact.hip): "fx_available" (1 if the loaded keys are certified and exact_impl admits it),
 // "fx_bound" (proven bound on |computed - exact| of a rounded sum for the loaded keys), "fx_kmax" (largest |key transform value|); of the last
 // mkt_exact_polymul_batch on this context: "fx_last_resid" (diagnostic), "polymul_amax" (max|a_i|), "fx_polymul_bound" (fx_polymul_bound, -1 if not evaluated);
-// of the rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" (its compile-time gadget, 0 = taken at run time)
+// of the rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" (its compile-time gadget, 0 = taken at run time);
+// of the guard mode of device_mem.h (MKT_MEM_GUARD): "mem_guard_check" drains this context's device, compares the guards of every live guarded buffer of that
+// device and gives the findings since the process started (the latest one's text: mkt_last_error), "mem_guard_buffers" the buffers that sweep looked at,
+// "mem_guard_released" the guarded buffers compared at their release so far
 int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     if (!c || !name || !out) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
@@ -968,6 +980,14 @@ int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     else if (k == "fx_polymul_bound") *out = c->pm_bound;
     else if (k == "rot_static_l") *out = c->rot_static_l;
     else if (k == "rot_static_logB") *out = c->rot_static_logB;
+    else if (k == "mem_guard_check") {
+        DevGuard dg(c->device);
+        *out = (double)mkt::memguard::sweep(c->device);
+        mkt::memguard::Finding f;
+        if (mkt::memguard::last_finding(f)) c->err = mkt::memguard::text(f);
+    }
+    else if (k == "mem_guard_buffers") *out = (double)mkt::memguard::swept();
+    else if (k == "mem_guard_released") *out = (double)mkt::memguard::released();
     else return fail(c, MKT_ERR_ARG, "mkt_get_metric: unknown metric '" + k + "'");
     return MKT_OK;
 }
@@ -1202,10 +1222,11 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
     int r;
     hipError_t e = hipSuccess;
     if (brk_seeded) {
-        if ((r = sb.in(brk_seeded, body_polys * poly_bytes(c), mem, true))) return r;
+        // seeded_brk_expand_kernel copies bodies and writes polynomials 16 bytes at a time, from the base pointers on: both refused here, before any launch, unless so aligned
+        if ((r = sb.in(brk_seeded, body_polys * poly_bytes(c), mem, true, 16))) return r;
         void *dst;
         if (load) { HIPCHK(c, full.alloc(brk_polys_total * poly_bytes(c))); dst = full.p; }
-        else { if ((r = so.in(brk_out, brk_polys_total * poly_bytes(c), mem, false))) return r; dst = so.dev; }
+        else { if ((r = so.in(brk_out, brk_polys_total * poly_bytes(c), mem, false, 16))) return r; dst = so.dev; }
         mktd::SeededBrkArgs a{};
         mkt::seed_to_key(mask_seed, a.mkey);
         a.party = party; a.unienc = p.scheme == MKT_CCS; a.kr = c->sh.kr; a.l = a.unienc ? p.l_uni : p.l_gsw;

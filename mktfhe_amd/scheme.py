@@ -518,7 +518,9 @@ class Scheme(_Batched):
     def get_metric(self, name):
         """diagnostics of the Float64-pipe EXACT implementation (mkt_get_metric): "fx_available", "fx_bound", "fx_kmax"; of the last exact_polymul:
         "polymul_amax", "fx_polymul_bound" (-1: not evaluated), "fx_last_resid" (a diagnostic, not a certificate); of the rotation launch that
-        last_kernel_name() names: "rot_static_l", "rot_static_logB" (the instantiation's compile-time gadget, 0 = taken at run time)"""
+        last_kernel_name() names: "rot_static_l", "rot_static_logB" (the instantiation's compile-time gadget, 0 = taken at run time); of the
+        guard mode of the engine's device memory (MKT_MEM_GUARD in the environment when the context is created; mktfhe.h): "mem_guard_check"
+        (drains the device, compares every guard, -> guards found written since the process started), "mem_guard_buffers" and "mem_guard_released" """
         v = C.c_double(0.0)
         self._ck(_lib.lib().mkt_get_metric(self.h, name.encode(), C.byref(v)))
         return v.value
