@@ -204,11 +204,17 @@ __global__ __launch_bounds__((2 * Plan<LOGM, LOGR>::NT)) __attribute__((amdgpu_w
     }
 }
 
+// two thread groups in one workgroup and their staging in LDS: the sizes at which the kernel exists
+template <int LM>
+constexpr bool ccs_pipe_fits() {
+    using P = Plan<LM, LOGR, 1>;
+    return 2 * P::NT <= 1024 && ((size_t)P::M + 2 * P::LDS_CPLX) * sizeof(cplx) <= 160 * 1024;
+}
 template <int LM, typename WORD, int LT, int BT>
 static hipError_t launch_ccs_pipe_one(const CcsArgs &a, size_t B, hipStream_t s) {
     using P = Plan<LM, LOGR, 1>;
     constexpr size_t LB = ((size_t)P::M + 2 * P::LDS_CPLX) * sizeof(cplx);
-    if constexpr (2 * P::NT > 1024 || LB > 160 * 1024) { return hipErrorInvalidValue; } else {
+    if constexpr (!ccs_pipe_fits<LM>()) { return hipErrorInvalidValue; } else {
         hipError_t e = set_lds(ccs_pipe_kernel<LM, WORD, LT, BT>, LB); if (e != hipSuccess) return e;
         note_rot_kernel("ccs_pipe_kernel", LT, BT);
         hipLaunchKernelGGL((ccs_pipe_kernel<LM, WORD, LT, BT>), dim3((unsigned)B), dim3(2 * P::NT), LB, s, a);
@@ -227,6 +233,21 @@ hipError_t launch_ccs_pipe(int logM, int W, const CcsArgs &a, size_t B, hipStrea
         return launch_ccs_pipe_one<LM, uint32_t, 0, 0>(a, B, s);
     });
     return hipGetLastError();
+}
+// the kernel exists at this size?  (ccs_pipe_fits, for the plan)
+bool ccs_pipe_supported(int logM) {
+    bool fits = false;
+    const auto probe = [&]() -> hipError_t { MKT_DISPATCH_LOGM(logM, { fits = ccs_pipe_fits<LM>(); }); return hipSuccess; };
+    return probe() == hipSuccess && fits;
+}
+// one thread group per ciphertext or two: plan_ccs (rot_plan.h)
+hipError_t launch_ccs(int logM, int W, const CcsArgs &a, int pipe, size_t B, hipStream_t s) {
+    RotCall c{};
+    c.logM = logM; c.W = W; c.l = a.l; c.blk_len = 1; c.kr = a.k; c.rows = 1; c.ncts = B; c.nrot = B;
+    c.ccs_pipe = pipe; c.can_ccs_pipe = ccs_pipe_supported(logM);
+    const RotPlan p = plan_ccs(c);
+    if (!p.nseg) return hipSuccess;
+    return p.seg[0].kind == RotKernel::CCS_PIPE ? launch_ccs_pipe(logM, W, a, B, s) : launch_ccs_blindrotate(logM, W, a, B, s);
 }
 
 }  // namespace mktd

@@ -401,17 +401,7 @@ int do_blindrotate(mkt_ctx *c, const uint32_t *lwe, int stride, int pre, const u
         q.l = p.l_uni; q.logB = p.logB_uni; q.brk = c->ks->d_brk; q.brk_party_stride = c->ks->stride(T_BRK); q.pub_b = c->ks->d_pub; q.crs = c->ks->d_crs;
         q.monomial = c->ks->d_monomial; q.acc = acc; q.scratch = scratch; q.vscratch = lev;
         q.stagger = c->tune.ccs_stagger; q.dev_order = c->dev_order;
-        // batches that leave compute units idle run each ciphertext on two thread groups (ccs_pipe.hip); option ccs_pipe: 0 never,
-        // 1 always, -1: below one chip-fill of one-group workgroups (4 per CU at M = 512, 2 at M = 1024)
-        const int pipe = c->tune.ccs_pipe;
-        const size_t fill = (size_t)256 * (c->logM <= 9 ? 4 : 2);
-        const bool use_pipe = pipe == 1 || (pipe < 0 && B * 2 <= fill);
-        if (use_pipe) {
-            const hipError_t e = mktd::launch_ccs_pipe(c->logM, p.W, q, B, c->stream);
-            if (e == hipSuccess) return MKT_OK;
-            if (e != hipErrorInvalidValue) return hipfail(c, e, "launch_ccs_pipe");
-        }
-        HIPCHK(c, mktd::launch_ccs_blindrotate(c->logM, p.W, q, B, c->stream));
+        HIPCHK(c, mktd::launch_ccs(c->logM, p.W, q, c->tune.ccs_pipe, B, c->stream));   // one thread group per ciphertext or two: rot_plan.h plan_ccs
         return MKT_OK;
     }
     case Route::EXACT_KMS: {   // 64-bit ring, split tables: phase 1 and phase 2 with exact products (ntt_exact.hip)

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rot_plan.h"
+
 namespace mktd {
 
 struct cplx;
@@ -52,11 +54,11 @@ struct RotArgs {
     int variant;              // tuning: 10*LOGR + transforms per group (0 = default)
     int stagger;              // start-up delay of alternate workgroup groups, in units of 512 cycles (0 = off)
     int wide;                 // latency variant: 0 automatic, 1 never, 2 always where supported (MKT_ROT_WIDE)
-    unsigned block0;          // first workgroup index of this launch (a rotation batch may be issued as several launches)
-    unsigned split;           // workgroups per launch (0 = the whole batch in one launch)
+    unsigned block0;          // first rotation of this launch: the kernels add it to their workgroup index; the caller's value (0) is RotCall::block0, run_rot_plan sets it for every launch
+    unsigned split;           // rotations per launch (MKT_ROT_SPLIT): 0 = the family's rule, (unsigned)-1 = one launch; read by rot_call for plan_k1 as an int, by no launcher and no kernel
     int dev_order;            // device point order of the resident tables (fft_device.h dev_pos)
     int map_mode;             // workgroup id -> (ciphertext, slot): 0 slot-major, 1 rows of one (ciphertext, party) eight ids apart (kernel_common.h rot_decode)
-    int blk_group;            // block schemes: rotations per workgroup -- 0 automatic, 1 one (blindrotate_k1_kernel<LB>), 2 / 4 (rot_block.hip)
+    int blk_group;            // rotations per workgroup (MKT_ROT_BLKG) -- 0 automatic, 1 one (blindrotate_k1_kernel<LB>, blindrotate_kr_kernel), 2 / 4 (rot_block.hip); read by rot_call for plan_k1 / plan_kr alone
 };
 
 // KMS phase 2 (bootstrapping.jl:448-558), one workgroup per ciphertext.
@@ -272,8 +274,18 @@ hipError_t launch_lut_extract(int W, const void *acc, int nout, int logN, int ka
 hipError_t launch_ks_at_table(const uint32_t *coef, size_t ncoef, uint32_t *src, uint32_t *coef_rows, size_t rows, hipStream_t s);
 // its gather front end: out[g] = cst[g] e_b + sum_{t<4} wt[g][t] pool[idx[g][t]] (int8 weights, 0 skips the term; rows clamped into the pool); out [B][len]
 hipError_t launch_lut_linear(const uint32_t *pool, size_t pool_rows, const uint32_t *idx, const int8_t *wt, const uint32_t *cst, uint32_t *out, int len, size_t B, hipStream_t s);
-hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);
 bool blockg_supported(int logM, int G);
+bool ccs_pipe_supported(int logM);   // the two-group CCS kernel at this size (workgroup of 2 * M / 16 threads, LDS budget; ccs_pipe.hip)
+// the rotation call of a RotArgs launch (rot_plan.h): the switches travel in the argument struct, the kernels that exist come from their predicates
+inline RotCall rot_call(int logM, int W, int kr, const RotArgs &a, size_t nrot) {
+    RotCall c{};
+    c.logM = logM; c.W = W; c.l = a.l; c.blk_len = a.blk_len; c.kr = kr;
+    c.rows = (size_t)a.rows_per_gate; c.ncts = a.ngates; c.nrot = nrot;
+    c.wide = a.wide; c.split = (int)a.split; c.blk_group = a.blk_group; c.variant = a.variant; c.block0 = a.block0;
+    c.can_wide = wide_supported(logM, a.l, a.blk_len); c.can_g2 = blockg_supported(logM, 2); c.can_g4 = blockg_supported(logM, 4);
+    return c;
+}
+hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);
 hipError_t launch_rot_blockg_u32(int logM, int G, int npolys, const RotArgs &a, size_t nslots, hipStream_t s);   // npolys = RLWE length + 1 (2; 3 at block length 1 or 3 and 4 at block length 1, 32-bit ring, G = 4)
 hipError_t launch_rot_blockg_u64(int logM, int G, int npolys, const RotArgs &a, size_t nslots, hipStream_t s);
 hipError_t launch_blindrotate_kr(int logM, int W, int kr, const RotArgs &a, size_t nrot, hipStream_t s);
@@ -282,6 +294,7 @@ hipError_t launch_blindrotate_kany(int logM, int W, int kr, const RotArgs &a, cp
 hipError_t launch_kms_phase2(int logM, int W, const Phase2Args &a, size_t B, hipStream_t s);
 hipError_t launch_ccs_blindrotate(int logM, int W, const CcsArgs &a, size_t B, hipStream_t s);
 hipError_t launch_ccs_pipe(int logM, int W, const CcsArgs &a, size_t B, hipStream_t s);   // one ciphertext on two thread groups (ccs_pipe.hip); vscratch [B][3][N]
+hipError_t launch_ccs(int logM, int W, const CcsArgs &a, int pipe, size_t B, hipStream_t s);   // one of the two by plan_ccs; pipe: the option ccs_pipe
 hipError_t launch_keyswitch(int W, const KsArgs &a, size_t B, hipStream_t s);
 bool transform_supported(int logM);
 
@@ -342,9 +355,8 @@ struct FxRotArgs {
     int logB_lev;
     void *acc_io;             // [rot][2][N] ring words, in place
     int stagger; unsigned block0; int map_mode;
-    int split;                // workgroups per launch: 0 = one chip-fill, -1 = everything in one launch (fx_exact.hip launch_fx_blindrotate)
+    int split;                // rotations per launch: 0 = the family's rule, -1 = everything in one launch; read by launch_fx_blindrotate for plan_fx alone (block0: as RotArgs)
 };
-bool fx_supported(int logM, int W, int l);
 hipError_t launch_fx_key_fwd(int logM, int W, const cplx *om, const cplx *twist, const void *p, cplx *out, size_t npolys, unsigned long long *kmax, hipStream_t s);   // out [npolys][W/16][M] or NULL (measure only); kmax: largest |transform value|^2 (bit pattern, atomicMax) or NULL
 hipError_t launch_fx_polymul(int logM, int W, const cplx *om, const cplx *twist, const cplx *nat, const void *a, const void *b, void *out, size_t B, unsigned long long *resid, hipStream_t s);
 hipError_t launch_fx_blindrotate(int logM, int W, const FxRotArgs &a, size_t nrot, hipStream_t s);

@@ -510,8 +510,6 @@ hipError_t fx_rot_launch(const FxRotArgs &a, size_t nrot, hipStream_t s) {
     default: return hipErrorInvalidValue;            \
     }
 
-bool fx_supported(int logM, int W, int l) { return logM >= 6 && logM <= 11 && (W == 32 || W == 64) && (l == 2 || l == 3); }
-
 hipError_t launch_fx_key_fwd(int logM, int W, const cplx *om, const cplx *twist, const void *p, cplx *out, size_t np, unsigned long long *kmax, hipStream_t s) {
     if (!np) return hipSuccess;
     const int grid = (int)(np < 16384 ? np : 16384);
@@ -539,29 +537,20 @@ hipError_t launch_fx_polymul(int logM, int W, const cplx *om, const cplx *twist,
     return hipGetLastError();
 }
 
+// where the batch is cut into launches: plan_fx (rot_plan.h)
 hipError_t launch_fx_blindrotate(int logM, int W, const FxRotArgs &a, size_t nrot, hipStream_t s) {
     if (!nrot) return hipSuccess;
     if (!fx_supported(logM, W, a.l)) return hipErrorInvalidValue;
-    // One launch per chip-fill on the 64-bit ring up to N = 1024.  Every rotation of a party walks the same key rows, step by step, and the workgroups of ONE fill run in
-    // lock-step, so a fill reads each row from the fabric once per L2 and then hits; in a single launch of several fills the later workgroups start whenever a slot frees,
-    // the resident ones spread over all key bits and the 4 x larger key of this arithmetic no longer fits the L2s (headline: hit rate 0.66 -> 0.96, 34.3 -> 31.6 ms).  At
-    // N = 2048 (512 workgroups per fill, hit rate 0.98 either way) the six launch tails cost more than the locality gives (KMS2party 105.2 vs 101.7 ms in one launch), on the
-    // 32-bit ring it makes no difference (profiles/r06_experiments.txt).  a.split: 0 = this rule, -1 = one launch, > 0 = that many workgroups per launch.
-    size_t chunk = nrot;
-    if (a.split == 0 && W == 64 && logM <= 9) chunk = (size_t)256 * 4;
-    else if (a.split > 0) chunk = (size_t)a.split;
-    for (size_t b0 = 0; b0 < nrot; b0 += chunk) {
-        FxRotArgs b = a;
-        b.block0 = a.block0 + (unsigned)b0;
-        const size_t n = nrot - b0 < chunk ? nrot - b0 : chunk;
-        hipError_t e = hipSuccess;
+    RotCall c{};
+    c.logM = logM; c.W = W; c.l = a.l; c.blk_len = 1; c.kr = 1; c.rows = (size_t)a.rows_per_gate; c.ncts = a.ngates; c.nrot = nrot;
+    c.split = a.split; c.block0 = a.block0; c.can_fx = true;
+    return run_rot_plan(plan_fx(c), a, [&](const RotSeg &, const FxRotArgs &b, size_t n) {
         MKT_FX_DISPATCH(logM, {
-            if (W == 64) e = a.l == 2 ? fx_rot_launch<LM, uint64_t, 2>(b, n, s) : fx_rot_launch<LM, uint64_t, 3>(b, n, s);
-            else e = a.l == 2 ? fx_rot_launch<LM, uint32_t, 2>(b, n, s) : fx_rot_launch<LM, uint32_t, 3>(b, n, s);
+            if (W == 64) return a.l == 2 ? fx_rot_launch<LM, uint64_t, 2>(b, n, s) : fx_rot_launch<LM, uint64_t, 3>(b, n, s);
+            return a.l == 2 ? fx_rot_launch<LM, uint32_t, 2>(b, n, s) : fx_rot_launch<LM, uint32_t, 3>(b, n, s);
         });
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipSuccess;
+    });
 }
 
 }  // namespace mktd

@@ -1639,16 +1639,7 @@ static hipError_t launch_rot_lt(const RotArgs &a, size_t nrot, hipStream_t s) {
     hipError_t e = set_lds(blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>, lds_bytes);
     if (e != hipSuccess) return e;
     note_rot_kernel("blindrotate_k1_kernel", LT, BT);
-    if (a.split == 0 || a.split >= nrot) {
-        hipLaunchKernelGGL((blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>), dim3((unsigned)nrot), dim3(P::NT), lds_bytes, s, a);
-        return hipGetLastError();
-    }
-    RotArgs b = a;
-    for (size_t b0 = 0; b0 < nrot; b0 += a.split) {
-        b.block0 = (unsigned)b0;
-        const size_t g = nrot - b0 < a.split ? nrot - b0 : a.split;
-        hipLaunchKernelGGL((blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>), dim3((unsigned)g), dim3(P::NT), lds_bytes, s, b);
-    }
+    hipLaunchKernelGGL((blindrotate_k1_kernel<LM, WORD, LB, LR, NB, LT, BT>), dim3((unsigned)nrot), dim3(P::NT), lds_bytes, s, a);
     return hipGetLastError();
 }
 
@@ -1677,25 +1668,17 @@ static hipError_t launch_rot_one(const RotArgs &a, size_t nrot, hipStream_t s) {
     }
 }
 
-// variant = 10*LR + NB for the plain schemes (tuning knob).  Only LR == LOGR variants are built: the device
-// point order of the key tables is tied to the points-per-thread of the schedule.
-static inline int rot_variant(const RotArgs &a, int LM) {
-    int variant = a.variant;
-    if (variant == 0) variant = (LM <= 10 || a.blk_len > 1) ? 22 : 21;   // pairs of transforms up to M = 1024 (re-measured with the specialised kernels: +4 % at M = 1024) and for the block schemes; single transforms above (LDS)
-    if ((2 * a.l) % (variant % 10) != 0) variant = (variant / 10) * 10 + 1;
-    return variant;
-}
+// variant = 10 * LR + NB as the plan resolved it (rot_plan.h rot_variant)
 template <int LM, typename WORD>
-static hipError_t launch_rot_plain(const RotArgs &a, size_t nrot, hipStream_t s) {
-    switch (rot_variant(a, LM)) {
+static hipError_t launch_rot_plain(int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
+    switch (variant) {
     case 21: return launch_rot_one<LM, WORD, 1, LOGR, 1>(a, nrot, s);
     case 22: return launch_rot_one<LM, WORD, 1, LOGR, 2>(a, nrot, s);
     default: return hipErrorInvalidValue;
     }
 }
 template <int LM, typename WORD>
-static hipError_t launch_rot_blk(const RotArgs &a, size_t nrot, hipStream_t s) {
-    const int variant = rot_variant(a, LM);
+static hipError_t launch_rot_blk(int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
     switch (a.blk_len) {
     case 2: return variant % 10 == 1 ? launch_rot_one<LM, WORD, 2, LOGR, 1>(a, nrot, s) : launch_rot_one<LM, WORD, 2, LOGR, 2>(a, nrot, s);
     case 3: return variant % 10 == 1 ? launch_rot_one<LM, WORD, 3, LOGR, 1>(a, nrot, s) : launch_rot_one<LM, WORD, 3, LOGR, 2>(a, nrot, s);
@@ -1706,105 +1689,51 @@ static hipError_t launch_rot_blk(const RotArgs &a, size_t nrot, hipStream_t s) {
 #endif  // TU 1-3, 5
 
 #if MKT_IN_TU(1)
-hipError_t launch_rot_plain_u32(int logM, const RotArgs &a, size_t nrot, hipStream_t s) {
-    MKT_DISPATCH_LOGM(logM, { return launch_rot_plain<LM, uint32_t>(a, nrot, s); });
+hipError_t launch_rot_plain_u32(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
+    MKT_DISPATCH_LOGM(logM, { return launch_rot_plain<LM, uint32_t>(variant, a, nrot, s); });
     return hipSuccess;
 }
 #endif
 #if MKT_IN_TU(2)
-hipError_t launch_rot_plain_u64(int logM, const RotArgs &a, size_t nrot, hipStream_t s) {
-    MKT_DISPATCH_LOGM(logM, { return launch_rot_plain<LM, uint64_t>(a, nrot, s); });
+hipError_t launch_rot_plain_u64(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
+    MKT_DISPATCH_LOGM(logM, { return launch_rot_plain<LM, uint64_t>(variant, a, nrot, s); });
     return hipSuccess;
 }
 #endif
 #if MKT_IN_TU(3)
-hipError_t launch_rot_block_u32(int logM, const RotArgs &a, size_t nrot, hipStream_t s) {
-    MKT_DISPATCH_LOGM(logM, { return launch_rot_blk<LM, uint32_t>(a, nrot, s); });
+hipError_t launch_rot_block_u32(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
+    MKT_DISPATCH_LOGM(logM, { return launch_rot_blk<LM, uint32_t>(variant, a, nrot, s); });
     return hipSuccess;
 }
 #endif
 #if MKT_IN_TU(5)
-hipError_t launch_rot_block_u64(int logM, const RotArgs &a, size_t nrot, hipStream_t s) {
-    MKT_DISPATCH_LOGM(logM, { return launch_rot_blk<LM, uint64_t>(a, nrot, s); });
+hipError_t launch_rot_block_u64(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s) {
+    MKT_DISPATCH_LOGM(logM, { return launch_rot_blk<LM, uint64_t>(variant, a, nrot, s); });
     return hipSuccess;
 }
 #endif
 
 #if MKT_IN_TU(0)
-hipError_t launch_rot_plain_u32(int logM, const RotArgs &a, size_t nrot, hipStream_t s);
-hipError_t launch_rot_plain_u64(int logM, const RotArgs &a, size_t nrot, hipStream_t s);
-hipError_t launch_rot_block_u32(int logM, const RotArgs &a, size_t nrot, hipStream_t s);
-hipError_t launch_rot_block_u64(int logM, const RotArgs &a, size_t nrot, hipStream_t s);
-bool wide_supported(int logM, int l, int blk_len);
+hipError_t launch_rot_plain_u32(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s);
+hipError_t launch_rot_plain_u64(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s);
+hipError_t launch_rot_block_u32(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s);
+hipError_t launch_rot_block_u64(int logM, int variant, const RotArgs &a, size_t nrot, hipStream_t s);
 hipError_t launch_blindrotate_wide(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s);
+// which kernel, how many rotations per workgroup, where the batch is cut: plan_k1 (rot_plan.h)
 hipError_t launch_blindrotate_k1(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s) {
-    if (!nrot) return hipSuccess;
-    // few rotations in flight (a single gate, small batches): the latency variant spreads one rotation over 2l thread
-    // groups of one CU; a.wide: 0 = automatic (at most one rotation per CU, M <= 512: measured 3-16 % less latency there,
-    // 2x MORE at M = 1024 where the groups need 8 points per thread), 1 = never, 2 = always where supported
-    if (a.wide != 1 && wide_supported(logM, a.l, a.blk_len) && (a.wide == 2 || (nrot <= 256 && logM <= 9)))
-        return launch_blindrotate_wide(logM, W, a, nrot, s);
-    // A batch is run in rounds of one chip-fill (256 CUs x 4 two-wave workgroups at M = 512), and a round costs one
-    // rotation's serial latency however few workgroups it holds.  A last round of at most one rotation per CU goes to the
-    // latency variant instead (3.2 instead of 5.9 ms at KMS k = 2, N = 1024); same (ciphertext, slot) numbering via block0.
-    constexpr size_t FILL = 1024;
-    if (a.wide == 0 && a.blk_len == 1 && logM == 9 && a.split == 0 && nrot > FILL && nrot % FILL != 0 && nrot % FILL <= 256 && wide_supported(logM, a.l, a.blk_len)) {
-        const size_t rem = nrot % FILL, head = nrot - rem;
-        hipError_t e = W == 64 ? launch_rot_plain_u64(logM, a, head, s) : launch_rot_plain_u32(logM, a, head, s);
-        if (e != hipSuccess) return e;
-        RotArgs b = a;
-        b.block0 = (unsigned)head;
-        return launch_blindrotate_wide(logM, W, b, rem, s);
-    }
-    // ONE chip-fill and a remainder of 288..512 rotations run as two EQUAL launches (three workgroups per CU each) instead of four
-    // per CU and then two: a round costs 3.4 / 5.0 / 5.35 / 6.3 ms at 1 / 2 / 3 / 4 workgroups per CU (KMS k = 2, N = 1024: two
-    // workgroups of a CU land on the same SIMD pair), so 2 x 5.35 beats 6.3 + 5.0 -- measured 512 KMS gates 11.2 -> 10.1 ms, 470:
-    // 11.1 -> 10.1, 448: equal, 427 (remainder 257): 9.6 -> 10.0, hence the lower bound; CGGIparam 1300 / 1536 gates 15.6 / 16.3 ->
-    // 14.5 / 14.7 ms.  Behind two or more fills the single launch drains better (853 gates: 15.6 vs 16.0 ms) and keeps the batch.
-    // Same (ciphertext, slot) numbering via block0; gates/s no longer dips below the 256-gate rate at 512 gates.
-    if (a.blk_len == 1 && logM == 9 && a.split == 0 && nrot > FILL && nrot <= 2 * FILL && nrot % FILL >= 288 && nrot % FILL <= 512) {
-        const size_t tail = FILL + nrot % FILL, head = nrot - tail, half = (tail + 1) / 2;
-        RotArgs b = a;
-        const size_t part[3] = {head, half, tail - half};
-        size_t b0 = 0;
-        for (int i = 0; i < 3; i++) {
-            if (!part[i]) continue;
-            b.block0 = a.block0 + (unsigned)b0;
-            const hipError_t e = W == 64 ? launch_rot_plain_u64(logM, b, part[i], s) : launch_rot_plain_u32(logM, b, part[i], s);
-            if (e != hipSuccess) return e;
-            b0 += part[i];
+    return run_rot_plan(plan_k1(rot_call(logM, W, 1, a, nrot)), a, [&](const RotSeg &g, const RotArgs &b, size_t n) {
+        switch (g.kind) {
+        case RotKernel::WIDE:    return launch_blindrotate_wide(logM, W, b, n, s);
+        case RotKernel::GROUPED: return W == 64 ? launch_rot_blockg_u64(logM, g.group, 2, b, (size_t)b.rows_per_gate, s) : launch_rot_blockg_u32(logM, g.group, 2, b, (size_t)b.rows_per_gate, s);
+        case RotKernel::BLOCK:   return W == 64 ? launch_rot_block_u64(logM, g.variant, b, n, s) : launch_rot_block_u32(logM, g.variant, b, n, s);
+        case RotKernel::PLAIN:   return W == 64 ? launch_rot_plain_u64(logM, g.variant, b, n, s) : launch_rot_plain_u32(logM, g.variant, b, n, s);
+        default:                 return hipErrorInvalidValue;
         }
-        return hipSuccess;
-    }
-    if (a.blk_len > 1) {
-        // block schemes: G rotations of one slot per workgroup (rot_block.hip) once the batch fills the chip that way
-        // automatic: four rotations per workgroup where that workgroup exists (M <= 512) and the batch still fills the
-        // chip with one workgroup per compute unit (measured: Blockparam 5.54 -> 5.39 ms per 1024 gates; one rotation per
-        // workgroup below that, and at M = 1024 where only two rotations fit and run 15 % slower)
-        int G = a.blk_group;
-        if (G == 0) G = (blockg_supported(logM, 4) && logM == 9 && nrot >= 1024) ? ((W == 32 && nrot >= 4096) ? 2 : 4) : 1;   // from 4096 rotations two rotations per workgroup, two workgroups per CU: 204 k against 196 k gates/s (Blockparam, 8192 and 16 384 gates)
-        // 257..512 rotations: one 4-wave workgroup of two rotations per CU instead of two 2-wave workgroups, which share a SIMD pair
-        // (tools/simd_place.hip): Blockparam 384 / 512 gates 4.51 -> 3.90 ms; up to 256 and from 513 to 1023 one rotation per workgroup is ahead
-        if (a.blk_group == 0 && W == 32 && logM == 9 && nrot > 256 && nrot <= 512 && blockg_supported(logM, 2)) G = 2;
-        // 64-bit ring at M = 1024 (KMS_block, params.jl:87-125): two rotations per workgroup halve the key elements a thread holds, which
-        // leaves room to re-request each for the next digit right after its last use (rot_block.hip); ahead up to about one KMS2partyblock
-        // batch of 1024 gates (512 / 1024 gates: 16.6 / 32.3 ms against 17.2 / 33.3), behind from 2048 (63.4 against 62.5 ms)
-        if (a.blk_group == 0 && W == 64 && logM == 10 && nrot >= 1536 && nrot <= 4096 && blockg_supported(logM, 2)) G = 2;
-        if (G > 1 && blockg_supported(logM, G) && a.blk_len >= 2 && a.blk_len <= 4) {
-            const size_t nslots = (size_t)a.rows_per_gate;
-            const hipError_t e = W == 64 ? launch_rot_blockg_u64(logM, G, 2, a, nslots, s) : launch_rot_blockg_u32(logM, G, 2, a, nslots, s);
-            if (e != hipErrorInvalidValue) return e;     // a shape the grouped kernels do not cover (LDS budget): one rotation per workgroup below
-        }
-        return W == 64 ? launch_rot_block_u64(logM, a, nrot, s) : launch_rot_block_u32(logM, a, nrot, s);
-    }
-    return W == 64 ? launch_rot_plain_u64(logM, a, nrot, s) : launch_rot_plain_u32(logM, a, nrot, s);
+    });
 }
 #endif  // TU 0
 
 #if MKT_IN_TU(7)
-#ifndef MKT_KR_BLKG_MIN
-#define MKT_KR_BLKG_MIN 1     // rotations from which the grouped kernel is the default: ahead at every batch size (128 gates: 9.1 vs 13.9 ms, tools/blkg_ab.sh)
-#endif
 template <int LM, typename WORD, int KR, bool BLK, int BL = 0>
 static hipError_t launch_kr_one(const RotArgs &a, size_t nrot, hipStream_t s) {
     using P = Plan<LM, LOGR>;
@@ -1822,27 +1751,17 @@ static hipError_t launch_kr_word(int kr, const RotArgs &a, size_t nrot, hipStrea
     return kr == 2 ? launch_kr_one<LM, WORD, 2, false>(a, nrot, s) : launch_kr_one<LM, WORD, 3, false>(a, nrot, s);
 }
 
+// grouped kernel or not: plan_kr (rot_plan.h)
 hipError_t launch_blindrotate_kr(int logM, int W, int kr, const RotArgs &a, size_t nrot, hipStream_t s) {
-    if (!nrot) return hipSuccess;
-    if (kr < 2 || kr > 3) return hipErrorInvalidValue;
-    // 32-bit ring, LMSS with RLWE length 2 and block length 3, CGGI with RLWE length 2 or 3: four rotations per workgroup share every
-    // key element (rot_block.hip); blk_group (MKT_ROT_BLKG): 0 = by batch size, 1 = never, 4 = always
-    if (W == 32 && a.ngates == nrot && ((kr == 2 && (a.blk_len == 3 || a.blk_len == 1)) || (kr == 3 && a.blk_len == 1))) {
-        int G = a.blk_group;
-        // by default where it measured ahead (tools/blkg_ab.sh, tools/kr_time.py): block length 3 at RLWE length 2 (14.1 -> 10.0 ms per 1024
-        // gates) and the plain CMux at RLWE length 3 (38.8 -> 24.3 ms); the plain CMux at RLWE length 2 stays on the one-rotation kernel
-        // (17.0 vs 17.9 ms at 1024 gates, 13.0 vs 17.8 at 256)
-        if (G == 0) G = (blockg_supported(logM, 4) && nrot >= MKT_KR_BLKG_MIN && !(kr == 2 && a.blk_len == 1)) ? 4 : 1;
-        if (G == 4 && blockg_supported(logM, 4)) {
-            const hipError_t e = launch_rot_blockg_u32(logM, 4, kr + 1, a, (size_t)a.rows_per_gate, s);
-            if (e != hipErrorInvalidValue) return e;
-        }
-    }
-    MKT_DISPATCH_LOGM(logM, {
-        if (W == 64) return launch_kr_word<LM, uint64_t>(kr, a, nrot, s);
-        return launch_kr_word<LM, uint32_t>(kr, a, nrot, s);
+    if (kr < 2 || kr > 3) return nrot ? hipErrorInvalidValue : hipSuccess;
+    return run_rot_plan(plan_kr(rot_call(logM, W, kr, a, nrot)), a, [&](const RotSeg &g, const RotArgs &b, size_t n) {
+        if (g.kind == RotKernel::GROUPED) return launch_rot_blockg_u32(logM, g.group, kr + 1, b, (size_t)b.rows_per_gate, s);
+        MKT_DISPATCH_LOGM(logM, {
+            if (W == 64) return launch_kr_word<LM, uint64_t>(kr, b, n, s);
+            return launch_kr_word<LM, uint32_t>(kr, b, n, s);
+        });
+        return hipSuccess;
     });
-    return hipSuccess;
 }
 #endif  // TU 7
 
@@ -2151,7 +2070,6 @@ static hipError_t launch_wide_lm(const RotArgs &a, size_t nrot, hipStream_t s) {
     default: return hipErrorInvalidValue;
     }
 }
-bool wide_supported(int logM, int l, int blk_len) { return blk_len == 1 && logM >= 8 && logM <= 10 && l >= 2 && l <= 4; }
 hipError_t launch_blindrotate_wide(int logM, int W, const RotArgs &a, size_t nrot, hipStream_t s) {
     if (!nrot) return hipSuccess;
     switch (logM) {

@@ -1630,34 +1630,38 @@ hipError_t launch_ntt_fwd_split(int logN, const uint64_t *tab, const void *p, ui
 #endif  // unit 0
 #if MKT_NTT_IN(2)
 hipError_t launch_exact_kms_phase1(int logN, const uint64_t *tab, const ExactKmsArgs &a, size_t B, hipStream_t s) {      // internal: phase 1 of launch_exact_kms (unit 2)
-    if (!B || a.phase2_only) return hipSuccess;
+    if (!B || a.phase2_only) return hipSuccess;                                      // phase2_only: phase 1 ran on the Float64 pipe (fx_exact.hip) and levkey holds its rows
     note_rot_kernel("exact_kms_phase1_kernel");
+    RotCall c{};                                                                     // which of the four kernels: plan_exact_kms_phase1 (rot_plan.h)
+    c.logM = logN - 1; c.W = 64; c.l = a.l_gsw; c.blk_len = a.blk_len; c.kr = 1; c.rows = (size_t)a.rtot; c.ncts = B; c.nrot = B * (size_t)a.rtot; c.exact_wide = a.wide;
+    const RotKernel kind = plan_exact_kms_phase1(c).seg[0].kind;
     const uint4 *tb = reinterpret_cast<const uint4 *>(tab);
     MKT_NTT_DISPATCH(logN, {
         const size_t lds = lds_bytes<LN>(1, 2);                                      // two staging buffers: the halves of a lifted sum are inverse-transformed side by side
         hipError_t e = hipSuccess;
-        if (a.phase2_only) {                                                       // phase 1 ran on the Float64 pipe (fx_exact.hip) and levkey holds its rows
-        } else if (a.blk_len > 1 && a.wide != 0) {                                // exact_wide = 0: the per-key-bit kernel below (tests force both)
+        switch (kind) {
+        case RotKernel::XKMS_BLOCK_WIDE:
             note_rot_kernel("exact_kms_block_phase1_kernel");
             e = ntt_set_lds(exact_kms_block_phase1_kernel<LN>, lds); if (e != hipSuccess) return e;
             hipLaunchKernelGGL((exact_kms_block_phase1_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride, a.mono,
                                a.lwe, a.lwe_stride, a.pre_switched, a.n, a.l_gsw, a.logB_gsw, a.blk_len, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
-        } else if (a.blk_len > 1) {
+            break;
+        case RotKernel::XKMS_BLOCK:
             e = ntt_set_lds(exact_kms_phase1_kernel<LN, true>, lds); if (e != hipSuccess) return e;
             hipLaunchKernelGGL((exact_kms_phase1_kernel<LN, true>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride, a.mono,
                                a.lwe, a.lwe_stride, a.pre_switched, a.n, a.l_gsw, a.logB_gsw, a.blk_len, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
-        } else {
-            if (a.wide != 0 && a.l_gsw == 2) {                                     // the paired-transform kernel (default); exact_wide = 0: the one-at-a-time kernel below (tests force both)
-                const size_t lds2 = lds_bytes<LN>(1, 2);
-                note_rot_kernel("exact_kms_phase1_p2pf_kernel");
-                e = ntt_set_lds(exact_kms_phase1_p2pf_kernel<LN>, lds2); if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((exact_kms_phase1_p2pf_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds2, s, tb, a.brk, a.brk_party_stride,
-                                   a.lwe, a.lwe_stride, a.pre_switched, a.n, a.logB_gsw, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
-            } else {
-                e = ntt_set_lds(exact_kms_phase1_kernel<LN, false>, lds); if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((exact_kms_phase1_kernel<LN, false>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride, a.mono,
-                                   a.lwe, a.lwe_stride, a.pre_switched, a.n, a.l_gsw, a.logB_gsw, 1, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
-            }
+            break;
+        case RotKernel::XKMS_P2PF:
+            note_rot_kernel("exact_kms_phase1_p2pf_kernel");
+            e = ntt_set_lds(exact_kms_phase1_p2pf_kernel<LN>, lds); if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((exact_kms_phase1_p2pf_kernel<LN>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride,
+                               a.lwe, a.lwe_stride, a.pre_switched, a.n, a.logB_gsw, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
+            break;
+        default:
+            e = ntt_set_lds(exact_kms_phase1_kernel<LN, false>, lds); if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((exact_kms_phase1_kernel<LN, false>), dim3((unsigned)(B * (size_t)a.rtot)), dim3(1 << (LN - NLR)), lds, s, tb, a.brk, a.brk_party_stride, a.mono,
+                               a.lwe, a.lwe_stride, a.pre_switched, a.n, a.l_gsw, a.logB_gsw, 1, B, a.rtot, a.slot_party, a.slot_row, a.logB_lev, a.levkey);
+            break;
         }
     });
     return hipGetLastError();
