@@ -109,14 +109,16 @@ enum {
 typedef struct {
     int32_t scheme;          /* MKT_CGGI .. MKT_KMS_BLOCK */
     int32_t n;               /* LWE dimension per party (block schemes: blk_d * blk_len) */
-    int32_t N;               /* ring dimension (power of two, 256..4096) */
+    int32_t N;               /* ring dimension (power of two, 32..4096) */
     int32_t k;               /* SK: RLWE length (any; beyond 3 on a run-time-k kernel, F64REF only); MK: number of parties */
     int32_t W;               /* ring word bits: 32 or 64 */
     int32_t l_gsw, logB_gsw; /* RGSW gadget (CGGI/LMSS/KMS) */
     int32_t l_lev, logB_lev; /* LEV gadget (KMS) */
     int32_t l_uni, logB_uni; /* UniEnc gadget (CCS/KMS) */
     int32_t f, logD;         /* key-switch gadget */
-    int32_t blk_len, blk_d;  /* block length and count (LMSS/KMS_block) */
+    int32_t blk_len, blk_d;  /* block length and count (LMSS/KMS_block).  Any block length >= 1 is a valid parameter; an MKT_ARITH_F64REF context serves
+                                block length 1 .. 4 at RLWE length 1 (LMSS with k = 1, KMS_block) and mkt_ctx_create refuses a longer one there with
+                                MKT_ERR_UNSUPPORTED.  LMSS with k >= 2 and MKT_ARITH_EXACT contexts serve any block length */
 } mkt_params;
 
 typedef struct mkt_ctx mkt_ctx;

@@ -649,7 +649,7 @@ bool exact_gate_ok(const mkt_ctx *c) {
     return bound < half_P;
 }
 #define MKT_EXACT_GATE(c) do { if ((c) && (c)->exact && !exact_gate_ok(c)) return fail((c), MKT_ERR_UNSUPPORTED, "MKT_ARITH_EXACT evaluates gates for CGGI and LMSS (32-bit ring), for CCS (32-bit ring) and for KMS / KMS_block (64-bit ring, tables split in 32-bit halves), gadgets within the two-prime modulus; other schemes offer the transform-level entry points (mkt_transform_*_batch, mkt_exact_polymul_batch)"); } while (0)
-#define MKT_F64_OR_EXACT_KMS(c) do { if ((c) && (c)->exact && !(mkt::is_mk((c)->p.scheme) && exact_gate_ok(c))) return fail((c), MKT_ERR_UNSUPPORTED, "on an MKT_ARITH_EXACT context this entry point serves the multi-key gate paths only"); } while (0)
+#define MKT_F64_OR_EXACT_KMS(c) do { if ((c) && (c)->exact && !mkt::is_mk((c)->p.scheme)) return fail((c), MKT_ERR_UNSUPPORTED, "on an MKT_ARITH_EXACT context this entry point serves the multi-key gate paths only"); MKT_EXACT_GATE(c); } while (0)   // (a multi-key set beyond the modulus: the refusal that names it)
 #define MKT_F64_ONLY(c) do { if ((c) && (c)->exact) return fail((c), MKT_ERR_UNSUPPORTED, "this entry point is the Float64-reference gate path; not offered by an MKT_ARITH_EXACT context"); } while (0)
 
 // ---- MKT_ARITH_EXACT on the Float64 pipe (fx_exact.hip) ----
@@ -773,6 +773,10 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     if (arith_mode != MKT_ARITH_F64REF && arith_mode != MKT_ARITH_EXACT) return fail(nullptr, MKT_ERR_ARG, "unknown arithmetic mode");
     const int logN = __builtin_ctz((unsigned)params->N);
     if (!mktd::transform_supported(logN - 1)) return fail(nullptr, MKT_ERR_UNSUPPORTED, "ring dimension not instantiated (N must be 32..4096)");
+    // the Float64 rotation of a block scheme with one mask polynomial (LMSS at RLWE length 1, KMS_block) holds the block length as a template
+    // constant, 1 .. 4 (kernels.hip launch_rot_blk, rot_block.hip launch_blk_lb); refused here, not by the first rotation's launcher
+    if (arith_mode == MKT_ARITH_F64REF && (params->scheme == MKT_KMS_BLOCK || (params->scheme == MKT_LMSS && params->k == 1)) && params->blk_len > 4)
+        return fail(nullptr, MKT_ERR_UNSUPPORTED, "block length beyond 4 is not instantiated for MKT_ARITH_F64REF at RLWE length 1 (LMSS with k = 1, KMS_block): block length 1 .. 4 there, any with k >= 2 or under MKT_ARITH_EXACT");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) return fail(nullptr, MKT_ERR_NO_DEVICE, "no HIP device available: the engine has no CPU fallback");

@@ -760,7 +760,7 @@ static void ks_balanced_word(const ora_scheme *s, int party, int c, int j, uint3
 static void keyswitch_lmss(const ora_scheme *s, const uint64_t *acc, uint32_t *out) {
     int n = s->p.n, N = s->p.N;
     memset(out, 0, sizeof(uint32_t) * (size_t)(n + 1));
-    out[n] = (uint32_t)acc[0];                                                     /* :174 */
+    out[n] = (uint32_t)(acc[0] >> (s->p.W - 32));                                  /* :174; a 64-bit ring word is truncated to the LWE word, as every extracted word is */
     int current = 0; /* 0-based `current - 1` */
     for (int i = 0; i < s->p.k; i++) {
         const uint64_t *a = acc + (size_t)(1 + i) * N;

@@ -4,6 +4,8 @@
 // the dynamic LDS bytes and, for the kernels whose first argument carries one, block0.  main drives the public launchers (device_api.h) over
 // the shipped shapes, one shape per transform size, the batch sizes around every cutting rule and the switch values of
 // tests/test_gpu_switches.py, and ends with the line count and an FNV-1a digest of the log.  `log` as first argument prints the log itself.
+// `kernels` prints every instantiation the units registered, launched or not; `reach` answers, for the shapes and option settings on its
+// standard input, which of them a call launches (tests/test_size_ladder_cpu.py: no instantiation without a case).
 //
 // One source for two trees: tests/test_rot_plan_cpu.py pins the digest of this program built against the commit before rot_plan.h.  That
 // commit has no launch_ccs: its rule (one thread group per ciphertext or two) stood in context.cpp's do_blindrotate, and a build against it
@@ -40,6 +42,8 @@ hipError_t launch_ccs(int logM, int W, const CcsArgs &q, int pipe, size_t B, hip
 namespace {
 
 bool g_print = false;
+bool g_reach = false;            // `reach`: hipLaunchKernel notes the instantiation and logs nothing
+std::string g_reached;
 uint64_t g_hash = 0xcbf29ce484222325ull;
 size_t g_lines = 0;
 void emit(const std::string &line) {
@@ -80,6 +84,7 @@ hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *lds, hipSt
 hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t) {
     const auto it = names().find(fn);
     const std::string n = it == names().end() ? "?" : it->second;
+    if (g_reach) { g_reached += (g_reached.empty() ? "" : " | ") + n; return hipSuccess; }
     char tail[96];
     long block0 = -1;                                                  // the kernels whose first argument is a RotArgs / an FxRotArgs
     if (n.rfind("blindrotate_k1_kernel", 0) == 0 || n.rfind("blindrotate_wide_kernel", 0) == 0 || n.rfind("blindrotate_kr_kernel", 0) == 0 ||
@@ -180,9 +185,108 @@ void ccs_calls(const Shape &sh, size_t B, int pipe) {
     done(launch_ccs(logm(sh), sh.W, q, pipe, B, nullptr));
 }
 
+// ---- `kernels`: every instantiation the units registered, launched or not, one per line
+int print_kernels() {
+    std::map<std::string, int> sorted;
+    for (const auto &kv : names()) sorted[kv.second]++;
+    for (const auto &kv : sorted) puts(kv.first.c_str());
+    return 0;
+}
+
+// ---- `reach`: one shape and one option setting per line of standard input, as key=value words (the members of Reach; scheme by name); the
+// route is that of context.cpp (rot_route / do_blindrotate) over the same public launchers, and the answer is one line: the tag, then every
+// instantiation launched, in order, " | " between them, or the launcher's refusal.  fx stands for fx_usable of a certified key: the
+// Float64 pipe wherever exact_impl admits it and the kernel exists for the shape
+struct Reach {
+    char tag[64] = "-", scheme[16] = "CGGI";
+    int N = 256, k = 1, W = 32, l = 3, logB = 9, blk_len = 1, rows = 1, count = 5;
+    int variant = 0, wide = 0, blkg = 0, split = 0, ccs_pipe = -1, exact = 0, exact_wide = 1, exact_kany = 0, exact_impl = -1;
+};
+bool reach_parse(char *line, Reach &q) {
+    const struct { const char *key; int Reach::*m; } ints[] = {
+        {"N", &Reach::N}, {"k", &Reach::k}, {"W", &Reach::W}, {"l", &Reach::l}, {"logB", &Reach::logB}, {"blk_len", &Reach::blk_len}, {"rows", &Reach::rows},
+        {"count", &Reach::count}, {"variant", &Reach::variant}, {"wide", &Reach::wide}, {"blkg", &Reach::blkg}, {"split", &Reach::split}, {"ccs_pipe", &Reach::ccs_pipe},
+        {"exact", &Reach::exact}, {"exact_wide", &Reach::exact_wide}, {"exact_kany", &Reach::exact_kany}, {"exact_impl", &Reach::exact_impl}};
+    for (char *tok = strtok(line, " \t\n"); tok; tok = strtok(nullptr, " \t\n")) {
+        char *eq = strchr(tok, '=');
+        if (!eq) return false;
+        *eq = 0;
+        bool known = false;
+        if (!strcmp(tok, "tag")) { snprintf(q.tag, sizeof q.tag, "%s", eq + 1); known = true; }
+        if (!strcmp(tok, "scheme")) { snprintf(q.scheme, sizeof q.scheme, "%s", eq + 1); known = true; }
+        for (const auto &f : ints) if (!strcmp(tok, f.key)) { q.*f.m = atoi(eq + 1); known = true; }
+        if (!known) return false;
+    }
+    return true;
+}
+hipError_t reach_one(const Reach &q) {
+    const char *const schemes[] = {"CGGI", "LMSS", "CCS", "KMS", "KMS_BLOCK"};
+    int sc = -1;
+    for (int i = 0; i < 5; i++) if (!strcmp(q.scheme, schemes[i])) sc = i;
+    if (sc < 0 || q.N < 32 || q.N > 4096 || (q.N & (q.N - 1)) || q.count < 1 || q.rows < 1) return hipErrorInvalidValue;
+    const bool kms = sc == KMS || sc == KMS_BLOCK, block = sc == LMSS || sc == KMS_BLOCK;
+    const Shape sh{q.tag, (Scheme)sc, q.N, q.k, q.W, q.l, q.logB, block ? q.blk_len : 1, kms ? q.rows : 1};
+    const int lm = logm(sh), logN = lm + 1;
+    const size_t B = (size_t)q.count, nrot = B * (size_t)sh.rows;
+    cplx *const scratch = reinterpret_cast<cplx *>(16);
+    uint64_t *const xscratch = reinterpret_cast<uint64_t *>(16);
+    if (!q.exact) {
+        if (sc == CCS) { CcsArgs c{}; c.k = sh.k; c.l = sh.l; c.logB = sh.logB; return launch_ccs(lm, sh.W, c, q.ccs_pipe, B, nullptr); }
+        RotArgs a = rot_args(sh, nrot, Opts{q.variant, q.wide, q.blkg, q.split});
+        a.blk_accum = block;
+        if (kms) {
+            const hipError_t e = launch_blindrotate_k1(lm, sh.W, a, nrot, nullptr);
+            if (e != hipSuccess) return e;
+            Phase2Args p2{};
+            return launch_kms_phase2(lm, sh.W, p2, B, nullptr);
+        }
+        if (sh.k > 3) return launch_blindrotate_kany(lm, sh.W, sh.k, a, scratch, nrot, nullptr);
+        if (sh.k > 1) return launch_blindrotate_kr(lm, sh.W, sh.k, a, nrot, nullptr);
+        return launch_blindrotate_k1(lm, sh.W, a, nrot, nullptr);
+    }
+    const bool fx = q.exact_impl != 0 && fx_supported(lm, sh.W, sh.l);
+    if (sc == CCS) { ExactCcsHostArgs c{}; c.k = sh.k; c.l = sh.l; c.logB = sh.logB; return launch_exact_ccs(logN, nullptr, c, B, nullptr); }
+    if (kms) {
+        ExactKmsArgs x{};
+        x.k = sh.k; x.l_gsw = sh.l; x.logB_gsw = sh.logB; x.rtot = sh.rows; x.blk_len = sh.blk_len; x.wide = q.exact_wide;
+        if (sc == KMS && fx) {
+            FxRotArgs f{};
+            f.l = sh.l; f.logB = sh.logB; f.split = q.split; f.map_mode = 1; f.rows_per_gate = sh.rows; f.ngates = B; f.init_mode = 1;
+            const hipError_t e = launch_fx_blindrotate(lm, sh.W, f, nrot, nullptr);
+            if (e != hipSuccess) return e;
+            x.phase2_only = 1;
+        }
+        return launch_exact_kms(logN, nullptr, x, B, nullptr);
+    }
+    if (sh.k > 3 || q.exact_kany == 1) return launch_exact_blindrotate_kany(logN, nullptr, nullptr, nullptr, nullptr, 0, 1, sh.blk_len * 3, sh.k, sh.l, sh.logB, sh.blk_len, nullptr, xscratch, B, nullptr);
+    if (sh.k > 1 || (block && sh.blk_len != 3)) return launch_exact_blindrotate_kr(logN, nullptr, nullptr, nullptr, nullptr, 0, 1, sh.blk_len * 3, sh.k, sh.l, sh.logB, sh.blk_len, nullptr, B, nullptr);
+    if (sc == CGGI && fx) {
+        FxRotArgs f{};
+        f.l = sh.l; f.logB = sh.logB; f.split = q.split; f.map_mode = 1; f.rows_per_gate = 1; f.ngates = B;
+        return launch_fx_blindrotate(lm, sh.W, f, B, nullptr);
+    }
+    return launch_exact_blindrotate(logN, nullptr, nullptr, nullptr, nullptr, 0, 1, sh.blk_len * 3, sh.l, sh.logB, sh.blk_len, nullptr, B, nullptr);
+}
+int reach_all() {
+    g_reach = true;
+    char line[1024];
+    while (fgets(line, sizeof line, stdin)) {
+        Reach q;
+        if (line[0] == '\n' || line[0] == '#') continue;
+        if (!reach_parse(line, q)) { fprintf(stderr, "reach: a word that is no known key=value\n"); return 2; }
+        g_reached.clear();
+        const hipError_t e = reach_one(q);
+        if (e != hipSuccess) g_reached += std::string(g_reached.empty() ? "" : " | ") + (e == hipErrorInvalidValue ? "-> invalid value" : "-> error");
+        printf("%s: %s\n", q.tag, g_reached.c_str());
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "kernels")) return print_kernels();
+    if (argc > 1 && !strcmp(argv[1], "reach")) return reach_all();
     g_print = argc > 1 && !strcmp(argv[1], "log");
     for (const Shape &sh : SHAPES) {
         for (const size_t count : COUNTS) {

@@ -24,7 +24,7 @@ import numpy as np
 import mpmath as mp
 from mpmath.libmp import libmpf
 
-SIZES = (16, 256, 1024, 2048, 4096)
+SIZES = (16, 32, 256, 1024, 2048, 4096)
 
 
 def rn(x, prec):

@@ -305,6 +305,38 @@ def acc_edge(p, gadgets, rng, B):
     return acc
 
 
+def single_exponent_rows(p):
+    """rows of switched exponents with exactly ONE non-zero entry: at the first / last mask position and on both sides of the first block
+    and party border, each with every value of {1, N-1, N, N+1, 2N-1, 2N} (one CMux: a mismatch points at a digit); one more row makes
+    the batch odd"""
+    N, nm = p.N, p.lwe_len - 1
+    L = p.blk_len if p.blk_len > 1 else 1
+    pos = sorted({0, nm - 1, L - 1, min(L, nm - 1)} | ({p.n - 1, p.n} if p.nparty > 1 else set()))
+    vals = (1, N - 1, N, N + 1, 2 * N - 1, 2 * N)
+    at = np.zeros((len(pos) * len(vals) + 1, nm), dtype=np.uint32)
+    for i, q in enumerate(pos):
+        for j, v in enumerate(vals):
+            at[i * len(vals) + j, q] = v
+    at[-1, nm // 2] = N + 1
+    return at
+
+
+def dense_exponents(p, rng, B):
+    at = rng.integers(0, 2 * p.N + 1, (B, p.lwe_len - 1)).astype(np.uint32)
+    at[0, :3] = [0, 2 * p.N, p.N]
+    return at
+
+
+def rot_inputs(p, B, seed):
+    """the crafted inputs of a blind rotation: the single-exponent rows, then one dense batch of B, each with accumulators on the gadgets' digit
+    boundaries and a non-zero acc.a on entry -> (atilde [R][lwe_len - 1], acc [R][1 + k][N] uint64) twice"""
+    rng = np.random.default_rng(seed)
+    for at in (single_exponent_rows(p), dense_exponents(p, rng, B)):
+        acc = acc_edge(p, rot_gadgets(p), rng, len(at))
+        assert (acc[:, 1:].reshape(len(at), -1) != 0).any(axis=1).all()                  # acc.a is not zero on entry
+        yield at, acc
+
+
 def ks_words(f, logD):
     """name -> 32-bit extracted word on a boundary of the key switch's digits (unbalanced: the fields of divbits(w, 32 - f logD),
     gsw.jl:34-40; balanced: gadget_words)"""
@@ -609,3 +641,40 @@ class LateProducer:
             t.copy_(host, non_blocking=True)
         self.kept.append((host, t))
         return t
+
+
+# ---- tests/csrc/launch_log.cpp, built over the library's rotation units (tests/test_rot_plan_cpu.py, tests/test_size_ladder_cpu.py) ----
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+LAUNCH_LOG_CSRC = os.path.join(ROOT, "mktfhe_amd", "csrc")
+
+# UNITS: (source, defines, object name): kernels.hip units 0-7, rot_block.hip at both widths, ccs_pipe.hip, fx_exact.hip, ntt_exact.hip units 1 (the
+# CGGI / LMSS rotations), 2 (KMS phase 1) and 3 (launch_exact_kms, which calls it, and CCS)
+LAUNCH_LOG_UNITS = ([("kernels.hip", [f"-DMKT_TU={t}"], f"kernels_tu{t}") for t in range(8)] + [("rot_block.hip", [f"-DMKT_BLK_WORD={w}"], f"rot_block_{w}") for w in (32, 64)]
+         + [("ccs_pipe.hip", [], "ccs_pipe"), ("fx_exact.hip", [], "fx_exact")] + [("ntt_exact.hip", [f"-DMKT_NTT_TU={t}"], f"ntt_exact_{t}") for t in (1, 2, 3)])
+
+
+def build_launch_log(csrc, out, defines=()):
+    """the launch-log program over the units of `csrc`: host-only objects, a dummy for each unit's fat-binary symbol, no HIP runtime"""
+    import re
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    hipcc = os.path.join(ROCM, "bin", "hipcc")
+    flags = ["-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-cuda-compat", "-Wno-pass-failed", "-Wno-unused-function", "-Wno-unused-value"]
+
+    def unit(u):
+        src, defs, name = u
+        obj = os.path.join(out, name + ".o")
+        subprocess.run([hipcc, "--cuda-host-only", *flags, *defs, "-c", os.path.join(csrc, src), "-o", obj], check=True, capture_output=True, text=True)
+        return obj
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        objs = list(pool.map(unit, LAUNCH_LOG_UNITS))
+    syms = sorted(set(re.findall(r"\bU (__hip_fatbin_\w+)", subprocess.run(["nm", *objs], check=True, capture_output=True, text=True).stdout)))
+    assert len(syms) == len(LAUNCH_LOG_UNITS), syms
+    fat = os.path.join(out, "fatbins.cpp")
+    with open(fat, "w") as f:
+        f.write('extern "C" {\n' + "".join(f"unsigned long long {s}[4];\n" for s in syms) + "}\n")
+    exe = os.path.join(out, "launch_log")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include"), "-I" + csrc, *defines,
+                    os.path.join(ROOT, "tests", "csrc", "launch_log.cpp"), fat, *objs, "-lpthread", "-o", exe], check=True, capture_output=True, text=True)
+    return exe

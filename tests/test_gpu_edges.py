@@ -30,8 +30,8 @@ import pytest
 import edge_cases as EC
 import ref_lut as R
 import ref_lut_many as RM
-from helpers import (O, acc_edge, gate_input, gpu_scheme, keygen, ks_at_edge_check, ks_edge_check, lut_edge_tables, lwe_edge_rows, mk, oracle_scheme,
-                     rot_gadgets)
+from helpers import (O, gate_input, gpu_scheme, keygen, ks_at_edge_check, ks_edge_check, lut_edge_tables, lwe_edge_rows, mk, oracle_scheme)
+from helpers import rot_inputs as _rot_inputs
 from ref_gate3 import linear3
 from test_keyswitch_at_cpu import checker_at
 
@@ -53,36 +53,6 @@ def _engines(p, seed, opts, exact=False):
     for k, v in opts.items():
         sg.set_option(k, v)
     return crs, keys, so, sg
-
-
-def single_exponent_rows(p):
-    """rows of switched exponents with exactly ONE non-zero entry: at the first / last mask position and on both sides of the first block
-    and party border, each with every value of {1, N-1, N, N+1, 2N-1, 2N} (one CMux: a mismatch points at a digit); one more row makes
-    the batch odd"""
-    N, nm = p.N, p.lwe_len - 1
-    L = p.blk_len if p.blk_len > 1 else 1
-    pos = sorted({0, nm - 1, L - 1, min(L, nm - 1)} | ({p.n - 1, p.n} if p.nparty > 1 else set()))
-    vals = (1, N - 1, N, N + 1, 2 * N - 1, 2 * N)
-    at = np.zeros((len(pos) * len(vals) + 1, nm), dtype=np.uint32)
-    for i, q in enumerate(pos):
-        for j, v in enumerate(vals):
-            at[i * len(vals) + j, q] = v
-    at[-1, nm // 2] = N + 1
-    return at
-
-
-def dense_exponents(p, rng, B):
-    at = rng.integers(0, 2 * p.N + 1, (B, p.lwe_len - 1)).astype(np.uint32)
-    at[0, :3] = [0, 2 * p.N, p.N]
-    return at
-
-
-def _rot_inputs(p, B, seed):
-    rng = np.random.default_rng(seed)
-    for at in (single_exponent_rows(p), dense_exponents(p, rng, B)):
-        acc = acc_edge(p, rot_gadgets(p), rng, len(at))
-        assert (acc[:, 1:].reshape(len(at), -1) != 0).any(axis=1).all()                  # acc.a is not zero on entry
-        yield at, acc
 
 
 # ---------------------------------------------------------------- 1. blind rotation from arbitrary accumulators

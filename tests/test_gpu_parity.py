@@ -21,7 +21,7 @@ def golden_tw():
     return np.load(os.path.join(os.path.dirname(__file__), "golden", "twiddles.npz"))
 
 
-@pytest.mark.parametrize("N,W", [(256, 32), (1024, 32), (1024, 64), (2048, 64), (4096, 64)])
+@pytest.mark.parametrize("N,W", [(32, 32), (256, 32), (1024, 32), (1024, 64), (2048, 64), (4096, 64)])
 def test_twiddles_and_monomial(require_gpu, golden_tw, N, W):
     p = mk.CGGIparam.scaled(n=8, N=N, W=W)
     s = mk.Scheme(p)
@@ -33,7 +33,7 @@ def test_twiddles_and_monomial(require_gpu, golden_tw, N, W):
     s.close()
 
 
-@pytest.mark.parametrize("N,W", [(64, 32), (256, 64), (512, 32), (1024, 32), (1024, 64), (2048, 64), (2048, 32), (4096, 64)])
+@pytest.mark.parametrize("N,W", [(32, 32), (32, 64), (64, 32), (128, 32), (128, 64), (256, 64), (512, 32), (1024, 32), (1024, 64), (2048, 64), (2048, 32), (4096, 64)])
 def test_transform_bitexact(require_gpu, N, W):
     rng = np.random.default_rng(N + W)
     p = mk.CGGIparam.scaled(n=8, N=N, W=W)
@@ -939,7 +939,7 @@ def test_largest_party_counts_at_full_size(require_gpu, name, decrypts):
     sg.close()
 
 
-@pytest.mark.parametrize("N,W", [(32, 32), (64, 64), (256, 32), (1024, 32), (1024, 64), (2048, 64), (4096, 32)])
+@pytest.mark.parametrize("N,W", [(32, 32), (64, 64), (128, 32), (128, 64), (256, 32), (512, 32), (512, 64), (1024, 32), (1024, 64), (2048, 32), (2048, 64), (4096, 32)])
 def test_exact_mode_integer_ntt(require_gpu, N, W):
     """MKT_ARITH_EXACT, transform level: the negacyclic NTT over Z_P[X]/(X^N+1), P = p1 p2 (two 30-bit primes, residue pairs).  Forward transforms
     equal a pure-Python restatement residue for residue (same network and table as the reference's FFT, fft.jl:105-155),

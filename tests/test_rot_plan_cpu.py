@@ -12,45 +12,13 @@ and PARENT_DIGEST are what that build printed, and this tree must print the same
 import os
 import re
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-from helpers import ROOT
+from helpers import LAUNCH_LOG_CSRC as CSRC, ROOT, build_launch_log
 
-ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
-CSRC = os.path.join(ROOT, "mktfhe_amd", "csrc")
 PARENT = "2bc678c"
 PARENT_LINES, PARENT_DIGEST = 1076909, "d962c193e7d1c656"
-
-# (source, defines, object name): kernels.hip units 0-7, rot_block.hip at both widths, ccs_pipe.hip, fx_exact.hip, ntt_exact.hip units 2 (KMS
-# phase 1) and 3 (launch_exact_kms, which calls it)
-UNITS = ([("kernels.hip", [f"-DMKT_TU={t}"], f"kernels_tu{t}") for t in range(8)] + [("rot_block.hip", [f"-DMKT_BLK_WORD={w}"], f"rot_block_{w}") for w in (32, 64)]
-         + [("ccs_pipe.hip", [], "ccs_pipe"), ("fx_exact.hip", [], "fx_exact")] + [("ntt_exact.hip", [f"-DMKT_NTT_TU={t}"], f"ntt_exact_{t}") for t in (2, 3)])
-
-
-def build_launch_log(csrc, out, defines=()):
-    """the launch-log program over the units of `csrc`: host-only objects, a dummy for each unit's fat-binary symbol, no HIP runtime"""
-    hipcc = os.path.join(ROCM, "bin", "hipcc")
-    flags = ["-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-cuda-compat", "-Wno-pass-failed", "-Wno-unused-function", "-Wno-unused-value"]
-
-    def unit(u):
-        src, defs, name = u
-        obj = os.path.join(out, name + ".o")
-        subprocess.run([hipcc, "--cuda-host-only", *flags, *defs, "-c", os.path.join(csrc, src), "-o", obj], check=True, capture_output=True, text=True)
-        return obj
-
-    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        objs = list(pool.map(unit, UNITS))
-    syms = sorted(set(re.findall(r"\bU (__hip_fatbin_\w+)", subprocess.run(["nm", *objs], check=True, capture_output=True, text=True).stdout)))
-    assert len(syms) == len(UNITS), syms
-    fat = os.path.join(out, "fatbins.cpp")
-    with open(fat, "w") as f:
-        f.write('extern "C" {\n' + "".join(f"unsigned long long {s}[4];\n" for s in syms) + "}\n")
-    exe = os.path.join(out, "launch_log")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include"), "-I" + csrc, *defines,
-                    os.path.join(ROOT, "tests", "csrc", "launch_log.cpp"), fat, *objs, "-lpthread", "-o", exe], check=True, capture_output=True, text=True)
-    return exe
 
 
 @pytest.fixture(scope="module")
