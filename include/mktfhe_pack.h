@@ -45,8 +45,32 @@
  *
  * TRUST.  The packing key is an evaluation key: public, shipped to the evaluator with the others.  mkt_client_rlwe_phase is a test harness
  * that takes all secrets; the protocol's end is one ring share per party (mkt_client_rlwe_partial_decrypt), merged by anyone.
- * NOT HERE: a seeded packing key, a key-blob section, generation on the party's GPU, mkt_multi_* variants, the ring share on
- * the GPU, mod-switching the packed ciphertext, rotating it as a table.
+ *
+ * SEEDED (DESIGN.md 1h "Seeded, in a blob, made on the party's GPU").  kr of the 1 + kr polynomials of every row are uniform randomness, so a
+ * party ships a PUBLIC 256-bit mask seed and the b polynomials, and the evaluator regenerates the masks -- the seeded form of mktfhe.h "seeded
+ * evaluation keys", for the third large key.  The message s_i[q] g_t already sits in the body, so nothing else changes.
+ * STREAMS 19 and 20 (rng_chacha.h; ids 1-18 are taken).
+ *   19, STREAM_PACK_MASK: keyed by the PUBLIC mask seed and read through stream_block exactly as stream 13 is.  Mask polynomial
+ *     P = (q l_pk + t) kr + c.  32-bit ring: coefficient j = word j & 15 of block j >> 4; 64-bit ring: words 2 (j & 7), 2 (j & 7) + 1 of block
+ *     j >> 3, low word first.  The stream index is  P | (uint64)(l_pk | logB_pk << 8) << 32:  P always fits 32 bits, the gadget rides in the high
+ *     word.  This domain separation is required, not decoration: under one mask seed two generations with DIFFERENT gadgets would otherwise
+ *     share the mask of row (q, t), their bodies would differ by s_i[q] (g_t - g'_t) plus noise, and that opens the LWE key bit to anyone.
+ *   20, STREAM_PACK_NOISE: keyed by the party's SECRET seed, Rng(key(seed), i, 20, q, t): N draws noise(sigma_ring) in coefficient order, from
+ *     the first draw; no mask is drawn from it.  Stream 17 is not read: a party that publishes both forms from one seed shares no noise
+ *     between them.
+ * ROW (q, t): a_c = mask polynomial P, unmodified;  b = -sum_c a_c (*) z_c + e + s_i[q] 2^(W - (t + 1) logB_pk) X^0;  z as above (RING KEY).
+ * COMPACT LAYOUT pk_seeded: [n][l_pk][N] ring words, the b polynomials.  Expansion yields exactly the layout of mkt_load_packing_key,
+ * [n][l_pk][1 + kr][N] ordered (b, a_0 ..): the expanded key is an ordinary packing key.  Sizes at the gadget (4, 4): KMS2party 73.4 MB ->
+ * 36.7 MB per party, CGGIparam 20.6 MB -> 10.3 MB.
+ * A (MASK SEED, PARTY) PAIR SERVES ONE PACKING-KEY GENERATION PER GADGET: two generations under it with one gadget share their masks, and the
+ * difference of their bodies is noise alone.  The same public mask seed may serve the party's seeded evaluation keys too (mktfhe.h): the
+ * stream ids differ.  The mask seed is published; it must not be the generation seed nor the seed of the party's secrets (MKT_ERR_ARG).
+ * TRUST of mkt_packing_keygen_device: the trust paragraph of mkt_keygen_device_seeded (mktfhe.h) applies verbatim -- a PARTY-LOCAL call that
+ * hands the party's secret keys and the stream key of its noise to this context's GPU, the party's own; on a shared evaluator it would hand the
+ * secrets to the evaluator.  The secrets are uploaded for the length of the call, zeroed on the device before they are freed, and the host
+ * copy of the stream key in the kernel-argument struct is zeroed with them.
+ *
+ * NOT HERE: mkt_multi_* variants, the ring share on the GPU, mod-switching the packed ciphertext, rotating it as a table.
  */
 #ifndef MKTFHE_PACK_H
 #define MKTFHE_PACK_H
@@ -63,6 +87,15 @@ extern "C" {
  * MKT_ERR_ARG: NULL pointers, a bad gadget, party out of range, foreign or wrong-party keys */
 int mkt_client_packing_keygen(const mkt_params *params, const mkt_client_party *keys, int party, int l_pk, int logB_pk, const uint8_t *seed,
                               void *pk_out);
+/* the same key in the SEEDED form above -> pk_seeded_out, [n][l_pk][N] ring words (the bodies).  seed: 256 bits keying the SECRET stream 20,
+ * NULL = fresh; mask_seed: the PUBLIC 256 bits keying stream 19, which the party ships with the bodies.  MKT_ERR_ARG, nothing written: what
+ * mkt_client_packing_keygen refuses, mask_seed NULL, seed given and bytewise equal to mask_seed, mask_seed equal to the seed of the party's secrets */
+int mkt_client_packing_keygen_seeded(const mkt_params *params, const mkt_client_party *keys, int party, int l_pk, int logB_pk, const uint8_t *seed,
+                                     const uint8_t *mask_seed, void *pk_seeded_out);
+/* the definition of expansion: pk_seeded [n][l_pk][N] -> pk_out [n][l_pk][1 + kr][N], bodies copied, masks from stream 19.  Needs no key.
+ * MKT_ERR_ARG, nothing written: NULL pointers, a bad gadget, party out of range */
+int mkt_client_packing_key_expand(const mkt_params *params, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded,
+                                  void *pk_out);
 /* TEST HARNESS (needs all keys): phase_out[j] = the top 32 bits of coefficient j of  b + sum_slot a_slot z_slot,  computed exactly;
  * rlwe [1 + k][N] ring words, keys = nparties pointers in party order */
 int mkt_client_rlwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const void *rlwe, uint32_t *phase_out);
@@ -87,6 +120,24 @@ int mkt_client_rlwe_merge_decrypt(const mkt_params *params, const void *rlwe, co
  * later load with another gadget is MKT_ERR_ARG.  RLWE lengths kr > 3 are MKT_ERR_UNSUPPORTED.  Like every key that is resident as a
  * transform, a loaded packing key makes mkt_set_twiddles return MKT_ERR_STATE */
 int mkt_load_packing_key(mkt_ctx *ctx, int party, const void *pk, int l_pk, int logB_pk);
+/* the words of mkt_client_packing_key_expand, written on the context's device and stream into caller memory: pk_seeded and pk_out both live in
+ * `mem`.  Needs no key loaded and changes no resident table.  With MKT_MEM_DEVICE both pointers must be 16-byte aligned (the kernel moves 16
+ * bytes at a time): MKT_ERR_ARG otherwise, before anything is launched -- the rule of mkt_seeded_keys_expand.  Returns once the words are written */
+int mkt_packing_key_expand(mkt_ctx *ctx, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded, void *pk_out, int mem);
+/* mkt_load_packing_key of the expansion of (mask_seed, pk_seeded), HOST pointers: exactly the same resident state, the masks regenerated on the
+ * device (MKT_ARITH_F64REF: expanded into a staging buffer, then pre-transformed slot-major; MKT_ARITH_EXACT: written in coefficient form,
+ * [polynomial][row], by the expansion kernel itself).  The expanded key never travels to the host.  Refusals as mkt_load_packing_key, plus
+ * mask_seed NULL.  One party may load seeded and another unseeded in one context */
+int mkt_load_packing_key_seeded(mkt_ctx *ctx, int party, const uint8_t *mask_seed, const void *pk_seeded, int l_pk, int logB_pk);
+/* PARTY-LOCAL (TRUST above): the words of mkt_client_packing_keygen_seeded for the same `seed`, word for word, made on this context's device
+ * -> pk_seeded_out (HOST, may be NULL with install).  seed: the generation seed as in the host call; NULL draws fresh entropy ON THE HOST and
+ * only the derived ChaCha20 key goes to the device -- in the kernel-argument struct, the way the party's stream key reaches the device in
+ * mkt_keygen_device_seeded.  install = 1: the bodies, still on the device, are also expanded and installed as mkt_load_packing_key_seeded
+ * would (its refusals apply, checked before anything runs).  install = 0 needs no key loaded and changes no resident table; with a NULL
+ * output it is MKT_ERR_ARG.  MKT_ERR_ARG, nothing written and no table touched: mask_seed NULL, seed given and equal to mask_seed, mask_seed
+ * equal to the seed of the party's secrets, a bad gadget, party out of range, foreign or wrong-party keys */
+int mkt_packing_keygen_device(mkt_ctx *ctx, int party, const mkt_client_party *keys, int l_pk, int logB_pk, const uint8_t *seed,
+                              const uint8_t *mask_seed, void *pk_seeded_out, int install);
 /* the pack defined above: pool [pool_rows][k*n + 1], idx [B] or NULL, rlwe_out [ceil(B / N)][1 + k][N] ring words, all living in `mem`.
  * Validation as mkt_gate_batch_gather: with MKT_MEM_HOST an idx[j] >= pool_rows is MKT_ERR_ARG and nothing is written; with MKT_MEM_DEVICE
  * indices are clamped to the last row.  idx NULL needs B <= pool_rows.  B == 0 succeeds and writes nothing; an empty pool with B > 0 and an

@@ -19,6 +19,7 @@ from .decrypt import partial_decrypt, merge_phase, merge_decrypt  # noqa: F401
 from .seeded import SeededBatch, seeded_encrypt, seeded_expand  # noqa: F401
 from .seeded_keys import party_keygen_seeded, seeded_keys_expand, load_seeded, seeded_section_words, keygen_device_seeded  # noqa: F401
 from .pack import packing_keygen, load_packing_key, pack, rlwe_phase, rlwe_partial_decrypt, rlwe_merge_phase, rlwe_merge_decrypt  # noqa: F401
+from .pack import packing_keygen_seeded, packing_key_expand, load_packing_key_seeded, packing_keygen_device  # noqa: F401
 from ._lib import MktError, LIB_PATH, build_id  # noqa: F401
 from . import keyblob  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402

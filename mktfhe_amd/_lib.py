@@ -153,6 +153,11 @@ PACK_SYMBOLS = {
     "mkt_client_rlwe_merge_decrypt": (_i, [_pp, _vp, _vp, _i, _sz, _vp]),
     "mkt_load_packing_key": (_i, [_vp, _i, _vp, _i, _i]),
     "mkt_pack_batch": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i]),
+    "mkt_client_packing_keygen_seeded": (_i, [_pp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mkt_client_packing_key_expand": (_i, [_pp, _i, _i, _i, _vp, _vp, _vp]),
+    "mkt_packing_key_expand": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "mkt_load_packing_key_seeded": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "mkt_packing_keygen_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

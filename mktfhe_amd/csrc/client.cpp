@@ -507,16 +507,21 @@ int mkt_client_seeded_expand(const mkt_params *params, int party, const uint8_t 
 
 namespace {
 
-// mask polynomial P of the bootstrapping key (stream 13) as ring words
-void brk_mask_poly(const uint32_t mkey[8], uint32_t party, uint64_t P, int N, int W, uint64_t *a) {
+// the mask polynomial at index `idx` of a public stream as ring words: every keystream word used, 16 coefficients of a block on the 32-bit
+// ring, 8 on the 64-bit one (low word first)
+void mask_poly(const uint32_t mkey[8], uint32_t stream, uint32_t party, uint64_t idx, int N, int W, uint64_t *a) {
     uint32_t w[16];
     if (W == 32) for (int q0 = 0; q0 < N; q0 += 16) {
-        mktrng::stream_block(mkey, mktrng::STREAM_BRK_MASK, party, P, (uint32_t)(q0 >> 4), w);
+        mktrng::stream_block(mkey, stream, party, idx, (uint32_t)(q0 >> 4), w);
         for (int i = 0; i < 16; i++) a[q0 + i] = w[i];
     } else for (int q0 = 0; q0 < N; q0 += 8) {
-        mktrng::stream_block(mkey, mktrng::STREAM_BRK_MASK, party, P, (uint32_t)(q0 >> 3), w);
+        mktrng::stream_block(mkey, stream, party, idx, (uint32_t)(q0 >> 3), w);
         for (int i = 0; i < 8; i++) a[q0 + i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
     }
+}
+// mask polynomial P of the bootstrapping key (stream 13) as ring words
+void brk_mask_poly(const uint32_t mkey[8], uint32_t party, uint64_t P, int N, int W, uint64_t *a) {
+    mask_poly(mkey, mktrng::STREAM_BRK_MASK, party, P, N, W, a);
 }
 // the n mask words of key-switching-key row R (stream 12)
 void ksk_mask_row(const uint32_t mkey[8], uint32_t party, uint64_t R, int n, uint32_t *row) {
@@ -724,6 +729,65 @@ int mkt_client_packing_keygen(const mkt_params *params, const mkt_client_party *
         }
     });
     explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// the seeded form (mktfhe_pack.h "SEEDED"): the bodies of the rows, masks from the public stream 19, noise from the secret stream 20
+int mkt_client_packing_keygen_seeded(const mkt_params *params, const mkt_client_party *K, int party, int l_pk, int logB_pk, const uint8_t *seed,
+                                     const uint8_t *mask_seed, void *pk_seeded_out) {
+    if (!params || !K || !pk_seeded_out || !mask_seed || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
+    if (seed && std::memcmp(seed, mask_seed, 32) == 0) return MKT_ERR_ARG;      // the mask seed is published: the noise would be too
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    if (std::memcmp(mask_seed, K->key, sizeof K->key) == 0) return MKT_ERR_ARG;  // nor may it be the seed of the party's secrets
+    const int N = p.N, W = p.W, kr = sh.ksk_kr;
+    const uint64_t wm = wmask(W);
+    uint32_t key[8], mkey[8];
+    if (seed_to_key(seed, key)) return MKT_ERR_STATE;
+    seed_to_key(mask_seed, mkey);
+    parallel_for(p.n, [&](int q) {
+        std::vector<uint64_t> a(N), b(N);
+        for (int t = 0; t < l_pk; t++) {
+            const uint32_t S = (uint32_t)q * (uint32_t)l_pk + (uint32_t)t;
+            std::fill(b.begin(), b.end(), 0);
+            for (int c = 0; c < kr; c++) {
+                mask_poly(mkey, mktrng::STREAM_PACK_MASK, (uint32_t)party, mktrng::pack_mask_index(S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk), N, W, a.data());
+                mul_small_acc(a.data(), K->zring[(size_t)pack_zoff(p) + c].data(), b.data(), N, true);
+            }
+            Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_NOISE, (uint32_t)q, (uint32_t)t);
+            for (int j = 0; j < N; j++) b[j] = (b[j] + r.noise(K->sigma_ring)) & wm;
+            b[0] = (b[0] + ((uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk))) & wm;
+            store_poly_raw(pk_seeded_out, S, b.data(), N, W);
+        }
+    });
+    explicit_bzero(key, sizeof key);
+    return MKT_OK;
+}
+
+// the definition of expansion: bodies copied, masks regenerated; needs no key
+int mkt_client_packing_key_expand(const mkt_params *params, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded, void *pk_out) {
+    if (!params || !mask_seed || !pk_seeded || !pk_out || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
+    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    const mkt_params &p = *params;
+    const Shape sh = shape_of(p);
+    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
+    const int N = p.N, W = p.W, kr = sh.ksk_kr, polys = kr + 1;
+    const size_t pb = (size_t)N * sh.word;
+    uint32_t mkey[8];
+    seed_to_key(mask_seed, mkey);
+    parallel_for(p.n, [&](int q) {
+        std::vector<uint64_t> a(N);
+        for (int t = 0; t < l_pk; t++) {
+            const uint32_t S = (uint32_t)q * (uint32_t)l_pk + (uint32_t)t;
+            std::memcpy((uint8_t *)pk_out + (size_t)S * polys * pb, (const uint8_t *)pk_seeded + (size_t)S * pb, pb);
+            for (int c = 0; c < kr; c++) {
+                mask_poly(mkey, mktrng::STREAM_PACK_MASK, (uint32_t)party, mktrng::pack_mask_index(S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk), N, W, a.data());
+                store_poly_raw(pk_out, (size_t)S * polys + 1 + c, a.data(), N, W);
+            }
+        }
+    });
     return MKT_OK;
 }
 

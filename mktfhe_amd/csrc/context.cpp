@@ -16,6 +16,7 @@
 #include "device_mem.h"
 #include "fft_device.h"
 #include "host_internal.h"
+#include "rng_chacha.h"
 
 using mktd::cplx;
 using mkt::DevBuf;
@@ -1223,7 +1224,7 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
         else { if ((r = so.in(brk_out, brk_polys_total * poly_bytes(c), mem, false, 16))) return r; dst = so.dev; }
         mktd::SeededBrkArgs a{};
         mkt::seed_to_key(mask_seed, a.mkey);
-        a.party = party; a.unienc = p.scheme == MKT_CCS; a.kr = c->sh.kr; a.l = a.unienc ? p.l_uni : p.l_gsw;
+        a.stream = mktrng::STREAM_BRK_MASK; a.party = party; a.unienc = p.scheme == MKT_CCS; a.kr = c->sh.kr; a.l = a.unienc ? p.l_uni : p.l_gsw;
         a.log_units = c->logN + (p.W == 64 ? 1 : 0) - 4; a.body = sb.dev; a.out = dst; a.npolys = brk_polys_total;
         e = mktd::launch_seeded_brk_expand(a, c->stream);
         if (e == hipSuccess && load) e = install_brk(c, party, dst);
@@ -1861,26 +1862,42 @@ int mkt_exact_polymul_batch(mkt_ctx *c, const void *a, const void *b, void *out,
 constexpr size_t PACK_CHUNK = 16;      // packs per launch sequence: bounds the workspace (KMS2party: 16 packs = 0.3 GiB of columns, 0.15 GiB of slabs)
 constexpr int PACK_EXACT_COLS = 64;    // MKT_ARITH_EXACT: columns per decompose / exact-product launch
 
-int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int logB_pk) {
-    if (!c || !pk || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
-    if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
+// what every load of a packing key checks before it touches anything (`who`: the entry point, for the message); then the party's slot of the
+// resident table, allocated by the first load, which fixes the context's gadget
+static int pack_load_guard(mkt_ctx *c, const std::string &who, int l_pk, int logB_pk) {
+    if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, who + ": the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
     const mkt_params &p = c->p;
-    const int np = c->sh.ksk_kr + 1;
-    if (!mktd::pack_supported(np)) return fail(c, MKT_ERR_UNSUPPORTED, "mkt_load_packing_key: RLWE lengths beyond 3 are not served");
+    if (!mktd::pack_supported(c->sh.ksk_kr + 1)) return fail(c, MKT_ERR_UNSUPPORTED, who + ": RLWE lengths beyond 3 are not served");
     // EXACT: every product of a digit polynomial (N digits of magnitude <= 2^(logB_pk - 1)) with a centered 32-bit piece of a key polynomial must stay below P / 2
     if (c->exact && (double)p.N * std::ldexp(1.0, logB_pk - 1) * 2147483648.0 >= 0.5 * (double)NTT_P[0] * (double)NTT_P[1])
-        return fail(c, MKT_ERR_UNSUPPORTED, "mkt_load_packing_key: the rows of this gadget could reach P / 2 of the two-prime modulus");
+        return fail(c, MKT_ERR_UNSUPPORTED, who + ": the rows of this gadget could reach P / 2 of the two-prime modulus");
     if (int w = keys_writable(c)) return w;
+    const KeySet &ks = *c->ks;
+    if (ks.d_pack.p && (ks.pack_l != l_pk || ks.pack_logB != logB_pk)) return fail(c, MKT_ERR_ARG, who + ": all parties of a context use one packing gadget");
+    return MKT_OK;
+}
+static int pack_party_slot(mkt_ctx *c, int party, int l_pk, int logB_pk, char **dst) {
     KeySet &ks = *c->ks;
-    if (ks.d_pack.p && (ks.pack_l != l_pk || ks.pack_logB != logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_load_packing_key: all parties of a context use one packing gadget");
-    DevGuard dg(c->device);
-    const size_t rows = (size_t)p.n * l_pk, polys = rows * np, pb = poly_bytes(c);
-    const size_t per = polys * (c->exact ? pb : (size_t)c->M * sizeof(cplx));
+    const size_t polys = mkt::pack_key_polys(c->p, c->sh, l_pk);
+    const size_t per = polys * (c->exact ? poly_bytes(c) : (size_t)c->M * sizeof(cplx));
     if (!ks.d_pack.p) {
         HIPCHK(c, ks.d_pack.alloc(per * c->sh.nparty));
         ks.pack_l = l_pk; ks.pack_logB = logB_pk; ks.pack_party_bytes = per; ks.pack_loaded.assign((size_t)c->sh.nparty, 0);
     }
-    char *dst = ks.d_pack.as<char>() + (size_t)party * per;
+    *dst = ks.d_pack.as<char>() + (size_t)party * per;
+    return MKT_OK;
+}
+
+int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int logB_pk) {
+    if (!c || !pk || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = pack_load_guard(c, "mkt_load_packing_key", l_pk, logB_pk)) return r;
+    const mkt_params &p = c->p;
+    const int np = c->sh.ksk_kr + 1;
+    KeySet &ks = *c->ks;
+    DevGuard dg(c->device);
+    const size_t rows = (size_t)p.n * l_pk, polys = rows * np, pb = poly_bytes(c);
+    char *dst;
+    if (int r = pack_party_slot(c, party, l_pk, logB_pk, &dst)) return r;
     if (!c->exact) {          // pre-transformed like the bootstrapping key, in the slot-major point order whatever the context's own
         DevBuf tmp;
         HIPCHK(c, tmp.alloc(polys * pb));
@@ -1896,6 +1913,90 @@ int mkt_load_packing_key(mkt_ctx *c, int party, const void *pk, int l_pk, int lo
     }
     ks.pack_loaded[(size_t)party] = 1;
     return MKT_OK;
+}
+
+// The seeded packing key (mktfhe_pack.h "SEEDED"; pack_keys.hip): party `party`'s key regenerated on this context's device from the public mask
+// seed and the bodies [n][l_pk][N], the words of mkt_client_packing_key_expand.  load: into the resident table -- F64REF through a coefficient
+// staging buffer and the forward transform, as mkt_load_packing_key after its upload; EXACT straight into [polynomial][row] from the kernel --
+// else into the caller's pk_out (`mem`).  `mem` says where pk_seeded lives in either case: the bodies mkt_packing_keygen_device has just made
+// on this device are installed from there.  Nothing is secret.  The caller has checked the arguments (load: pack_load_guard)
+static int pack_key_seeded_impl(mkt_ctx *c, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded, bool load, void *pk_out, int mem) {
+    const mkt_params &p = c->p;
+    DevGuard dg(c->device);
+    const size_t rows = (size_t)p.n * l_pk, polys = mkt::pack_key_polys(p, c->sh, l_pk), pb = poly_bytes(c);
+    Staged sb{c}, so{c};
+    DevBuf full;              // F64REF load: the expanded key in coefficient form
+    int r;
+    // the expansion kernel copies bodies and writes polynomials 16 bytes at a time, from the base pointers on: refused before any launch unless so aligned
+    if ((r = sb.in(pk_seeded, rows * pb, mem, true, 16))) return r;
+    char *slot = nullptr;
+    void *dst;
+    if (!load) { if ((r = so.in(pk_out, polys * pb, mem, false, 16))) return r; dst = so.dev; }
+    else {
+        if ((r = pack_party_slot(c, party, l_pk, logB_pk, &slot))) return r;
+        if (c->exact) dst = slot; else { HIPCHK(c, full.alloc(polys * pb)); dst = full.p; }
+    }
+    mktd::PackKeyExpandArgs a{};
+    mkt::seed_to_key(mask_seed, a.mkey);
+    a.party = party; a.kr = c->sh.ksk_kr; a.l = l_pk; a.logB = logB_pk; a.log_units = c->logN + (p.W == 64 ? 1 : 0) - 4;
+    a.transposed = load && c->exact ? 1 : 0; a.body = sb.dev; a.out = dst; a.rows = rows;
+    hipError_t e = mktd::launch_pack_key_expand(a, c->stream);
+    if (e == hipSuccess && load && !c->exact) e = mktd::launch_transform_fwd(c->logM, p.W, c->twp(), dst, reinterpret_cast<cplx *>(slot), polys, 1, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hipfail(c, e, "seeded packing key expansion");
+    if (!load) return so.out(pk_out);
+    c->ks->pack_loaded[(size_t)party] = 1;
+    return MKT_OK;
+}
+
+int mkt_packing_key_expand(mkt_ctx *c, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded, void *pk_out, int mem) {
+    if (!c || !mask_seed || !pk_seeded || !pk_out || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_packing_key_expand: the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
+    return pack_key_seeded_impl(c, party, l_pk, logB_pk, mask_seed, pk_seeded, false, pk_out, mem);
+}
+
+int mkt_load_packing_key_seeded(mkt_ctx *c, int party, const uint8_t *mask_seed, const void *pk_seeded, int l_pk, int logB_pk) {
+    if (!c || !mask_seed || !pk_seeded || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = pack_load_guard(c, "mkt_load_packing_key_seeded", l_pk, logB_pk)) return r;
+    return pack_key_seeded_impl(c, party, l_pk, logB_pk, mask_seed, pk_seeded, true, nullptr, MKT_MEM_HOST);
+}
+
+// The bodies generated on the party's own GPU (pack_keys.hip): the words of mkt_client_packing_keygen_seeded for the same `seed`, word for word.
+// Party-local like mkt_keygen_device_seeded, and the stream key reaches the device as it does there: in the kernel-argument struct, whose host
+// copy is zeroed with the device secrets (wipe_secrets) -- NULL `seed` draws fresh entropy on the host, only the derived ChaCha key travels.
+// install: the bodies, still on the device, also go through the expansion and install of mkt_load_packing_key_seeded
+int mkt_packing_keygen_device(mkt_ctx *c, int party, const mkt_client_party *K, int l_pk, int logB_pk, const uint8_t *seed, const uint8_t *mask_seed,
+                              void *pk_seeded_out, int install) {
+    if (!c || !K || !mask_seed || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!pk_seeded_out && !install) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: neither an output nor an install was asked for");
+    if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
+    const mkt_params &p = c->p;
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the party's keys were made for other parameters / another party index");
+    if ((seed && std::memcmp(seed, mask_seed, 32) == 0) || std::memcmp(mask_seed, K->key, sizeof K->key) == 0)
+        return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the mask seed is a secret seed of the call (it is published: the secrets would be too)");
+    const int kr = c->sh.ksk_kr, zoff = mkt::is_kms(p.scheme) ? 1 : 0, N = p.N;
+    if ((int)K->zring.size() < zoff + kr) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the party's keys lack a ring key");
+    if (install) if (int r = pack_load_guard(c, "mkt_packing_keygen_device", l_pk, logB_pk)) return r;
+    DevGuard dg(c->device);
+    const size_t body_bytes = (size_t)p.n * l_pk * poly_bytes(c);
+    DevBuf bodies;                            // freed behind the secrets' drain of the stream
+    DeviceSecret lwe{c}, z{c};
+    mktd::PackKeygenArgs a{};
+    hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
+    if (e == hipSuccess) e = z.alloc((size_t)kr * N);
+    for (int q = 0; q < kr && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[(size_t)zoff + q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = bodies.alloc(body_bytes);
+    if (e != hipSuccess) return hipfail(c, e, "device packing keygen setup");
+    if (mkt::seed_to_key(seed, a.key)) { explicit_bzero(&a, sizeof a); return fail(c, MKT_ERR_STATE, "mkt_packing_keygen_device: no entropy"); }
+    mkt::seed_to_key(mask_seed, a.mkey);
+    a.party = party; a.N = N; a.n = p.n; a.W = p.W; a.kr = kr; a.l = l_pk; a.logB = logB_pk; a.sigma_ring = K->sigma_ring;
+    a.lwekey = lwe.as<const uint32_t>(); a.zring = z.as<const int8_t>(); a.body = bodies.p;
+    e = mktd::launch_pack_keygen(a, c->stream);
+    if (e == hipSuccess && pk_seeded_out) e = hipMemcpyAsync(pk_seeded_out, bodies.p, body_bytes, hipMemcpyDeviceToHost, c->stream);
+    e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);       // (drains the stream: the output has landed)
+    if (e != hipSuccess) return hipfail(c, e, "device packing keygen");
+    if (!install) return MKT_OK;
+    return pack_key_seeded_impl(c, party, l_pk, logB_pk, mask_seed, bodies.p, true, nullptr, MKT_MEM_DEVICE);
 }
 
 // the readiness check of a pack: every party's packing key, and nothing else

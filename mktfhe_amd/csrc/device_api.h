@@ -209,8 +209,12 @@ struct SeededKskArgs {
 };
 // Bootstrapping key: out = npolys polynomials in the coefficient layout of mkt_load_brk, each 1 << log_units units of 64 bytes (N W / 512);
 // bodies copied from `body` (the compact section), masks from stream 13.  unienc 0: groups of kr + 1 (b, a_0 ..); 1: groups of 3 l (CCS)
+// stream / idx_hi: the mask stream (13; 19 for a packing key, pack_keys.hip) and the high word of its stream index (0; the packing gadget).
+// t_rows != 0 (unienc 0 only): out is [kr + 1][t_rows] polynomials, polynomial q of group r at q t_rows + r, t_rows = npolys / (kr + 1)
 struct SeededBrkArgs {
     uint32_t mkey[8];
+    uint32_t stream, idx_hi;
+    uint64_t t_rows;
     int party, unienc, kr, l, log_units;
     const void *body;            // 16-byte aligned
     void *out;                   // 16-byte aligned
@@ -218,6 +222,28 @@ struct SeededBrkArgs {
 };
 hipError_t launch_seeded_ksk_expand(const SeededKskArgs &a, hipStream_t s);
 hipError_t launch_seeded_brk_expand(const SeededBrkArgs &a, hipStream_t s);
+
+// The seeded packing key (pack_keys.hip; mktfhe_pack.h "SEEDED").  Expansion: the words of mkt_client_packing_key_expand through the tile frame of
+// seeded_brk_expand_kernel -- body [rows][N] -> out [rows][1 + kr][N], or [1 + kr][rows][N] with `transposed` (the EXACT resident layout), rows = n l_pk
+struct PackKeyExpandArgs {
+    uint32_t mkey[8];            // the PUBLIC mask seed
+    int party, kr, l, logB, log_units, transposed;
+    const void *body;            // 16-byte aligned
+    void *out;                   // 16-byte aligned
+    uint64_t rows;
+};
+hipError_t launch_pack_key_expand(const PackKeyExpandArgs &a, hipStream_t s);
+// Generation: the words of mkt_client_packing_keygen_seeded, one workgroup per row (q, t); only the bodies are stored
+struct PackKeygenArgs {
+    uint32_t key[8];             // ChaCha20 key of the SECRET noise stream 20 (the generation seed)
+    uint32_t mkey[8];            // key of the mask stream 19: the PUBLIC mask seed
+    int party, N, n, W, kr, l, logB;
+    double sigma_ring;
+    const uint32_t *lwekey;      // [n]
+    const int8_t *zring;         // [kr][N]: the ring keys the key-switching key switches from
+    void *body;                  // [n][l][N] ring words
+};
+hipError_t launch_pack_keygen(const PackKeygenArgs &a, hipStream_t s);
 
 // Packed outputs (pack.hip; mktfhe_pack.h): one launch sequence packs `npacks` ciphertexts, pack0 .. pack0 + npacks - 1 of the call
 constexpr int PACK_QCHUNK = 4;   // mask words per workgroup of the product kernel: k n / 4 workgroups per pack (280 at the headline shape)

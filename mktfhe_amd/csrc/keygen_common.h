@@ -40,6 +40,19 @@ __device__ __forceinline__ void fill_noise(const Rng &proto, uint64_t first, uin
 
 template <typename WORD> __device__ __forceinline__ uint64_t wmask_of() { return sizeof(WORD) == 8 ? ~0ull : 0xFFFFFFFFull; }
 
+// al[q] <- coefficient q of the mask polynomial at index `idx` of the public stream `stream` (13: the bootstrapping key; 19: the packing key),
+// q < N: one keystream block per lane and pass, 16 coefficients of the 32-bit ring or 8 of the 64-bit one, low word first
+template <typename WORD>
+__device__ __forceinline__ void fill_mask_poly(const uint32_t mkey[8], uint32_t stream, uint32_t party, uint64_t idx, uint64_t *al, int N) {
+    constexpr int PER = sizeof(WORD) == 8 ? 8 : 16;                 // coefficients per keystream block
+    for (int b = threadIdx.x; b < N / PER; b += KG_THREADS) {
+        uint32_t w[16];
+        mktrng::stream_block(mkey, stream, party, idx, (uint32_t)b, w);
+#pragma unroll
+        for (int i = 0; i < PER; i++) al[PER * b + i] = sizeof(WORD) == 8 ? ((uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32)) : (uint64_t)w[i];
+    }
+}
+
 // acc[r] (+)= sum_i s_i * a[(m - i) mod N] with the negacyclic sign, m = t + r * KG_THREADS; s in {-1, 0, 1};
 // client.cpp mul_small_acc (out[i + j] -/+= a[j]) restated per output coefficient.  `negate` flips the sign.
 template <int MAXR>

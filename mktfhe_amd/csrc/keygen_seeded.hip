@@ -28,13 +28,7 @@ namespace {
 // al[q] <- coefficient q of mask polynomial P of the bootstrapping key (stream 13), q < N
 template <typename WORD>
 __device__ __forceinline__ void fill_brk_mask(const KeygenSeededArgs &a, uint64_t P, uint64_t *al, int N) {
-    constexpr int PER = sizeof(WORD) == 8 ? 8 : 16;                 // coefficients per keystream block
-    for (int b = threadIdx.x; b < N / PER; b += KG_THREADS) {
-        uint32_t w[16];
-        mktrng::stream_block(a.mkey, mktrng::STREAM_BRK_MASK, (uint32_t)a.party, P, (uint32_t)b, w);
-#pragma unroll
-        for (int i = 0; i < PER; i++) al[PER * b + i] = sizeof(WORD) == 8 ? ((uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32)) : (uint64_t)w[i];
-    }
+    fill_mask_poly<WORD>(a.mkey, mktrng::STREAM_BRK_MASK, (uint32_t)a.party, P, al, N);   // (keygen_common.h: shared with pack_keys.hip)
 }
 
 template <typename WORD, int MAXR>

@@ -172,5 +172,15 @@ constexpr uint32_t STREAM_UNI_NOISE = 16;
 // in the two index words, N noise draws in coefficient order.
 constexpr uint32_t STREAM_PACK_KEY = 17;
 constexpr uint32_t STREAM_PACK_SMUDGE = 18;
+// 19, 20: the seeded packing key (mktfhe_pack.h "SEEDED"; client.cpp and pack_keys.hip).  19 is keyed by the PUBLIC mask seed and read through
+// stream_block exactly as 13 is: mask polynomial P = (q l_pk + t) kr + c of row (q, t), with the GADGET in the high word of the stream index
+// (pack_mask_index) -- two generations under one seed with different gadgets share no mask.  20 is keyed by the party's SECRET seed: one
+// stream per row (index words q, t), N noise draws in coefficient order from the first draw; no mask is drawn from it.
+constexpr uint32_t STREAM_PACK_MASK = 19;
+constexpr uint32_t STREAM_PACK_NOISE = 20;
+// the stream index of mask polynomial P (always below 2^32) of a packing key made with the gadget (l_pk, logB_pk)
+MKT_HD uint64_t pack_mask_index(uint32_t P, int l_pk, int logB_pk) {
+    return (uint64_t)P | ((uint64_t)((uint32_t)l_pk | ((uint32_t)logB_pk << 8)) << 32);
+}
 
 }  // namespace mktrng

@@ -16,6 +16,9 @@
 // BOOTSTRAPPING KEY.  The output is the coefficient layout of mkt_load_brk, dense, polynomials of N ring words: N W / 512 units each.  A
 // polynomial is either a body, copied from the compact upload (its lanes do no cipher work; whole waves of them from N = 1024 on), or mask
 // polynomial P: unit u is keystream block u of P's stream on either ring (32-bit: coefficients 16 u ..; 64-bit: coefficients 8 u .., low word first).
+// PACKING KEY (mktfhe_pack.h "SEEDED"; launched from pack_keys.hip).  The same kernel: a packing key is n l_pk groups of (b, a_0 .. a_{kr-1}) like
+// an RGSW key, its masks on stream 19 with the gadget in the high word of the stream index (SeededBrkArgs::stream, idx_hi).  t_rows != 0 writes
+// the layout an MKT_ARITH_EXACT context keeps resident, [polynomial][row], each polynomial still a dense run of 16-byte stores.
 #include "party_rows.h"
 #include "rng_chacha.h"
 
@@ -100,7 +103,7 @@ __global__ void __launch_bounds__(SK_THREADS) seeded_brk_expand_kernel(SeededBrk
             const BrkPoly bp = brk_poly(a, grp, rem + ((u0 + t) >> lc));
             if (bp.mask) {
                 uint32_t x[16];
-                mktrng::stream_block(a.mkey, mktrng::STREAM_BRK_MASK, (uint32_t)a.party, bp.idx, (u0 + t) & umask, x);
+                mktrng::stream_block(a.mkey, a.stream, (uint32_t)a.party, bp.idx | ((uint64_t)a.idx_hi << 32), (u0 + t) & umask, x);
 #pragma unroll
                 for (int i = 0; i < 16; i++) im[t * SK_PITCH + i] = x[i];
             }
@@ -108,12 +111,17 @@ __global__ void __launch_bounds__(SK_THREADS) seeded_brk_expand_kernel(SeededBrk
         __syncthreads();
         uint4 *base = reinterpret_cast<uint4 *>(a.out) + g0 * 4u;
         for (uint32_t v = t; v < 4u * cnt; v += SK_THREADS) {
-            const uint32_t s = v >> 2, k = v & 3u;
-            const BrkPoly bp = brk_poly(a, grp, rem + ((u0 + s) >> lc));
+            const uint32_t s = v >> 2, k = v & 3u, x = rem + ((u0 + s) >> lc);
+            const BrkPoly bp = brk_poly(a, grp, x);
+            uint4 *dst = base + v;
+            if (a.t_rows) {                                                              // [polynomial][row]: polynomial q of row grp + ds
+                const uint32_t ds = x / period, q = x - ds * period;
+                dst = reinterpret_cast<uint4 *>(a.out) + (((((uint64_t)q * a.t_rows + grp + ds) << lc) + ((u0 + s) & umask)) << 2) + k;
+            }
             if (bp.mask) {
                 const uint32_t *src = im + s * SK_PITCH + 4u * k;
-                base[v] = make_uint4(src[0], src[1], src[2], src[3]);
-            } else base[v] = body[(((bp.idx << lc) + ((u0 + s) & umask)) << 2) + k];
+                *dst = make_uint4(src[0], src[1], src[2], src[3]);
+            } else *dst = body[(((bp.idx << lc) + ((u0 + s) & umask)) << 2) + k];
         }
     }
 }
@@ -137,7 +145,8 @@ hipError_t launch_seeded_ksk_expand(const SeededKskArgs &a, hipStream_t s) {
 
 hipError_t launch_seeded_brk_expand(const SeededBrkArgs &a, hipStream_t s) {
     if (!a.npolys) return hipSuccess;
-    if (a.party < 0 || a.log_units < 0 || a.log_units > 16 || (a.unienc ? a.l < 1 : a.kr < 1)) return hipErrorInvalidValue;
+    if (a.party < 0 || a.log_units < 0 || a.log_units > 16 || (a.unienc ? a.l < 1 : a.kr < 1) || !a.stream) return hipErrorInvalidValue;
+    if (a.t_rows && (a.unienc || a.t_rows * ((uint64_t)a.kr + 1) != a.npolys)) return hipErrorInvalidValue;      // the transposed form: whole rows of kr + 1
     if (((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.body)) & 15u) || !a.body || !a.out) return hipErrorInvalidValue;
     hipLaunchKernelGGL(seeded_brk_expand_kernel, dim3(sk_grid(a.npolys << a.log_units)), dim3(SK_THREADS), SK_LDS, s, a);
     return hipGetLastError();

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .params import Params
-from .scheme import MEM_DEVICE, PartyKeys, _arg, _count, _empty, _is_torch, _np_ptr, _row0, _rows, _seed_arg
+from .scheme import MEM_DEVICE, PartyKeys, _arg, _count, _empty, _is_torch, _np_ptr, _row0, _rows, _seed32, _seed_arg
 
 
 def _kr(params):
@@ -69,6 +69,79 @@ def load_packing_key(scheme, party, pk, l, logB):
     if pk.size != p.n * l * (1 + _kr(p)) * p.N:
         raise ValueError(f"packing key of {pk.size} ring words, expected {(p.n, l, 1 + _kr(p), p.N)}")
     scheme._ck(_lib.lib().mkt_load_packing_key(scheme.h, int(party), _np_ptr(pk), l, logB))
+
+
+def _fresh_seed():
+    buf = (C.c_uint8 * 32)()
+    check(_lib.lib().mkt_client_random_seed(buf))
+    return bytes(buf)
+
+
+def _bodies(params, pk_seeded, l):
+    """the compact section -> contiguous host array of n l N ring words"""
+    b = np.ascontiguousarray(pk_seeded, dtype=params.ring_dtype)
+    if b.size != params.n * l * params.N:
+        raise ValueError(f"seeded packing key of {b.size} ring words, expected {(params.n, l, params.N)}")
+    return b
+
+
+def packing_keygen_seeded(keys: PartyKeys, params: Params, l=4, logB=4, mask_seed=None, deterministic_seed=None):
+    """mkt_client_packing_keygen_seeded: the packing key of the party `keys` belongs to in the seeded form -> (mask_seed, pk_seeded): the
+    PUBLIC 32-byte mask seed (None draws a fresh one) and the bodies (n, l, N) ring words; the party ships both, the evaluator regenerates
+    the masks (load_packing_key_seeded).  A (mask seed, party) pair serves ONE generation per gadget.  Fresh noise unless deterministic_seed
+    (tests only) pins it"""
+    l, logB = _gadget(l, logB)
+    mask_seed = _fresh_seed() if mask_seed is None else bytes(mask_seed)
+    mp, _keepm = _seed32(mask_seed)
+    sp, _keep = _seed_arg(deterministic_seed)
+    out = np.empty((params.n, l, params.N), dtype=params.ring_dtype)
+    check(_lib.lib().mkt_client_packing_keygen_seeded(C.byref(params.c()), keys.h, int(keys.party), l, logB, sp, mp, _np_ptr(out)))
+    return mask_seed, out
+
+
+def packing_key_expand(params: Params, party, l, logB, mask_seed, pk_seeded, scheme=None):
+    """-> the ordinary packing key (n, l, 1 + kr, N) of a seeded one.  Needs no key.  scheme None: on the host (mkt_client_packing_key_expand,
+    the definition), numpy.  scheme = a Scheme: on its GPU (mkt_packing_key_expand; no key needed, no resident table changed), the same words,
+    living where pk_seeded lives (numpy array or GPU tensor)"""
+    l, logB = _gadget(l, logB)
+    mp, _keep = _seed32(mask_seed)
+    shape = (params.n, l, 1 + _kr(params), params.N)
+    if scheme is None:
+        b = _bodies(params, pk_seeded, l)
+        out = np.empty(shape, dtype=params.ring_dtype)
+        check(_lib.lib().mkt_client_packing_key_expand(C.byref(params.c()), int(party), l, logB, mp, _np_ptr(b), _np_ptr(out)))
+        return out
+    if int(np.prod(tuple(np.shape(pk_seeded)))) != params.n * l * params.N:
+        raise ValueError(f"seeded packing key of shape {tuple(np.shape(pk_seeded))}, expected {(params.n, l, params.N)}")
+    out = _empty(pk_seeded, shape, params.ring_dtype, "int64" if params.W == 64 else "int32")
+    src, dst = _arg(pk_seeded, params.ring_dtype), _arg(out, params.ring_dtype, writable=True)
+    if src[1] == MEM_DEVICE:
+        scheme._follow_torch([src[2], dst[2]])
+    scheme._ck(_lib.lib().mkt_packing_key_expand(scheme.h, int(party), l, logB, mp, src[0], dst[0], src[1]))      # (returns once the words are written)
+    return out
+
+
+def load_packing_key_seeded(scheme, party, mask_seed, pk_seeded, l, logB):
+    """mkt_load_packing_key_seeded: the resident state of load_packing_key(packing_key_expand(...)), the masks regenerated on the scheme's GPU;
+    the expanded key never exists on the host"""
+    l, logB = _gadget(l, logB)
+    mp, _keep = _seed32(mask_seed)
+    b = _bodies(scheme.params, pk_seeded, l)
+    scheme._ck(_lib.lib().mkt_load_packing_key_seeded(scheme.h, int(party), mp, _np_ptr(b), l, logB))
+
+
+def packing_keygen_device(scheme, party, keys: PartyKeys, l=4, logB=4, mask_seed=None, deterministic_seed=None, install=False):
+    """mkt_packing_keygen_device: packing_keygen_seeded on the party's OWN GPU -> (mask_seed, pk_seeded), word for word what the host call
+    makes for the same deterministic_seed.  This hands the party's SECRETS to scheme's GPU: the party's own step.  install=True: the key
+    also becomes resident on `scheme`, as load_packing_key_seeded of the result would make it"""
+    l, logB = _gadget(l, logB)
+    mask_seed = _fresh_seed() if mask_seed is None else bytes(mask_seed)
+    mp, _keepm = _seed32(mask_seed)
+    sp, _keep = _seed_arg(deterministic_seed)
+    p = scheme.params
+    out = np.empty((p.n, l, p.N), dtype=p.ring_dtype)
+    scheme._ck(_lib.lib().mkt_packing_keygen_device(scheme.h, int(party), keys.h, l, logB, sp, mp, _np_ptr(out), 1 if install else 0))
+    return mask_seed, out
 
 
 def pack(scheme, ct_or_pool, idx=None, out=None):

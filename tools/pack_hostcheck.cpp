@@ -47,6 +47,24 @@ static int run(mkt_params p, int l, int logB, double beta) {
     if (mkt_client_rlwe_merge_phase(&p, ct.data(), shares.data(), nparty + 1, 1, merged.data()) != MKT_ERR_ARG) return 16;
     if (mkt_client_rlwe_partial_decrypt(&p, K[0], 0, ct.data(), -1.0, seed, 0, noisy.data(), 1) != MKT_ERR_ARG) return 17;
     if (mkt_client_rlwe_partial_decrypt(&p, K[0], 0, nullptr, 0.0, seed, 0, nullptr, 0)) return 18;
+    // the seeded form (mktfhe_pack.h "SEEDED"): bodies, then the expansion; row (0, 0) of the expanded key opens like a row of the full one
+    uint8_t mseed[32];
+    mkt_client_test_seed(4, mseed);
+    std::vector<uint8_t> body((size_t)p.n * l * N * word, 0xA5), full((size_t)p.n * l * (kr + 1) * N * word, 0x5A), was = body;
+    if (mkt_client_packing_keygen_seeded(&p, K[0], 0, l, logB, seed, nullptr, body.data()) != MKT_ERR_ARG) return 19;
+    if (mkt_client_packing_keygen_seeded(&p, K[0], 0, l, logB, mseed, mseed, body.data()) != MKT_ERR_ARG) return 20;
+    if (mkt_client_packing_keygen_seeded(&p, K[0], nparty > 1 ? 1 : 2, l, logB, seed, mseed, body.data()) != MKT_ERR_ARG) return 21;
+    if (mkt_client_packing_keygen_seeded(&p, K[0], 0, 3, 11, seed, mseed, body.data()) != MKT_ERR_ARG || body != was) return 22;
+    if (mkt_client_packing_keygen_seeded(&p, K[0], 0, l, logB, nullptr, mseed, body.data())) return 23;
+    if (mkt_client_packing_key_expand(&p, 0, l, logB, nullptr, body.data(), full.data()) != MKT_ERR_ARG) return 24;
+    if (mkt_client_packing_key_expand(&p, nparty, l, logB, mseed, body.data(), full.data()) != MKT_ERR_ARG) return 25;
+    if (mkt_client_packing_key_expand(&p, 0, l, logB, mseed, body.data(), full.data())) return 26;
+    if (std::memcmp(full.data(), body.data(), (size_t)N * word)) return 27;                        // polynomial 0 of row (0, 0) is its body
+    std::memcpy(ct.data(), full.data(), (size_t)(1 + kr) * N * word);
+    if (nparty > 1) std::memset(ct.data() + (size_t)2 * N * word, 0, (size_t)(p.k - 1) * N * word);
+    if (mkt_client_rlwe_phase(&p, K.data(), nparty, ct.data(), ph.data())) return 28;
+    if ((uint32_t)(ph[0] - want0 + (1u << 20)) > (2u << 20)) return 29;
+    for (int j = 1; j < N; j++) if ((uint32_t)(ph[(size_t)j] + (1u << 20)) > (2u << 20)) return 30;
     for (auto *k : K) mkt_client_party_destroy(k);
     std::printf("scheme %d n %d N %d W %d gadget (%d, %d): %zu key bytes per party\n", p.scheme, p.n, N, p.W, l, logB, pk[0].size());
     return 0;

@@ -9,6 +9,12 @@ every call on device tensors between two device events; the medians are reported
 a pack runs nparty n (l_pk + 1 + kr) transforms, a bootstrap nparty n (kr + 1) (l_gsw + 1) (the blind rotation's CMux count; the KMS
 schemes' second phase and every key switch are left out, so the estimate flatters the pack).
 --noise: the three cases of tests/test_gpu_pack.py (measured / predicted deviation, derived bands), written beside the timings.
+--keys: instead of the above, the cost of the packing KEY of one party (the last), alternating after one warm-up of each, `reps` times:
+  keygen_host     mkt_client_packing_keygen (the host generator, up to 16 threads)          wall clock: host work
+  keygen_device   mkt_packing_keygen_device (pack_keys.hip; secrets up, bodies down)        device events on the context's stream, and wall clock
+  load_full       mkt_load_packing_key from a host array [n][l][1 + kr][N]                  device events, and wall clock
+  load_seeded     mkt_load_packing_key_seeded from a host array [n][l][N]                   device events, and wall clock
+on a context that holds no other key; medians with the spread (min, max).  Writes pack_keys_<build id>.json.
 Writes pack_<build id>.json (and pack_noise_<build id>.json) into --out-dir.  A measurement path: it fails without a GPU."""
 import argparse
 import json
@@ -77,18 +83,67 @@ def measure(p, l, logB, reps, torch):
     return out
 
 
+def measure_keys(p, l, logB, reps, torch):
+    import time
+    party = p.nparty - 1
+    crs = mk.CRS(p, 11) if p.multikey else None
+    key = mk.PartyKeys(p, party=party, crs=crs, secrets_only=True, deterministic_seed=11 + party)
+    sch = mk.Scheme(p)
+    st = torch.cuda.Stream()
+    sch.set_stream(st.cuda_stream)                      # the events below are recorded on the stream the context enqueues on
+    ms_seed, body = mk.packing_keygen_seeded(key, p, l, logB, deterministic_seed=70)
+    full = mk.packing_key_expand(p, party, l, logB, ms_seed, body)
+    calls = {"keygen_host": lambda: mk.packing_keygen(key, p, l, logB, deterministic_seed=70),
+             "keygen_device": lambda: mk.packing_keygen_device(sch, party, key, l, logB, mask_seed=ms_seed, deterministic_seed=70),
+             "load_full": lambda: mk.load_packing_key(sch, party, full, l, logB),
+             "load_seeded": lambda: mk.load_packing_key_seeded(sch, party, ms_seed, body, l, logB)}
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record(st)
+        fn()
+        e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
+
+    for fn in calls.values():
+        fn()                                            # warm-up: code objects, the resident table
+    ev, wall = {k: [] for k in calls}, {k: [] for k in calls}
+    for _ in range(reps):
+        for k, fn in calls.items():                     # alternating
+            a, b = timed(fn)
+            ev[k].append(a)
+            wall[k].append(b)
+    sch.close()
+    stat = lambda v: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}      # noqa: E731
+    kr = 1 if p.multikey else p.k
+    return {"set": p.name, "n": p.n, "N": p.N, "W": p.W, "kr": kr, "gadget": [l, logB], "party": party, "reps": reps,
+            "full_bytes": int(full.nbytes), "seeded_bytes": int(body.nbytes) + 32, "host_threads": min(16, os.cpu_count() or 4),
+            "device_event_ms": {k: stat(v) for k, v in ev.items() if k != "keygen_host"}, "wall_ms": {k: stat(v) for k, v in wall.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="KMS2party_N1024_l2,KMS2party")
     ap.add_argument("--gadget", default="4,4")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--keys", action="store_true")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "a GPU is required: nothing here is measured on a CPU"
     l, logB = (int(v) for v in a.gadget.split(","))
     head = {"build_id": mk.build_id(), "device": torch.cuda.get_device_name(0)}
+    if a.keys:
+        rec = dict(head, tool="pack_time --keys", results=[measure_keys(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
+        os.makedirs(a.out_dir, exist_ok=True)
+        line = json.dumps(rec)
+        print(line)
+        with open(os.path.join(a.out_dir, f"pack_keys_{mk.build_id()}.json"), "w") as f:
+            f.write(line + "\n")
+        return
     res = dict(head, tool="pack_time", results=[measure(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
     files = {f"pack_{mk.build_id()}.json": res}
     if a.noise:
