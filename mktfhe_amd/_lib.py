@@ -160,6 +160,11 @@ PACK_SYMBOLS = {
     "mkt_packing_keygen_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
 }
 
+# every symbol include/mktfhe_ring_share.h declares (ring shares of packed results on the party's GPU), bound beside the two tables above
+RING_SHARE_SYMBOLS = {
+    "mkt_rlwe_partial_decrypt_batch": (_i, [_vp, _i, _vp, _vp, _dbl, _vp, _u64, _vp, _sz, _i]),
+}
+
 _lib = None
 
 
@@ -181,7 +186,7 @@ def lib():
         except Exception:  # noqa: BLE001
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **PACK_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **PACK_SYMBOLS, **RING_SHARE_SYMBOLS}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -17,6 +17,7 @@
 #include "fft_device.h"
 #include "host_internal.h"
 #include "rng_chacha.h"
+#include "../../include/mktfhe_ring_share.h"
 
 using mktd::cplx;
 using mkt::DevBuf;
@@ -2072,6 +2073,39 @@ int mkt_pack_batch(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, const uin
         }
     }
     return so.out(rlwe_out);
+}
+
+// Ring shares of packed results (mktfhe_ring_share.h; ring_share.hip): party `party`'s shares of G packs on this context's device, the words of
+// mkt_client_rlwe_partial_decrypt -- a party-local call like mkt_partial_decrypt_batch, on a context that needs no key of any kind.  The kr ring
+// key polynomials the packs are under are uploaded for the call and wiped before they are freed
+int mkt_rlwe_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const void *rlwe, double sigma_smudge, const uint8_t *seed,
+                                   uint64_t row0, void *share_out, size_t G, int mem) {
+    if (!c || !K || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::smudge_sigma_ok(sigma_smudge)) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: sigma_smudge must be finite, 0 <= sigma_smudge <= 2^31");
+    const mkt_params &p = c->p;
+    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
+    const int kr = c->sh.ksk_kr, zoff = mkt::is_kms(p.scheme) ? 1 : 0, N = p.N;
+    if ((int)K->zring.size() < zoff + kr) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: the party's keys lack a ring key");
+    if (!G) return MKT_OK;
+    if (!rlwe || !share_out) return fail(c, MKT_ERR_ARG, "bad argument");
+    DevGuard dg(c->device);
+    Timer whole(c, 0);
+    const size_t pb = poly_bytes(c);
+    Staged sx{c}, so{c};
+    DeviceSecret z{c};
+    int r;
+    if ((r = sx.in(rlwe, G * (size_t)(1 + c->sh.kacc) * pb, mem, true)) || (r = so.in(share_out, G * pb, mem, false))) return r;
+    mktd::RingShareArgs a{};
+    if (mkt::seed_to_key(seed, a.key)) { explicit_bzero(&a, sizeof a); return fail(c, MKT_ERR_STATE, "mkt_rlwe_partial_decrypt_batch: no entropy from the OS"); }
+    hipError_t e = z.alloc((size_t)kr * N);
+    for (int q = 0; q < kr && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[(size_t)zoff + q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    a.party = party; a.N = N; a.W = p.W; a.kr = kr; a.npoly = 1 + c->sh.kacc; a.sigma = sigma_smudge; a.row0 = row0;
+    a.poly0 = mkt::is_mk(p.scheme) ? 1 + party : 1; a.poly_step = mkt::is_mk(p.scheme) ? 0 : 1;
+    a.rlwe = sx.dev; a.zring = z.as<const int8_t>(); a.out = so.dev; a.G = G;
+    if (e == hipSuccess) e = mktd::launch_ring_share(a, c->stream);
+    e = wipe_secrets(e, z, a);
+    if (e != hipSuccess) return hipfail(c, e, "device ring share");
+    return so.out(share_out);
 }
 
 int mkt_enable_timing(mkt_ctx *c, int on) {

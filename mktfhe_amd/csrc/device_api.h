@@ -245,6 +245,24 @@ struct PackKeygenArgs {
 };
 hipError_t launch_pack_keygen(const PackKeygenArgs &a, hipStream_t s);
 
+// A party's ring shares of packed ciphertexts on the device (ring_share.hip; mktfhe_ring_share.h), the words of mkt_client_rlwe_partial_decrypt:
+// out[g] = sum_{c < kr} rlwe[g][poly0 + c * poly_step] (*) zring[c] + (draw j of stream 18 at pack row0 + g, lifted by W - 32 bits)_j, g < G
+struct RingShareArgs {
+    uint32_t key[8];             // 256-bit ChaCha20 key of the call's noise streams (rng_chacha.h)
+    int party, N, W, kr;
+    int npoly;                   // polynomials of one ciphertext, 1 + k
+    int poly0, poly_step;        // ciphertext polynomial of component c: the multi-key schemes (1 + party, 0), else (1, 1)
+    int slices;                  // workgroups that share one pack (set by the launcher: ring_share_slices)
+    double sigma;
+    uint64_t row0;
+    const void *rlwe;            // [G][npoly][N] ring words
+    const int8_t *zring;         // [kr][N]: the ring keys the packed ciphertext is under
+    void *out;                   // [G][N] ring words
+    size_t G;
+};
+int ring_share_slices(int N, size_t G);   // a power of two in N / 256 (one below N = 256) .. N / 16: more of them the fewer packs there are
+hipError_t launch_ring_share(RingShareArgs a, hipStream_t s);
+
 // Packed outputs (pack.hip; mktfhe_pack.h): one launch sequence packs `npacks` ciphertexts, pack0 .. pack0 + npacks - 1 of the call
 constexpr int PACK_QCHUNK = 4;   // mask words per workgroup of the product kernel: k n / 4 workgroups per pack (280 at the headline shape)
 struct PackArgs {

@@ -3,7 +3,7 @@
     pk_i   = packing_keygen(keys_i, params, l, logB)                  party i, once: an evaluation key, shipped with the others
     load_packing_key(scheme, i, pk_i, l, logB)                        evaluator, for every party
     rlwe   = pack(scheme, results)                                    evaluator: (ceil(B / N), k + 1, N) ring words for B rows of k*n+1
-    sh_i   = rlwe_partial_decrypt(rlwe, keys_i, params, i, sigma)     party i, alone: (packs, N) ring words
+    sh_i   = rlwe_partial_decrypt(rlwe, keys_i, params, i, sigma)     party i, alone: (packs, N) ring words (scheme=: on the party's own GPU)
     bits   = rlwe_merge_decrypt(rlwe[g], [sh_0[g], ...], params)      anyone: coefficient j = result row g N + j
 
 Coefficient j of a packed ciphertext carries the phase of row j, so it is also an ordinary accumulator of keyswitch_at, which reads row j
@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .params import Params
-from .scheme import MEM_DEVICE, PartyKeys, _arg, _count, _empty, _is_torch, _np_ptr, _row0, _rows, _seed32, _seed_arg
+from .scheme import MEM_DEVICE, PartyKeys, _arg, _Buf, _count, _empty, _is_torch, _np_ptr, _row0, _rows, _seed32, _seed_arg
 
 
 def _kr(params):
@@ -190,11 +190,23 @@ def rlwe_phase(rlwe, keys, params: Params):
     return out.reshape(lead + (params.N,))
 
 
-def rlwe_partial_decrypt(rlwe, key: PartyKeys, params: Params, party, sigma_smudge, deterministic_seed=None, row0=0):
+def rlwe_partial_decrypt(rlwe, key: PartyKeys, params: Params, party, sigma_smudge, deterministic_seed=None, row0=0, scheme=None):
     """party `party`'s ring shares of packed ciphertexts (..., k + 1, N) -> ring words (..., N): sum_c a_c (*) z_c + e, reading that party's
     polynomial(s) only.  sigma_smudge: deviation of the smudging noise in words of the 32-bit torus, 0 <= sigma_smudge <= 2^31.  The noise is
-    fresh per call; deterministic_seed (tests only) pins it, and row0 is then the index of this call's first PACK under that seed"""
+    fresh per call; deterministic_seed (tests only) pins it, and row0 is then the index of this call's first PACK under that seed.
+    scheme None: on the host (mkt_client_rlwe_partial_decrypt), numpy out.  scheme = a Scheme: on its GPU (mkt_rlwe_partial_decrypt_batch of
+    include/mktfhe_ring_share.h; it needs no key loaded), the same words; rlwe a numpy array or a GPU tensor, (G, k + 1, N) or one pack
+    (k + 1, N), the shares live where rlwe lives.  That hands this party's secret ring key(s) to that GPU: the party's own device, not the
+    evaluator's"""
     sp, _keep = _seed_arg(deterministic_seed)
+    if scheme is not None:
+        shape = tuple(np.shape(rlwe))
+        if shape[-2:] != (params.k + 1, params.N) or len(shape) > 3:
+            raise ValueError(f"packed ciphertexts of shape {shape}, expected (G, {params.k + 1}, {params.N}) or ({params.k + 1}, {params.N})")
+        G = int(np.prod(shape[:-2]))
+        out = _empty(rlwe, shape[:-2] + (params.N,), params.ring_dtype, "int64" if params.W == 64 else "int32")
+        return scheme._call("rlwe_partial_decrypt_batch", G, int(party), key.h, _Buf(rlwe, params.ring_dtype, G * (params.k + 1), params.N),
+                            float(sigma_smudge), sp, _row0(row0), _Buf(out, params.ring_dtype, G, params.N, out=True))[-1]
     c, lead = _cts(rlwe, params)
     G = int(np.prod(lead))
     out = np.empty(lead + (params.N,), dtype=params.ring_dtype)

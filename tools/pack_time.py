@@ -15,6 +15,10 @@ schemes' second phase and every key switch are left out, so the estimate flatter
   load_full       mkt_load_packing_key from a host array [n][l][1 + kr][N]                  device events, and wall clock
   load_seeded     mkt_load_packing_key_seeded from a host array [n][l][N]                   device events, and wall clock
 on a context that holds no other key; medians with the spread (min, max).  Writes pack_keys_<build id>.json.
+--shares: instead of the above, the ring share of one party (the last) at G = 1, 8, 64 packs, alternating after one warm-up of each, `reps` times:
+  host     mkt_client_rlwe_partial_decrypt on host arrays (one thread, a loop over packs)            wall clock: host work
+  device   mkt_rlwe_partial_decrypt_batch on device tensors (ring_share.hip; ring keys up, wiped)     wall clock, and device events
+a sample is as many back-to-back calls as fill 20 ms; per-call medians with the spread.  Writes ring_share_<build id>.json.
 Writes pack_<build id>.json (and pack_noise_<build id>.json) into --out-dir.  A measurement path: it fails without a GPU."""
 import argparse
 import json
@@ -123,6 +127,57 @@ def measure_keys(p, l, logB, reps, torch):
             "device_event_ms": {k: stat(v) for k, v in ev.items() if k != "keygen_host"}, "wall_ms": {k: stat(v) for k, v in wall.items()}}
 
 
+SHARE_PACKS = (1, 8, 64)
+SHARE_WINDOW_MS = 20.0      # a sample times as many back-to-back calls as fill this window: one call is a sub-millisecond window
+
+
+def measure_shares(p, reps, torch):
+    """the ring share of the last party, G = 1, 8, 64 packs of uniform ring words: host (mkt_client_rlwe_partial_decrypt, host arrays) against
+    device (mkt_rlwe_partial_decrypt_batch, device tensors in and out, on a context that holds no key).  Both calls return with their words
+    written -- the device call drains its stream when it wipes the secrets -- so both are timed by the host clock; the device call also
+    between two events on its stream"""
+    import time
+    party = p.nparty - 1
+    crs = mk.CRS(p, 11) if p.multikey else None
+    key = mk.PartyKeys(p, party=party, crs=crs, secrets_only=True, deterministic_seed=11 + party)
+    sch = mk.Scheme(p)
+    st = torch.cuda.Stream()
+    sch.set_stream(st.cuda_stream)
+    rng = np.random.default_rng(5)
+    sigma, seed = 2.0 ** 20, bytes(range(32))
+    stat = lambda v: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}      # noqa: E731
+    rows = []
+    for G in SHARE_PACKS:
+        ct = rng.integers(0, 2**63, (G, p.k + 1, p.N), dtype=np.uint64).astype(p.ring_dtype)
+        dct = torch.from_numpy(ct.view(np.int64 if p.W == 64 else np.int32)).cuda()
+        calls = {"host": lambda: mk.rlwe_partial_decrypt(ct, key, p, party, sigma, deterministic_seed=seed),
+                 "device": lambda: mk.rlwe_partial_decrypt(dct, key, p, party, sigma, deterministic_seed=seed, scheme=sch)}
+
+        def timed(fn, inner):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record(st)
+            for _ in range(inner):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / inner, e0.elapsed_time(e1) / inner
+
+        same = np.array_equal(calls["host"](), calls["device"]().cpu().numpy().view(p.ring_dtype))      # warm-up of each, and the words agree
+        inner = {k: max(1, min(500, int(np.ceil(SHARE_WINDOW_MS / max(timed(fn, 3)[0], 1e-3))))) for k, fn in calls.items()}
+        wall, ev = {k: [] for k in calls}, []
+        for _ in range(reps):
+            for k, fn in calls.items():                 # alternating
+                w, e = timed(fn, inner[k])
+                wall[k].append(w)
+                if k == "device":
+                    ev.append(e)
+        rows.append({"G": G, "same_words": bool(same), "calls_per_sample": inner, "wall_ms_per_call": {k: stat(v) for k, v in wall.items()},
+                     "device_event_ms_per_call": stat(ev), "host_over_device": round(statistics.median(wall["host"]) / statistics.median(wall["device"]), 3)})
+    sch.close()
+    return {"set": p.name, "N": p.N, "W": p.W, "k": p.k, "kr": 1 if p.multikey else p.k, "party": party, "reps": reps, "sigma_smudge": sigma, "packs": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="KMS2party_N1024_l2,KMS2party")
@@ -130,18 +185,22 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--keys", action="store_true")
+    ap.add_argument("--shares", action="store_true")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "a GPU is required: nothing here is measured on a CPU"
     l, logB = (int(v) for v in a.gadget.split(","))
     head = {"build_id": mk.build_id(), "device": torch.cuda.get_device_name(0)}
-    if a.keys:
-        rec = dict(head, tool="pack_time --keys", results=[measure_keys(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
+    if a.keys or a.shares:
+        if a.keys:
+            name, rec = "pack_keys", dict(head, tool="pack_time --keys", results=[measure_keys(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
+        else:
+            name, rec = "ring_share", dict(head, tool="pack_time --shares", results=[measure_shares(getattr(mk, s), a.reps, torch) for s in a.sets.split(",")])
         os.makedirs(a.out_dir, exist_ok=True)
         line = json.dumps(rec)
         print(line)
-        with open(os.path.join(a.out_dir, f"pack_keys_{mk.build_id()}.json"), "w") as f:
+        with open(os.path.join(a.out_dir, f"{name}_{mk.build_id()}.json"), "w") as f:
             f.write(line + "\n")
         return
     res = dict(head, tool="pack_time", results=[measure(getattr(mk, s), l, logB, a.reps, torch) for s in a.sets.split(",")])
