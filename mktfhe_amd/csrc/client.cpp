@@ -86,25 +86,72 @@ using namespace mkt;
 
 namespace {
 
-void store_poly(std::vector<uint8_t> &dst, size_t poly_index, const uint64_t *v, int N, int W) {
-    if (W == 64) std::memcpy(dst.data() + poly_index * N * 8, v, (size_t)N * 8);
-    else { uint32_t *d = (uint32_t *)dst.data() + poly_index * N; for (int i = 0; i < N; i++) d[i] = (uint32_t)v[i]; }
+// polynomial poly_index of an array of native-width polynomials <- v
+void store_poly(void *dst, size_t poly_index, const uint64_t *v, int N, int W) {
+    if (W == 64) std::memcpy((uint8_t *)dst + poly_index * N * 8, v, (size_t)N * 8);
+    else { uint32_t *d = (uint32_t *)dst + poly_index * N; for (int i = 0; i < N; i++) d[i] = (uint32_t)v[i]; }
 }
 void load_poly(const void *src, size_t poly_index, uint64_t *v, int N, int W) {
     if (W == 64) std::memcpy(v, (const uint8_t *)src + poly_index * N * 8, (size_t)N * 8);
     else { const uint32_t *s = (const uint32_t *)src + poly_index * N; for (int i = 0; i < N; i++) v[i] = s[i]; }
 }
 
-// RLWEsample (lwe.jl:78-93): a_c uniform, b = -sum a_c z_c + e; polys laid out (b, a_0..a_{kz-1}) in out
-void rlwe_sample(Rng &rng, const std::vector<std::vector<int8_t>> &z, int zoff, int kz, double sigma, int N, int W, uint64_t *out) {
-    uint64_t m = wmask(W);
-    std::memset(out, 0, sizeof(uint64_t) * (size_t)N);
-    for (int c = 0; c < kz; c++) {
+// The one step under every generator: body = -sum_c a_c (*) z_c + e + message.  Its two halves:
+// b = -sum_{c < kz} a_c (*) z[zoff + c]; mask(c) supplies the N ring words of a_c when it is their turn (a stream is drawn there, in order)
+template <typename MASK>
+void rlwe_body_acc(uint64_t *b, const std::vector<std::vector<int8_t>> &z, int zoff, int kz, int N, MASK mask) {
+    std::fill(b, b + N, 0);
+    for (int c = 0; c < kz; c++) mul_small_acc(mask(c), z[(size_t)zoff + c].data(), b, N, true);
+}
+// b[q] = (b[q] + e_q + msg(q)) mod 2^W, e_q the next N deviates of rng in coefficient order.  The sums are wrapping integers, so the order of
+// the terms is free; the number and the order of the draws is not
+template <typename MSG>
+void add_noise(uint64_t *b, int N, int W, Rng &rng, double sigma, MSG msg) {
+    const uint64_t m = wmask(W);
+    for (int q = 0; q < N; q++) b[q] = (b[q] + rng.noise(sigma) + msg(q)) & m;
+}
+inline uint64_t no_message(int) { return 0; }
+
+// RLWEsample (lwe.jl:78-93): a_c uniform, b = -sum a_c z_c + e + msg; polys laid out (b, a_0..a_{kz-1}) in out.  Draw order: mask c, then
+// its product, for each c; then the N noise draws
+template <typename MSG>
+void rlwe_sample(Rng &rng, const std::vector<std::vector<int8_t>> &z, int zoff, int kz, double sigma, int N, int W, uint64_t *out, MSG msg) {
+    const uint64_t m = wmask(W);
+    rlwe_body_acc(out, z, zoff, kz, N, [&](int c) {
         uint64_t *a = out + (size_t)(1 + c) * N;
         for (int i = 0; i < N; i++) a[i] = rng.next() & m;
-        mul_small_acc(a, z[zoff + c].data(), out, N, true);
-    }
-    for (int i = 0; i < N; i++) out[i] = (out[i] + rng.noise(sigma)) & m;
+        return a;
+    });
+    add_noise(out, N, W, rng, sigma, msg);
+}
+
+// the ternary r of UniEnc (unienc.jl:36-55): the next N draws of rng, (draw mod 3) - 1
+std::vector<int8_t> draw_ternary(Rng &rng, int N) {
+    std::vector<int8_t> rt(N);
+    for (int q = 0; q < N; q++) rt[q] = (int8_t)((int)(rng.next() % 3) - 1);
+    return rt;
+}
+// the UniEnc row d = crs_j r + msg + e (unienc.jl:36-55), e the next N deviates of rng; a is scratch
+template <typename MSG>
+void unienc_d_row(const void *crs, int j, const int8_t *rt, Rng &rng, double sigma, int N, int W, uint64_t *a, uint64_t *d, MSG msg) {
+    load_poly(crs, j, a, N, W);
+    std::fill(d, d + N, 0);
+    mul_small_acc(a, rt, d, N, false);                 // crs[j]*r
+    add_noise(d, N, W, rng, sigma, msg);
+}
+
+// key-switching row (d, t) of the extracted coefficient z = z_c[j] carries ((d + 1) z) << (32 - (t + 1) logD)  (lev.jl:31-37)
+inline uint32_t ksk_row_msg(int8_t z, int d, int t, int logD) { return (uint32_t)((uint32_t)z * (uint32_t)(d + 1)) << (32 - (t + 1) * logD); }
+// the rows (c, j), cj = c N + j, a block scheme leaves out: inside the embedded LWE key (keygen.jl:46,:147)
+inline bool ksk_row_absent(const mkt_params &p, long cj) { return is_block(p.scheme) && cj < p.n; }
+
+// the checked opening of an entry point: valid parameters and one of their parties -> the shape; MKT_ERR_ARG otherwise.  Calls that take
+// every party at once open with party 0
+int open_party(const mkt_params *params, int party, Shape &sh) {
+    std::string why;
+    if (!params || validate_params(*params, why)) return MKT_ERR_ARG;
+    sh = shape_of(*params);
+    return party < 0 || party >= sh.nparty ? (int)MKT_ERR_ARG : (int)MKT_OK;
 }
 
 void parallel_for(int n, const std::function<void(int)> &fn) {
@@ -153,8 +200,8 @@ int mkt_client_test_seed(uint64_t n, uint8_t out[32]) {
 }
 
 int mkt_client_crs(const mkt_params *params, const uint8_t *seed, void *crs_out) {
-    if (!params || !crs_out) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!crs_out || open_party(params, 0, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
     if (!is_mk(p.scheme)) return MKT_ERR_ARG;
     uint32_t key[8];
@@ -175,14 +222,11 @@ int mkt_client_crs(const mkt_params *params, const uint8_t *seed, void *crs_out)
 // key-switching keys are then generated on the device (mkt_keygen_device) from the same seeded streams
 static int party_keygen_impl(const mkt_params *params, const uint8_t *seed, int party, const void *crs,
                              double sigma_lwe, double sigma_ring, bool heavy, mkt_client_party **out) {
-    if (!params || !out) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!out || open_party(params, party, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
     if (is_mk(p.scheme) && !crs) return MKT_ERR_ARG;
     const int N = p.N, n = p.n, W = p.W;
-    const uint64_t wm = wmask(W);
     auto *K = new mkt_client_party();
     K->p = p; K->sh = sh; K->party = party;
     if (seed_to_key(seed, K->key)) { delete K; return MKT_ERR_STATE; }
@@ -221,11 +265,11 @@ static int party_keygen_impl(const mkt_params *params, const uint8_t *seed, int 
             std::vector<uint64_t> buf((size_t)polys * N);
             for (int c = 0; c <= kr; c++) for (int j = 0; j < l; j++) {
                 Rng r(ps, pa, 2, (uint32_t)i, (uint32_t)(c * l + j));
-                rlwe_sample(r, K->zring, 0, kr, sigma_ring, N, W, buf.data());
+                rlwe_sample(r, K->zring, 0, kr, sigma_ring, N, W, buf.data(), no_message);
                 uint64_t g = 1ull << (W - (j + 1) * p.logB_gsw);
-                buf[(size_t)c * N] = (buf[(size_t)c * N] + (uint64_t)K->lwekey[i] * g) & wm;  // c = 0: b[0]; c >= 1: a_{c-1}[0]
+                buf[(size_t)c * N] = (buf[(size_t)c * N] + (uint64_t)K->lwekey[i] * g) & wmask(W);  // c = 0: b[0]; c >= 1: a_{c-1}[0]
                 for (int q = 0; q < polys; q++)
-                    store_poly(K->brk, ((size_t)i * rows + (size_t)c * l + j) * polys + q, buf.data() + (size_t)q * N, N, W);
+                    store_poly(K->brk.data(), ((size_t)i * rows + (size_t)c * l + j) * polys + q, buf.data() + (size_t)q * N, N, W);
             }
         });
     } else {
@@ -234,22 +278,15 @@ static int party_keygen_impl(const mkt_params *params, const uint8_t *seed, int 
         K->brk.assign((size_t)n * 3 * l * N * sh.word, 0);
         parallel_for(n, [&](int i) {
             Rng r(ps, pa, 2, (uint32_t)i);
-            std::vector<int8_t> rt(N);
-            for (int q = 0; q < N; q++) rt[q] = (int8_t)((int)(r.next() % 3) - 1);      // ternary r
+            const std::vector<int8_t> rt = draw_ternary(r, N);
             std::vector<uint64_t> a(N), d(N), rl((size_t)2 * N);
-            std::vector<std::vector<int8_t>> rk{rt};
             for (int j = 0; j < l; j++) {
                 uint64_t g = 1ull << (W - (j + 1) * p.logB_uni);
-                load_poly(crs, j, a.data(), N, W);
-                std::fill(d.begin(), d.end(), 0);
-                mul_small_acc(a.data(), rt.data(), d.data(), N, false);                 // crs[j]*r
-                d[0] += (uint64_t)K->lwekey[i] * g;
-                for (int q = 0; q < N; q++) d[q] = (d[q] + r.noise(sigma_ring)) & wm;
-                store_poly(K->brk, (size_t)i * 3 * l + j, d.data(), N, W);
-                rlwe_sample(r, K->zring, 0, 1, sigma_ring, N, W, rl.data());             // f.stack[j] = RLWE_z(g_j * r)
-                for (int q = 0; q < N; q++) rl[q] = (rl[q] + g * (uint64_t)(int64_t)rt[q]) & wm;
-                store_poly(K->brk, (size_t)i * 3 * l + l + 2 * j, rl.data(), N, W);
-                store_poly(K->brk, (size_t)i * 3 * l + l + 2 * j + 1, rl.data() + N, N, W);
+                unienc_d_row(crs, j, rt.data(), r, sigma_ring, N, W, a.data(), d.data(), [&](int q) { return q ? 0 : (uint64_t)K->lwekey[i] * g; });
+                store_poly(K->brk.data(), (size_t)i * 3 * l + j, d.data(), N, W);
+                rlwe_sample(r, K->zring, 0, 1, sigma_ring, N, W, rl.data(), [&](int q) { return g * (uint64_t)(int64_t)rt[q]; });   // f.stack[j] = RLWE_z(g_j * r)
+                store_poly(K->brk.data(), (size_t)i * 3 * l + l + 2 * j, rl.data(), N, W);
+                store_poly(K->brk.data(), (size_t)i * 3 * l + l + 2 * j + 1, rl.data() + N, N, W);
             }
         });
     }
@@ -262,30 +299,23 @@ static int party_keygen_impl(const mkt_params *params, const uint8_t *seed, int 
         std::vector<uint64_t> a(N), b(N);
         Rng r(ps, pa, 3);
         for (int j = 0; j < l; j++) {
-            load_poly(crs, j, a.data(), N, W);
-            std::fill(b.begin(), b.end(), 0);
-            mul_small_acc(a.data(), K->zring[zi].data(), b.data(), N, true);            // -z*crs[j]
-            for (int q = 0; q < N; q++) b[q] = (b[q] + r.noise(sigma_ring)) & wm;
-            store_poly(K->pub, j, b.data(), N, W);
+            rlwe_body_acc(b.data(), K->zring, zi, 1, N, [&](int) { load_poly(crs, j, a.data(), N, W); return a.data(); });   // -z*crs[j]
+            add_noise(b.data(), N, W, r, sigma_ring, no_message);
+            store_poly(K->pub.data(), j, b.data(), N, W);
         }
         if (is_kms(p.scheme)) {
             K->rlk_d.assign((size_t)l * N * sh.word, 0);
             K->rlk_f.assign((size_t)l * 2 * N * sh.word, 0);
             Rng r2(ps, pa, 4);
-            std::vector<int8_t> rt(N);
-            for (int q = 0; q < N; q++) rt[q] = (int8_t)((int)(r2.next() % 3) - 1);
+            const std::vector<int8_t> rt = draw_ternary(r2, N);
             std::vector<uint64_t> d(N), rl((size_t)2 * N);
             for (int j = 0; j < l; j++) {
                 uint64_t g = 1ull << (W - (j + 1) * p.logB_uni);
-                load_poly(crs, j, a.data(), N, W);
-                std::fill(d.begin(), d.end(), 0);
-                mul_small_acc(a.data(), rt.data(), d.data(), N, false);
-                for (int q = 0; q < N; q++) d[q] = (d[q] + g * (uint64_t)K->zring[0][q] + r2.noise(sigma_ring)) & wm;  // + g_j * z'
-                store_poly(K->rlk_d, j, d.data(), N, W);
-                rlwe_sample(r2, K->zring, 1, 1, sigma_ring, N, W, rl.data());
-                for (int q = 0; q < N; q++) rl[q] = (rl[q] + g * (uint64_t)(int64_t)rt[q]) & wm;
-                store_poly(K->rlk_f, 2 * j, rl.data(), N, W);
-                store_poly(K->rlk_f, 2 * j + 1, rl.data() + N, N, W);
+                unienc_d_row(crs, j, rt.data(), r2, sigma_ring, N, W, a.data(), d.data(), [&](int q) { return g * (uint64_t)K->zring[0][q]; });  // + g_j * z'
+                store_poly(K->rlk_d.data(), j, d.data(), N, W);
+                rlwe_sample(r2, K->zring, 1, 1, sigma_ring, N, W, rl.data(), [&](int q) { return g * (uint64_t)(int64_t)rt[q]; });
+                store_poly(K->rlk_f.data(), 2 * j, rl.data(), N, W);
+                store_poly(K->rlk_f.data(), 2 * j + 1, rl.data() + N, N, W);
             }
         }
     }
@@ -298,11 +328,11 @@ static int party_keygen_impl(const mkt_params *params, const uint8_t *seed, int 
         K->ksk.assign((size_t)kk * N * dr * f * n1, 0);
         parallel_for(kk * N, [&](int cj) {
             int c = cj / N, j = cj % N;
-            if (is_block(p.scheme) && (long)c * N + j < n) return;       // keygen.jl:46,:147: only beyond the embedded LWE key
+            if (ksk_row_absent(p, cj)) return;
             Rng r(ps, pa, 5, (uint32_t)cj);
             for (int d = 0; d < dr; d++) for (int t = 0; t < f; t++) {
                 uint32_t *row = K->ksk.data() + ((((size_t)c * N + j) * dr + d) * f + t) * n1;
-                uint32_t msg = (uint32_t)((uint32_t)K->zring[zoff + c][j] * (uint32_t)(d + 1)) << (32 - (t + 1) * logD);
+                uint32_t msg = ksk_row_msg(K->zring[zoff + c][j], d, t, logD);
                 uint32_t dot = 0;
                 for (int q = 0; q < n; q++) { row[q] = (uint32_t)r.next(); dot += row[q] * K->lwekey[q]; }
                 row[n] = (uint32_t)r.noise(sigma_lwe) - dot + msg;
@@ -531,8 +561,13 @@ void ksk_mask_row(const uint32_t mkey[8], uint32_t party, uint64_t R, int n, uin
         for (int i = 0; i < 16 && q0 + i < n; i++) row[q0 + i] = w[i];
     }
 }
-// the rows (c, j) a block scheme leaves out: inside the embedded LWE key (keygen.jl:46,:147)
-inline bool ksk_row_absent(const mkt_params &p, long cj) { return is_block(p.scheme) && cj < p.n; }
+// sample S of an expanded key (b, a_0 .. a_{kz-1}): the body as it was shipped, the kz masks mask(c) regenerated behind it
+template <typename MASK>
+void expand_sample(void *out, size_t S, const void *bodies, int kz, int N, int W, MASK mask) {
+    const size_t pb = (size_t)N * (W / 8);
+    std::memcpy((uint8_t *)out + S * (kz + 1) * pb, (const uint8_t *)bodies + S * pb, pb);
+    for (int c = 0; c < kz; c++) store_poly(out, S * (kz + 1) + 1 + c, mask(c), N, W);
+}
 
 }  // namespace
 
@@ -547,7 +582,6 @@ int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed
     const mkt_params &p = K->p;
     const Shape &sh = K->sh;
     const int N = p.N, n = p.n, W = p.W;
-    const uint64_t wm = wmask(W);
     const uint32_t *ps = K->key; const uint32_t pa = (uint32_t)party;
     uint32_t mkey[8];
     seed_to_key(mask_seed, mkey);
@@ -562,18 +596,11 @@ int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed
             std::vector<uint64_t> a(N), b(N);
             for (int c = 0; c <= kr; c++) for (int j = 0; j < l; j++) {
                 const uint64_t S = (uint64_t)i * rows + (uint64_t)c * l + j;
-                std::fill(b.begin(), b.end(), 0);
-                for (int cc = 0; cc < kr; cc++) {
-                    brk_mask_poly(mkey, pa, S * kr + cc, N, W, a.data());
-                    mul_small_acc(a.data(), K->zring[cc].data(), b.data(), N, true);
-                }
+                rlwe_body_acc(b.data(), K->zring, 0, kr, N, [&](int cc) { brk_mask_poly(mkey, pa, S * kr + cc, N, W, a.data()); return a.data(); });
                 Rng r(ps, pa, mktrng::STREAM_BRK_NOISE, (uint32_t)S, (uint32_t)(S >> 32));
                 const uint64_t g = (uint64_t)K->lwekey[i] << (W - (j + 1) * p.logB_gsw);
-                for (int q = 0; q < N; q++) {
-                    const uint64_t m = c == 0 ? (q == 0 ? 1u : 0u) : (uint64_t)K->zring[c - 1][q];
-                    b[q] = (b[q] + r.noise(sigma_ring) + g * m) & wm;
-                }
-                store_poly(K->brk_seeded, S, b.data(), N, W);
+                add_noise(b.data(), N, W, r, sigma_ring, [&](int q) { return g * (c == 0 ? (q == 0 ? 1u : 0u) : (uint64_t)K->zring[c - 1][q]); });
+                store_poly(K->brk_seeded.data(), S, b.data(), N, W);
             }
         });
     } else {
@@ -581,22 +608,15 @@ int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed
         const int l = p.l_uni;
         parallel_for(n, [&](int i) {
             Rng r(ps, pa, mktrng::STREAM_UNI_NOISE, (uint32_t)i);
-            std::vector<int8_t> rt(N);
-            for (int q = 0; q < N; q++) rt[q] = (int8_t)((int)(r.next() % 3) - 1);
+            const std::vector<int8_t> rt = draw_ternary(r, N);
             std::vector<uint64_t> a(N), d(N);
             for (int j = 0; j < l; j++) {
                 const uint64_t g = 1ull << (W - (j + 1) * p.logB_uni);
-                load_poly(crs, j, a.data(), N, W);
-                std::fill(d.begin(), d.end(), 0);
-                mul_small_acc(a.data(), rt.data(), d.data(), N, false);
-                d[0] += (uint64_t)K->lwekey[i] * g;
-                for (int q = 0; q < N; q++) d[q] = (d[q] + r.noise(sigma_ring)) & wm;
-                store_poly(K->brk_seeded, (size_t)i * 2 * l + j, d.data(), N, W);
-                brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data());
-                std::fill(d.begin(), d.end(), 0);
-                mul_small_acc(a.data(), K->zring[0].data(), d.data(), N, true);
-                for (int q = 0; q < N; q++) d[q] = (d[q] + r.noise(sigma_ring) + g * (uint64_t)(int64_t)rt[q]) & wm;
-                store_poly(K->brk_seeded, (size_t)i * 2 * l + l + j, d.data(), N, W);
+                unienc_d_row(crs, j, rt.data(), r, sigma_ring, N, W, a.data(), d.data(), [&](int q) { return q ? 0 : (uint64_t)K->lwekey[i] * g; });
+                store_poly(K->brk_seeded.data(), (size_t)i * 2 * l + j, d.data(), N, W);
+                rlwe_body_acc(d.data(), K->zring, 0, 1, N, [&](int) { brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data()); return a.data(); });
+                add_noise(d.data(), N, W, r, sigma_ring, [&](int q) { return g * (uint64_t)(int64_t)rt[q]; });
+                store_poly(K->brk_seeded.data(), (size_t)i * 2 * l + l + j, d.data(), N, W);
             }
         });
     }
@@ -610,7 +630,7 @@ int mkt_client_party_keygen_seeded(const mkt_params *params, const uint8_t *seed
             std::vector<uint32_t> row(n);
             for (int d = 0; d < dr; d++) for (int t = 0; t < f; t++) {
                 const uint64_t R = ((uint64_t)cj * dr + d) * f + t;
-                const uint32_t msg = (uint32_t)((uint32_t)K->zring[zoff + c][j] * (uint32_t)(d + 1)) << (32 - (t + 1) * logD);
+                const uint32_t msg = ksk_row_msg(K->zring[zoff + c][j], d, t, logD);
                 ksk_mask_row(mkey, pa, R, n, row.data());
                 uint32_t dot = 0;
                 for (int q = 0; q < n; q++) dot += row[q] * K->lwekey[q];
@@ -629,11 +649,9 @@ const uint8_t *mkt_client_mask_seed(const mkt_client_party *p) { return p && p->
 // the ordinary keys of a seeded party: the layouts of mkt_load_brk (MKT_FMT_INT_COEFF) and mkt_load_ksk; needs no key
 int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uint8_t *mask_seed, const void *brk_seeded, const uint32_t *ksk_seeded,
                                   void *brk_out, uint32_t *ksk_out) {
-    if (!params || !mask_seed) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!mask_seed || open_party(params, party, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
     if (!brk_seeded != !brk_out || !ksk_seeded != !ksk_out) return MKT_ERR_ARG;
     const int N = p.N, n = p.n, W = p.W;
     const uint32_t pa = (uint32_t)party;
@@ -645,13 +663,7 @@ int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uin
         const size_t samples = (size_t)n * (kr + 1) * p.l_gsw;
         parallel_for((int)samples, [&](int S) {
             std::vector<uint64_t> a(N);
-            uint8_t *o = (uint8_t *)brk_out + (size_t)S * (kr + 1) * pb;
-            std::memcpy(o, (const uint8_t *)brk_seeded + (size_t)S * pb, pb);
-            for (int cc = 0; cc < kr; cc++) {
-                brk_mask_poly(mkey, pa, (uint64_t)S * kr + cc, N, W, a.data());
-                if (W == 64) std::memcpy(o + (size_t)(1 + cc) * pb, a.data(), pb);
-                else { uint32_t *d = (uint32_t *)(o + (size_t)(1 + cc) * pb); for (int q = 0; q < N; q++) d[q] = (uint32_t)a[q]; }
-            }
+            expand_sample(brk_out, (size_t)S, brk_seeded, kr, N, W, [&](int cc) { brk_mask_poly(mkey, pa, (uint64_t)S * kr + cc, N, W, a.data()); return a.data(); });
         });
     } else if (brk_out) {
         const int l = p.l_uni;
@@ -659,14 +671,9 @@ int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uin
             std::vector<uint64_t> a(N);
             const uint8_t *src = (const uint8_t *)brk_seeded + (size_t)i * 2 * l * pb;
             uint8_t *o = (uint8_t *)brk_out + (size_t)i * 3 * l * pb;
-            std::memcpy(o, src, (size_t)l * pb);
-            for (int j = 0; j < l; j++) {
-                std::memcpy(o + (size_t)(l + 2 * j) * pb, src + (size_t)(l + j) * pb, pb);
-                brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data());
-                uint8_t *d8 = o + (size_t)(l + 2 * j + 1) * pb;
-                if (W == 64) std::memcpy(d8, a.data(), pb);
-                else { uint32_t *d = (uint32_t *)d8; for (int q = 0; q < N; q++) d[q] = (uint32_t)a[q]; }
-            }
+            std::memcpy(o, src, (size_t)l * pb);                       // the d_j as they are; behind them the f_j are l samples of one mask each
+            for (int j = 0; j < l; j++)
+                expand_sample(o + (size_t)l * pb, (size_t)j, src + (size_t)l * pb, 1, N, W, [&](int) { brk_mask_poly(mkey, pa, (uint64_t)i * l + j, N, W, a.data()); return a.data(); });
         });
     }
     if (ksk_out) {
@@ -690,12 +697,13 @@ int mkt_client_seeded_keys_expand(const mkt_params *params, int party, const uin
 
 namespace {
 
-void store_poly_raw(void *dst, size_t poly_index, const uint64_t *v, int N, int W) {
-    if (W == 64) std::memcpy((uint8_t *)dst + poly_index * N * 8, v, (size_t)N * 8);
-    else { uint32_t *d = (uint32_t *)dst + poly_index * N; for (int i = 0; i < N; i++) d[i] = (uint32_t)v[i]; }
-}
 // the ring keys a packed ciphertext is under (the ones the key-switching key switches from): first ring-key polynomial of a party, how many
 inline int pack_zoff(const mkt_params &p) { return is_kms(p.scheme) ? 1 : 0; }
+// mask polynomial P of a party's packing key (stream 19, the gadget in the high index word) as ring words, into a
+const uint64_t *pack_mask_poly(const uint32_t mkey[8], int party, uint32_t P, int l_pk, int logB_pk, int N, int W, uint64_t *a) {
+    mask_poly(mkey, mktrng::STREAM_PACK_MASK, (uint32_t)party, mktrng::pack_mask_index(P, l_pk, logB_pk), N, W, a);
+    return a;
+}
 // acc += sum_c a_{slot(party, c)} (*) z_{party, c} for one party's components of one packed ciphertext [1 + k][N]
 void ring_share_acc(const mkt_params &p, const Shape &sh, const mkt_client_party *K, int party, const void *rlwe, uint64_t *acc, uint64_t *a) {
     for (int c = 0; c < sh.ksk_kr; c++) {
@@ -710,22 +718,20 @@ extern "C" {
 
 // row (q, t) = RLWE_z(s[q] g_t): rlev_encrypt (lev.jl:88-94) of the constant s[q]; one stream per row
 int mkt_client_packing_keygen(const mkt_params *params, const mkt_client_party *K, int party, int l_pk, int logB_pk, const uint8_t *seed, void *pk_out) {
-    if (!params || !K || !pk_out || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!K || !pk_out || !pack_gadget_ok(l_pk, logB_pk) || open_party(params, party, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    if (!party_keys_match(K, p, party)) return MKT_ERR_ARG;
     const int N = p.N, W = p.W, kr = sh.ksk_kr, polys = kr + 1;
-    const uint64_t wm = wmask(W);
     uint32_t key[8];
     if (seed_to_key(seed, key)) return MKT_ERR_STATE;
     parallel_for(p.n, [&](int q) {
         std::vector<uint64_t> buf((size_t)polys * N);
         for (int t = 0; t < l_pk; t++) {
             Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_KEY, (uint32_t)q, (uint32_t)t);
-            rlwe_sample(r, K->zring, pack_zoff(p), kr, K->sigma_ring, N, W, buf.data());
-            buf[0] = (buf[0] + ((uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk))) & wm;
-            for (int c = 0; c < polys; c++) store_poly_raw(pk_out, ((size_t)q * l_pk + t) * polys + c, buf.data() + (size_t)c * N, N, W);
+            const uint64_t g = (uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk);
+            rlwe_sample(r, K->zring, pack_zoff(p), kr, K->sigma_ring, N, W, buf.data(), [&](int j) { return j ? 0 : g; });
+            for (int c = 0; c < polys; c++) store_poly(pk_out, ((size_t)q * l_pk + t) * polys + c, buf.data() + (size_t)c * N, N, W);
         }
     });
     explicit_bzero(key, sizeof key);
@@ -735,31 +741,26 @@ int mkt_client_packing_keygen(const mkt_params *params, const mkt_client_party *
 // the seeded form (mktfhe_pack.h "SEEDED"): the bodies of the rows, masks from the public stream 19, noise from the secret stream 20
 int mkt_client_packing_keygen_seeded(const mkt_params *params, const mkt_client_party *K, int party, int l_pk, int logB_pk, const uint8_t *seed,
                                      const uint8_t *mask_seed, void *pk_seeded_out) {
-    if (!params || !K || !pk_seeded_out || !mask_seed || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!K || !pk_seeded_out || !mask_seed || !pack_gadget_ok(l_pk, logB_pk) || open_party(params, party, sh)) return MKT_ERR_ARG;
     if (seed && std::memcmp(seed, mask_seed, 32) == 0) return MKT_ERR_ARG;      // the mask seed is published: the noise would be too
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    if (!party_keys_match(K, p, party)) return MKT_ERR_ARG;
     if (std::memcmp(mask_seed, K->key, sizeof K->key) == 0) return MKT_ERR_ARG;  // nor may it be the seed of the party's secrets
     const int N = p.N, W = p.W, kr = sh.ksk_kr;
-    const uint64_t wm = wmask(W);
     uint32_t key[8], mkey[8];
     if (seed_to_key(seed, key)) return MKT_ERR_STATE;
     seed_to_key(mask_seed, mkey);
     parallel_for(p.n, [&](int q) {
         std::vector<uint64_t> a(N), b(N);
+        const auto pack_mask = [&](uint32_t S, int c) { return pack_mask_poly(mkey, party, S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk, N, W, a.data()); };
         for (int t = 0; t < l_pk; t++) {
             const uint32_t S = (uint32_t)q * (uint32_t)l_pk + (uint32_t)t;
-            std::fill(b.begin(), b.end(), 0);
-            for (int c = 0; c < kr; c++) {
-                mask_poly(mkey, mktrng::STREAM_PACK_MASK, (uint32_t)party, mktrng::pack_mask_index(S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk), N, W, a.data());
-                mul_small_acc(a.data(), K->zring[(size_t)pack_zoff(p) + c].data(), b.data(), N, true);
-            }
+            rlwe_body_acc(b.data(), K->zring, pack_zoff(p), kr, N, [&](int c) { return pack_mask(S, c); });
             Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_NOISE, (uint32_t)q, (uint32_t)t);
-            for (int j = 0; j < N; j++) b[j] = (b[j] + r.noise(K->sigma_ring)) & wm;
-            b[0] = (b[0] + ((uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk))) & wm;
-            store_poly_raw(pk_seeded_out, S, b.data(), N, W);
+            const uint64_t g = (uint64_t)K->lwekey[q] << (W - (t + 1) * logB_pk);
+            add_noise(b.data(), N, W, r, K->sigma_ring, [&](int j) { return j ? 0 : g; });
+            store_poly(pk_seeded_out, S, b.data(), N, W);
         }
     });
     explicit_bzero(key, sizeof key);
@@ -768,24 +769,17 @@ int mkt_client_packing_keygen_seeded(const mkt_params *params, const mkt_client_
 
 // the definition of expansion: bodies copied, masks regenerated; needs no key
 int mkt_client_packing_key_expand(const mkt_params *params, int party, int l_pk, int logB_pk, const uint8_t *mask_seed, const void *pk_seeded, void *pk_out) {
-    if (!params || !mask_seed || !pk_seeded || !pk_out || !pack_gadget_ok(l_pk, logB_pk)) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!mask_seed || !pk_seeded || !pk_out || !pack_gadget_ok(l_pk, logB_pk) || open_party(params, party, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty) return MKT_ERR_ARG;
-    const int N = p.N, W = p.W, kr = sh.ksk_kr, polys = kr + 1;
-    const size_t pb = (size_t)N * sh.word;
+    const int N = p.N, W = p.W, kr = sh.ksk_kr;
     uint32_t mkey[8];
     seed_to_key(mask_seed, mkey);
     parallel_for(p.n, [&](int q) {
         std::vector<uint64_t> a(N);
         for (int t = 0; t < l_pk; t++) {
             const uint32_t S = (uint32_t)q * (uint32_t)l_pk + (uint32_t)t;
-            std::memcpy((uint8_t *)pk_out + (size_t)S * polys * pb, (const uint8_t *)pk_seeded + (size_t)S * pb, pb);
-            for (int c = 0; c < kr; c++) {
-                mask_poly(mkey, mktrng::STREAM_PACK_MASK, (uint32_t)party, mktrng::pack_mask_index(S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk), N, W, a.data());
-                store_poly_raw(pk_out, (size_t)S * polys + 1 + c, a.data(), N, W);
-            }
+            expand_sample(pk_out, S, pk_seeded, kr, N, W, [&](int c) { return pack_mask_poly(mkey, party, S * (uint32_t)kr + (uint32_t)c, l_pk, logB_pk, N, W, a.data()); });
         }
     });
     return MKT_OK;
@@ -793,10 +787,9 @@ int mkt_client_packing_key_expand(const mkt_params *params, int party, int l_pk,
 
 // TEST HARNESS: the top 32 bits of b + sum a z, every product exact
 int mkt_client_rlwe_phase(const mkt_params *params, const mkt_client_party *const *keys, int nparties, const void *rlwe, uint32_t *phase_out) {
-    if (!params || !keys || !rlwe || !phase_out) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!keys || !rlwe || !phase_out || open_party(params, 0, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
     if (nparties != sh.nparty) return MKT_ERR_ARG;
     for (int i = 0; i < nparties; i++) if (!keys[i] || !party_keys_match(keys[i], p, i)) return MKT_ERR_ARG;
     std::vector<uint64_t> acc(p.N), a(p.N);
@@ -809,11 +802,10 @@ int mkt_client_rlwe_phase(const mkt_params *params, const mkt_client_party *cons
 // share[g] = sum_c a_{slot(party,c)}[g] (*) z_c + e[g], e[g] the N smudging words of pack row0 + g (stream 18), lifted to the ring's width
 int mkt_client_rlwe_partial_decrypt(const mkt_params *params, const mkt_client_party *K, int party, const void *rlwe, double sigma_smudge,
                                     const uint8_t *seed, uint64_t row0, void *share_out, size_t G) {
-    if (!params || !K || !smudge_sigma_ok(sigma_smudge)) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!K || !smudge_sigma_ok(sigma_smudge) || open_party(params, party, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    const Shape sh = shape_of(p);
-    if (party < 0 || party >= sh.nparty || !party_keys_match(K, p, party)) return MKT_ERR_ARG;
+    if (!party_keys_match(K, p, party)) return MKT_ERR_ARG;
     if (!G) return MKT_OK;
     if (!rlwe || !share_out) return MKT_ERR_ARG;
     uint32_t key[8];
@@ -825,7 +817,7 @@ int mkt_client_rlwe_partial_decrypt(const mkt_params *params, const mkt_client_p
         ring_share_acc(p, sh, K, party, (const uint8_t *)rlwe + g * ctb, acc.data(), a.data());
         Rng r(key, (uint32_t)party, mktrng::STREAM_PACK_SMUDGE, (uint32_t)(row0 + g), (uint32_t)((row0 + g) >> 32));
         for (int j = 0; j < p.N; j++) acc[j] = (acc[j] + (r.noise(sigma_smudge) << (p.W - 32))) & wmask(p.W);
-        store_poly_raw(share_out, g, acc.data(), p.N, p.W);
+        store_poly(share_out, g, acc.data(), p.N, p.W);
     }
     explicit_bzero(key, sizeof key);
     return MKT_OK;
@@ -833,10 +825,10 @@ int mkt_client_rlwe_partial_decrypt(const mkt_params *params, const mkt_client_p
 
 // top 32 bits of b[j] + sum_i share_i[j], j < count; shares [nparty][N]
 static int rlwe_merge(const mkt_params *params, const void *rlwe, const void *shares, int nparties, size_t count, uint32_t *phase_out, uint8_t *bits_out) {
-    if (!params || !rlwe || !shares || (!phase_out && !bits_out)) return MKT_ERR_ARG;
-    std::string why; if (validate_params(*params, why)) return MKT_ERR_ARG;
+    Shape sh;
+    if (!rlwe || !shares || (!phase_out && !bits_out) || open_party(params, 0, sh)) return MKT_ERR_ARG;
     const mkt_params &p = *params;
-    if (nparties != shape_of(p).nparty || count > (size_t)p.N) return MKT_ERR_ARG;
+    if (nparties != sh.nparty || count > (size_t)p.N) return MKT_ERR_ARG;
     std::vector<uint64_t> acc(p.N), s(p.N);
     load_poly(rlwe, 0, acc.data(), p.N, p.W);
     for (int i = 0; i < nparties; i++) { load_poly(shares, (size_t)i, s.data(), p.N, p.W); for (int j = 0; j < p.N; j++) acc[j] += s[j]; }

@@ -542,11 +542,19 @@ struct Staged {
 
 // A secret on the device for the length of one scope (the TRUST note in mktfhe.h): uploaded on the context's stream; zeroed on that stream and
 // the stream drained before the buffer is freed, by whatever path the scope is left.  Declared AFTER a call's Staged objects: its wipe is drained before they free
+struct RingKeys { int first = 0, count = 0; };   // a party's ring-key polynomials [first, first + count)
 struct DeviceSecret {
     mkt_ctx *c; DevBuf buf; size_t bytes = 0;
     template <class T> T *as() const { return buf.as<T>(); }
     hipError_t alloc(size_t nbytes) { bytes = nbytes; return buf.alloc(nbytes); }
     hipError_t in(const void *host, size_t nbytes) { const hipError_t e = alloc(nbytes); return e != hipSuccess ? e : hipMemcpyAsync(buf.p, host, nbytes, hipMemcpyHostToDevice, c->stream); }
+    // ring-key polynomials rk of K, end to end (the host keeps them one vector each)
+    hipError_t ring_keys(const mkt_client_party *K, RingKeys rk) {
+        const size_t N = (size_t)c->p.N;
+        hipError_t e = alloc((size_t)rk.count * N);
+        for (int q = 0; q < rk.count && e == hipSuccess; q++) e = hipMemcpyAsync(as<int8_t>() + q * N, K->zring[(size_t)rk.first + q].data(), N, hipMemcpyHostToDevice, c->stream);
+        return e;
+    }
     hipError_t wipe_now() {   // behind everything enqueued so far; the result of draining the stream
         if (!buf.p) return hipSuccess;
         (void)hipMemsetAsync(buf.p, 0, bytes, c->stream);
@@ -568,11 +576,10 @@ struct KeygenOut { DevBuf *buf; size_t bytes; };
 template <class Args> hipError_t keygen_setup(mkt_ctx *c, const mkt_client_party *K, const void *crs, DeviceSecret &lwe, DeviceSecret &z, std::initializer_list<KeygenOut> outs, DevBuf &crs_int, Args &a) {
     const mkt_params &p = c->p;
     const bool unienc = p.scheme == MKT_CCS;
-    const int N = p.N, nz = (int)K->zring.size();
+    const int N = p.N;
     const size_t crs_bytes = (size_t)p.l_uni * poly_bytes(c);
     hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
-    if (e == hipSuccess) e = z.alloc((size_t)nz * N);
-    for (int q = 0; q < nz && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = z.ring_keys(K, {0, (int)K->zring.size()});
     for (const KeygenOut &o : outs) if (e == hipSuccess) e = o.buf->alloc(o.bytes);
     if (e == hipSuccess && unienc) e = crs_int.alloc(crs_bytes);
     if (e == hipSuccess && unienc) e = hipMemcpyAsync(crs_int.p, crs, crs_bytes, hipMemcpyHostToDevice, c->stream);
@@ -591,6 +598,16 @@ bool ring_keys_cover(const mkt_ctx *c, const mkt_client_party *K) {
     return nz >= (c->p.scheme == MKT_CCS ? 1 : c->sh.kr) && nz >= (mkt::is_kms(c->p.scheme) ? 1 : 0) + c->sh.ksk_kr;
 }
 bool mem_ok(int mem) { return mem == MKT_MEM_DEVICE || mem == MKT_MEM_HOST; }
+// the ring keys packed ciphertexts are under: the ones the key-switching key switches from (the uni key of the KMS schemes: 1)
+RingKeys pack_ring_keys(const mkt_ctx *c) { return c ? RingKeys{mkt::is_kms(c->p.scheme) ? 1 : 0, c->sh.ksk_kr} : RingKeys{}; }
+// The refusals a party-local call `who` opens with: a null context or key, a bad argument of its own (args_ok) or a party out of range; keys made
+// for other parameters or another party; and, where the call reads ring keys itself, keys without the polynomials rk
+int party_call_guard(mkt_ctx *c, const char *who, bool args_ok, int party, const mkt_client_party *K, RingKeys rk = {}) {
+    if (!c || !K || !args_ok || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (!mkt::party_keys_match(K, c->p, party)) return fail(c, MKT_ERR_ARG, std::string(who) + ": the party's keys were made for other parameters / another party index");
+    if ((int)K->zring.size() < rk.first + rk.count) return fail(c, MKT_ERR_ARG, std::string(who) + ": the party's keys lack a ring key");
+    return MKT_OK;
+}
 
 // ---- MKT_ARITH_EXACT: tables of the two-prime negacyclic NTT (ntt_exact.hip), computed on the host, uploaded once ----
 constexpr uint32_t NTT_P[2] = {1073668097u, 1073692673u};        // 131063 * 2^13 + 1, 131066 * 2^13 + 1: the two largest NTT primes below 2^30 (ntt_exact.hip)
@@ -1090,8 +1107,8 @@ int mkt_load_crs(mkt_ctx *c, const void *a, int fmt) {
 // (keygen.hip: the seeded streams of mkt_client_party_keygen, identical words), pre-transformed in place of an upload.
 static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, const void *crs, void *brk_out, uint32_t *ksk_out) {
     if (int r = key_write_guard(c, K != nullptr, party, Gate::EXACT)) return r;
+    if (int r = party_call_guard(c, "mkt_keygen_device", true, party, K)) return r;
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: the party's keys were made for other parameters / another party index");
     const bool unienc = p.scheme == MKT_CCS;
     if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device: CCS needs the integer CRS");
     DevGuard dg(c->device);
@@ -1132,10 +1149,9 @@ int mkt_keygen_device_export(mkt_ctx *c, int party, const mkt_client_party *K, c
 // mkt_keygen_device, on a context that needs no evaluation key.  The n key words are uploaded for the call and wiped before they are freed.
 int mkt_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const uint32_t *lwe, double sigma_smudge, const uint8_t *seed,
                               uint64_t row0, uint32_t *share_out, size_t B, int mem) {
-    if (!c || !K || !lwe || !share_out || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = party_call_guard(c, "mkt_partial_decrypt_batch", lwe && share_out && mem_ok(mem), party, K)) return r;
     if (!mkt::smudge_sigma_ok(sigma_smudge)) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: sigma_smudge must be finite, 0 <= sigma_smudge <= 2^31");
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
     if (!B) return MKT_OK;
     DevGuard dg(c->device);
     Timer whole(c, 0);
@@ -1175,11 +1191,10 @@ int mkt_seeded_expand_batch(mkt_ctx *c, int party, const uint8_t *mask_seed, uin
 // the party's call, party-local like mkt_partial_decrypt_batch: the n key words are uploaded for the call and wiped before they are freed
 int mkt_seeded_encrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const uint32_t *mu, double sigma_lwe, const uint8_t *mask_seed,
                              const uint8_t *noise_seed, uint64_t row0, uint32_t *body_out, size_t B, int mem) {
-    if (!c || !K || !mask_seed || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = party_call_guard(c, "mkt_seeded_encrypt_batch", mask_seed && mem_ok(mem), party, K)) return r;
     if (!mkt::smudge_sigma_ok(sigma_lwe)) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: sigma_lwe must be finite, 0 <= sigma_lwe <= 2^31");
     if (noise_seed && std::memcmp(noise_seed, mask_seed, 32) == 0) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the noise seed is the public mask seed");
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_seeded_encrypt_batch: the party's keys were made for other parameters / another party index");
     if (!B) return MKT_OK;
     if (!mu || !body_out) return fail(c, MKT_ERR_ARG, "bad argument");
     DevGuard dg(c->device);
@@ -1263,11 +1278,10 @@ int mkt_load_seeded_keys(mkt_ctx *c, int party, const uint8_t *mask_seed, const 
 // expansion and install of mkt_load_seeded_keys.  Party-local like mkt_keygen_device: the secrets are wiped before they are freed.
 int mkt_keygen_device_seeded(mkt_ctx *c, int party, const mkt_client_party *K, const void *crs, const uint8_t *mask_seed, void *brk_seeded_out,
                              uint32_t *ksk_seeded_out, int install) {
-    if (!c || !K || !mask_seed || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    if (int r = party_call_guard(c, "mkt_keygen_device_seeded", mask_seed != nullptr, party, K)) return r;
     if (!brk_seeded_out != !ksk_seeded_out) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the two compact outputs come together");
     if (!brk_seeded_out && !install) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: neither an output nor an install was asked for");
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: the party's keys were made for other parameters / another party index");
     const bool unienc = p.scheme == MKT_CCS;
     if (unienc && !crs) return fail(c, MKT_ERR_ARG, "mkt_keygen_device_seeded: CCS needs the integer CRS");
     // (the stream key is the seed's 32 bytes as eight little-endian words, seed_to_key: compared where it lies, no copy of it made)
@@ -1968,15 +1982,14 @@ int mkt_load_packing_key_seeded(mkt_ctx *c, int party, const uint8_t *mask_seed,
 // install: the bodies, still on the device, also go through the expansion and install of mkt_load_packing_key_seeded
 int mkt_packing_keygen_device(mkt_ctx *c, int party, const mkt_client_party *K, int l_pk, int logB_pk, const uint8_t *seed, const uint8_t *mask_seed,
                               void *pk_seeded_out, int install) {
-    if (!c || !K || !mask_seed || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    const RingKeys rk = pack_ring_keys(c);
+    if (int r = party_call_guard(c, "mkt_packing_keygen_device", mask_seed != nullptr, party, K, rk)) return r;
     if (!pk_seeded_out && !install) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: neither an output nor an install was asked for");
     if (!mkt::pack_gadget_ok(l_pk, logB_pk)) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the packing gadget needs 1 <= logB_pk <= 16, 1 <= l_pk, l_pk * logB_pk <= 32");
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the party's keys were made for other parameters / another party index");
+    const int N = p.N;
     if ((seed && std::memcmp(seed, mask_seed, 32) == 0) || std::memcmp(mask_seed, K->key, sizeof K->key) == 0)
         return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the mask seed is a secret seed of the call (it is published: the secrets would be too)");
-    const int kr = c->sh.ksk_kr, zoff = mkt::is_kms(p.scheme) ? 1 : 0, N = p.N;
-    if ((int)K->zring.size() < zoff + kr) return fail(c, MKT_ERR_ARG, "mkt_packing_keygen_device: the party's keys lack a ring key");
     if (install) if (int r = pack_load_guard(c, "mkt_packing_keygen_device", l_pk, logB_pk)) return r;
     DevGuard dg(c->device);
     const size_t body_bytes = (size_t)p.n * l_pk * poly_bytes(c);
@@ -1984,13 +1997,12 @@ int mkt_packing_keygen_device(mkt_ctx *c, int party, const mkt_client_party *K, 
     DeviceSecret lwe{c}, z{c};
     mktd::PackKeygenArgs a{};
     hipError_t e = lwe.in(K->lwekey.data(), (size_t)p.n * 4);
-    if (e == hipSuccess) e = z.alloc((size_t)kr * N);
-    for (int q = 0; q < kr && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[(size_t)zoff + q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = z.ring_keys(K, rk);
     if (e == hipSuccess) e = bodies.alloc(body_bytes);
     if (e != hipSuccess) return hipfail(c, e, "device packing keygen setup");
     if (mkt::seed_to_key(seed, a.key)) { explicit_bzero(&a, sizeof a); return fail(c, MKT_ERR_STATE, "mkt_packing_keygen_device: no entropy"); }
     mkt::seed_to_key(mask_seed, a.mkey);
-    a.party = party; a.N = N; a.n = p.n; a.W = p.W; a.kr = kr; a.l = l_pk; a.logB = logB_pk; a.sigma_ring = K->sigma_ring;
+    a.party = party; a.N = N; a.n = p.n; a.W = p.W; a.kr = rk.count; a.l = l_pk; a.logB = logB_pk; a.sigma_ring = K->sigma_ring;
     a.lwekey = lwe.as<const uint32_t>(); a.zring = z.as<const int8_t>(); a.body = bodies.p;
     e = mktd::launch_pack_keygen(a, c->stream);
     if (e == hipSuccess && pk_seeded_out) e = hipMemcpyAsync(pk_seeded_out, bodies.p, body_bytes, hipMemcpyDeviceToHost, c->stream);
@@ -2080,12 +2092,11 @@ int mkt_pack_batch(mkt_ctx *c, const uint32_t *pool, size_t pool_rows, const uin
 // key polynomials the packs are under are uploaded for the call and wiped before they are freed
 int mkt_rlwe_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party *K, const void *rlwe, double sigma_smudge, const uint8_t *seed,
                                    uint64_t row0, void *share_out, size_t G, int mem) {
-    if (!c || !K || !mem_ok(mem) || party < 0 || party >= c->sh.nparty) return fail(c, MKT_ERR_ARG, "bad argument");
+    const RingKeys rk = pack_ring_keys(c);
+    if (int r = party_call_guard(c, "mkt_rlwe_partial_decrypt_batch", mem_ok(mem), party, K, rk)) return r;
     if (!mkt::smudge_sigma_ok(sigma_smudge)) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: sigma_smudge must be finite, 0 <= sigma_smudge <= 2^31");
     const mkt_params &p = c->p;
-    if (!mkt::party_keys_match(K, p, party)) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: the party's keys were made for other parameters / another party index");
-    const int kr = c->sh.ksk_kr, zoff = mkt::is_kms(p.scheme) ? 1 : 0, N = p.N;
-    if ((int)K->zring.size() < zoff + kr) return fail(c, MKT_ERR_ARG, "mkt_rlwe_partial_decrypt_batch: the party's keys lack a ring key");
+    const int N = p.N;
     if (!G) return MKT_OK;
     if (!rlwe || !share_out) return fail(c, MKT_ERR_ARG, "bad argument");
     DevGuard dg(c->device);
@@ -2097,9 +2108,8 @@ int mkt_rlwe_partial_decrypt_batch(mkt_ctx *c, int party, const mkt_client_party
     if ((r = sx.in(rlwe, G * (size_t)(1 + c->sh.kacc) * pb, mem, true)) || (r = so.in(share_out, G * pb, mem, false))) return r;
     mktd::RingShareArgs a{};
     if (mkt::seed_to_key(seed, a.key)) { explicit_bzero(&a, sizeof a); return fail(c, MKT_ERR_STATE, "mkt_rlwe_partial_decrypt_batch: no entropy from the OS"); }
-    hipError_t e = z.alloc((size_t)kr * N);
-    for (int q = 0; q < kr && e == hipSuccess; q++) e = hipMemcpyAsync(z.as<int8_t>() + (size_t)q * N, K->zring[(size_t)zoff + q].data(), (size_t)N, hipMemcpyHostToDevice, c->stream);
-    a.party = party; a.N = N; a.W = p.W; a.kr = kr; a.npoly = 1 + c->sh.kacc; a.sigma = sigma_smudge; a.row0 = row0;
+    hipError_t e = z.ring_keys(K, rk);
+    a.party = party; a.N = N; a.W = p.W; a.kr = rk.count; a.npoly = 1 + c->sh.kacc; a.sigma = sigma_smudge; a.row0 = row0;
     a.poly0 = mkt::is_mk(p.scheme) ? 1 + party : 1; a.poly_step = mkt::is_mk(p.scheme) ? 0 : 1;
     a.rlwe = sx.dev; a.zring = z.as<const int8_t>(); a.out = so.dev; a.G = G;
     if (e == hipSuccess) e = mktd::launch_ring_share(a, c->stream);

@@ -6,9 +6,10 @@
 // bootstrapping key is left in coefficient form for the caller to pre-transform (context.cpp).
 //
 // Randomness: the ChaCha20 streams of client.cpp (rng_chacha.h).  The streams are counter-based, so the workgroup
-// fills a whole polynomial in parallel -- lane t generates keystream blocks t, t + 256, ... (8 uniform draws or
-// 4 Gaussian deviates each) -- and still produces exactly the words the sequential host loop draws; the exact
-// negacyclic product with the binary key is N^2/2 word additions spread over the workgroup.
+// fills a whole polynomial in parallel and still produces exactly the words the sequential host loop draws.  The two
+// polynomial kernels are built from the steps of keygen_common.h (accumulate_masks, noise_and_store, draw_ternary,
+// unienc_d_row): what stands here is where their masks, noise and messages come from, and that the masks are stored.
+// The key-switching kernel is an algorithm of its own: one lane per coefficient, drawing sequentially.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,7 +22,8 @@ namespace mktd {
 namespace {
 
 // One RLWE sample of an RGSW row (gsw.jl:174-178, lev.jl:88-102, lwe.jl:78-93) per workgroup:
-// sample index = (i * rows + c * l + j); out polys (b, a_0..a_{kr-1}) at native width.
+// sample index = (i * rows + c * l + j); out polys (b, a_0..a_{kr-1}) at native width.  Masks: draws [cc N, (cc + 1) N) of the
+// sample's secret stream 2, stored as they are multiplied; noise: the 2 N draws behind them.
 template <typename WORD, int MAXR>
 __global__ __launch_bounds__(KG_THREADS) void keygen_rgsw_kernel(KeygenArgs a) {
     extern __shared__ uint64_t kg_smem[];
@@ -32,27 +34,14 @@ __global__ __launch_bounds__(KG_THREADS) void keygen_rgsw_kernel(KeygenArgs a) {
     const int sample = blockIdx.x, i = sample / rows, cj = sample % rows, c = cj / a.l, j = cj % a.l;
     WORD *out = reinterpret_cast<WORD *>(a.out) + (size_t)sample * polys * N;
     const Rng rng(a.key, (uint32_t)a.party, 2, (uint32_t)i, (uint32_t)cj);
-    uint64_t acc[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) acc[r] = 0;
-    for (int cc = 0; cc < a.kr; cc++) {
-        fill_uniform(rng, (uint64_t)cc * N, al, N, wm);
-        __syncthreads();
-        for (int q = t; q < N; q += KG_THREADS) out[(size_t)(1 + cc) * N + q] = (WORD)al[q];
-        mul_small_acc_dev<MAXR>(al, a.zring + (size_t)(a.zoff + cc) * N, acc, N, true);
-        __syncthreads();
-    }
-    fill_noise(rng, (uint64_t)a.kr * N, al, N, a.sigma_ring);
-    __syncthreads();
-    const uint64_t g = (uint64_t)1 << (a.W - (j + 1) * a.logB);
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) {
-        const int m = t + r * KG_THREADS;
-        if (m >= N) break;
-        out[m] = (WORD)((acc[r] + al[m]) & wm);
-    }
+    uint64_t acc[MAXR] = {};
+    accumulate_masks<MAXR>(al, a.zring + (size_t)a.zoff * N, a.kr, N, acc,
+                           [&](int cc) { fill_uniform(rng, (uint64_t)cc * N, al, N, wm); },
+                           [&](int cc) { store_words(out + (size_t)(1 + cc) * N, al, N); });
+    noise_and_store<WORD>(out, al, acc, N, rng, (uint64_t)a.kr * N, a.sigma_ring, [](int) { return (uint64_t)0; });
     __syncthreads();
     // message: + s_i * g_j on coefficient 0 of polynomial c (c = 0: b; c >= 1: a_{c-1})
+    const uint64_t g = (uint64_t)1 << (a.W - (j + 1) * a.logB);
     if (t == 0) out[(size_t)c * N] = (WORD)((out[(size_t)c * N] + (uint64_t)a.lwekey[i] * g) & wm);
 }
 
@@ -60,7 +49,7 @@ __global__ __launch_bounds__(KG_THREADS) void keygen_rgsw_kernel(KeygenArgs a) {
 template <typename WORD, int MAXR>
 __global__ __launch_bounds__(KG_THREADS) void keygen_unienc_kernel(KeygenArgs a) {
     extern __shared__ uint64_t kg_smem[];
-    const int N = a.N, t = threadIdx.x, l = a.l, i = blockIdx.x;
+    const int N = a.N, l = a.l, i = blockIdx.x;
     uint64_t *al = kg_smem;                        // [N] words
     int8_t *rt = reinterpret_cast<int8_t *>(kg_smem + N);   // [N] ternary r
     const uint64_t wm = wmask_of<WORD>();
@@ -69,47 +58,18 @@ __global__ __launch_bounds__(KG_THREADS) void keygen_unienc_kernel(KeygenArgs a)
     const Rng rng(a.key, (uint32_t)a.party, 2, (uint32_t)i);
     // stream layout of the host loop: draws [0, N) ternary r; per j at base = N + 5 N j: noise of d (2 draws each),
     // base + 2N: mask of f[j], base + 3N: noise of f[j]
-    fill_uniform(rng, 0, al, N, ~0ull);
-    __syncthreads();
-    for (int q = t; q < N; q += KG_THREADS) rt[q] = (int8_t)((int)(al[q] % 3) - 1);
-    __syncthreads();
+    draw_ternary(rng, al, rt, N);
     for (int j = 0; j < l; j++) {
+        uint64_t acc[MAXR] = {};
         const uint64_t g = (uint64_t)1 << (a.W - (j + 1) * a.logB);
-        uint64_t acc[MAXR];
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) acc[r] = 0;
-        for (int q = t; q < N; q += KG_THREADS) al[q] = crs[(size_t)j * N + q];
-        __syncthreads();
-        mul_small_acc_dev<MAXR>(al, rt, acc, N, false);                         // crs[j] * r
-        __syncthreads();
         const uint64_t base = (uint64_t)N + (uint64_t)5 * N * j;
-        fill_noise(rng, base, al, N, a.sigma_ring);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) {
-            const int m = t + r * KG_THREADS;
-            if (m >= N) break;
-            uint64_t v = acc[r];
-            if (m == 0) v += (uint64_t)a.lwekey[i] * g;
-            out[(size_t)j * N + m] = (WORD)((v + al[m]) & wm);
-            acc[r] = 0;
-        }
-        __syncthreads();
+        unienc_d_row<WORD, MAXR>(out + (size_t)j * N, crs + (size_t)j * N, rt, (uint64_t)a.lwekey[i] * g, rng, base, a.sigma_ring, al, acc, N);
         // f.stack[j] = RLWE_z(g_j * r): a uniform, b = -a z + e + g r
         WORD *fb = out + (size_t)(l + 2 * j) * N, *fa = fb + N;
-        fill_uniform(rng, base + (uint64_t)2 * N, al, N, wm);
-        __syncthreads();
-        for (int q = t; q < N; q += KG_THREADS) fa[q] = (WORD)al[q];
-        mul_small_acc_dev<MAXR>(al, a.zring + (size_t)a.zoff * N, acc, N, true);
-        __syncthreads();
-        fill_noise(rng, base + (uint64_t)3 * N, al, N, a.sigma_ring);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) {
-            const int m = t + r * KG_THREADS;
-            if (m >= N) break;
-            fb[m] = (WORD)((acc[r] + al[m] + g * (uint64_t)(int64_t)rt[m]) & wm);
-        }
+        accumulate_masks<MAXR>(al, a.zring + (size_t)a.zoff * N, 1, N, acc,
+                               [&](int) { fill_uniform(rng, base + (uint64_t)2 * N, al, N, wm); },
+                               [&](int) { store_words(fa, al, N); });
+        noise_and_store<WORD>(fb, al, acc, N, rng, base + (uint64_t)3 * N, a.sigma_ring, [&](int m) { return g * (uint64_t)(int64_t)rt[m]; });
         __syncthreads();
     }
 }
@@ -140,12 +100,8 @@ hipError_t launch_keygen_brk(const KeygenArgs &a, int unienc, hipStream_t s) {
     if (N > 16 * KG_THREADS) return hipErrorInvalidValue;
     const size_t lds = (size_t)N * 8 + (unienc ? (size_t)N : 0);
     const unsigned grid = unienc ? (unsigned)a.n : (unsigned)(a.n * (a.kr + 1) * a.l);
-#define MKT_KG_LAUNCH(K, WORD) \
-    do { if (N <= 4 * KG_THREADS) hipLaunchKernelGGL((K<WORD, 4>), dim3(grid), dim3(KG_THREADS), lds, s, a); \
-         else hipLaunchKernelGGL((K<WORD, 16>), dim3(grid), dim3(KG_THREADS), lds, s, a); } while (0)
-    if (unienc) { if (a.W == 64) MKT_KG_LAUNCH(keygen_unienc_kernel, uint64_t); else MKT_KG_LAUNCH(keygen_unienc_kernel, uint32_t); }
-    else { if (a.W == 64) MKT_KG_LAUNCH(keygen_rgsw_kernel, uint64_t); else MKT_KG_LAUNCH(keygen_rgsw_kernel, uint32_t); }
-#undef MKT_KG_LAUNCH
+    if (unienc) MKT_KG_LAUNCH(keygen_unienc_kernel, a.W, N, grid, lds, s, a);
+    else MKT_KG_LAUNCH(keygen_rgsw_kernel, a.W, N, grid, lds, s, a);
     return hipGetLastError();
 }
 

@@ -5,15 +5,15 @@
 // (seeded_keys.hip).  The noise comes from the party's secret streams 14, 15 and 16.  Everything but the Gaussian deviate is wrapping integer
 // arithmetic, whose order does not matter; the deviate is the one box_muller of rng_chacha.h, contraction off.  No inline assembly, plain stores.
 //
-// BOOTSTRAPPING KEY, RGSW.  One workgroup per sample S = i rows + c l + j, shaped like keygen_rgsw_kernel (keygen.hip) and built from the
-// same steps (keygen_common.h): for each cc < kr mask polynomial P = S kr + cc goes into LDS -- one keystream block per lane and pass, 16
-// coefficients of the 32-bit ring or 8 of the 64-bit one, low word first -- and -a_cc z_cc is accumulated in registers (4 per lane up to
-// N = 1024, 16 above); then the N noise words of stream 14 at index S, and the message IN THE BODY: s_i g_j at coefficient 0 for c = 0,
-// s_i g_j z_{c-1} on every coefficient for c >= 1.  Only the body is stored: 1 / (kr + 1) of the full generator's stores.
+// BOOTSTRAPPING KEY, RGSW.  One workgroup per sample S = i rows + c l + j, the steps of keygen_rgsw_kernel (keygen.hip), stated once in
+// keygen_common.h: accumulate_masks with mask polynomial P = S kr + cc of stream 13 for cc < kr (fill_mask_poly: one keystream block per lane
+// and pass, 16 coefficients of the 32-bit ring or 8 of the 64-bit one, low word first), then noise_and_store with the N noise words of
+// stream 14 at index S and the message IN THE BODY: s_i g_j at coefficient 0 for c = 0, s_i g_j z_{c-1} on every coefficient for c >= 1.
+// Only the body is stored: 1 / (kr + 1) of the full generator's stores.
 // BOOTSTRAPPING KEY, UniEnc (CCS).  One workgroup per key bit i, ONE secret stream (16, index i) in the order of the host loop: draws
-// [0, N) the ternary r; then per gadget row j the 2 N draws of d_j's noise at N + 4 N j and the 2 N draws of f_j.b's noise behind them (no
-// mask is drawn from this stream, unlike stream 2 of keygen_unienc_kernel).  d_j = crs_j r + s_i g_j X^0 + e is stored whole,
-// f_j.b = -a z + e + g_j r with a = mask polynomial i l + j of stream 13.
+// [0, N) the ternary r (draw_ternary); then per gadget row j the 2 N draws of d_j's noise at N + 4 N j and the 2 N draws of f_j.b's noise
+// behind them (no mask is drawn from this stream, unlike stream 2 of keygen_unienc_kernel).  d_j = crs_j r + s_i g_j X^0 + e is stored
+// whole (unienc_d_row), f_j.b = -a z + e + g_j r is the body step again with a = mask polynomial i l + j of stream 13.
 // KEY-SWITCHING KEY.  One word per row R = ((c N + j) Drows + d) f + t: body[R] = e_R - <a_R, s> + msg(R), a sibling of seeded.hip's encrypt
 // kernel on the five-wave tile of party_rows.h: the LWE key staged in LDS zero-padded to whole blocks (the surplus words of a row's last
 // block multiply zeros), `width` lanes share a row's keystream blocks of stream 12 and gather the sum with lane exchanges, the noise wave
@@ -34,82 +34,37 @@ __device__ __forceinline__ void fill_brk_mask(const KeygenSeededArgs &a, uint64_
 template <typename WORD, int MAXR>
 __global__ __launch_bounds__(KG_THREADS) void keygen_seeded_rgsw_kernel(KeygenSeededArgs a) {
     uint64_t *al = reinterpret_cast<uint64_t *>(mkt_smem);          // [N] a mask polynomial, then the noise
-    const int N = a.N, t = threadIdx.x;
-    const uint64_t wm = wmask_of<WORD>();
+    const int N = a.N;
     const int rows = (a.kr + 1) * a.l;
     const uint32_t S = blockIdx.x;
     const int i = (int)(S / (uint32_t)rows), cj = (int)(S % (uint32_t)rows), c = cj / a.l, j = cj % a.l;
     WORD *out = reinterpret_cast<WORD *>(a.brk_body) + (size_t)S * N;
-    uint64_t acc[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) acc[r] = 0;
-    for (int cc = 0; cc < a.kr; cc++) {
-        fill_brk_mask<WORD>(a, (uint64_t)S * (uint32_t)a.kr + (uint32_t)cc, al, N);
-        __syncthreads();
-        mul_small_acc_dev<MAXR>(al, a.zring + (size_t)cc * N, acc, N, true);
-        __syncthreads();
-    }
+    uint64_t acc[MAXR] = {};
+    accumulate_masks<MAXR>(al, a.zring, a.kr, N, acc, [&](int cc) { fill_brk_mask<WORD>(a, (uint64_t)S * (uint32_t)a.kr + (uint32_t)cc, al, N); });
     const Rng rng(a.key, (uint32_t)a.party, mktrng::STREAM_BRK_NOISE, S, 0u);
-    fill_noise(rng, 0, al, N, a.sigma_ring);
-    __syncthreads();
     const uint64_t g = (uint64_t)a.lwekey[i] << (a.W - (j + 1) * a.logB);
     const int8_t *zm = a.zring + (size_t)(c > 0 ? c - 1 : 0) * N;   // m_c = z_{c-1} for c >= 1
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) {
-        const int m = t + r * KG_THREADS;
-        if (m >= N) break;
-        const uint64_t msg = c == 0 ? (m == 0 ? (uint64_t)1 : (uint64_t)0) : (uint64_t)(int64_t)zm[m];
-        out[m] = (WORD)((acc[r] + al[m] + g * msg) & wm);
-    }
+    noise_and_store<WORD>(out, al, acc, N, rng, 0, a.sigma_ring,
+                          [&](int m) { return g * (c == 0 ? (m == 0 ? (uint64_t)1 : (uint64_t)0) : (uint64_t)(int64_t)zm[m]); });
 }
 
 template <typename WORD, int MAXR>
 __global__ __launch_bounds__(KG_THREADS) void keygen_seeded_unienc_kernel(KeygenSeededArgs a) {
     uint64_t *al = reinterpret_cast<uint64_t *>(mkt_smem);          // [N] words
-    const int N = a.N, t = threadIdx.x, l = a.l, i = blockIdx.x;
+    const int N = a.N, l = a.l, i = blockIdx.x;
     int8_t *rt = reinterpret_cast<int8_t *>(al + N);                // [N] ternary r
-    const uint64_t wm = wmask_of<WORD>();
     WORD *out = reinterpret_cast<WORD *>(a.brk_body) + (size_t)i * 2 * l * N;    // d_0 .. d_{l-1}, f_0.b .. f_{l-1}.b
     const WORD *crs = reinterpret_cast<const WORD *>(a.crs);
     const Rng rng(a.key, (uint32_t)a.party, mktrng::STREAM_UNI_NOISE, (uint32_t)i);
-    fill_uniform(rng, 0, al, N, ~0ull);
-    __syncthreads();
-    for (int q = t; q < N; q += KG_THREADS) rt[q] = (int8_t)((int)(al[q] % 3) - 1);
-    __syncthreads();
+    draw_ternary(rng, al, rt, N);
     for (int j = 0; j < l; j++) {
+        uint64_t acc[MAXR] = {};
         const uint64_t g = (uint64_t)1 << (a.W - (j + 1) * a.logB);
         const uint64_t base = (uint64_t)N + (uint64_t)4 * N * j;    // first draw of d_j's noise; f_j.b's follows 2 N draws on
-        uint64_t acc[MAXR];
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) acc[r] = 0;
-        for (int q = t; q < N; q += KG_THREADS) al[q] = crs[(size_t)j * N + q];
-        __syncthreads();
-        mul_small_acc_dev<MAXR>(al, rt, acc, N, false);             // crs_j r
-        __syncthreads();
-        fill_noise(rng, base, al, N, a.sigma_ring);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) {
-            const int m = t + r * KG_THREADS;
-            if (m >= N) break;
-            uint64_t v = acc[r];
-            if (m == 0) v += (uint64_t)a.lwekey[i] * g;
-            out[(size_t)j * N + m] = (WORD)((v + al[m]) & wm);
-            acc[r] = 0;
-        }
-        __syncthreads();
-        fill_brk_mask<WORD>(a, (uint64_t)i * (uint32_t)l + (uint32_t)j, al, N);
-        __syncthreads();
-        mul_small_acc_dev<MAXR>(al, a.zring, acc, N, true);         // -a z
-        __syncthreads();
-        fill_noise(rng, base + (uint64_t)2 * N, al, N, a.sigma_ring);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) {
-            const int m = t + r * KG_THREADS;
-            if (m >= N) break;
-            out[(size_t)(l + j) * N + m] = (WORD)((acc[r] + al[m] + g * (uint64_t)(int64_t)rt[m]) & wm);
-        }
+        unienc_d_row<WORD, MAXR>(out + (size_t)j * N, crs + (size_t)j * N, rt, (uint64_t)a.lwekey[i] * g, rng, base, a.sigma_ring, al, acc, N);
+        accumulate_masks<MAXR>(al, a.zring, 1, N, acc, [&](int) { fill_brk_mask<WORD>(a, (uint64_t)i * (uint32_t)l + (uint32_t)j, al, N); });   // -a z
+        noise_and_store<WORD>(out + (size_t)(l + j) * N, al, acc, N, rng, base + (uint64_t)2 * N, a.sigma_ring,
+                              [&](int m) { return g * (uint64_t)(int64_t)rt[m]; });
         __syncthreads();
     }
 }
@@ -163,12 +118,8 @@ hipError_t launch_keygen_seeded_brk(const KeygenSeededArgs &a, int unienc, hipSt
     if (!a.brk_body || !a.lwekey || !a.zring || (unienc && !a.crs)) return hipErrorInvalidValue;
     const size_t lds = (size_t)N * 8 + (unienc ? (size_t)N : 0);
     const unsigned grid = unienc ? (unsigned)a.n : (unsigned)(a.n * (a.kr + 1) * a.l);
-#define MKT_KGS_LAUNCH(K, WORD) \
-    do { if (N <= 4 * KG_THREADS) hipLaunchKernelGGL((K<WORD, 4>), dim3(grid), dim3(KG_THREADS), lds, s, a); \
-         else hipLaunchKernelGGL((K<WORD, 16>), dim3(grid), dim3(KG_THREADS), lds, s, a); } while (0)
-    if (unienc) { if (a.W == 64) MKT_KGS_LAUNCH(keygen_seeded_unienc_kernel, uint64_t); else MKT_KGS_LAUNCH(keygen_seeded_unienc_kernel, uint32_t); }
-    else { if (a.W == 64) MKT_KGS_LAUNCH(keygen_seeded_rgsw_kernel, uint64_t); else MKT_KGS_LAUNCH(keygen_seeded_rgsw_kernel, uint32_t); }
-#undef MKT_KGS_LAUNCH
+    if (unienc) MKT_KG_LAUNCH(keygen_seeded_unienc_kernel, a.W, N, grid, lds, s, a);
+    else MKT_KG_LAUNCH(keygen_seeded_rgsw_kernel, a.W, N, grid, lds, s, a);
     return hipGetLastError();
 }
 

@@ -9,9 +9,9 @@
 // differ passed as arguments: the stream (19), the high word of the stream index (the gadget, pack_mask_index of rng_chacha.h) and, for the
 // resident layout of an MKT_ARITH_EXACT context, the [polynomial][row] destination.  Body polynomials are copied and do no cipher work.
 //
-// GENERATION.  One workgroup of KG_THREADS lanes per row S = q l_pk + t, built from keygen_common.h like keygen_seeded_rgsw_kernel at c = 0:
-// for each c < kr mask polynomial P = S kr + c of stream 19 goes into LDS and -a_c (*) z_c is accumulated in registers (4 per lane up to
-// N = 1024, 16 above); then the N noise words of stream 20 at index (q, t); then s[q] g_t at coefficient 0.  Only the body is stored.
+// GENERATION.  One workgroup of KG_THREADS lanes per row S = q l_pk + t, the two steps of keygen_common.h like keygen_seeded_rgsw_kernel at
+// c = 0: accumulate_masks with mask polynomial P = S kr + c of stream 19 for c < kr, then noise_and_store with the N noise words of stream 20
+// at index (q, t) and the message s[q] g_t at coefficient 0.  Only the body is stored.
 #include "device_api.h"
 #include "keygen_common.h"
 #include "kernel_common.h"
@@ -22,29 +22,16 @@ namespace {
 template <typename WORD, int MAXR>
 __global__ __launch_bounds__(KG_THREADS) void pack_keygen_kernel(PackKeygenArgs a) {
     uint64_t *al = reinterpret_cast<uint64_t *>(mkt_smem);          // [N] a mask polynomial, then the noise
-    const int N = a.N, t = threadIdx.x;
-    const uint64_t wm = wmask_of<WORD>();
+    const int N = a.N;
     const uint32_t S = blockIdx.x, q = S / (uint32_t)a.l, tt = S - q * (uint32_t)a.l;
     WORD *out = reinterpret_cast<WORD *>(a.body) + (size_t)S * N;
-    uint64_t acc[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) acc[r] = 0;
-    for (int c = 0; c < a.kr; c++) {
+    uint64_t acc[MAXR] = {};
+    accumulate_masks<MAXR>(al, a.zring, a.kr, N, acc, [&](int c) {
         fill_mask_poly<WORD>(a.mkey, mktrng::STREAM_PACK_MASK, (uint32_t)a.party, mktrng::pack_mask_index(S * (uint32_t)a.kr + (uint32_t)c, a.l, a.logB), al, N);
-        __syncthreads();
-        mul_small_acc_dev<MAXR>(al, a.zring + (size_t)c * N, acc, N, true);
-        __syncthreads();
-    }
+    });
     const Rng rng(a.key, (uint32_t)a.party, mktrng::STREAM_PACK_NOISE, q, tt);
-    fill_noise(rng, 0, al, N, a.sigma_ring);
-    __syncthreads();
     const uint64_t g = (uint64_t)a.lwekey[q] << (a.W - (int)(tt + 1u) * a.logB);
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) {
-        const int m = t + r * KG_THREADS;
-        if (m >= N) break;
-        out[m] = (WORD)((acc[r] + al[m] + (m == 0 ? g : (uint64_t)0)) & wm);
-    }
+    noise_and_store<WORD>(out, al, acc, N, rng, 0, a.sigma_ring, [&](int m) { return m == 0 ? g : (uint64_t)0; });
 }
 
 }  // namespace
@@ -67,11 +54,7 @@ hipError_t launch_pack_keygen(const PackKeygenArgs &a, hipStream_t s) {
     if (a.logB < 1 || a.l * a.logB > 32 || (a.W != 32 && a.W != 64) || !a.body || !a.lwekey || !a.zring) return hipErrorInvalidValue;
     const size_t lds = (size_t)N * 8;
     const unsigned grid = (unsigned)(a.n * a.l);
-#define MKT_PKG_LAUNCH(WORD) \
-    do { if (N <= 4 * KG_THREADS) hipLaunchKernelGGL((pack_keygen_kernel<WORD, 4>), dim3(grid), dim3(KG_THREADS), lds, s, a); \
-         else hipLaunchKernelGGL((pack_keygen_kernel<WORD, 16>), dim3(grid), dim3(KG_THREADS), lds, s, a); } while (0)
-    if (a.W == 64) MKT_PKG_LAUNCH(uint64_t); else MKT_PKG_LAUNCH(uint32_t);
-#undef MKT_PKG_LAUNCH
+    MKT_KG_LAUNCH(pack_keygen_kernel, a.W, N, grid, lds, s, a);
     return hipGetLastError();
 }
 

@@ -51,9 +51,7 @@ __global__ __launch_bounds__(RS_THREADS) void ring_share_kernel(RingShareArgs a)
             for (int i = part; i < N; i += P) {
                 const int si = zl[i];                               // wave-uniform from L = 64 up
                 if (!si) continue;
-                const uint64_t v = al[(m - i) & (N - 1)];
-                const bool wrap = i > m;                            // the term came around X^N = -1
-                acc += ((si < 0) != wrap) ? (uint64_t)0 - v : v;
+                acc += negacyclic_term(al, N, m, i, si, false);
             }
         }
         __syncthreads();

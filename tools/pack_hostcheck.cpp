@@ -1,7 +1,8 @@
 // Stand-alone host check of the packed-output functions of mktfhe_amd/csrc/client.cpp (no GPU, no Python): generates packing keys at reduced
 // shapes (KMS on the 64-bit ring with two parties; CCS; CGGI with RLWE length 2), builds a packed ciphertext of known phase by hand from the
 // key rows (coefficient 0 of row (q, t) carries s[q] g_t), opens it with the all-keys harness, by ring shares with and without smudging noise
-// and by the merge, and runs the refusals.  Meant to be built with the host sanitizers, from the repository root:
+// and by the merge, and runs the refusals.  Then the evaluation keys: one full and one seeded generation and the expansion of the seeded
+// sections, so that every shared step of the generators runs under the sanitizers.  Meant to be built with them, from the repository root:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -Iinclude \
 //       tools/pack_hostcheck.cpp mktfhe_amd/csrc/client.cpp mktfhe_amd/csrc/twiddle.cpp -lpthread -o pack_hostcheck && ./pack_hostcheck
 #include <cstdio>
@@ -70,12 +71,48 @@ static int run(mkt_params p, int l, int logB, double beta) {
     return 0;
 }
 
+// one party's evaluation keys in both forms, and the seeded sections expanded: the expansion carries the bodies where the layout puts them
+static int keys(mkt_params p) {
+    const int nparty = (p.scheme >= MKT_CCS) ? p.k : 1, word = p.W / 8, N = p.N;
+    uint8_t seed[32], mseed[32];
+    mkt_client_test_seed(5, seed);
+    mkt_client_test_seed(6, mseed);
+    std::vector<uint8_t> crs((size_t)(p.l_uni ? p.l_uni : 1) * N * word);
+    if (nparty > 1 && mkt_client_crs(&p, seed, crs.data())) return 40;
+    const void *a = nparty > 1 ? crs.data() : nullptr;
+    mkt_client_party *F = nullptr, *S = nullptr;
+    if (mkt_client_party_keygen(&p, seed, nparty - 1, a, 131072.0, 16.0, &F)) return 41;
+    if (mkt_client_party_keygen_seeded(&p, seed, seed, nparty - 1, a, 131072.0, 16.0, &S) != MKT_ERR_ARG || S) return 42;
+    if (mkt_client_party_keygen_seeded(&p, seed, mseed, nparty - 1, a, 131072.0, 16.0, &S)) return 43;
+    size_t brk_bytes = 0, ksk_bytes = 0, sb = 0, sk = 0;
+    mkt_client_brk(F, &brk_bytes);
+    mkt_client_ksk(F, &ksk_bytes);
+    const uint8_t *bodies = (const uint8_t *)mkt_client_brk_seeded(S, &sb);
+    const uint32_t *words = mkt_client_ksk_seeded(S, &sk);
+    if (!brk_bytes || !ksk_bytes || !sb || !sk || sb >= brk_bytes || sk >= ksk_bytes) return 44;
+    std::vector<uint8_t> brk(brk_bytes, 0x5A);
+    std::vector<uint32_t> ksk(ksk_bytes / 4, 0x5A5A5A5Au);
+    if (mkt_client_seeded_keys_expand(&p, nparty, mseed, bodies, words, brk.data(), ksk.data()) != MKT_ERR_ARG) return 45;
+    if (mkt_client_seeded_keys_expand(&p, nparty - 1, mseed, bodies, words, brk.data(), ksk.data())) return 46;
+    if (std::memcmp(brk.data(), bodies, (size_t)N * word)) return 47;                              // polynomial 0 is the first body in both forms
+    const size_t rows = sk / 4, n1 = (size_t)p.n + 1;
+    if (rows * n1 * 4 != ksk_bytes) return 48;
+    for (size_t R = 0; R < rows; R++) if (ksk[R * n1 + (size_t)p.n] != words[R]) return 49;         // the last word of a row is its body (0 where absent)
+    mkt_client_party_destroy(F);
+    mkt_client_party_destroy(S);
+    std::printf("scheme %d n %d N %d W %d: %zu + %zu key bytes, %zu + %zu seeded\n", p.scheme, p.n, N, p.W, brk_bytes, ksk_bytes, sb, sk);
+    return 0;
+}
+
 int main() {
     const mkt_params kms = { MKT_KMS, 5, 32, 2, 64, 3, 12, 2, 7, 3, 10, 8, 2, 0, 0 };
     const mkt_params ccs = { MKT_CCS, 4, 64, 3, 32, 0, 0, 0, 0, 3, 8, 8, 2, 0, 0 };
     const mkt_params cggi = { MKT_CGGI, 3, 32, 2, 32, 3, 9, 0, 0, 0, 0, 8, 2, 0, 0 };
+    const mkt_params ccs32 = { MKT_CCS, 3, 32, 2, 32, 0, 0, 0, 0, 3, 8, 8, 2, 0, 0 };
+    const mkt_params kmsblk = { MKT_KMS_BLOCK, 6, 32, 2, 64, 3, 12, 2, 7, 3, 10, 8, 2, 3, 2 };
     int r;
-    if ((r = run(kms, 4, 4, 85.4084)) || (r = run(ccs, 3, 5, 16.0)) || (r = run(cggi, 8, 4, 128.0)) || (r = run(kms, 1, 16, 85.4084))) { std::printf("FAILED at step %d\n", r); return 1; }
+    if ((r = run(kms, 4, 4, 85.4084)) || (r = run(ccs, 3, 5, 16.0)) || (r = run(cggi, 8, 4, 128.0)) || (r = run(kms, 1, 16, 85.4084)) ||
+        (r = run(ccs32, 4, 4, 16.0)) || (r = run(kmsblk, 3, 5, 85.4084)) || (r = keys(cggi)) || (r = keys(ccs32)) || (r = keys(kmsblk))) { std::printf("FAILED at step %d\n", r); return 1; }
     std::printf("ok\n");
     return 0;
 }
