@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "device_api.h"
+#include "ks_mfma.h"
 #include "device_mem.h"
 #include "fft_device.h"
 #include "host_internal.h"
@@ -74,7 +75,7 @@ const mktd::LaunchTuning &mktd::launch_tuning() {
     static const LaunchTuning t = [] {
         LaunchTuning q{};
         q.fft_grid = env_int("MKT_FFT_GRID", 0); q.fft_nb = env_int("MKT_FFT_NB", 1); q.fft_igrid = env_int("MKT_FFT_IGRID", 0);
-        q.ks_g = env_int("MKT_KS_G", 32); q.ks_blocks = env_int("MKT_KS_BLOCKS", 0); q.ks_waves = env_int("MKT_KS_WAVES", 0); q.ks_pair = env_int("MKT_KS_PAIR", -1); q.ntt_grid = env_int("MKT_NTT_GRID", 0);
+        q.ks_g = env_int("MKT_KS_G", 32); q.ks_blocks = env_int("MKT_KS_BLOCKS", 0); q.ks_waves = env_int("MKT_KS_WAVES", 0); q.ks_pair = env_int("MKT_KS_PAIR", -1); q.ks_mfma = env_int("MKT_KS_MFMA", -1); q.ntt_grid = env_int("MKT_NTT_GRID", 0);
         return q;
     }();
     return t;
@@ -82,7 +83,7 @@ const mktd::LaunchTuning &mktd::launch_tuning() {
 
 // The resident tables of a key set, in the order they are allocated and replicated.  describe_key_set states each one ONCE;
 // allocation, replication, release and the per-party base pointers all read that description.
-enum KeyTable { T_TW, T_MONOMIAL, T_BRK, T_KSK, T_PUB, T_CRS, T_RLK_D, T_RLK_F, T_SLOT_PARTY, T_SLOT_ROW, T_FX_TAB, T_FX_BRK, T_FX_STAT, T_NTT, T_COUNT };
+enum KeyTable { T_TW, T_MONOMIAL, T_BRK, T_KSK, T_PUB, T_CRS, T_RLK_D, T_RLK_F, T_SLOT_PARTY, T_SLOT_ROW, T_FX_TAB, T_FX_BRK, T_FX_STAT, T_NTT, T_KSK_PLANES, T_COUNT };
 struct ResidentTable {
     void **slot = nullptr; size_t elems = 0, esize = 0;   // the KeySet member that holds the device pointer; elements per party (or in the whole table): the party stride; bytes per element
     bool per_party = false, present = false, cloned = false;   // [nparty][elems], else one per key set; this scheme, arithmetic and shape have the table; mkt_internal_clone_keys copies it (false: every context builds its own at mkt_ctx_create)
@@ -99,6 +100,7 @@ struct KeySet {
     cplx *d_monomial = nullptr;  // [2N][M]
     cplx *d_brk = nullptr;
     uint32_t *d_ksk = nullptr; mkt::KskLayout ksk;   // host_internal.h: rows, the callers' pitch, the resident pitch
+    int8_t *d_ksk_planes = nullptr;   // the same key as signed byte planes for the matrix-core key switch (ks_mfma.h), where the shape has the kernel and the memory was there; else null
     cplx *d_rlk_d = nullptr, *d_rlk_f = nullptr, *d_pub = nullptr, *d_crs = nullptr;
     mkt::LoadedKeys loaded;      // which pieces of which party are resident (host_internal.h)
     // rotation slots (KMS phase 1: party-major rows)
@@ -161,6 +163,7 @@ struct mkt_ctx {
     std::vector<TimedSpan> spans;
     Tune tune{};
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
+    int ks_mfma_last = 0;               // 1 if the last key switch ran the matrix-core kernel (mkt_get_metric "ks_mfma_last")
     int rot_static_l = 0, rot_static_logB = 0;   // ... and its compile-time gadget, 0 = taken at run time (mkt_get_metric "rot_static_l" / "rot_static_logB")
     // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
     double pm_amax = 0.0;               // max|a_i| of the last call
@@ -452,6 +455,8 @@ int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, const uin
     a.acc = acc; a.out = out; a.ksk = c->ks->d_ksk; a.ksk_party_stride = c->ks->stride(T_KSK); a.n1p = c->ks->ksk.n1p;
     a.N = p.N; a.n = p.n; a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.kacc = c->sh.kacc;
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
+    a.planes = c->ks->d_ksk_planes; a.sum_mfma = mktd::launch_ks_mfma; a.planes_block_stride = mktd::ksm_block_bytes(p.N, p.f, a.n1p);   // (a party's key of a multi-key scheme is one block: describe_key_set)
+    c->ks_mfma_last = mktd::ks_uses_mfma(a, B);
     size_t dw = 0, pw = 0;
     mktd::ks_scratch_words(a, B, &dw, &pw);
     HIPCHK(c, c->ws.ksd.reserve((dw + pw) * 4));
@@ -749,6 +754,12 @@ void describe_key_set(mkt_ctx *c) {
     row(T_FX_BRK,     ks.d_fx_brk,     fx_per,                                                        true,      fx,      true);
     row(T_FX_STAT,    ks.d_fx_stat,    1,                                                             false,     fx,      true);
     row(T_NTT,        ks.d_ntt,        (N + 4) * 2,                                                   false,     c->exact, false);   // (N + 4) points of 4 words (upload_ntt_tables)
+    // second form of the key-switching key (ks_mfma.h): one block of planes per component of a party's key, 4/3 of its rows' bytes.  Unbalanced
+    // digits with D = 4 (three rows per digit), no 32-bit sum able to overflow (ks_mfma_fits), MKT_KS_MFMA not 0.  OPTIONAL: mkt_ctx_create
+    // goes on without it where the allocation fails, and every key switch then runs the kernels it ran before
+    const bool planes = mktd::launch_tuning().ks_mfma != 0 && p.logD == 2 && !mkt::is_block(p.scheme) && c->sh.ksk_drows == 3 && (!mk || c->sh.ksk_kr == 1) &&
+                        mkt::ks_mfma_fits(p.N, mk ? 1 : c->sh.kacc, p.f);
+    row(T_KSK_PLANES, ks.d_ksk_planes, (size_t)c->sh.ksk_kr * mktd::ksm_block_bytes(p.N, p.f, ks.ksk.n1p),   true,      planes,   true);
 }
 
 // ---- the one install path of a party's keys ----  The start of every call that writes keys: the argument check (ptrs_ok: the call's own pointers; party NO_PARTY: the CRS, or a party
@@ -775,6 +786,16 @@ hipError_t ksk_zero(mkt_ctx *c, int party) { return hipMemsetAsync(c->ks->party<
 hipError_t ksk_repitch(mkt_ctx *c, uint32_t *dst, int dpitch, const uint32_t *src, int spitch, hipMemcpyKind kind) { return hipMemcpy2DAsync(dst, (size_t)dpitch * 4, src, (size_t)spitch * 4, (size_t)c->ks->ksk.n1 * 4, c->ks->ksk.rows, kind, c->stream); }
 hipError_t ksk_to_resident(mkt_ctx *c, int party, const uint32_t *rows, hipMemcpyKind kind) { return ksk_repitch(c, c->ks->party<uint32_t>(T_KSK, party), c->ks->ksk.n1p, rows, c->ks->ksk.n1, kind); }
 hipError_t ksk_to_rows(mkt_ctx *c, const uint32_t *padded, uint32_t *rows, hipMemcpyKind kind) { return ksk_repitch(c, rows, c->ks->ksk.n1, padded, c->ks->ksk.n1p, kind); }
+// ... and, once a party's rows stand in the resident table (every install ends here), their byte planes where the key set keeps them
+hipError_t ksk_to_planes(mkt_ctx *c, int party) {
+    KeySet &ks = *c->ks;
+    if (!ks.d_ksk_planes) return hipSuccess;
+    const size_t comp_words = (size_t)c->p.N * c->sh.ksk_drows * c->p.f * ks.ksk.n1p, block = mktd::ksm_block_bytes(c->p.N, c->p.f, ks.ksk.n1p);
+    for (int comp = 0; comp < c->sh.ksk_kr; comp++)
+        if (hipError_t e = mktd::launch_ks_mfma_pack(ks.party<uint32_t>(T_KSK, party) + comp * comp_words, ks.party<int8_t>(T_KSK_PLANES, party) + comp * block,
+                                                     c->p.N, c->p.f, c->sh.ksk_drows, ks.ksk.n1p, c->stream); e != hipSuccess) return e;
+    return hipSuccess;
+}
 
 }  // namespace
 
@@ -838,7 +859,11 @@ int mkt_ctx_create(const mkt_params *params, int arith_mode, int device, mkt_ctx
     // count, 32-bit row offsets); a larger key would read zeros silently, so it is refused here (largest shipped set: 0.25 GB)
     if (c->ks->stride(T_BRK) * sizeof(cplx) > 0x7fffffffull) { c->err = "per-party bootstrapping key exceeds the 2 GiB window of the rotation kernels' buffer descriptors"; return bail(MKT_ERR_UNSUPPORTED); }
 #define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { c->err = std::string(#call) + ": " + hipGetErrorString(_e); return bail(_e == hipErrorOutOfMemory ? MKT_ERR_NOMEM : MKT_ERR_HIP); } } while (0)
-    for (int t = 0; t < T_COUNT; t++) if (c->ks->tab[t].present) { CK(c->ks->own[t].alloc(c->ks->tab[t].bytes(np))); *c->ks->tab[t].slot = c->ks->own[t].p; }
+    for (int t = 0; t < T_COUNT; t++) if (c->ks->tab[t].present) {
+        if (t == T_KSK_PLANES && c->ks->own[t].alloc(c->ks->tab[t].bytes(np)) != hipSuccess) { (void)hipGetLastError(); c->ks->tab[t].present = false; continue; }   // optional (describe_key_set)
+        if (t != T_KSK_PLANES) CK(c->ks->own[t].alloc(c->ks->tab[t].bytes(np)));
+        *c->ks->tab[t].slot = c->ks->own[t].p;
+    }
     CK(hipMemcpy(c->ks->d_slot_party, sp.data(), sp.size() * sizeof(int), hipMemcpyHostToDevice));
     CK(hipMemcpy(c->ks->d_slot_row, sr.data(), sr.size() * sizeof(int), hipMemcpyHostToDevice));
     if (c->ks->d_fx_tab) {
@@ -928,8 +953,22 @@ int mkt_internal_clone_keys(mkt_ctx *src, mkt_ctx *dst, int no_peer) {
     // not order: both devices are drained before the replica may be used (one-time cost, off the evaluation path)
     { DevGuard g(sd); HIPCHK(dst, hipDeviceSynchronize()); }
     { DevGuard g(dd); HIPCHK(dst, hipDeviceSynchronize()); }
+    if (b.d_ksk_planes && !a.d_ksk_planes) {   // the optional planes: the source went without, the replica builds its own from the rows that have landed
+        DevGuard g(dd);
+        for (int party = 0; party < dst->sh.nparty; party++) if (b.loaded.has(mkt::K_KSK, party)) HIPCHK(dst, ksk_to_planes(dst, party));
+        HIPCHK(dst, hipStreamSynchronize(dst->stream));
+    }
     return MKT_OK;
 }
+// The host side of the matrix-core key switch, for the tests that need no device: the planes of one block from rows at the resident pitch
+// (the function the device packer runs per byte), their size, the admission bound and MKT_KS_MFMA as the launcher reads it
+size_t mkt_internal_ks_mfma_block_bytes(int N, int f, int n1p) { return mktd::ksm_block_bytes(N, f, n1p); }
+void mkt_internal_ks_mfma_pack_host(const uint32_t *rows, int N, int f, int drows, int n1p, int8_t *planes) {
+    const size_t bytes = mktd::ksm_block_bytes(N, f, n1p);
+    for (size_t off = 0; off < bytes; off++) planes[off] = mktd::ksm_plane_byte(rows, N, f, drows, n1p, off);
+}
+int mkt_internal_ks_mfma_fits(long long N, long long kr, long long f) { return mkt::ks_mfma_fits(N, kr, f) ? 1 : 0; }
+int mkt_internal_ks_mfma_env(void) { return env_int("MKT_KS_MFMA", -1); }   // what launch_tuning() reads, read again
 #ifndef MKT_BUILD_ID
 #define MKT_BUILD_ID "unknown"
 #endif
@@ -986,6 +1025,9 @@ int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     if (!c || !name || !out) return fail(c, MKT_ERR_ARG, "null argument");
     const std::string k(name);
     if (k == "fx_available") *out = fx_usable(c) ? 1.0 : 0.0;
+    else if (k == "ks_mfma") *out = mktd::launch_tuning().ks_mfma;          // MKT_KS_MFMA as read: negative automatic, 0 never, positive always where served
+    else if (k == "ks_mfma_planes") *out = c->ks->d_ksk_planes ? 1.0 : 0.0; // the key set keeps the byte planes
+    else if (k == "ks_mfma_last") *out = c->ks_mfma_last;                   // the last key switch on this context ran the matrix-core kernel
     else if (k == "fx_bound") *out = c->ks->d_fx_brk ? fx_bound(c, c->ks->fx_kmax) : -1.0;
     else if (k == "fx_kmax") *out = c->ks->fx_kmax;
     else if (k == "fx_last_resid") *out = c->fx_last_resid;
@@ -1072,6 +1114,7 @@ int mkt_load_ksk(mkt_ctx *c, int party, const uint32_t *data) {
     DevGuard dg(c->device);
     HIPCHK(c, ksk_zero(c, party));
     HIPCHK(c, ksk_to_resident(c, party, data, hipMemcpyHostToDevice));
+    HIPCHK(c, ksk_to_planes(c, party));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ks->loaded.mark(mkt::K_KSK, party);
     return MKT_OK;
@@ -1126,6 +1169,7 @@ static int keygen_device_impl(mkt_ctx *c, int party, const mkt_client_party *K, 
     if (e == hipSuccess) e = ksk_zero(c, party);
     a.zoff = mkt::is_kms(p.scheme) ? 1 : 0;      // the key switch targets the uni key of the KMS schemes
     if (e == hipSuccess) e = mktd::launch_keygen_ksk(a, c->ks->party<uint32_t>(T_KSK, party), c->ks->ksk.n1p, c->sh.ksk_kr, c->sh.ksk_drows, mkt::is_block(p.scheme) ? 1 : 0, c->stream);
+    if (e == hipSuccess) e = ksk_to_planes(c, party);
     e = wipe_secrets(wipe_secrets(e, z, a), lwe, a);
     if (e != hipSuccess) return hipfail(c, e, "device keygen");
     c->ks->loaded.mark(mkt::K_KSK, party);
@@ -1256,6 +1300,7 @@ static int seeded_keys_impl(mkt_ctx *c, int party, const uint8_t *mask_seed, con
         a.absent_below = mkt::is_block(p.scheme) ? p.n : 0; a.body = sk.as<const uint32_t>(); a.out = dst; a.rows = rows;
         e = mktd::launch_seeded_ksk_expand(a, c->stream);
         if (e == hipSuccess && !load) e = ksk_to_rows(c, dst, ksk_out, mem == MKT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && load) e = ksk_to_planes(c, party);
         if (e != hipSuccess) return hipfail(c, e, "seeded key-switching key expansion");
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));

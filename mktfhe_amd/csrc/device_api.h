@@ -14,7 +14,7 @@ struct TwPtrs { const cplx *psi, *psiinv, *roots, *rootsinv; };
 
 // Launcher-level A/B switches (grid shapes of the transform and key-switch kernels): process-wide, read from the
 // environment on FIRST USE only -- the call path never calls getenv (context.cpp).  0 = the built-in default.
-struct LaunchTuning { int fft_grid, fft_nb, fft_igrid, ks_g, ks_blocks, ks_waves, ks_pair, ntt_grid; };
+struct LaunchTuning { int fft_grid, fft_nb, fft_igrid, ks_g, ks_blocks, ks_waves, ks_pair, ntt_grid, ks_mfma; };
 const LaunchTuning &launch_tuning();
 // base name of the blind-rotation kernel the calling thread launched last (set by every rotation launcher; read by
 // mkt_last_kernel_name so that bench.py's roofline names the kernel that actually ran)
@@ -97,6 +97,7 @@ struct CcsArgs {
     int dev_order;            // device point order of the resident tables
 };
 
+struct KsmArgs;
 struct KsArgs {
     const void *acc;          // [B][1+kacc][N] ring words
     uint32_t *out;            // [B][lwe_len]
@@ -115,9 +116,21 @@ struct KsArgs {
     const uint32_t *src;
     const uint32_t *coef;
     size_t nacc;
+    // the key as signed byte planes (ks_mfma.h), one block per party or per component, or null: the matrix-core kernel in place of the
+    // digit-pair kernel where the launch-shape rule picks it (unbalanced digits, D = 4; the AT rows come through the same digit words)
+    const int8_t *planes;
+    size_t planes_block_stride;   // bytes
+    // ... and the launcher of that kernel (launch_ks_mfma): handed in by the caller that owns the planes, so that this unit names nothing of ks_mfma.hip
+    hipError_t (*sum_mfma)(const struct KsmArgs &, hipStream_t);
 };
 // words of KsArgs::digits / KsArgs::partial for a batch of B ciphertexts (0, 0: this shape runs on the per-digit kernel)
 void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *partial_words);
+// 1 if a key switch of B ciphertexts with these arguments (scratch present) runs the matrix-core kernel
+int ks_uses_mfma(const KsArgs &a, size_t B);
+// ks_mfma.hip: the byte planes of one block from its resident rows [N][drows][f][n1p]; digit words x planes -> partial sums per slab
+struct KsmArgs;
+hipError_t launch_ks_mfma_pack(const uint32_t *rows, int8_t *planes, int N, int f, int drows, int n1p, hipStream_t s);
+hipError_t launch_ks_mfma(const KsmArgs &a, hipStream_t s);
 
 // Evaluation-key generation on the device (keygen.hip): one party's secrets and the stream key of client.cpp
 struct KeygenArgs {

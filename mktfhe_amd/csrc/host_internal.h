@@ -78,6 +78,9 @@ struct KskLayout {
     size_t resident_words() const { return rows * (size_t)n1p; }
 };
 inline KskLayout ksk_layout(const mkt_params &p, const Shape &s) { return KskLayout{ksk_rows(p, s), p.n + 1, (p.n + 1 + 3) / 4 * 4}; }
+// The second resident form of the same key (ks_mfma.h: signed byte planes for the int8 matrix cores) is admitted where no 32-bit accumulator
+// can overflow: one product of at most 255 in magnitude per (component summed into the output word, coefficient, digit)
+inline bool ks_mfma_fits(long long N, long long kr, long long f) { return N > 0 && kr > 0 && f > 0 && N * kr * f * 255 < (1ll << 31); }
 
 // Which key pieces of which party are resident (KeySet::loaded): the one record that key loads write and check_ready, mkt_set_twiddles and
 // the key replication read.  The CRS belongs to no party (party < 0): it is marked for all of them.

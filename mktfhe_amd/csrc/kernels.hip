@@ -2,6 +2,7 @@
 // Hand-written for MI355X only; no portability layers.  All floating point is IEEE double with
 // contraction off (one rounding per reference operation); see fft_device.h for the mapping.
 #include "kernel_common.h"
+#include "ks_mfma.h"
 
 #include <type_traits>
 
@@ -1809,9 +1810,18 @@ hipError_t launch_ccs_blindrotate(int logM, int W, const CcsArgs &a, size_t B, h
 
 #if MKT_IN_TU(0)
 namespace {
-struct KsPlan { int G, waves, ngroups, parties, gblocks, slabs, jslab; bool pair; };
+struct KsPlan { int G, waves, ngroups, parties, gblocks, slabs, jslab; bool pair, mfma; };
 // launch shape of a key switch; pair: digit pairs (keyswitch_pair_kernel: D = 4 and an even digit count, 32 ciphertexts per wave,
 // scratch present), else the per-digit kernel with atomics
+// Smallest batch the automatic rule gives to the matrix-core kernel (see ks_plan).  Whole key switch (digit words, sums, reduction), median ms,
+// digit-pair kernel -> matrix cores (tools/ks_mfma_crossover.py, profiles/ks_mfma_crossover.txt):
+//   KMS k = 2, N = 1024    16: 0.143 -> 0.092    64: 0.145 -> 0.092    256: 0.172 -> 0.100    512: 0.268 -> 0.115    1 024: 0.464 -> 0.181
+//   CGGIparam              16: 0.111 -> 0.069    64: 0.110 -> 0.068    256: 0.142 -> 0.076    512: 0.169 -> 0.084    1 024: 0.270 -> 0.122
+// The new kernel's time is flat below 512 ciphertexts (one pass over the planes) and under the pair kernel's smallest; batches 1, 2, 4 and 8
+// are in the profile beside these (second record): no batch at which the older kernel wins, hence no threshold above 1
+constexpr int KS_MFMA_MIN_BATCH = 1;
+// compute units of the part: the matrix-core kernel holds one workgroup per unit at a time and is launched in whole rounds of them
+constexpr int KS_MFMA_CUS = 256;
 KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
     KsPlan q{};
     q.G = 32;
@@ -1826,8 +1836,33 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
     q.pair = lt.ks_pair != 0 && a.logD == 2 && a.f % 2 == 0 && q.G == 32 && have_scratch;
     // (measured and left out: eight waves of 16 ciphertexts around one table -- half the slabs; KMS k=2 0.94 vs 0.79 ms, CGGIparam 0.51 vs 0.52)
     if (q.pair && lt.ks_blocks <= 0) target_blocks = 1024;   // tools/ks_pair_sweep.sh, every kind of set: one round of three 4-wave workgroups per CU (Blockparam 1024 / 16 384 gates 0.12 / 1.35 ms; 0.19 / 1.44 at 2048)
-    q.ngroups = (int)((B + q.G - 1) / q.G);
     q.parties = a.mk ? a.kacc : 1;
+    // The matrix-core kernel (ks_mfma.hip) where the caller hands its launcher and the byte planes in (the key set keeps them): unbalanced
+    // digits, D = 4, any digit count.  It streams the planes once per 512 ciphertexts at a rate the batch does not change; the rule is
+    // KS_MFMA_MIN_BATCH, measured beside the constant.  MKT_KS_MFMA = 1 takes it at every batch, 0 never
+    q.mfma = a.sum_mfma && lt.ks_mfma != 0 && a.planes && !a.balanced && a.logD == 2 && a.drows == 3 && have_scratch && (lt.ks_mfma > 0 || B >= (size_t)KS_MFMA_MIN_BATCH);
+    if (q.mfma) {
+        q.G = 32; q.waves = KSM_WAVES; q.pair = false;
+        q.ngroups = (int)((B + 31) / 32);
+        // One workgroup per compute unit at a time (512 registers a lane), so the slabs are counted in rounds of the part: from the count
+        // that gives two rounds, the fewest slabs whose last round is at least nine tenths full.  1 024 gates at the headline, 72 workgroups a
+        // slab: 7 slabs (504 workgroups) 0.151 ms, 14 0.169, 4 0.196, 2 0.192, 1 0.331; 4 096 gates, 288 a slab: 1 slab 0.775 ms, 2 0.60, 4 (the rule) in the second record
+        // (profiles/ks_mfma_probe.txt); a slab keeps at least one round of the operand ring
+        const int gtiles = (int)((B + KSM_WAVE_GATES * KSM_WAVES - 1) / (KSM_WAVE_GATES * KSM_WAVES));
+        const int per_slab = gtiles * q.parties * ksm_coltiles(a.n1p);
+        int most = ksm_steps(a.N, a.f) / KSM_RING;
+        if (most < 1) most = 1;
+        int first = 2 * KS_MFMA_CUS / per_slab;
+        first = first < 1 ? 1 : (first > most ? most : first);
+        q.slabs = first;
+        for (int sl = first; sl <= most && sl < first + 8; sl++) {
+            const long wg = (long)per_slab * sl, rounds = (wg + KS_MFMA_CUS - 1) / KS_MFMA_CUS;
+            if (wg * 10 >= rounds * KS_MFMA_CUS * 9) { q.slabs = sl; break; }
+        }
+        q.gblocks = gtiles; q.jslab = 0;
+        return q;
+    }
+    q.ngroups = (int)((B + q.G - 1) / q.G);
     // enough workgroups to fill the chip, slabs of at least 8 coefficients
     auto nslabs = [&] {
         int sl = (target_blocks + q.ngroups * q.parties - 1) / (q.ngroups * q.parties);
@@ -1849,9 +1884,11 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
 
 void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *partial_words) {
     const KsPlan q = ks_plan(a, B, true);
-    *digit_words = q.pair ? (size_t)a.kacc * q.ngroups * (size_t)a.N * 32 : 0;                    // [kacc][ceil(B / 32)][N][32]
-    *partial_words = q.pair ? (size_t)q.slabs * q.parties * B * (size_t)a.n1p : 0;                 // [slab][party][B][n1p]
+    const bool scratch = q.pair || q.mfma;
+    *digit_words = scratch ? (size_t)a.kacc * q.ngroups * (size_t)a.N * 32 : 0;                    // [kacc][ceil(B / 32)][N][32]
+    *partial_words = scratch ? (size_t)q.slabs * q.parties * B * (size_t)a.n1p : 0;                // [slab][party][B][n1p]
 }
+int ks_uses_mfma(const KsArgs &a, size_t B) { return B && ks_plan(a, B, true).mfma ? 1 : 0; }
 
 // AT: the rows extract at a coefficient of a named accumulator (KsArgs::src / ::coef); the plain key switch keeps kernels of its own
 template <bool AT>
@@ -1867,6 +1904,14 @@ static hipError_t launch_keyswitch_as(int W, const KsArgs &a, size_t B, hipStrea
     auto with_word = [&](auto f) { if (W == 64) f(uint64_t{}); else f(uint32_t{}); };
     auto with_bal = [&](auto f) { if (a.balanced) f(std::true_type{}); else f(std::false_type{}); };
     auto with_waves = [&](auto f) { if (q.waves == 4) f(C4{}); else if (q.waves == 2) f(C2{}); else f(C1{}); };
+    if (q.mfma) {      // digit words -> partial sums per slab on the matrix cores -> output
+        const dim3 dgrid((unsigned)((a.N + 7) / 8), (unsigned)ngroups, (unsigned)a.kacc);
+        with_word([&](auto w) { hipLaunchKernelGGL((ks_digits_kernel<decltype(w), false, AT>), dgrid, dim3(256), 0, s, a, (int)B, ngroups); });
+        const KsmArgs m{a.planes, a.planes_block_stride, a.digits, a.partial, (int)B, ngroups, a.N, a.f, a.n1p, a.kacc, a.mk, q.slabs};
+        if (hipError_t e = a.sum_mfma(m, s); e != hipSuccess) return e;
+        with_word([&](auto w) { hipLaunchKernelGGL((ks_reduce_kernel<decltype(w), AT>), words, dim3(256), 0, s, a, B, q.slabs, q.parties); });
+        return hipGetLastError();
+    }
     if (q.pair) {      // digit words -> partial sums per slab -> output
         const dim3 dgrid((unsigned)((a.N + 7) / 8), (unsigned)ngroups, (unsigned)a.kacc);
         with_word([&](auto w) { with_bal([&](auto bal) {
