@@ -175,6 +175,9 @@ const char *mkt_last_kernel_name(const mkt_ctx *ctx);
  * Of the blind-rotation launch that mkt_last_kernel_name names: "rot_static_l", "rot_static_logB" -- the gadget length and the log2 of the
  * gadget base that the instantiation which ran holds as COMPILE-TIME constants, each 0 where it takes the value at run time (and after
  * mkt_exact_polymul_batch).  They say which specialisation of a kernel name a call reached (the tests assert it); no result depends on them.
+ * Of the context's last key switch (plain, at a coefficient, or inside a gate or bootstrap): "ks_last_kernel" -- 0 none yet, 1 the per-digit
+ * kernel, 2 the digit-pair kernel, 3 the matrix cores --, "ks_last_g" (ciphertexts per wave tile), "ks_last_waves" (waves per workgroup),
+ * "ks_last_slabs"; "ks_mfma_last" = 1 iff "ks_last_kernel" = 3.  What the MKT_KS_* variables chose; no result depends on them.
  * MEMORY GUARDS (diagnostic): with MKT_MEM_GUARD=<KiB> in the environment at mkt_ctx_create / mkt_multi_create (0 or unset: off; no batch call reads
  * it), every device buffer the library allocates from then on -- key tables, workspace, staged copies -- lies between two filled guards of that length.
  * "mem_guard_check" drains the context's device, compares the guards of every live buffer of that device and gives the number of guards found written

@@ -164,6 +164,7 @@ struct mkt_ctx {
     Tune tune{};
     const char *last_rot_kernel = "";   // name of the blind-rotation kernel the last call launched (mkt_last_kernel_name)
     int ks_mfma_last = 0;               // 1 if the last key switch ran the matrix-core kernel (mkt_get_metric "ks_mfma_last")
+    mktd::KsReport ks_last{};           // the plan of the last key switch (mkt_get_metric "ks_last_kernel" / "_g" / "_waves" / "_slabs"; kernel 0: none yet)
     int rot_static_l = 0, rot_static_logB = 0;   // ... and its compile-time gadget, 0 = taken at run time (mkt_get_metric "rot_static_l" / "rot_static_logB")
     // mkt_exact_polymul_batch: per-call scratch and what the last call measured (per context: forks run the product concurrently)
     double pm_amax = 0.0;               // max|a_i| of the last call
@@ -456,9 +457,10 @@ int do_keyswitch(mkt_ctx *c, const void *acc, uint32_t *out, size_t B, const uin
     a.N = p.N; a.n = p.n; a.f = p.f; a.logD = p.logD; a.drows = c->sh.ksk_drows; a.kacc = c->sh.kacc;
     a.mk = mkt::is_mk(p.scheme) ? 1 : 0; a.balanced = mkt::is_block(p.scheme) ? 1 : 0; a.lmss = p.scheme == MKT_LMSS ? 1 : 0;
     a.planes = c->ks->d_ksk_planes; a.sum_mfma = mktd::launch_ks_mfma; a.planes_block_stride = mktd::ksm_block_bytes(p.N, p.f, a.n1p);   // (a party's key of a multi-key scheme is one block: describe_key_set)
-    c->ks_mfma_last = mktd::ks_uses_mfma(a, B);
-    size_t dw = 0, pw = 0;
-    mktd::ks_scratch_words(a, B, &dw, &pw);
+    const mktd::KsReport plan = mktd::ks_report(mktd::ks_shape(a, true), B, mktd::launch_tuning());   // scratch present: it is sized from this plan, below
+    if (B) c->ks_last = plan;
+    c->ks_mfma_last = B && plan.kernel == 3;
+    const size_t dw = plan.digit_words, pw = plan.partial_words;
     HIPCHK(c, c->ws.ksd.reserve((dw + pw) * 4));
     if (dw) { a.digits = c->ws.ksd.as<uint32_t>(); a.partial = a.digits + dw; }
     Timer tm(c, 2);
@@ -969,6 +971,18 @@ void mkt_internal_ks_mfma_pack_host(const uint32_t *rows, int N, int f, int drow
 }
 int mkt_internal_ks_mfma_fits(long long N, long long kr, long long f) { return mkt::ks_mfma_fits(N, kr, f) ? 1 : 0; }
 int mkt_internal_ks_mfma_env(void) { return env_int("MKT_KS_MFMA", -1); }   // what launch_tuning() reads, read again
+// The launch rule of the key switch (kernels.hip ks_plan) for a set, a batch and the five switch values, no context and no device.
+// set [10]: N, f, logD, drows, n1p, kacc, mk, balanced, planes present, scratch present; sw [5]: MKT_KS_G, _WAVES, _BLOCKS, _PAIR, _MFMA as read;
+// out [9]: kernel (1 per-digit, 2 digit-pair, 3 matrix cores), G, waves, ngroups, parties, gblocks, slabs, digit words, partial words
+void mkt_internal_ks_plan(const int *set, unsigned long long B, const int *sw, unsigned long long *out) {
+    const mktd::KsShape a{set[0], set[1], set[2], set[3], set[4], set[5], set[6], set[7], set[8], set[9]};
+    mktd::LaunchTuning lt{};
+    lt.ks_g = sw[0]; lt.ks_waves = sw[1]; lt.ks_blocks = sw[2]; lt.ks_pair = sw[3]; lt.ks_mfma = sw[4];
+    const mktd::KsReport r = mktd::ks_report(a, (size_t)B, lt);
+    const unsigned long long v[9] = {(unsigned long long)r.kernel, (unsigned long long)r.G, (unsigned long long)r.waves, (unsigned long long)r.ngroups, (unsigned long long)r.parties,
+                                     (unsigned long long)r.gblocks, (unsigned long long)r.slabs, r.digit_words, r.partial_words};
+    for (int i = 0; i < 9; i++) out[i] = v[i];
+}
 #ifndef MKT_BUILD_ID
 #define MKT_BUILD_ID "unknown"
 #endif
@@ -1028,6 +1042,10 @@ int mkt_get_metric(mkt_ctx *c, const char *name, double *out) {
     else if (k == "ks_mfma") *out = mktd::launch_tuning().ks_mfma;          // MKT_KS_MFMA as read: negative automatic, 0 never, positive always where served
     else if (k == "ks_mfma_planes") *out = c->ks->d_ksk_planes ? 1.0 : 0.0; // the key set keeps the byte planes
     else if (k == "ks_mfma_last") *out = c->ks_mfma_last;                   // the last key switch on this context ran the matrix-core kernel
+    else if (k == "ks_last_kernel") *out = c->ks_last.kernel;               // ... and its plan: 0 no key switch yet, 1 per-digit (keyswitch_mg_kernel), 2 digit-pair, 3 matrix cores
+    else if (k == "ks_last_g") *out = c->ks_last.G;
+    else if (k == "ks_last_waves") *out = c->ks_last.waves;
+    else if (k == "ks_last_slabs") *out = c->ks_last.slabs;
     else if (k == "fx_bound") *out = c->ks->d_fx_brk ? fx_bound(c, c->ks->fx_kmax) : -1.0;
     else if (k == "fx_kmax") *out = c->ks->fx_kmax;
     else if (k == "fx_last_resid") *out = c->fx_last_resid;

@@ -109,7 +109,7 @@ struct KsArgs {
     int mk;                   // 1: component i -> party i's KSK and mask block i; 0: single block, ksk comp i
     int balanced;             // block schemes: copy the first words, balanced digits
     int lmss;                 // LMSS flavour of the copy rule (global coefficient index across components)
-    uint32_t *digits;         // scratch of the digit-pair kernel (both or neither; sizes: ks_scratch_words): prepared digit words
+    uint32_t *digits;         // scratch of the digit-pair kernel (both or neither; sizes: ks_report): prepared digit words
     uint32_t *partial;        //   and the partial sums of every slab; null: the per-digit kernel with atomics
     // key switch at a coefficient (mktfhe.h): out[g] = keyswitch!(E_coef[g](acc[src[g]])).  Both null = the plain key switch, which runs
     // kernels of its own; else acc holds nacc rows, src [B] rows of acc (null: g; clamped to nacc - 1), coef [B] (null: 0; read mod N)
@@ -123,10 +123,16 @@ struct KsArgs {
     // ... and the launcher of that kernel (launch_ks_mfma): handed in by the caller that owns the planes, so that this unit names nothing of ks_mfma.hip
     hipError_t (*sum_mfma)(const struct KsmArgs &, hipStream_t);
 };
-// words of KsArgs::digits / KsArgs::partial for a batch of B ciphertexts (0, 0: this shape runs on the per-digit kernel)
-void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *partial_words);
-// 1 if a key switch of B ciphertexts with these arguments (scratch present) runs the matrix-core kernel
-int ks_uses_mfma(const KsArgs &a, size_t B);
+// What the launch rule of the key switch reads of a call, as plain values (planes: the byte planes and their launcher are there; scratch: digits
+// and partial are), and what it decides.  kernel: 1 per-digit (keyswitch_mg_kernel), 2 digit-pair, 3 matrix cores; digit_words / partial_words:
+// the words of KsArgs::digits / KsArgs::partial for the batch, computed with scratch taken as present (the caller sizes its buffer from them before there is
+// one; 0, 0: this shape runs on the per-digit kernel).  No device, no context: mkt_internal_ks_plan hands the rule to tests/test_ks_plan_cpu.py
+struct KsShape { int N, f, logD, drows, n1p, kacc, mk, balanced, planes, scratch; };
+struct KsReport { int kernel, G, waves, ngroups, parties, gblocks, slabs; size_t digit_words, partial_words; };
+inline KsShape ks_shape(const KsArgs &a, bool scratch) {
+    return KsShape{a.N, a.f, a.logD, a.drows, a.n1p, a.kacc, a.mk, a.balanced, a.planes && a.sum_mfma ? 1 : 0, scratch ? 1 : 0};
+}
+KsReport ks_report(const KsShape &a, size_t B, const LaunchTuning &lt);
 // ks_mfma.hip: the byte planes of one block from its resident rows [N][drows][f][n1p]; digit words x planes -> partial sums per slab
 struct KsmArgs;
 hipError_t launch_ks_mfma_pack(const uint32_t *rows, int8_t *planes, int N, int f, int drows, int n1p, hipStream_t s);

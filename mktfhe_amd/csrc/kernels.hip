@@ -1812,7 +1812,8 @@ hipError_t launch_ccs_blindrotate(int logM, int W, const CcsArgs &a, size_t B, h
 namespace {
 struct KsPlan { int G, waves, ngroups, parties, gblocks, slabs, jslab; bool pair, mfma; };
 // launch shape of a key switch; pair: digit pairs (keyswitch_pair_kernel: D = 4 and an even digit count, 32 ciphertexts per wave,
-// scratch present), else the per-digit kernel with atomics
+// scratch present), else the per-digit kernel with atomics.  PURE: the set (KsShape), the batch and the switches come in as arguments (as
+// rot_plan.h has it for the rotations), so that mkt_internal_ks_plan walks the rule without a device (tests/test_ks_plan_cpu.py)
 // Smallest batch the automatic rule gives to the matrix-core kernel (see ks_plan).  Whole key switch (digit words, sums, reduction), median ms,
 // digit-pair kernel -> matrix cores (tools/ks_mfma_crossover.py, profiles/ks_mfma_crossover.txt):
 //   KMS k = 2, N = 1024    16: 0.143 -> 0.092    64: 0.145 -> 0.092    256: 0.172 -> 0.100    512: 0.268 -> 0.115    1 024: 0.464 -> 0.181
@@ -1822,7 +1823,8 @@ struct KsPlan { int G, waves, ngroups, parties, gblocks, slabs, jslab; bool pair
 constexpr int KS_MFMA_MIN_BATCH = 1;
 // compute units of the part: the matrix-core kernel holds one workgroup per unit at a time and is launched in whole rounds of them
 constexpr int KS_MFMA_CUS = 256;
-KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
+KsPlan ks_plan(const KsShape &a, size_t B, const LaunchTuning &lt) {
+    const bool have_scratch = a.scratch != 0;
     KsPlan q{};
     q.G = 32;
     int target_blocks = 1024;   // swept on MI355X (tools/ks_sweep.sh): 1.6 ms vs 4.7 ms single-gate at KMS k=2 N=1024
@@ -1830,7 +1832,6 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
     // batch leaves few slabs (and one wave per staged table, below): Blockparam 4096 gates 2.12 -> 1.32 ms, 16 384 gates 8.49 -> 4.94 ms,
     // KMS2partyblock 1024 gates 2.73 -> 2.35 ms; the unbalanced variant is fastest at 1024 at every batch size (tools/ks_blocks_sweep*.sh)
     if (a.balanced) target_blocks = a.mk ? 4096 : 8192;
-    const LaunchTuning &lt = launch_tuning();
     if (lt.ks_g == 8 || lt.ks_g == 16) q.G = lt.ks_g;   // launch_keyswitch has the 8-, 16- and 32-wide tiles only: any other MKT_KS_G keeps 32
     if (lt.ks_blocks > 0) target_blocks = lt.ks_blocks;
     q.pair = lt.ks_pair != 0 && a.logD == 2 && a.f % 2 == 0 && q.G == 32 && have_scratch;
@@ -1839,8 +1840,9 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
     q.parties = a.mk ? a.kacc : 1;
     // The matrix-core kernel (ks_mfma.hip) where the caller hands its launcher and the byte planes in (the key set keeps them): unbalanced
     // digits, D = 4, any digit count.  It streams the planes once per 512 ciphertexts at a rate the batch does not change; the rule is
-    // KS_MFMA_MIN_BATCH, measured beside the constant.  MKT_KS_MFMA = 1 takes it at every batch, 0 never
-    q.mfma = a.sum_mfma && lt.ks_mfma != 0 && a.planes && !a.balanced && a.logD == 2 && a.drows == 3 && have_scratch && (lt.ks_mfma > 0 || B >= (size_t)KS_MFMA_MIN_BATCH);
+    // KS_MFMA_MIN_BATCH, measured beside the constant.  MKT_KS_MFMA = 1 takes it at every batch, 0 never.  It is looked at FIRST: where it
+    // serves, MKT_KS_G, MKT_KS_WAVES, MKT_KS_BLOCKS and MKT_KS_PAIR choose nothing (they shape the older kernels, which run where it does not)
+    q.mfma = lt.ks_mfma != 0 && a.planes && !a.balanced && a.logD == 2 && a.drows == 3 && have_scratch && (lt.ks_mfma > 0 || B >= (size_t)KS_MFMA_MIN_BATCH);
     if (q.mfma) {
         q.G = 32; q.waves = KSM_WAVES; q.pair = false;
         q.ngroups = (int)((B + 31) / 32);
@@ -1859,6 +1861,10 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
             const long wg = (long)per_slab * sl, rounds = (wg + KS_MFMA_CUS - 1) / KS_MFMA_CUS;
             if (wg * 10 >= rounds * KS_MFMA_CUS * 9) { q.slabs = sl; break; }
         }
+        // the kernel cuts ceil(steps / slabs) steps per slab: only as many slabs as have steps (as the older path has it below; without this
+        // N = 128, f = 8 launched 21 slabs of 7 steps over 128, two of them with nothing to sum).  No shipped set's count moves
+        const int per = (ksm_steps(a.N, a.f) + q.slabs - 1) / q.slabs;
+        q.slabs = (ksm_steps(a.N, a.f) + per - 1) / per;
         q.gblocks = gtiles; q.jslab = 0;
         return q;
     }
@@ -1882,18 +1888,26 @@ KsPlan ks_plan(const KsArgs &a, size_t B, bool have_scratch) {
 }
 }  // namespace
 
-void ks_scratch_words(const KsArgs &a, size_t B, size_t *digit_words, size_t *partial_words) {
-    const KsPlan q = ks_plan(a, B, true);
+static void scratch_words(KsShape a, size_t B, const LaunchTuning &lt, size_t *digit_words, size_t *partial_words) {
+    a.scratch = 1;                                                                                 // the sizes are asked for before there is a buffer
+    const KsPlan q = ks_plan(a, B, lt);
     const bool scratch = q.pair || q.mfma;
     *digit_words = scratch ? (size_t)a.kacc * q.ngroups * (size_t)a.N * 32 : 0;                    // [kacc][ceil(B / 32)][N][32]
     *partial_words = scratch ? (size_t)q.slabs * q.parties * B * (size_t)a.n1p : 0;                // [slab][party][B][n1p]
 }
-int ks_uses_mfma(const KsArgs &a, size_t B) { return B && ks_plan(a, B, true).mfma ? 1 : 0; }
+KsReport ks_report(const KsShape &a, size_t B, const LaunchTuning &lt) {
+    const KsPlan q = ks_plan(a, B, lt);
+    KsReport r{};
+    r.kernel = q.mfma ? 3 : q.pair ? 2 : 1;
+    r.G = q.G; r.waves = q.waves; r.ngroups = q.ngroups; r.parties = q.parties; r.gblocks = q.gblocks; r.slabs = q.slabs;
+    scratch_words(a, B, lt, &r.digit_words, &r.partial_words);
+    return r;
+}
 
 // AT: the rows extract at a coefficient of a named accumulator (KsArgs::src / ::coef); the plain key switch keeps kernels of its own
 template <bool AT>
 static hipError_t launch_keyswitch_as(int W, const KsArgs &a, size_t B, hipStream_t s) {
-    const KsPlan q = ks_plan(a, B, a.digits && a.partial);
+    const KsPlan q = ks_plan(ks_shape(a, a.digits && a.partial), B, launch_tuning());
     const int ngroups = q.ngroups;
     const dim3 grid((unsigned)(q.gblocks * q.slabs), (unsigned)q.parties, (unsigned)((a.n1p + KS_CHUNK_WORDS - 1) / KS_CHUNK_WORDS));
     const size_t ks_lds = q.pair ? (size_t)KS_STAGES * 16 * KS_LANES * sizeof(uint4) : (size_t)KS_STAGES * (1 + a.drows * (a.balanced ? 2 : 1)) * KS_LANES * sizeof(uint4);

@@ -520,7 +520,8 @@ class Scheme(_Batched):
         "polymul_amax", "fx_polymul_bound" (-1: not evaluated), "fx_last_resid" (a diagnostic, not a certificate); of the rotation launch that
         last_kernel_name() names: "rot_static_l", "rot_static_logB" (the instantiation's compile-time gadget, 0 = taken at run time); of the
         guard mode of the engine's device memory (MKT_MEM_GUARD in the environment when the context is created; mktfhe.h): "mem_guard_check"
-        (drains the device, compares every guard, -> guards found written since the process started), "mem_guard_buffers" and "mem_guard_released" """
+        (drains the device, compares every guard, -> guards found written since the process started), "mem_guard_buffers" and "mem_guard_released";
+        of the context's last key switch: "ks_last_kernel" (0 none yet, 1 per-digit, 2 digit-pair, 3 matrix cores), "ks_last_g", "ks_last_waves", "ks_last_slabs" """
         v = C.c_double(0.0)
         self._ck(_lib.lib().mkt_get_metric(self.h, name.encode(), C.byref(v)))
         return v.value

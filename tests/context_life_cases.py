@@ -17,8 +17,8 @@ from mktfhe_amd.scheme import _Buf
 SETS = {
     "cggi": (mk.CGGIparam.scaled(n=12, N=256), mk.ARITH_F64REF),                 # register route, no scratch; carries the chunk-crossing steps
     "kany": (mk.CGGIparam.scaled(n=8, N=256, k=4), mk.ARITH_F64REF),             # F64_KANY: scratch in memory
-    "lmss": (mk.Blockparam.scaled(n=30, N=256, blk_d=10), mk.ARITH_F64REF),      # balanced key-switch digits, per-digit kernel
-    "kms": (mk.KMS2party.scaled(n=8, N=256), mk.ARITH_F64REF),                   # ws_lev + ws_scratch; 64-bit ring; digit-pair key switch
+    "lmss": (mk.Blockparam.scaled(n=30, N=256, blk_d=10), mk.ARITH_F64REF),      # balanced key-switch digits: never the matrix cores
+    "kms": (mk.KMS2party.scaled(n=8, N=256), mk.ARITH_F64REF),                   # ws_lev + ws_scratch; 64-bit ring; key switch on the matrix cores (the digit-pair kernel under MKT_KS_MFMA = 0)
     "ccs": (mk.CCS2party.scaled(n=8, N=256), mk.ARITH_F64REF),                   # vscratch in ws_lev; ccs_pipe either way
     "x-kr": (mk.CGGIparam.scaled(n=8, N=256, k=2), mk.ARITH_EXACT),              # EXACT_KR <-> EXACT_KANY under exact_kany
     "x-kms": (mk.KMS2party_N1024_l2.scaled(n=6, N=256), mk.ARITH_EXACT),         # Float64 pipe <-> integer NTT under exact_impl, exact_wide, ws_fxacc

@@ -118,7 +118,9 @@ EXACT_CASES = [
 ]
 EXACT_PAIR_SETS = [mk.CGGIparam.scaled(n=6, N=1024), mk.CGGIparam.scaled(n=4, N=4096), mk.KMS2party_N1024_l2.scaled(n=4), mk.KMS2party.scaled(n=2, N=4096)]
 
-# key switch: the four full-length sets (digit-pair kernel: D = 4, f even), other gadgets (per-digit kernel; f = 5: stage-buffer
+# key switch: the four full-length sets (D = 4, f even: the matrix-core kernel for the unbalanced digits of CGGIparam and CCS2party, the
+# digit-pair kernel for the balanced ones of Blockparam_k2 and KMS2partyblock -- and for all four under MKT_KS_MFMA = 0, as the switch
+# children of tests/test_gpu_switches.py run them), other gadgets (per-digit kernel; f = 5: stage-buffer
 # parity), LMSS with n > N (whole components copied), and the LMSS copy rule's remaining branches: a component wholly beyond n (every
 # coefficient switched) on the per-digit and on the digit-pair kernel, components wholly copied (and one cut at 44) on the per-digit kernel
 KS_SETS = [

@@ -501,12 +501,15 @@ def gate_input(op, rows):
     return (x & 0xFFFFFFFF).astype(np.uint32)
 
 
-def ks_edge_check(p, so, sg, rng, batches):
-    """sg.keyswitch(ks_edge_acc) == the oracle's keyswitch! for EVERY ciphertext of every batch size -> number of ciphertexts compared"""
+def ks_edge_check(p, so, sg, rng, batches, after=None):
+    """sg.keyswitch(ks_edge_acc) == the oracle's keyswitch! for EVERY ciphertext of every batch size -> number of ciphertexts compared.
+    after(B): called behind each key switch (the switch children read which kernel it ran)"""
     checks = 0
     for B in batches:
         acc = ks_edge_acc(p, rng, B)
         out = sg.keyswitch(acc.astype(p.ring_dtype))
+        if after:
+            after(B)
         for j in range(B):
             assert np.array_equal(out[j], so.keyswitch(acc[j])), ("keyswitch (edge words)", p.name, p.n, p.f, p.logD, B, j)
             checks += 1
@@ -545,6 +548,67 @@ def ks_at_edge_check(p, so, sg, rng, batches, coefs, device=True):
                     assert not len(bad), ("keyswitch_at (edge words), device memory", p.name, p.n, p.f, p.logD, v, B, bad[:4])
                 checks += B
     return checks
+
+
+# ---- which key-switch kernel a set and a setting of the launcher switches imply: the rule of kernels.hip ks_plan RESTATED (never read from
+# the library), for tests/test_ks_plan_cpu.py and for the switch children, which report what ran (mkt_get_metric "ks_last_kernel" ...)
+KS_PER_DIGIT, KS_PAIR, KS_MFMA = 1, 2, 3
+KS_SWITCH_DEFAULTS = {"MKT_KS_G": 32, "MKT_KS_WAVES": 0, "MKT_KS_BLOCKS": 0, "MKT_KS_PAIR": -1, "MKT_KS_MFMA": -1}      # an unset variable reads as
+
+
+def ks_switch_values(setting):
+    """{variable: text} -> (MKT_KS_G, MKT_KS_WAVES, MKT_KS_BLOCKS, MKT_KS_PAIR, MKT_KS_MFMA) as the launcher reads them"""
+    assert set(setting) <= set(KS_SWITCH_DEFAULTS), setting
+    return tuple(int(setting.get(k, d)) for k, d in KS_SWITCH_DEFAULTS.items())
+
+
+def ks_set_ints(p, mfma=-1, scratch=1):
+    """-> [N, f, logD, rows per digit, n1p, kacc, mk, balanced, planes present, scratch present] of a parameter set on a context created under
+    MKT_KS_MFMA = mfma: the byte planes are kept where the matrix-core kernel can serve (unbalanced D = 4, no 32-bit sum able to overflow)"""
+    block = p.scheme in (mk.LMSS, mk.KMS_BLOCK)
+    D = 1 << p.logD
+    planes = mfma != 0 and p.logD == 2 and not block and p.N * (1 if p.multikey else p.k) * p.f * 255 < 2**31
+    return [p.N, p.f, p.logD, D // 2 if block else D - 1, 4 * ((p.n + 1 + 3) // 4), p.k, int(p.multikey), int(block), int(planes), scratch]
+
+
+def ks_kernel_rule(ints, sw):
+    """(the ten values of ks_set_ints, the five of ks_switch_values) -> (kernel, tile width G, waves per workgroup).  The matrix cores are
+    asked first: where they serve, MKT_KS_G / _WAVES / _BLOCKS / _PAIR choose nothing"""
+    N, f, logD, drows, n1p, kacc, mk_, balanced, planes, scratch = ints
+    g, waves, blocks, pair, mfma = sw
+    if mfma != 0 and planes and scratch and not balanced and logD == 2 and drows == 3:
+        return KS_MFMA, 32, 4
+    G = g if g in (8, 16) else 32
+    is_pair = pair != 0 and logD == 2 and f % 2 == 0 and G == 32 and bool(scratch)
+    w = waves if waves > 0 else 4
+    if w not in (2, 4) or G != 32 or (balanced and waves <= 0 and not is_pair):
+        w = 1
+    return (KS_PAIR if is_pair else KS_PER_DIGIT), G, w
+
+
+def ks_expected(p, setting):
+    """the (kernel, G, waves) a key switch of set p runs in a process started under `setting`"""
+    sw = ks_switch_values(setting)
+    return ks_kernel_rule(ks_set_ints(p, sw[4]), sw)
+
+
+def ks_ran(s):
+    """what the last key switch on the context ran, as ks_expected states it"""
+    return tuple(int(s.get_metric(m)) for m in ("ks_last_kernel", "ks_last_g", "ks_last_waves"))
+
+
+KS_PLAN_FIELDS = ("kernel", "G", "waves", "ngroups", "parties", "gblocks", "slabs", "digit_words", "partial_words")
+
+
+def ks_plan_of(ints, B, sw=tuple(KS_SWITCH_DEFAULTS.values())):
+    """the library's own plan (mkt_internal_ks_plan: no context, no device) for the ten values of ks_set_ints, a batch and the five switch values"""
+    import ctypes as C
+    from mktfhe_amd import _lib
+    f = _lib.lib().mkt_internal_ks_plan
+    f.restype, f.argtypes = None, [C.POINTER(C.c_int), C.c_ulonglong, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+    out = (C.c_ulonglong * len(KS_PLAN_FIELDS))()
+    f((C.c_int * 10)(*ints), B, (C.c_int * 5)(*sw), out)
+    return dict(zip(KS_PLAN_FIELDS, (int(v) for v in out)))
 
 
 # ---- one call in host or in device memory, and the same call on a context that has made no other (tests/context_life_cases.py) ----

@@ -27,7 +27,7 @@ import context_life_cases as K
 import footprint as F
 import stream_cases as S
 from context_life_cases import CHUNK, STEP
-from helpers import ROOT, host_words, mk, same_words
+from helpers import ROOT, host_words, ks_expected, ks_ran, mk, same_words
 
 pytestmark = pytest.mark.gpu
 
@@ -140,14 +140,17 @@ def one_call(s, step, i, B, where, want, sweep_on=None, **kw):
         assert same_words(got, want), (what, "the words differ from the plain call's with the guard mode off")
 
 
-def call_loop(s, i, steps, Bs, ref, wheres=WHERES, sweep_on=None, **kw):
-    """-> calls made.  A finding fails the test at once; the total the later tests compare with follows what the process has seen"""
+def call_loop(s, i, steps, Bs, ref, wheres=WHERES, sweep_on=None, after=None, **kw):
+    """-> calls made.  A finding fails the test at once; the total the later tests compare with follows what the process has seen.
+    after(step, B): called behind each call (the key-switch children read which kernel it ran)"""
     n = 0
     try:
         for step in steps:
             for B in Bs:
                 for where in wheres:
                     one_call(s, step, i, B, where, ref(step, B), sweep_on, **kw)
+                    if after:
+                        after(step, B)
                     n += 1
     finally:
         _TOTAL[0] = swept((sweep_on(s) if sweep_on else [s])[0])[0]
@@ -290,10 +293,15 @@ def test_shards_write_only_what_they_own(require_gpu, monkeypatch):
 
 # ---- the key-switch kernel choices: process-wide launcher switches, one child process per setting (as tests/test_gpu_switches.py forces them);
 #      and the transforms at two per block (MKT_FFT_NB = 2: NBT), where B = 5 and 33 leave the last block half empty ----
-KS_SETTINGS = [{"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"}, {"MKT_KS_WAVES": "2"},
-               {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "1"}, {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "2"}, {"MKT_KS_BLOCKS": "1"},
-               {"MKT_KS_BLOCKS": "100000"}, {"MKT_KS_G": "12"}, {"MKT_KS_G": "64"}]
-KS_CHILD_SETS = ("cggi", "lmss", "kms")          # the plain, the per-digit (balanced) and the digit-pair key switch
+#      Every setting of the older kernels names MKT_KS_MFMA = 0 (else the matrix cores serve "cggi" and "kms" whatever it says); the last three
+#      are the matrix cores forced, forced beside switches that then choose nothing, and automatic.  Every key-switch child reports which
+#      kernel each call ran and the parent holds the report to helpers.ks_expected
+KS_SETTINGS = [{**e, "MKT_KS_MFMA": "0"} for e in (
+    {"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"}, {"MKT_KS_WAVES": "2"},
+    {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "1"}, {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "2"}, {"MKT_KS_BLOCKS": "1"},
+    {"MKT_KS_BLOCKS": "100000"}, {"MKT_KS_G": "12"}, {"MKT_KS_G": "64"})]
+KS_SETTINGS += [{"MKT_KS_MFMA": "1"}, {"MKT_KS_MFMA": "1", "MKT_KS_G": "8", "MKT_KS_PAIR": "0"}, {"MKT_KS_MFMA": "-1"}]
+KS_CHILD_SETS = ("cggi", "lmss", "kms")          # unbalanced digits on one key and on one key per party (the matrix cores, or the older kernels under MKT_KS_MFMA = 0); balanced digits (never the matrix cores)
 KS_CHILD_STEPS = ("gate_ops", "mux", "keyswitch", "keyswitch_at", "lut_many_bootstrap", "lut_bootstrap_at")
 FFT_SETTING = {"MKT_FFT_NB": "2"}
 FFT_CHILD_SETS = ("cggi", "kms", "ccs")
@@ -324,6 +332,14 @@ def test_launcher_kernel_choices_write_only_what_they_own(require_gpu, kind, set
     assert r.returncode == 0 and lines, f"child {setting}: rc {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     j = json.loads(lines[-1])
     assert j["ok"] and j["calls"] == len(CHILD[kind][0]) * len(CHILD[kind][1]) * 2 * len(WHERES) and j["env"] == setting, j
+    if kind == "ks":             # every call of every step ran the kernel, tile width and wave count that its set and the setting imply
+        assert sorted(j["ran"]) == sorted(f"{name}:{step}:{B}" for name in KS_CHILD_SETS for step in KS_CHILD_STEPS for B in (5, 33)), sorted(j["ran"])
+        import test_gpu_switches
+        for key, seen in j["ran"].items():
+            want = ks_expected(K.set_of(key.split(":")[0])[0], setting)
+            assert [tuple(r) for r in seen] == [want], (setting, key, "ran (kernel, G, waves)", seen, "implied", want)
+            if not key.startswith("lmss:"):      # unbalanced digits, D = 4, f = 8: also what the setting is written to reach (test_gpu_switches.KS_MEANT)
+                assert want == test_gpu_switches.KS_MEANT[KS_SETTINGS.index(setting)], (setting, key, want)
 
 
 class _Env:
@@ -335,20 +351,30 @@ class _Env:
 
 
 def _child(kind):
-    calls = 0
+    """-> (calls, {"<set>:<step>:<B>": the distinct (kernel, G, waves) that the key switches of those calls ran})"""
+    calls, ran = 0, {}
+
+    def note(name, s):
+        def after(step, B):
+            seen = ran.setdefault(f"{name}:{step.name}:{B}", [])
+            if ks_ran(s) not in seen:
+                seen.append(ks_ran(s))
+        return after
+
     for name in CHILD[kind][0]:
         os.environ.pop("MKT_MEM_GUARD", None)
         i, steps, Bs = inputs(name), [STEP[n] for n in CHILD[kind][1]], (5, 33)
         ref = references(name, lambda: K.new_scheme(name), i, steps, Bs)
         s = guarded(_Env, lambda: K.new_scheme(name))
         try:
-            calls += call_loop(s, i, steps, Bs, ref)
+            calls += call_loop(s, i, steps, Bs, ref, after=note(name, s) if kind == "ks" else None)
         finally:
             s.close()
-    return calls
+    return calls, ran
 
 
 if __name__ == "__main__":
     assert len(sys.argv) == 2 and sys.argv[1] in CHILD
     env = {k: v for k, v in os.environ.items() if k.startswith("MKT_") and k not in ("MKT_LIB_PATH", "MKT_MEM_GUARD")}
-    print(json.dumps({"ok": True, "calls": _child(sys.argv[1]), "env": env}))
+    calls, ran = _child(sys.argv[1])
+    print(json.dumps({"ok": True, "calls": calls, "env": env, "ran": ran}))

@@ -16,7 +16,7 @@ if __name__ == "__main__":
 import ref_lut as R
 import ref_lut_many as RM
 import edge_cases as EC
-from helpers import ROOT, edge_words, gpu_scheme, keygen, ks_at_edge_check, mk, oracle_scheme
+from helpers import ROOT, edge_words, gpu_scheme, keygen, ks_at_edge_check, ks_expected, ks_ran, mk, oracle_scheme
 from test_gpu_lut import _dk, _exact_scheme, _gpu, _host, _inputs, _keys, _sid, _tables
 from test_gpu_parity import SMALL
 from test_keyswitch_at_cpu import checker_at, thermometer_bits, thermometer_case, thermometer_coefs
@@ -51,7 +51,8 @@ def _unit_want(so, p, acc, src, coef):
     return np.stack([so.keyswitch(RM.extract(acc[int(src[g])], int(coef[g]), p.W)) for g in range(len(src))])
 
 
-def _unit_check(p, so, sg, rng, batches=(1, 33), device=True):
+def _unit_check(p, so, sg, rng, batches=(1, 33), device=True, after=None):
+    """after(B): called behind each key switch at a coefficient of the batch loop (the route children read which kernel it ran)"""
     acc = _acc(p, rng)
     a = acc.astype(p.ring_dtype)
     checks = 0
@@ -59,6 +60,8 @@ def _unit_check(p, so, sg, rng, batches=(1, 33), device=True):
         src, coef = _rows(p, B, rng)
         want = _unit_want(so, p, acc, src, coef)
         assert np.array_equal(mk.keyswitch_at(sg, a, src, coef), want), ("host memory", _sid(p), B)
+        if after:
+            after(B)
         if device:
             assert np.array_equal(_host(mk.keyswitch_at(sg, _gpu(a), _gpu(src), _gpu(coef)), np.uint32), want), ("device memory", _sid(p), B)
         checks += B
@@ -87,7 +90,10 @@ def test_small_sets_reach_both_routes_and_both_copy_rules():
 
 
 # ---- 2: every key-switch route: the launcher switches are read once per process, so one child process per setting, one at a time ----
-KS_SETTINGS = [{"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"}]
+# (the older kernels run where the matrix cores do not: their settings name MKT_KS_MFMA = 0; the last child forces the matrix cores.  Each child
+# reports which kernel its key switches ran and the parent holds the report to helpers.ks_expected)
+KS_SETTINGS = [{**e, "MKT_KS_MFMA": "0"} for e in ({"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"})] + [{"MKT_KS_MFMA": "1"}]
+CHILD_BATCHES = (1, 33, 70)
 CHILD_SETS = [mk.CGGIparam.scaled(n=20, N=256), mk.Blockparam.scaled(n=30, N=256, blk_d=10)]
 CHILD_TIMEOUT = 120
 _child_fault = []          # a child that died by a signal / abort / segfault / time limit: no further child is started
@@ -109,21 +115,27 @@ def test_key_switch_route_in_a_child_process(require_gpu, setting):
     assert r.returncode == 0 and lines, f"child {setting}: rc {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     j = json.loads(lines[-1])
     assert j["ok"] and j["checks"] > 0 and j["env"] == setting, j
+    assert sorted(j["ran"]) == sorted(f"{i}:{B}" for i in range(len(CHILD_SETS)) for B in CHILD_BATCHES + ("edges",)), sorted(j["ran"])
+    for key, seen in j["ran"].items():
+        want = ks_expected(CHILD_SETS[int(key.split(":")[0])], setting)
+        assert tuple(seen) == want, (setting, key, "ran (kernel, G, waves)", seen, "implied", want)
 
 
 def _child():
+    """-> (checks, {"<position in CHILD_SETS>:<batch, or edges>": the (kernel, G, waves) that key switch ran})"""
     rng = np.random.default_rng(97)
-    checks = 0
-    for p in CHILD_SETS:
+    checks, ran = 0, {}
+    for i, p in enumerate(CHILD_SETS):
         crs, keys = keygen(p, 92)
         sg = gpu_scheme(p, crs, keys)
         so = oracle_scheme(p, crs, keys)
-        checks += _unit_check(p, so, sg, rng, batches=(1, 33, 70))
+        checks += _unit_check(p, so, sg, rng, batches=CHILD_BATCHES, after=lambda B: ran.__setitem__(f"{i}:{B}", ks_ran(sg)))
         # the accumulators of tests/test_gpu_edges.py on the key-switch digits' boundaries, rotated by X^v and read back at v
         assert p in EC.KS_CHILD_SETS                                           # (tests/test_edges_cpu.py proves their classes for these sets)
         checks += ks_at_edge_check(p, so, sg, rng, EC.KS_BATCHES, EC.KS_AT_COEFS(p))
+        ran[f"{i}:edges"] = ks_ran(sg)
         sg.close()
-    return checks
+    return checks, ran
 
 
 # ---- 3: the bootstrap against the unit calls composed, and the three identities ----
@@ -387,5 +399,5 @@ def test_refusals_clamps_empty_batches_overlap_and_forks(require_gpu):
 
 if __name__ == "__main__":
     assert sys.argv[1:] == ["child"]
-    n = _child()
-    print(json.dumps({"ok": True, "checks": n, "env": {k: v for k, v in os.environ.items() if k.startswith("MKT_") and k != "MKT_LIB_PATH"}}))
+    n, ran = _child()
+    print(json.dumps({"ok": True, "checks": n, "ran": ran, "env": {k: v for k, v in os.environ.items() if k.startswith("MKT_") and k != "MKT_LIB_PATH"}}))

@@ -16,8 +16,8 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import (GATE_FUNCS, O, ROOT, bits_equal, edge_words, encrypt_bits, gpu_scheme, keygen, ks_edge_check, mixed_party_check, mk,
-                     oracle_scheme)
+from helpers import (GATE_FUNCS, O, ROOT, bits_equal, edge_words, encrypt_bits, gpu_scheme, keygen, ks_edge_check, ks_expected, ks_ran,
+                     mixed_party_check, mk, oracle_scheme)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +27,7 @@ SWITCHES = [
     "rot_map", "fx_polymul_force", "exact_kany",
     "MKT_ROT_WIDE", "MKT_ROT_BLKG", "MKT_ROT_VARIANT", "MKT_ROT_SPLIT", "MKT_ROT_STAGGER", "MKT_CCS_STAGGER", "MKT_CCS_PIPE",
     "MKT_EXACT_IMPL", "MKT_EXACT_WIDE", "MKT_EXACT_KANY", "MKT_ROT_MAP",
-    "MKT_KS_G", "MKT_KS_WAVES", "MKT_KS_BLOCKS", "MKT_KS_PAIR", "MKT_FFT_NB", "MKT_FFT_GRID", "MKT_FFT_IGRID", "MKT_NTT_GRID",
+    "MKT_KS_G", "MKT_KS_WAVES", "MKT_KS_BLOCKS", "MKT_KS_PAIR", "MKT_KS_MFMA", "MKT_FFT_NB", "MKT_FFT_GRID", "MKT_FFT_IGRID", "MKT_NTT_GRID",
 ]
 
 
@@ -408,9 +408,20 @@ def test_transform_default_grid_stride(require_gpu, N, W, B):
 
 
 # ---- process-wide launcher switches: one child process per setting, strictly one at a time
-KS_SETTINGS = [{"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"}, {"MKT_KS_WAVES": "2"},
-               {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "1"}, {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "2"}, {"MKT_KS_BLOCKS": "1"},
-               {"MKT_KS_BLOCKS": "100000"}, {"MKT_KS_G": "12"}, {"MKT_KS_G": "64"}]
+# The first eleven select among the older key-switch kernels, which run where the matrix cores do not: they name MKT_KS_MFMA = 0, or every
+# unbalanced D = 4 set of the child would run ks_mfma_kernel whatever else the setting says (ks_plan asks the matrix cores first).  The last
+# three: the matrix cores forced, forced with switches of the older kernels beside them (which then choose nothing), and automatic.
+# Every child reports which kernel each of its key switches ran; the parent holds the report to helpers.ks_expected
+KS_SETTINGS = [{**e, "MKT_KS_MFMA": "0"} for e in (
+    {"MKT_KS_PAIR": "0"}, {"MKT_KS_G": "8"}, {"MKT_KS_G": "16"}, {"MKT_KS_WAVES": "1"}, {"MKT_KS_WAVES": "2"},
+    {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "1"}, {"MKT_KS_PAIR": "0", "MKT_KS_WAVES": "2"}, {"MKT_KS_BLOCKS": "1"},
+    {"MKT_KS_BLOCKS": "100000"}, {"MKT_KS_G": "12"}, {"MKT_KS_G": "64"})]
+KS_SETTINGS += [{"MKT_KS_MFMA": "1"}, {"MKT_KS_MFMA": "1", "MKT_KS_G": "8", "MKT_KS_PAIR": "0"}, {"MKT_KS_MFMA": "-1"}]
+# What each setting is WRITTEN to reach, (kernel, G, waves), on a set with unbalanced digits, D = 4 and an even digit count (the child's first,
+# CGGIparam): helpers.ks_expected says what a setting implies, this says what it is for -- an entry that lost its "MKT_KS_MFMA": "0" would
+# still run what it implies (the matrix cores) and no longer what it is for.  tests/test_ks_plan_cpu.py holds the list to the rule without a GPU
+KS_MEANT = [(1, 32, 4), (1, 8, 1), (1, 16, 1), (2, 32, 1), (2, 32, 2), (1, 32, 1), (1, 32, 2), (2, 32, 4), (2, 32, 4), (2, 32, 4), (2, 32, 4),
+            (3, 32, 4), (3, 32, 4), (3, 32, 4)]
 FFT_SETTINGS = [{"MKT_FFT_NB": "2"}, {"MKT_FFT_GRID": "1", "MKT_FFT_IGRID": "3"}, {"MKT_FFT_GRID": "3", "MKT_FFT_IGRID": "1"},
                 {"MKT_FFT_NB": "2", "MKT_FFT_GRID": "3"}]
 NTT_SETTINGS = [{"MKT_NTT_GRID": "1"}, {"MKT_NTT_GRID": "3"}]
@@ -440,39 +451,68 @@ def test_launcher_switch_in_a_child_process(require_gpu, kind, setting):
     assert not _child_fault, f"an earlier child process faulted: {_child_fault}"
     j = _run_child(kind, setting)
     assert j["ok"] and j["checks"] > 0 and j["env"] == setting, j
+    if kind == "ks":
+        assert_ks_ran(j["ran"], setting)
+
+
+# the sets of the key-switch child: random accumulators at four batches and one NAND each, then (edge_cases.py) the gadget's own boundaries
+KS_PLAIN_SETS = [(p, (1, 33, 257, 1000)) for p in (
+    mk.CGGIparam, mk.CGGIparam.scaled(n=20, N=256), mk.KMS2party.scaled(n=12, N=256), mk.CCS2party.scaled(n=12, N=256),
+    mk.Blockparam.scaled(n=30, N=256, blk_d=10), mk.KMS2partyblock.scaled(n=24, N=256, blk_d=8))]
+KS_NAND_BATCH = 33
+
+
+def ks_child_calls():
+    """[(set, batch)] of every key switch the child reports, in its order; the report's keys are "<position of the set>:<batch>" """
+    from edge_cases import KS_BATCHES, KS_CHILD_FULL, KS_CHILD_SETS
+    calls = [(p, batches + (KS_NAND_BATCH,)) for p, batches in KS_PLAIN_SETS]
+    return calls + [KS_CHILD_FULL] + [(q, KS_BATCHES) for q in KS_CHILD_SETS]
+
+
+def assert_ks_ran(ran, setting):
+    """every key switch of the child ran the kernel, tile width and wave count that its set and the setting imply"""
+    calls = ks_child_calls()
+    assert setting in KS_SETTINGS and calls[0][0] == mk.CGGIparam
+    meant = KS_MEANT[KS_SETTINGS.index(setting)]
+    assert all(tuple(ran[f"0:{B}"]) == meant for B in calls[0][1]), (setting, "is written to reach (kernel, G, waves)", meant, "and ran", [ran[f"0:{B}"] for B in calls[0][1]])
+    assert sorted(ran) == sorted(f"{i}:{B}" for i, (_, batches) in enumerate(calls) for B in set(batches)), sorted(ran)
+    for i, (p, batches) in enumerate(calls):
+        for B in batches:
+            assert tuple(ran[f"{i}:{B}"]) == ks_expected(p, setting), (setting, _sid(p), p.f, p.logD, B, "ran (kernel, G, waves)", ran[f"{i}:{B}"], "implied", ks_expected(p, setting))
 
 
 # ---- child side
 def _child_ks():
+    """-> (checks, {"<position in ks_child_calls()>:<batch>": what that key switch ran})"""
     rng = np.random.default_rng(91)
-    checks = 0
-    for p, batches in ((mk.CGGIparam, (1, 33, 257, 1000)), (mk.CGGIparam.scaled(n=20, N=256), (1, 33, 257, 1000)),
-                       (mk.KMS2party.scaled(n=12, N=256), (1, 33, 257, 1000)), (mk.CCS2party.scaled(n=12, N=256), (1, 33, 257, 1000)),
-                       (mk.Blockparam.scaled(n=30, N=256, blk_d=10), (1, 33, 257, 1000)), (mk.KMS2partyblock.scaled(n=24, N=256, blk_d=8), (1, 33, 257, 1000))):
+    checks, ran = 0, {}
+    for i, (p, batches) in enumerate(KS_PLAIN_SETS):
         crs, keys = keygen(p, 92)
         so = oracle_scheme(p, crs, keys)
         sg = gpu_scheme(p, crs, keys)
+        assert ks_ran(sg)[0] == 0, "no key switch yet"
         for B in batches:
             acc = rng.integers(0, 2**p.W, (B, 1 + p.k, p.N), dtype=np.uint64)
             out = sg.keyswitch(acc.astype(p.ring_dtype))
+            ran[f"{i}:{B}"] = ks_ran(sg)
             for j in _sample(B, rng):
                 assert np.array_equal(out[j], so.keyswitch(acc[j])), (p.name, p.n, B, j)
                 checks += 1
-        B = 33
+        B = KS_NAND_BATCH
         c = encrypt_bits(p, keys, rng.integers(0, 2, 2 * B).astype(bool), seed=9300)
         out = sg.gate(0, c[:B], c[B:])
+        assert ran[f"{i}:{B}"] == ks_ran(sg), "the gate's key switch runs what the plain call of its batch ran"
         js = _sample(B, rng)
         assert np.array_equal(out[js], so.gate_batch(0, c[:B][js], c[B:][js], threads=8)), (p.name, "NAND")
         checks += len(js)
         sg.close()
     # the key-switch gadget's own boundaries (tests/test_gpu_edges.py), every ciphertext compared
-    from edge_cases import KS_BATCHES, KS_CHILD_FULL, KS_CHILD_SETS
-    for p, batches in [KS_CHILD_FULL] + [(q, KS_BATCHES) for q in KS_CHILD_SETS]:       # the full key length first: the launcher settings tile it
+    for i, (p, batches) in list(enumerate(ks_child_calls()))[len(KS_PLAIN_SETS):]:      # the full key length first: the launcher settings tile it
         crs, keys = keygen(p, 98)
         sg = gpu_scheme(p, crs, keys)
-        checks += ks_edge_check(p, oracle_scheme(p, crs, keys), sg, rng, batches)
+        checks += ks_edge_check(p, oracle_scheme(p, crs, keys), sg, rng, batches, after=lambda B: ran.__setitem__(f"{i}:{B}", ks_ran(sg)))
         sg.close()
-    return checks
+    return checks, ran
 
 
 def _child_fft():
@@ -543,7 +583,8 @@ if __name__ == "__main__":
     env = {k: v for k, v in os.environ.items() if k.startswith("MKT_") and k != "MKT_LIB_PATH"}
     try:
         n = {"ks": _child_ks, "fft": _child_fft, "ntt": _child_ntt}[kind]()
-        print(json.dumps({"kind": kind, "env": env, "ok": True, "checks": n}))
+        n, ran = n if kind == "ks" else (n, None)
+        print(json.dumps({"kind": kind, "env": env, "ok": True, "checks": n, **({"ran": ran} if kind == "ks" else {})}))
     except AssertionError as e:
         print(json.dumps({"kind": kind, "env": env, "ok": False, "checks": 0, "error": repr(e)[:2000]}))
         sys.exit(1)
